@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LR-patches/sec, fwd+bwd, WDSR-B r12 t9, 16x16 patches (+6 px border), batch 128 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 starts its own ranks: the parent process (which never touches the GPU and never imports torch) runs
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` as a CHILD,
@@ -16,7 +16,15 @@ The optimizer update and the cPSNR metric are not part of "fwd+bwd"; `--full-ste
 reports the result under "full_step" without changing `value`.
 
 Rank 0 prints ONE JSON line.  `value` comes from the wall clock around exactly K steps (barrier + synchronize on both
-sides, max over ranks); `step_ms` (median, p10, p90) from HIP events recorded on the launch stream at every step boundary.
+sides, max over ranks), `ms_per_step` is that wall clock / K; `step_ms` (median, p10, p90) from HIP events recorded on the launch
+stream at every step boundary.  `--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/*.npy: the
+prediction, the loss and the flat gradient of all parameters; the inputs are seeded, so runs with the same arguments compare
+output for output.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the side-stream choice, the K timed steps.  Everything
+else runs with `--full` only: the data-parallel self-diagnosis, the roofline and per-kernel-class legs, the sustained-MFMA
+probe, the native fp32-MFMA leg, board power, the other configurations and the CPU baseline below (their `--no-*` options
+still switch single legs off).
 `roofline` is measured live: the engine brackets the launches of the dominant kernel class with HIP events on the launch
 stream; `achieved` = SURVEY.md §8d's algorithmic MACs of that class / its time.
 `cpu_baseline` times the CPU oracle (torch-CPU restatement of the TF path; the TF reference itself cannot run here) on the
@@ -67,6 +75,10 @@ def parse_args(argv=None):
     ap.add_argument("--impl", type=int, default=4, help="4 = H3 kernels: fp32 products as three products of scaled fp16 piece pairs on the 16-bit MFMA pipe (default), "
                     "3 = x6 kernels: six bf16-piece products, "
                     "2 = native fp32 MFMA + strip convolution, 1 = fp32 MFMA row-tile kernels, 0 = generic direct kernels")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline (self-diagnosis, roofline, per-kernel classes, MFMA probe, "
+                    "fp32-MFMA leg, board power, other configs, CPU baseline); off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's prediction, loss and flat gradient (rank 0) "
+                    "as DIR/<name>.npy")
     ap.add_argument("--no-fp32-mfma-leg", action="store_true", help="skip the short extra run on the native fp32-MFMA kernels (impl 2)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short T=13 training and full-frame inference legs")
     ap.add_argument("--full-step", action="store_true", help="also time loss+metric+Nadam (reported separately)")
@@ -152,6 +164,40 @@ def cpu_baseline(seconds=20.0):
             "sample": "oracle/wdsr_torch.py fp32, batch 8 (cfg p16t9c85r12 on CPU), fwd + L1 loss + bwd, %d steps in %.1f s; `cores` = `threads` = "
                       "the torch thread count used (the fastest of 8 / 16 / 32 / 64 in a short calibration: oneDNN does not scale further at "
                       "this size), `host_cores` = os.cpu_count() of the box" % (n, dt)}
+
+
+def library_is_current(ge):
+    """True when the built HIP library exists and is newer than every source and header it is compiled from (what build() would
+    otherwise recompile: the .hip units and headers under the package's csrc/, and include/probav_hip.h)."""
+    import glob
+    if not os.path.exists(ge.LIB):
+        return False
+    deps = glob.glob(os.path.join(ge.CSRC, "*.hip")) + glob.glob(os.path.join(ge.CSRC, "*.h")) + [os.path.join(ROOT, "include", "probav_hip.h")]
+    t = os.path.getmtime(ge.LIB)
+    return all(os.path.getmtime(d) <= t for d in deps)
+
+
+DUMP_BYTES = 64 << 20                 # --dump-outputs writes at most this much
+
+
+def dump_outputs(d, pred, loss, grad):
+    """The last timed step's results as the caller of the step receives them, in float32: pred.npy (the network output), loss.npy
+    (the shift-compensated L1 loss) and grad_flat.npy (the gradient of all parameters, flat in the engine's order).  A prediction
+    too large for DUMP_BYTES is cut to a fixed, seeded sample of its samples, listed in pred_rows.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    out = {"loss": loss.detach().float().cpu().numpy(), "grad_flat": grad.detach().float().cpu().numpy()}
+    p = pred.float()
+    room = DUMP_BYTES - sum(a.nbytes for a in out.values())
+    per_row = p[0].numel() * 4
+    if p.shape[0] * per_row > room:
+        rows = np.sort(np.random.default_rng(0).choice(p.shape[0], max(1, room // per_row - 1), replace=False))
+        out["pred_rows"] = rows.astype(np.float64)
+        p = p[torch.as_tensor(rows, device=p.device)]
+    out["pred"] = p.cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def percentiles(ms):
@@ -289,8 +335,11 @@ def run_rank(args):
     import torch.distributed as dist
     import __graft_entry__ as ge
     # the library is built BEFORE the process group exists (a cold hipcc build takes minutes: inside the group it would sit in the other
-    # ranks' collective watchdog window); build() serialises the ranks on a file lock, the first one in compiles, the others find it done
-    ge.build()
+    # ranks' collective watchdog window); build() serialises the ranks on a file lock, the first one in compiles, the others find it done.
+    # A library newer than every source is used as it is: build() would still open its lock file beside the sources, and a built tree
+    # may be read-only to the user who benchmarks it
+    if not library_is_current(ge):
+        ge.build()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     force_dp = bool(args.force_dp) or os.environ.get("PROBAV_FORCE_DP") == "1"
@@ -325,13 +374,15 @@ def run_rank(args):
         data = tuple(torch.as_tensor(a).to(dev) for a in synth.synth_batch(B, seed=1234 + rank, numImgLR=T))
         return model, data
 
-    def stepper(model, data, opt=None):
+    def stepper(model, data, opt=None, keep=None):
         x, hr, mask = data
 
         seed = [None]
 
         def step(full=False, comm_events=None):
             pred = model(x, training=True)
+            if keep is not None:
+                keep["pred"] = pred.detach()
             loss = losses.shiftCompensatedL1Loss(hr, mask, pred)
             model.flat.grad = None
             if seed[0] is None:
@@ -385,13 +436,14 @@ def run_rank(args):
     T = args.frames
     model, data = make(T)
     opt = make_optimizer("nadam", model, 5e-4)
-    step = stepper(model, data, opt)
+    last = {} if args.dump_outputs else None          # the prediction of the latest step, for --dump-outputs
+    step = stepper(model, data, opt, last)
     h = model._handle()
     side_probe = None
     if args.side_stream_mode >= 0:
         _lib.check(L.probav_engine_side_stream(h, args.side_stream_mode), "probav_engine_side_stream")
     sampler, windows = None, {}
-    if rank == 0 and not args.no_power:
+    if rank == 0 and args.full and not args.no_power:
         props = torch.cuda.get_device_properties(dev)
         try:
             pci = "%04x:%02x:%02x.0" % (props.pci_domain_id, props.pci_bus_id, props.pci_device_id)
@@ -409,7 +461,7 @@ def run_rank(args):
         for _ in range(3):              # the probe ends by switching modes: the first step in the kept mode (new fork / join pattern, slabs of the other
             step()                      # mode's layout cold) is not a step of the steady state -- three untimed ones stand between it and the timed region
         sync()
-    use_events = not args.no_kernel_events
+    use_events = args.full and not args.no_kernel_events
     n = len(CLASSES)
 
     def read_profile():
@@ -429,13 +481,15 @@ def run_rank(args):
         hsh.update(loss.detach().cpu().numpy().tobytes())
         hsh.update(model.flat.grad.detach().cpu().numpy().tobytes())
         digest = hsh.hexdigest()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["pred"], loss, model.flat.grad)
     # Data-parallel self-diagnosis (N > 1, or --force-dp), behind the headline region: one run yields the curve's inputs AND what explains them --
     # every rank's own median step, the gradient all-reduce's own time per step (HIP events around the collective on the launch stream: its
     # wait for the slowest rank is inside), and a proof that the replicas hold the same bits: the all-reduced gradient and the parameters
     # digest identically on every rank (reference semantics: debug/trainClassMultiGPU0.py:67-84,153,162-178 -- one replica per GPU, the
     # gradients reduced once per step, the variables mirrored).
     dp_diag = None
-    if dp:
+    if dp and args.full:
         comm = []
         kd = min(10, args.steps)
         _, ms_d, _ = timed(step, kd, False, comm)
@@ -495,7 +549,7 @@ def run_rank(args):
     # what the matrix pipe of THIS device sustains (the boxes of a pool differ by ~8 % under fp16-MFMA load): a few milliseconds of
     # nothing but dependent fp16 MFMAs on every CU, right behind the timed steps (the device is warm)
     mfma_probe = None
-    if rank == 0:
+    if rank == 0 and args.full:
         seed = (torch.rand(128 * 8, device=dev) - 0.5).half()
         sink = torch.empty(256 * 256, device=dev)
         iters, launches = 2000, 8
@@ -518,7 +572,7 @@ def run_rank(args):
                               "matrix pipe alone is what limits the power)"}
 
     fp32_leg = None
-    if args.impl >= 3 and not args.no_fp32_mfma_leg:
+    if args.impl >= 3 and args.full and not args.no_fp32_mfma_leg:
         model.set_impl(2)
         for _ in range(2):
             step()
@@ -538,7 +592,7 @@ def run_rank(args):
         power = sampler.stop(windows)
 
     other = None
-    if world == 1 and T == 9 and not args.no_other_configs:
+    if world == 1 and T == 9 and args.full and not args.no_other_configs:
         other = {}
         # BASELINE.json config 3, realised as the reference's only longer-T network (T = 13, ConvReduceAndUpscalev3)
         del step, opt
@@ -750,7 +804,7 @@ def run_rank(args):
                     out["roofline"]["traffic_note"] = ("HBM bytes per launch of %s from %s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
                                                        "passes of this command; FETCH_SIZE doubled per the gfx950 note), not collected in this run"
                                                        % (hp["per_class"][dom]["kernel"], os.path.relpath(hbm_profile, ROOT)))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dp:

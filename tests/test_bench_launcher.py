@@ -67,3 +67,65 @@ def test_power_sampler_reads_hwmon_files_from_a_child_process(tmp_path):
     out = s.stop({"run": (t0 + 0.05, t1), "nothing": (t1 + 10, t1 + 11)})
     assert out["sensor"] == paths[1] and out["nothing"] is None
     assert out["run"]["samples"] >= 5 and out["run"]["board_power_W"]["mean"] == 1000.0 and out["run"]["sclk_GHz"]["max"] == 1.6
+
+
+def test_plain_run_is_the_headline_only_and_full_is_opt_in():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_a_large_prediction(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's prediction, loss and flat gradient as .npy; a prediction over the byte budget is cut
+    to a fixed, seeded sample of whole samples (the same rows on every run), listed in pred_rows.npy."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    pred = torch.arange(10 * 48 * 48, dtype=torch.float32).reshape(10, 48, 48, 1)
+    loss, grad = torch.tensor(1.5), torch.linspace(-1, 1, 1000)
+    bench.dump_outputs(str(tmp_path / "all"), pred, loss, grad)
+    got = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in ("pred", "loss", "grad_flat")}
+    assert not (tmp_path / "all" / "pred_rows.npy").exists()
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["pred"], pred.numpy())
+    np.testing.assert_array_equal(got["grad_flat"], grad.numpy())
+    assert float(got["loss"]) == 1.5
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 48 * 48 * 4 + 4000 + 4)      # room for 4 samples beside the loss and gradient
+    rows = []
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), pred, loss, grad)
+        r = np.load(str(tmp_path / d / "pred_rows.npy")).astype(np.int64)
+        p = np.load(str(tmp_path / d / "pred.npy"))
+        assert 1 <= len(r) <= 4 and p.shape == (len(r), 48, 48, 1)
+        np.testing.assert_array_equal(p, pred.numpy()[r])
+        total = sum(os.path.getsize(str(tmp_path / d / f)) - 128 for f in os.listdir(str(tmp_path / d)))     # (less each .npy header)
+        assert total <= bench.DUMP_BYTES
+        rows.append(r.tolist())
+    assert rows[0] == rows[1]
+
+
+def test_a_current_library_is_used_without_build(tmp_path):
+    """bench.py calls build() only when the library is missing or older than a source or header: build() opens a lock file beside
+    the sources, and a built tree may be read-only to the user who benchmarks it."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    csrc = tmp_path / "csrc"
+    csrc.mkdir()
+    unit, hdr, lib = csrc / "k.hip", csrc / "k.h", csrc / "libprobav_hip.so"
+    ge = types.SimpleNamespace(CSRC=str(csrc), LIB=str(lib))
+    unit.write_text("")
+    hdr.write_text("")
+    assert not bench.library_is_current(ge)                       # nothing built yet
+    lib.write_text("")
+    future = os.path.getmtime(os.path.join(ROOT, "include", "probav_hip.h")) + 100
+    os.utime(str(unit), (future, future))
+    os.utime(str(hdr), (future, future))
+    os.utime(str(lib), (future + 10, future + 10))
+    assert bench.library_is_current(ge)
+    os.utime(str(hdr), (future + 20, future + 20))                 # a header edited after the build
+    assert not bench.library_is_current(ge)

@@ -34,8 +34,8 @@ def _env(**extra):
     return env
 
 
-BENCH_FLAGS = ["--steps", "3", "--warmup", "2", "--batch", "8", "--no-cpu-baseline", "--no-other-configs", "--no-fp32-mfma-leg",
-               "--no-kernel-events", "--digest"]
+BENCH_FLAGS = ["--full", "--steps", "3", "--warmup", "2", "--batch", "8", "--no-cpu-baseline", "--no-other-configs", "--no-fp32-mfma-leg",
+               "--no-kernel-events", "--digest"]          # (--full: the data-parallel self-diagnosis `dp` is one of its legs)
 
 
 def _bench_line(cmd, env):

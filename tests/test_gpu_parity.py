@@ -14,6 +14,7 @@ import torch
 from oracle import wdsr_numpy as on
 from oracle import wdsr_torch as ot
 from probav_amd import synth
+from tests import load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,6 @@ def _keep_workspaces(monkeypatch):
     reference by default).  Per test, so that every other GPU module runs with the product's default."""
     monkeypatch.setenv("PROBAV_KEEP_WS", "1")
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 # Un-gated golden gradients, relative L2 per tensor: ONE fixed bar for every depth and kernel family, 5e-3 -- not a number fitted to what a build happens to measure
 # (ADVICE r4).  Where it comes from: the gradient of this network is discontinuous in its ReLU gates; an fp32 and an fp64 evaluation set the gates of pre-activations at ~0
 # differently, and each flipped gate moves a filter-gradient entry by ~1/sqrt(#voxels) of its norm.  With B = 2 (8 712 voxels per block) that is the 1e-3 ... 3e-3 every
@@ -365,7 +365,7 @@ def test_clip_round_half_to_even(dev):
 def test_end_to_end_against_golden(dev, T, impl):
     """forward, loss, metric and all 132 (138 / 129 / 153) gradients against the committed fp64 fixtures."""
     from probav_amd.loss import Losses
-    z = np.load(os.path.join(GOLD, "wdsr_t%d_b2.npz" % T))
+    z = load_golden("wdsr_t%d_b2" % T)
     seeds = {9: (101, 102), 13: (131, 132), 7: (71, 72), 19: (191, 192)}[T]
     params = synth.synth_params(seed=seeds[0], perturb=True, numImgLR=T)
     m = _model(dev, T, params)
@@ -384,10 +384,10 @@ def test_end_to_end_against_golden(dev, T, impl):
     names = m.variable_names
     assert len(grads) == z["grad_norms"].shape[0]
     if T == 9:
-        # ALL 132 gradient tensors element-wise against the committed fp64 gradient (tests/golden/wdsr_t9_b2_grads.npz): a norm cannot
+        # ALL 132 gradient tensors element-wise against the committed fp64 gradient (tests/golden/wdsr_t9_b2_grads.part*.npz): a norm cannot
         # see a wrong direction.  Metric here: relative L2 per tensor (ReLU gates at ~0 flip between an fp32 and an fp64 evaluation;
         # test_gradients_match_oracle_with_the_devices_relu_masks removes exactly that effect and then holds 1e-3 in the max norm).
-        gref = np.load(os.path.join(GOLD, "wdsr_t9_b2_grads.npz"))["grad_flat"].astype(np.float64)
+        gref = load_golden("wdsr_t9_b2_grads")["grad_flat"].astype(np.float64)
         gdev = m.flat.grad.detach().cpu().double().numpy()
         worst = {"g": (0.0, None), "v": (0.0, None), "bias": (0.0, None)}
         for L_ in m.layers:
@@ -408,7 +408,7 @@ def test_end_to_end_against_golden(dev, T, impl):
         tol = _grad_l2_tol(T, impl)
         assert abs(np.sqrt((g ** 2).sum()) - ref_norm) < tol * ref_norm + 1e-12, n
         key = "grad/" + n
-        if key in z.files:
+        if key in z:
             e2 = np.sqrt(((g - z[key]) ** 2).sum()) / (ref_norm + 1e-30)
             wk = "g" if n.endswith("/g") else "v"
             worst_sub[wk] = max(worst_sub[wk], e2)
@@ -757,7 +757,7 @@ def test_three_channel_input_branch_on_the_fp32_families(dev, impl):
 def _gate_masked_parity(dev, impl, T, B, C):
     from probav_amd.loss import Losses
     if (T, B, C) == (9, 2, 1):
-        z = np.load(os.path.join(GOLD, "wdsr_t9_b2.npz"))
+        z = load_golden("wdsr_t9_b2")
     else:
         z = dict(zip(("x", "hr", "mask"), synth.synth_batch(B, seed=300 + 10 * T + B, numImgLR=T, inChannels=C)))
     params = synth.synth_params(seed=101, perturb=True, numImgLR=T, inChannels=C)
@@ -810,7 +810,7 @@ def test_forward_and_reverse_pass_decide_the_same_relu_gates(dev, B, monkeypatch
     from probav_amd.introspect import hidden_tile
     T = 9
     if B == 2:
-        z = np.load(os.path.join(GOLD, "wdsr_t9_b2.npz"))
+        z = load_golden("wdsr_t9_b2")
         x = torch.as_tensor(z["x"]).to(dev)
     else:
         x = torch.as_tensor(synth.synth_batch(B, seed=4242)[0]).to(dev)

@@ -3,7 +3,6 @@
 Parity is unpinned by the reference (no TF here, no reference tests); what is checked is that the two
 independent restatements agree, that the analytic gradients match finite differences, and that the
 golden vectors in tests/golden/ are reproduced."""
-import os
 
 import numpy as np
 import pytest
@@ -12,8 +11,8 @@ import torch
 from oracle import wdsr_numpy as on
 from oracle import wdsr_torch as ot
 from probav_amd import synth
+from tests import load_golden
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def test_two_restatements_agree_fp64():
@@ -100,7 +99,7 @@ def test_depth_to_space_and_reflect_pad_conventions():
 
 @pytest.mark.parametrize("T", [9, 13, 7, 19])
 def test_golden_fixture_reproduced(T):
-    z = np.load(os.path.join(GOLD, "wdsr_t%d_b2.npz" % T))
+    z = load_golden("wdsr_t%d_b2" % T)
     seeds = {9: (101, 102), 13: (131, 132), 7: (71, 72), 19: (191, 192)}[T]
     params = synth.synth_params(seed=seeds[0], perturb=True, numImgLR=T)
     x, hr, mask = synth.synth_batch(2, seed=seeds[1], numImgLR=T)

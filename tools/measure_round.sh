@@ -23,8 +23,8 @@ prof "$O/pmc_b" "$O/pmc_b.log" --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS S
 prof "$O/hbm_f" "$O/hbm_f.log" --pmc FETCH_SIZE
 prof "$O/hbm_w" "$O/hbm_w.log" --pmc WRITE_SIZE
 cd "$R"
-python3 bench.py 2>"$O/bench_line.err" | tail -1 > "$O/bench_line.json"
-python3 bench.py --full-step --no-cpu-baseline --no-fp32-mfma-leg --no-other-configs 2>"$O/bench_line_fullstep.err" | tail -1 > "$O/bench_line_fullstep.json"
+python3 bench.py --full 2>"$O/bench_line.err" | tail -1 > "$O/bench_line.json"
+python3 bench.py --full --full-step --no-cpu-baseline --no-fp32-mfma-leg --no-other-configs 2>"$O/bench_line_fullstep.err" | tail -1 > "$O/bench_line_fullstep.json"
 python3 tools/pmc_summary.py "$O/pmc_a" > "$O/pmc_a.txt"
 python3 tools/pmc_summary.py "$O/pmc_b" > "$O/pmc_b.txt"
 python3 tools/hbm_summary.py "$O/hbm_f" "$O/hbm_w" 4 > "$O/hbm_traffic.json"
