@@ -242,6 +242,35 @@ int probav_debug_hidden(probav_engine* e, const float* params, const void* ws /*
  * orders; a pre-activation that is zero to rounding can be open in one and closed in the other (tests/test_gpu_parity.py bounds how many, and how large).  Process-wide. */
 int probav_debug_hidden_from_forward_kernel(int on);
 
+/* ---- dataset builder (utils/dataGenerator.py; proba-v_amd/prep.py), additions of ABI 7 ------------------------------------------------ */
+/* Frames are one flat [n_frames][H][W] array; a ragged list of image sets is that array plus set_offsets[n_sets+1] (int64, ascending,
+ * set_offsets[0] = 0).  Masks are uint8, nonzero = set.  Kernels and the registration error bound: csrc/kernels_prep.hip.
+ * counts[i] = number of nonzero bytes of data[i*chunk_len .. (i+1)*chunk_len): count_nonzero of every QM / SM frame, or of every patch's
+ * mask                                    replaces the per-frame / per-patch list comprehensions of utils/dataGenerator.py:381, 490, 632, 761 */
+int probav_prep_count_nonzero(const uint8_t* data, int64_t n_chunks, int64_t chunk_len, int32_t* counts, void* stream);
+/* Registers every 128 x 128 uint16 frame against its set's reference frame ref_frame[set] (an index into frames, chosen by the caller).
+ * shifts [n_frames][2] (y, x as skimage reports them: indices > 64 wrapped to negative), reg_frames = np.roll(frame, shift), reg_masks =
+ * np.roll(mask != 0, shift) as 0/1, reg_counts = their count of ones.  The shift is the argmax of the EXACT integer circular
+ * cross-correlation, ties to the first index in C order; the reference frame itself gets shift 0.  spec_scratch: n_sets * 128 * 128 * 2
+ * floats.  Preconditions (device arrays, so not checked on the host): set_offsets[0] = 0, non-decreasing, set_offsets[n_sets] = n_frames,
+ * and set_offsets[s] <= ref_frame[s] < set_offsets[s+1] (no empty set).  A frame whose set breaks them is not read or written: its shift
+ * is {PROBAV_PREP_BAD_SHIFT, PROBAV_PREP_BAD_SHIFT} (probav.prep raises on it).
+ *                                         replaces registerImagesInSet / registerFrame(tech='freq')   utils/dataGenerator.py:616-678 */
+#define PROBAV_PREP_BAD_SHIFT (-2147483647 - 1)
+int probav_prep_register(const uint16_t* frames, const uint8_t* masks, const int64_t* set_offsets, int n_sets, int64_t n_frames,
+                         const int32_t* ref_frame, float* spec_scratch, int32_t* shifts, uint16_t* reg_frames, uint8_t* reg_masks,
+                         int32_t* reg_counts, void* stream);
+/* Diagnostic of the registration: for pair = {ref, img} ([2][128][128] uint16) the fp32 correlation surface e[128][128] the kernel ranks
+ * shifts by (of the frames offset by their floor means c_ref, c_img) and info[4] = {B, c_ref, c_img, max e}: B bounds |e - exact| at every
+ * shift.  spec_scratch: 128 * 128 * 2 floats.                      (utils/dataGenerator.py:669, skimage register_translation) */
+int probav_prep_xcorr_surface(const uint16_t* pair, float* spec_scratch, float* surface, double* info, void* stream);
+/* Reflect pad by `pad` (np.pad 'reflect'), then every win x win window at `stride`, row-major: frames [S][T][H][W] fp32 and masks [S][T][H][W]
+ * uint8 -> patches [S][P][T][win][win], patch_masks (0/1) the same, counts [S][P][T] = ones of each patch mask, P = nh * nw,
+ * nh = (H + 2 pad - win) / stride + 1.  HR: pad 0, window = stride = 48.
+ *                                         replaces the pad + generatePatches of utils/dataGenerator.py:107-171, 553-596 */
+int probav_prep_patches(const float* frames, const uint8_t* masks, int S, int T, int H, int W, int pad, int win, int stride, float* patches,
+                        uint8_t* patch_masks, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,11 @@ SIGNATURES = {
                                             c_void_p, c_size_t, c_void_p]),
     "probav_forward_wc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "probav_backward_wc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
+    # dataset builder (csrc/kernels_prep.hip)
+    "probav_prep_count_nonzero": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "probav_prep_register": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "probav_prep_xcorr_surface": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "probav_prep_patches": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,431 @@
+"""Dataset builder: the reference's utils/dataGenerator.py (lines 33-273 and the helpers they call) on the GPU.
+
+Same function names, argument orders, directory layout, file names, shapes, dtypes and pickle protocols as the reference.  The clear
+counts of the raw frames, the registration of every LR frame against its set's clearest frame and the pad + unfold of the patches run
+as HIP kernels (csrc/kernels_prep.hip, behind include/probav_hip.h); the selections in between are numpy index bookkeeping over small
+count arrays, written with the SAME numpy calls on the same dtypes and shapes as the reference (its `np.argsort` is the default,
+unstable kind: tie order then depends on the numpy build exactly as the reference's does).
+
+Deliberate differences ('From the ESA download to train.py'):
+  - stage 1 writes ragged image sets as object arrays of per-set arrays (numpy >= 1.24 refuses the reference's implicit ragged arrays);
+  - registration takes the argmax of the EXACT integer cross-correlation (the reference's fp64 FFT agrees except where two shifts tie
+    exactly, which it breaks by rounding noise) and rolls exactly (the reference's Fourier shift leaves ~1e-12 residue);
+  - masks are booleans: a nonzero QM / SM pixel is clear;
+  - randomness is drawn from the `rng` that main() threads through (a numpy.random.RandomState; None = numpy's global state, as the
+    reference), in the reference's call order;
+  - splitPatches restates sklearn's train_test_split(test_size=split, random_state=17) without sklearn.
+"""
+import glob
+import logging
+import math
+import os
+
+import numpy as np
+
+from . import pngio
+
+LR_SIZE = 128          # registration geometry (PROBA-V LR frames)
+PREP_BAD_SHIFT = -2 ** 31   # PROBAV_PREP_BAD_SHIFT
+
+
+# ---- device helpers ----------------------------------------------------------------------------------------------------------------
+def _dev():
+    import torch
+    from . import _lib
+    _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("the dataset builder's registration and patch kernels run only as HIP kernels on a gfx950 device "
+                           "(no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to_dev(a, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def device_count_nonzero(a, chunk_len):
+    """count_nonzero of every consecutive chunk of `chunk_len` elements of a bool / uint8 array, on the device."""
+    import torch
+    from . import _lib
+    dev = _dev()
+    flat = np.ascontiguousarray(a).reshape(-1)
+    if flat.dtype == np.bool_:
+        flat = flat.view(np.uint8)
+    flat = (flat != 0).view(np.uint8) if flat.dtype != np.uint8 else flat
+    n = flat.size // chunk_len
+    d = _to_dev(flat, dev)
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        _lib.check(_lib.lib().probav_prep_count_nonzero(_lib.ptr(d), n, chunk_len, _lib.ptr(out), _lib.current_stream()),
+                   "probav_prep_count_nonzero")
+    return out.cpu().numpy()
+
+
+def device_register(frames, masks, set_offsets, ref_frame):
+    """frames [F,128,128] uint16, masks [F,128,128] (nonzero = clear), set_offsets [S+1], ref_frame [S] frame indices ->
+    (shifts [F,2] int32, rolled frames uint16, rolled masks bool, rolled clear counts int32)."""
+    import torch
+    from . import _lib
+    dev = _dev()
+    F = frames.shape[0]
+    S = len(set_offsets) - 1
+    o, r = np.asarray(set_offsets, np.int64), np.asarray(ref_frame, np.int64)
+    if S < 1 or o[0] != 0 or o[-1] != F or (np.diff(o) < 1).any() or len(r) != S or (r < o[:-1]).any() or (r >= o[1:]).any():
+        raise ValueError("registration needs set_offsets[0] = 0, set_offsets[-1] = n_frames, no empty set, one reference inside each set")
+    if frames.shape[1:] != (LR_SIZE, LR_SIZE) or masks.shape != frames.shape:
+        raise ValueError("registration takes %d x %d frames, got %r / %r" % (LR_SIZE, LR_SIZE, frames.shape, masks.shape))
+    fr = _to_dev(frames.astype(np.uint16, copy=False), dev)
+    mk = _to_dev((np.asarray(masks) != 0).view(np.uint8), dev)
+    off = _to_dev(np.asarray(set_offsets, np.int64), dev)
+    ref = _to_dev(np.asarray(ref_frame, np.int32), dev)
+    spec = torch.empty(S * LR_SIZE * LR_SIZE * 2, dtype=torch.float32, device=dev)
+    shifts = torch.empty(F, 2, dtype=torch.int32, device=dev)
+    rf = torch.empty_like(fr)
+    rm = torch.empty_like(mk)
+    rc = torch.empty(F, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    _lib.check(L.probav_prep_register(_lib.ptr(fr), _lib.ptr(mk), _lib.ptr(off), S, F, _lib.ptr(ref), _lib.ptr(spec), _lib.ptr(shifts),
+                                      _lib.ptr(rf), _lib.ptr(rm), _lib.ptr(rc), _lib.current_stream()), "probav_prep_register")
+    sh = shifts.cpu().numpy()
+    if (sh == PREP_BAD_SHIFT).any():
+        raise ValueError("probav_prep_register: set_offsets / ref_frame break the preconditions of include/probav_hip.h (empty set or a "
+                         "reference outside its set)")
+    return sh, rf.cpu().numpy(), rm.cpu().numpy().astype(bool), rc.cpu().numpy()
+
+
+def device_xcorr_surface(ref, img):
+    """Diagnostic: (fp32 surface [128,128], {B, c_ref, c_img, max}) the registration kernel ranks shifts by."""
+    import torch
+    from . import _lib
+    dev = _dev()
+    pair = _to_dev(np.stack([ref, img]).astype(np.uint16), dev)
+    spec = torch.empty(LR_SIZE * LR_SIZE * 2, dtype=torch.float32, device=dev)
+    surf = torch.empty(LR_SIZE, LR_SIZE, dtype=torch.float32, device=dev)
+    info = torch.empty(4, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().probav_prep_xcorr_surface(_lib.ptr(pair), _lib.ptr(spec), _lib.ptr(surf), _lib.ptr(info), _lib.current_stream()),
+               "probav_prep_xcorr_surface")
+    i = info.cpu().numpy()
+    return surf.cpu().numpy(), {"B": float(i[0]), "c_ref": int(i[1]), "c_img": int(i[2]), "max": float(i[3])}
+
+
+def device_patches(frames, masks, pad, win, stride):
+    """frames [S,T,H,W] (cast to fp32), masks [S,T,H,W] -> patches [S,P,T,win,win] fp32, masks bool, counts [S,P,T] int32."""
+    import torch
+    from . import _lib
+    dev = _dev()
+    S, T, H, W = frames.shape
+    nh, nw = (H + 2 * pad - win) // stride + 1, (W + 2 * pad - win) // stride + 1
+    fr = _to_dev(np.asarray(frames, np.float32), dev)
+    mk = _to_dev((np.asarray(masks) != 0).view(np.uint8), dev)
+    P = nh * nw
+    pt = torch.empty(S, P, T, win, win, dtype=torch.float32, device=dev)
+    pm = torch.empty(S, P, T, win, win, dtype=torch.uint8, device=dev)
+    pc = torch.empty(S, P, T, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().probav_prep_patches(_lib.ptr(fr), _lib.ptr(mk), S, T, H, W, pad, win, stride, _lib.ptr(pt), _lib.ptr(pm),
+                                              _lib.ptr(pc), _lib.current_stream()), "probav_prep_patches")
+    return pt.cpu().numpy(), pm.cpu().numpy().astype(bool), pc.cpu().numpy()
+
+
+def _objects(items):
+    out = np.empty(len(items), dtype=object)
+    for i, a in enumerate(items):
+        out[i] = a
+    return out
+
+
+# ---- checkpoint 1 (utils/dataGenerator.py:844-941) --------------------------------------------------------------------------------
+def loadAndSaveRawData(rawDataDir, arrayDir, band, isGrayScale=True, isTrainData=True):
+    if not isGrayScale:
+        raise ValueError("PROBA-V frames are greyscale (isGrayScale=True)")
+    os.makedirs(arrayDir, exist_ok=True)
+    key = 'TRAIN' if isTrainData else 'TEST'
+    dirList = sorted(glob.glob(os.path.join(rawDataDir, key.lower(), band, 'imgset*')))
+    read = lambda f: np.expand_dims(pngio.imread(f), axis=0)
+    for name, pat in (('imgLR', 'LR*.png'), ('mskLR', 'QM*.png')):
+        sets = _objects([np.array([read(f) for f in sorted(glob.glob(os.path.join(d, pat)))]) for d in dirList])
+        sets.dump(os.path.join(arrayDir, f'{key}{name}_{band}.npy'))
+    if isTrainData:
+        for name, fname in (('imgHR', 'HR.png'), ('mskHR', 'SM.png')):
+            a = np.expand_dims(np.array([read(os.path.join(d, fname)) for d in dirList]), axis=1)
+            a.dump(os.path.join(arrayDir, f'{key}{name}_{band}.npy'))
+
+
+def loadData(arrayDir, band):
+    if not os.path.exists(arrayDir):
+        raise Exception("[ ERROR ] Folder path does not exists...")
+    if not os.listdir(arrayDir):
+        raise Exception("[ ERROR ] No files in the provided directory...")
+    load = lambda n: np.load(os.path.join(arrayDir, f'{n}_{band}.npy'), allow_pickle=True)
+    TRAIN = (load('TRAINimgLR'), load('TRAINmskLR'), load('TRAINimgHR'), load('TRAINmskHR'))
+    TEST = (load('TESTimgLR'), load('TESTmskLR'))
+    return TRAIN, TEST
+
+
+# ---- checkpoint 2 (utils/dataGenerator.py:599-841) --------------------------------------------------------------------------------
+def registerImages(allImgLR, allMskLR):
+    """Per set: frames reordered by np.argsort(-clear count), the first is the reference, every other one registered against it
+    (device).  Returns an object array of float64 masked arrays [T, 1, 128, 128] (mask = ~clear)."""
+    sets_img = [np.asarray(allImgLR[i]) for i in range(len(allImgLR))]
+    sets_msk = [np.asarray(allMskLR[i]) for i in range(len(allMskLR))]
+    for a, m in zip(sets_img, sets_msk):
+        assert a.shape == m.shape, 'Input shape does not match!'
+    sizes = [len(a) for a in sets_img]
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    hw = sets_img[0].shape[-2:]
+    frames = np.concatenate([a.reshape(-1, *a.shape[-2:]) for a in sets_img]).astype(np.uint16)
+    masks = np.concatenate([(m != 0).reshape(-1, *m.shape[-2:]) for m in sets_msk])
+    counts = device_count_nonzero(masks, hw[0] * hw[1]).astype(np.int64)
+    order = np.concatenate([offsets[i] + np.argsort(-counts[offsets[i]:offsets[i + 1]]) for i in range(len(sizes))])
+    _, rf, rm, _ = device_register(frames[order], masks[order], offsets, offsets[:-1])
+    out = []
+    for i in range(len(sizes)):
+        sl = slice(offsets[i], offsets[i + 1])
+        data = rf[sl].astype(np.float64)[:, None]
+        out.append(np.ma.masked_array(data, mask=~rm[sl][:, None]))
+    return _objects(out)
+
+
+def convertToMaskedArray(imgSets, mskSets):
+    imgSets = np.squeeze(imgSets, axis=1)
+    mskSets = np.squeeze(mskSets, axis=1)
+    imgMskSets = np.ma.array([np.ma.masked_array(img, mask=~(msk != 0)) for img, msk in zip(imgSets, mskSets)])
+    imgMskSets = np.expand_dims(imgMskSets, axis=1)
+    assert (imgMskSets.shape == imgMskSets.mask.shape), 'Mask and Array shapes do not match!'
+    return imgMskSets
+
+
+def isImageSetNotCorrupted(imgSet, clarityThreshold):
+    isImageClearEnough = np.array([np.count_nonzero(img.mask) / (img.shape[1] * img.shape[2]) < (1 - clarityThreshold) for img in imgSet])
+    return np.sum(isImageClearEnough) != 0
+
+
+def removeCorruptedTrainImageSets(imgMskLR, imgMskHR, clarityThreshold):
+    booleanMask = np.array([isImageSetNotCorrupted(imgSet, clarityThreshold) for imgSet in imgMskLR])
+    imgSetRemoved = np.arange(len(imgMskLR))[~booleanMask]
+    return imgMskLR[booleanMask], imgMskHR[booleanMask], imgSetRemoved
+
+
+def removeCorruptedTestImageSets(imgMskLR, clarityThreshold):
+    booleanMask = np.array([isImageSetNotCorrupted(imgSet, clarityThreshold) for imgSet in imgMskLR])
+    return imgMskLR[booleanMask]
+
+
+def filterImgMskSet(imgSet, clarityThreshold):
+    isImageClearEnough = np.array([np.count_nonzero(img.mask) / (img.shape[1] * img.shape[2]) < (1 - clarityThreshold) for img in imgSet])
+    return imgSet[isImageClearEnough]
+
+
+def pickClearImg(imgMsk, numImgToPick, rng=None):
+    rng = np.random if rng is None else rng
+    sortedIndices = np.argsort(np.sum(imgMsk.mask, axis=(1, 2, 3)))
+    sortedImgMskArray = imgMsk[sortedIndices]
+    count = 0
+    if numImgToPick < len(imgMsk):
+        trimmedImgMsk = sortedImgMskArray[:numImgToPick]
+    else:
+        trimmedImgMsk = np.ma.copy(sortedImgMskArray)
+        count += (numImgToPick - len(trimmedImgMsk))
+        while len(trimmedImgMsk) < numImgToPick:
+            shuffledIndices = rng.choice(sortedIndices, size=len(sortedIndices), replace=False)
+            trimmedImgMsk = np.ma.concatenate((trimmedImgMsk, imgMsk[shuffledIndices]))
+        trimmedImgMsk = trimmedImgMsk[:numImgToPick]
+    return trimmedImgMsk, count
+
+
+def pickClearLRImgsPerImgSet(imgMskLR, numImgToPick, clarityThreshold, rng=None):
+    cache = []
+    for imgMsk in imgMskLR:
+        clearData, _ = pickClearImg(filterImgMskSet(imgMsk, clarityThreshold), numImgToPick=numImgToPick, rng=rng)
+        cache.append(np.expand_dims(clearData, axis=0))
+    return np.ma.concatenate(cache)
+
+
+# ---- checkpoint 3 (utils/dataGenerator.py:99-174, 553-596) ------------------------------------------------------------------------
+def _patches(imgSets, patchSize, stride, pad=0):
+    """Device pad + unfold of [S, T, C=1, H, W] masked frames -> ([S, P, T, 1, k, k] float32 masked array, masked-pixel counts [S, P, T])."""
+    S, T, C, H, W = imgSets.shape
+    if C != 1:
+        raise ValueError("greyscale frames expected (C = 1), got C = %d" % C)
+    data = np.ma.getdata(imgSets).reshape(S, T, H, W)
+    mask = np.ma.getmaskarray(imgSets).reshape(S, T, H, W)
+    p, m, c = device_patches(data, mask, pad, patchSize, stride)
+    return np.ma.masked_array(p[:, :, :, None], mask=m[:, :, :, None]), c
+
+
+def generatePatches(imgSets, patchSize, stride):
+    """[S, T, C, H, W] -> [S, P * T, C, k, k] in the reference's (patch, frame) order (utils/dataGenerator.py:553-596)."""
+    p, _ = _patches(imgSets, patchSize, stride)
+    S, P, T = p.shape[:3]
+    return p.reshape(S, P * T, *p.shape[3:])
+
+
+# ---- checkpoint 4 (utils/dataGenerator.py:326-551) --------------------------------------------------------------------------------
+def _mask_counts(patches):
+    m = np.ma.getmaskarray(patches)
+    return m.reshape(*m.shape[:-3], -1).sum(-1)
+
+
+def removeAndReplaceDirtyFrames(imgSet, k, clarityThreshold, counts=None):
+    """imgSet [P, T, C, H, W]: per patch, the frames that pass the threshold (all of them if none does), tiled to at least k, sorted by
+    masked-pixel count (np.argsort of the tiled counts, as the reference), first k."""
+    P, T, C, H, W = imgSet.shape
+    counts = _mask_counts(imgSet) if counts is None else counts
+    sel = np.empty((P, k), np.int64)
+    count = countNotReplaced = 0
+    for i in range(P):
+        cnt = np.asarray(counts[i], np.int64)
+        idx = np.nonzero(cnt / (H * W) < (1 - clarityThreshold))[0]
+        if len(idx) == 0:
+            idx = np.arange(T)
+            count += T
+            countNotReplaced += T
+        else:
+            count += T - len(idx)
+        tiled = np.tile(idx, math.ceil(k / len(idx)))
+        sel[i] = tiled[np.argsort(cnt[tiled])][:k]
+    out = imgSet[np.arange(P)[:, None], sel]
+    return np.ma.masked_array(np.ma.getdata(out), mask=np.ma.getmaskarray(out)), count, countNotReplaced
+
+
+def pickClearPatchesLR(patchesLR, k, clarityThreshold):
+    counts = _mask_counts(patchesLR)
+    sets = [removeAndReplaceDirtyFrames(s, k, clarityThreshold, c)[0] for s, c in zip(patchesLR, counts)]
+    return np.ma.concatenate([np.expand_dims(s, 0) for s in sets])
+
+
+def isPatchSetNotCorrupted(patchSet, clarityThreshold):
+    return np.sum(np.array([np.count_nonzero(p.mask) / (p.shape[-1] * p.shape[-2]) < (1 - clarityThreshold) for p in patchSet])) != 0
+
+
+def removeCorruptedTrainPatchSets(patchesLR, patchesHR, clarityThreshold):
+    booleanMask = np.array([isPatchSetNotCorrupted(s, clarityThreshold) for s in patchesHR])
+    return patchesLR[booleanMask], patchesHR[booleanMask]
+
+
+def pickClearPatches(patchesLR, patchesHR, clarityThreshold):
+    _, _, T, C, HLR, WLR = patchesLR.shape
+    reshapeLR = patchesLR.reshape((-1, T, C, HLR, WLR))
+    _, _, THR, C, HHR, WHR = patchesHR.shape
+    reshapeHR = patchesHR.reshape((-1, THR, C, HHR, WHR))
+    booleanMask = _mask_counts(reshapeHR)[:, 0] / (HHR * WHR) < (1 - clarityThreshold)
+    return reshapeLR[booleanMask], reshapeHR[booleanMask]
+
+
+# ---- checkpoint 5 (utils/dataGenerator.py:276-323) --------------------------------------------------------------------------------
+def splitPatches(patchesLR, patchesHR, config):
+    """sklearn train_test_split(LR, LR.mask, HR, HR.mask, test_size=split, random_state=17), restated: ShuffleSplit draws
+    RandomState(17).permutation(n); the first ceil(split * n) are the test part, the rest (in permutation order) the train part."""
+    n = len(patchesLR)
+    perm = np.random.RandomState(17).permutation(n)
+    n_test = math.ceil(config['split'] * n)
+    test, train = perm[:n_test], perm[n_test:]
+    return patchesLR[train], patchesLR[test], patchesHR[train], patchesHR[test]
+
+
+def augmentByShufflingLRImgs(patchLR, numPermute=9, rng=None):
+    rng = np.random if rng is None else rng
+    if numPermute == 0:
+        return patchLR
+    numLRImg = patchLR.shape[3]
+    cacheLR = [patchLR]
+    for _ in range(numPermute):
+        cacheLR.append(patchLR[:, :, :, rng.permutation(np.arange(numLRImg)), :])
+    return np.ma.concatenate(cacheLR)
+
+
+def augmentByFlipping(patches):
+    return np.ma.concatenate((patches, np.flip(patches, axis=1), np.flip(patches, axis=2), np.flip(patches, axis=(1, 2))))
+
+
+def augmentByRotating(patches):
+    return np.ma.concatenate((patches, np.rot90(patches, k=1, axes=(1, 2)), np.rot90(patches, k=2, axes=(1, 2)),
+                              np.rot90(patches, k=3, axes=(1, 2))))
+
+
+# ---- driver (utils/dataGenerator.py:33-273) ---------------------------------------------------------------------------------------
+def main(config, band, rng=None):
+    log = logging.getLogger("dataGenerator")
+    if band not in ('NIR', 'RED'):
+        raise ValueError("band must be NIR or RED, got %r" % band)
+    rawDataDir, cleanDataDir = config['raw_data'], config['preprocessing_out']
+    d = {k: os.path.join(cleanDataDir, k) for k in ('arrayDir', 'trimmedArrayDir', 'patchesDir', 'trimmedPatchesDir', 'resolverDir',
+                                                     'augmentedPatchesDir')}
+    for p in d.values():
+        os.makedirs(p, exist_ok=True)
+    path = lambda k, n: os.path.join(d[k], f'{n}_{band}.npy')
+    load = lambda k, n: np.load(path(k, n), allow_pickle=True)
+    ckpt = config['ckpt']
+
+    if 1 in ckpt:
+        log.info('Loading and dumping raw data...')
+        for b in ('NIR', 'RED'):
+            for isTrain in (True, False):
+                loadAndSaveRawData(rawDataDir, d['arrayDir'], b, isGrayScale=True, isTrainData=isTrain)
+
+    if 2 in ckpt:
+        TRAIN, TEST = loadData(d['arrayDir'], band)
+        allImgLR, allMskLR, allImgHR, allMskHR = TRAIN
+        allImgMskLR = registerImages(allImgLR, allMskLR)
+        allImgMskHR = convertToMaskedArray(allImgHR, allMskHR)
+        allImgMskHR.dump(path('resolverDir', 'TRAINimgHR'))
+        trmImgMskLR, trmImgMskHR, imgSetRemoved = removeCorruptedTrainImageSets(allImgMskLR, allImgMskHR, config['low_res_threshold'])
+        start = 0 if band == 'RED' else 594
+        np.savetxt(f'removedTrainSets{band}.txt', imgSetRemoved + start)
+        if len(imgSetRemoved):
+            print(f'[ WARNING ] Imgsets {imgSetRemoved} were removed')
+        trmImgMskLR = pickClearLRImgsPerImgSet(trmImgMskLR, config['num_low_res_imgs_pre'], config['low_res_threshold'], rng)
+        allImgLRTest, allMskLRTest = TEST
+        allImgMskLRTest = registerImages(allImgLRTest, allMskLRTest)
+        trmImgMskLRTest = removeCorruptedTestImageSets(allImgMskLRTest, config['low_res_threshold'])
+        trmImgMskLRTest = pickClearLRImgsPerImgSet(trmImgMskLRTest, config['num_low_res_imgs_pre'], config['low_res_threshold'], rng)
+        trmImgMskLR.dump(path('trimmedArrayDir', 'TRAINimgLR'))
+        trmImgMskHR.dump(path('trimmedArrayDir', 'TRAINimgHR'))
+        trmImgMskLRTest.dump(path('trimmedArrayDir', 'TESTimgLR'))
+
+    if 3 in ckpt:
+        pad = config['max_shift'] // 2 if config['max_shift'] > 0 else 0
+        k = config['patch_size'] + config['max_shift']
+        test = load('trimmedArrayDir', 'TESTimgLR')
+        _patches(test, k, config['patch_size'], pad)[0].dump(path('patchesDir', 'TESTpatchesLR'), protocol=4)
+        train = load('trimmedArrayDir', 'TRAINimgLR')
+        H = train.shape[3]
+        _patches(train, k, config['patch_stride'], pad)[0].dump(path('patchesDir', 'TRAINpatchesLR'), protocol=4)
+        hr = load('trimmedArrayDir', 'TRAINimgHR')
+        khr = config['patch_size'] * (hr.shape[3] // H)
+        _patches(hr, khr, khr, 0)[0].dump(path('patchesDir', 'TRAINpatchesHR'), protocol=4)
+
+    if 4 in ckpt:
+        test, train = load('patchesDir', 'TESTpatchesLR'), load('patchesDir', 'TRAINpatchesLR')
+        for thr in config['low_res_patch_thresholds']:
+            test = pickClearPatchesLR(test, k=config['num_low_res_imgs'], clarityThreshold=thr)
+        for thr in config['low_res_patch_thresholds']:
+            train = pickClearPatchesLR(train, k=config['num_low_res_imgs'], clarityThreshold=thr)
+        test.dump(path('resolverDir', 'TESTpatchesLR'), protocol=4)
+        train.dump(path('resolverDir', 'TRAINpatchesLR'), protocol=4)
+        hr = load('patchesDir', 'TRAINpatchesHR')
+        train, hr = removeCorruptedTrainPatchSets(train, hr, config['high_res_threshold'])
+        train, hr = pickClearPatches(train, hr, config['high_res_threshold'])
+        train = train.transpose((0, 3, 4, 1, 2))
+        hr = hr.transpose((0, 3, 4, 1, 2)).squeeze(4)
+        test.dump(path('trimmedPatchesDir', 'TESTpatchesLR'), protocol=4)
+        train.dump(path('trimmedPatchesDir', 'TRAINpatchesLR'), protocol=4)
+        hr.dump(path('trimmedPatchesDir', 'TRAINpatchesHR'), protocol=4)
+
+    if 5 in ckpt:
+        lr, hr = load('trimmedPatchesDir', 'TRAINpatchesLR'), load('trimmedPatchesDir', 'TRAINpatchesHR')
+        lr, lrVal, hr, hrVal = splitPatches(lr, hr, config)
+        lrVal.dump(path('augmentedPatchesDir', 'TRAINVALpatchesLR'), protocol=4)
+        hrVal.dump(path('augmentedPatchesDir', 'TRAINVALpatchesHR'), protocol=4)
+        lr = augmentByShufflingLRImgs(lr, numPermute=config['num_low_res_permute'], rng=rng)
+        if config['to_flip']:
+            lr = augmentByFlipping(lr)
+        if config['to_rotate']:
+            lr = augmentByRotating(lr)
+        lr.dump(path('augmentedPatchesDir', 'TRAINpatchesLR'), protocol=4)
+        hr = np.tile(hr, (config['num_low_res_permute'] + 1, 1, 1, 1))
+        if config['to_flip']:
+            hr = augmentByFlipping(hr)
+        if config['to_rotate']:
+            hr = augmentByRotating(hr)
+        hr.dump(path('augmentedPatchesDir', 'TRAINpatchesHR'), protocol=4)

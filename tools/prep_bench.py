@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Dataset builder timing on a synthetic corpus of ESA size (1160 train + 290 test sets, 9-35 frames of 128 x 128, textures rolled by
+small shifts plus noise): one JSON line with
+  stage2_device_ms / us_per_frame   the count + registration kernels (device events around probav_prep_count_nonzero + probav_prep_register)
+  stage34_wall_s                    patch unfold (device) + pickClearPatchesLR / pickClearPatches bookkeeping of the train LR / HR patches
+  png_decode_ms_per_frame           pngio.imread of 16-bit 128 x 128 frames (reported separately: disk + zlib, not the GPU)
+  numpy_register_est_s              the numpy fp64-FFT restatement of the reference's registration, timed on 50 sets and EXTRAPOLATED
+    python tools/prep_bench.py [--sets-train 1160 --sets-test 290]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def corpus(n_sets, rng):
+    N = 128
+    k = np.fft.fftfreq(N)
+    filt = 1.0 / (1e-3 + np.hypot(k[:, None], k[None, :]) ** 1.5)
+    sizes = rng.integers(9, 36, n_sets)
+    frames, masks = [], []
+    for n in sizes:
+        t = np.fft.ifft2(np.fft.fft2(rng.standard_normal((N, N))) * filt).real
+        t = 1000 + 20000 * (t - t.min()) / (t.max() - t.min())
+        for _ in range(n):
+            s = tuple(int(v) for v in rng.integers(-3, 4, 2))
+            frames.append(np.clip(np.roll(t, s, axis=(0, 1)) + rng.normal(0, 30, (N, N)), 0, 65535).astype(np.uint16))
+            masks.append(rng.random((N, N)) < 0.9)
+    return np.stack(frames), np.stack(masks), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets-train", type=int, default=1160)
+    ap.add_argument("--sets-test", type=int, default=290)
+    opt = ap.parse_args()
+    import torch
+    from probav_amd import pngio, prep
+    rng = np.random.default_rng(0)
+    F, M, off = corpus(opt.sets_train + opt.sets_test, rng)
+    n_frames = len(F)
+    prep.device_register(F[:off[2]], M[:off[2]], off[:3], off[:2])          # warm-up (code objects, attributes)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    counts = prep.device_count_nonzero(M, 128 * 128)
+    order = np.concatenate([off[i] + np.argsort(-counts[off[i]:off[i + 1]].astype(np.int64)) for i in range(len(off) - 1)])
+    prep.device_register(F[order], M[order], off, off[:-1])
+    e1.record()
+    torch.cuda.synchronize()
+    wall2 = time.perf_counter() - t0
+    # device-only time of the registration launches (no host copies): the inputs already resident
+    import ctypes
+    from probav_amd import _lib
+    dev = torch.device("cuda")
+    fr, mk = torch.from_numpy(F).to(dev), torch.from_numpy(M.view(np.uint8)).to(dev)
+    od, rf = torch.from_numpy(off).to(dev), torch.from_numpy(off[:-1].astype(np.int32)).to(dev)
+    spec = torch.empty((len(off) - 1) * 128 * 128 * 2, dtype=torch.float32, device=dev)
+    sh, of_, om, oc = (torch.empty(n_frames, 2, dtype=torch.int32, device=dev), torch.empty_like(fr), torch.empty_like(mk),
+                       torch.empty(n_frames, dtype=torch.int32, device=dev))
+    cnt = torch.empty(n_frames, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    torch.cuda.synchronize()
+    e0.record()
+    _lib.check(L.probav_prep_count_nonzero(_lib.ptr(mk), n_frames, 128 * 128, _lib.ptr(cnt), _lib.current_stream()))
+    _lib.check(L.probav_prep_register(_lib.ptr(fr), _lib.ptr(mk), _lib.ptr(od), len(off) - 1, n_frames, _lib.ptr(rf), _lib.ptr(spec),
+                                      _lib.ptr(sh), _lib.ptr(of_), _lib.ptr(om), _lib.ptr(oc), _lib.current_stream()))
+    e1.record()
+    torch.cuda.synchronize()
+    dev_ms = e0.elapsed_time(e1)
+    del fr, mk, spec, of_, om
+    # stages 3-4 on the train part: 9 frames per set
+    S = opt.sets_train
+    sel = np.stack([off[i] + np.arange(9) for i in range(S)])
+    lr = np.ma.masked_array(F[sel].astype(np.float64)[:, :, None], mask=~M[sel][:, :, None])
+    hr = np.ma.masked_array(np.kron(F[off[:S]], np.ones((3, 3), np.uint16))[:, None, None],
+                            mask=np.zeros((S, 1, 1, 384, 384), bool))
+    t0 = time.perf_counter()
+    pl, _ = prep._patches(lr, 22, 16, 3)
+    ph, _ = prep._patches(hr, 48, 48, 0)
+    pl = prep.pickClearPatchesLR(pl, 9, 0.85)
+    pl, ph = prep.pickClearPatches(*prep.removeCorruptedTrainPatchSets(pl, ph, 0.85), 0.85)
+    wall34 = time.perf_counter() - t0
+    # PNG decode
+    with tempfile.TemporaryDirectory() as d:
+        paths = []
+        for i in range(200):
+            p = os.path.join(d, "LR%03d.png" % i)
+            pngio.imsave_uint16(p, F[i])
+            paths.append(p)
+        t0 = time.perf_counter()
+        for p in paths:
+            pngio.imread(p)
+        png_ms = (time.perf_counter() - t0) * 1e3 / len(paths)
+    # numpy fp64 FFT restatement of the reference's registration (register_translation + fourier_shift), 50 sets, extrapolated
+    t0 = time.perf_counter()
+    nf = 0
+    for s in range(50):
+        ref = F[off[s]].astype(np.float64)
+        R = np.fft.fft2(ref)
+        for f in range(off[s] + 1, off[s + 1]):
+            img = F[f].astype(np.float64)
+            I = np.fft.fft2(img)
+            cc = np.fft.ifft2(R * np.conj(I))
+            y, x = np.unravel_index(np.argmax(np.abs(cc)), cc.shape)
+            np.fft.ifft2(I * np.exp(-2j * np.pi * (np.fft.fftfreq(128)[:, None] * y + np.fft.fftfreq(128)[None, :] * x))).real
+            np.fft.ifft2(np.fft.fft2(M[f].astype(np.float64)))
+            nf += 1
+    np_s = (time.perf_counter() - t0) * (n_frames / max(1, nf + 50))
+    print(json.dumps({"frames": int(n_frames), "sets": int(len(off) - 1), "stage2_device_ms": round(dev_ms, 2),
+                      "us_per_frame": round(dev_ms * 1e3 / n_frames, 3), "stage2_wall_s_with_copies": round(wall2, 3),
+                      "stage34_wall_s": round(wall34, 3), "png_decode_ms_per_frame": round(png_ms, 3),
+                      "numpy_register_est_s": round(np_s, 1), "numpy_register_est_note": "extrapolated from 50 sets"}))
+
+
+if __name__ == "__main__":
+    main()

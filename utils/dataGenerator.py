@@ -1,0 +1,34 @@
+"""Dataset builder CLI at the reference's path (utils/dataGenerator.py): raw ESA PROBA-V image sets -> the numpy.ma dumps that
+train.py and test.py read.  Runs on the GPU (probav_amd.prep); the same cfg keys, `ckpt=` stage selection and output layout as the
+reference.  --seed N seeds the frame picking and LR shuffling (equal to the reference after np.random.seed(N)); without it the run is
+unseeded, as the reference's is.
+
+    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0]
+"""
+import argparse
+import logging
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from probav_amd import prep  # noqa: E402
+from probav_amd.parseConfig import parseConfig  # noqa: E402
+
+
+def parser(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument('--cfg', default='cfg/FINALv2.cfg', type=str)
+    p.add_argument('--band', default='NIR', type=str, choices=['NIR', 'RED'])
+    p.add_argument('--seed', default=None, type=int)
+    return p.parse_args(argv)
+
+
+if __name__ == '__main__':
+    logging.basicConfig(format='%(asctime)s - %(message)s', level=logging.INFO)
+    opt = parser()
+    logging.info(f'[ CFG - INFO ] Using {opt.cfg} as config file...')
+    rng = None if opt.seed is None else np.random.RandomState(opt.seed)
+    prep.main(parseConfig(opt.cfg), opt.band, rng)
