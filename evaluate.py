@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Score super-resolved train images by the ESA PROBA-V measure (the reference's evaluate.py:17-87, which was left unfinished).
+
+    python evaluate.py --cfg C --toCompare DIR [--benchmark DIR] [--band NIR|RED|both] [--norm PATH] [--formula esa|reference] [--out DIR]
+    python evaluate.py --cfg C --band NIR --model          # the cfg's latest checkpoint on the TRAIN sets, no PNGs written
+
+--toCompare scores the imgsetNNNN.png of a folder (test.py's output) against resolverDir/TRAINimgHR_<band>.npy, matching by id: train ids
+below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted, skipped).  --model resolves resolverDir/TRAINpatchesLR_<band>.npy
+with the latest checkpoint exactly as `test.py --totest TRAIN` does (same ids, removedTrainSets<BAND>.txt skipped, the same uint16 cast) and
+scores the images on the device.  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
+Losses.shiftCompensatedcPSNR instead (HR unmasked, what the reference's script computes).  The score is mean(N_i / cPSNR_i) with N_i from
+norm.csv (default <raw_data>/norm.csv when present; lower is better).
+
+Prints one JSON line; writes <out>/scores.csv and, when matplotlib imports and there is a --benchmark, <out>/comparison.png.
+"""
+import argparse
+import contextlib
+import logging
+import os
+import sys
+
+import numpy as np
+
+from probav_amd import scoring
+
+logging.basicConfig(format="%(asctime)s - %(message)s", level=logging.INFO, stream=sys.stderr)
+logger = logging.getLogger("probav_amd")
+
+BAND_STATS = {"NIR": (8075.2045, 3160.7272), "RED": (5266.2245, 3431.8614)}      # test.py
+
+
+def parser(argv=None):
+    p = argparse.ArgumentParser(description="Score super-resolved PROBA-V train images by the ESA cPSNR")
+    p.add_argument("--cfg", type=str, default="cfg/p16t12c85r12pre19.cfg")
+    p.add_argument("--toCompare", type=str, default=None, help="folder of imgsetNNNN.png to score")
+    p.add_argument("--benchmark", type=str, default=None, help="folder of imgsetNNNN.png to compare against")
+    p.add_argument("--band", type=str, default="both", help="NIR, RED or both")
+    p.add_argument("--norm", type=str, default=None, help="norm.csv (default: <raw_data>/norm.csv if present)")
+    p.add_argument("--formula", type=str, default="esa", choices=("esa", "reference"))
+    p.add_argument("--model", action="store_true", help="score the cfg's latest checkpoint on resolverDir/TRAINpatchesLR_<band>.npy")
+    p.add_argument("--out", type=str, default=".", help="folder for scores.csv and comparison.png")
+    p.add_argument("--border", type=int, default=3, help=argparse.SUPPRESS)
+    opt = p.parse_args(argv)
+    opt.band = opt.band.upper()
+    if opt.band not in ("NIR", "RED", "BOTH"):
+        p.error("--band must be NIR, RED or both, got %r" % opt.band)
+    if opt.model == (opt.toCompare is not None):
+        p.error("give exactly one of --toCompare DIR and --model")
+    for name in ("toCompare", "benchmark"):
+        d = getattr(opt, name)
+        if d is not None and not os.path.isdir(d):
+            p.error("--%s: no such folder %r" % (name, d))
+    if opt.norm is not None and not os.path.isfile(opt.norm):
+        p.error("--norm: no such file %r" % opt.norm)
+    if not os.path.isfile(opt.cfg):
+        p.error("--cfg: no such file %r" % opt.cfg)
+    if not 0 <= opt.border <= 3:
+        p.error("--border must be in 0..3")
+    return opt
+
+
+def model_images(config, cfg_path, band):
+    """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN, without the PNGs."""
+    import torch
+    from probav_amd.modelsTF import WDSRConv3D
+    from probav_amd.testClass import evaluate_device
+    from probav_amd.trainClass import ModelTrainer
+    dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
+    patchLR = np.load(os.path.join(dataDir, "TRAINpatchesLR_%s.npy" % band), allow_pickle=True)
+    patchLR = np.array(patchLR).transpose((0, 1, 4, 5, 2, 3))
+    mean, std = BAND_STATS[band]
+    k = config["kernel_size"]
+    model = WDSRConv3D(name="superResolutionNet", band=band, mean=mean, std=std, maxShift=config["max_shift"]).build(
+        scale=config["scale"], numFilters=config["num_filters"], kernelSize=(k, k, k), numResBlocks=config["num_res_blocks"],
+        expRate=config["exp_rate"], decayRate=config["decay_rate"], numImgLR=config["num_low_res_imgs"],
+        patchSizeLR=config["patch_size"], isGrayScale=config["is_grayscale"]).to("cuda")
+    basename = os.path.basename(cfg_path).split(".")[0]
+    ckptDir = os.path.join(config["model_out"], "ckpt_%s" % basename, band)
+    with contextlib.redirect_stdout(sys.stderr):            # the restore messages: stdout carries the JSON line only
+        trainer = ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, band))
+    if trainer.latest_checkpoint is None and trainer._tf_latest() is None:
+        raise SystemExit("evaluate.py --model: no checkpoint under %s" % ckptDir)
+    y_preds = evaluate_device(model, patchLR)
+    del model, trainer
+    torch.cuda.empty_cache()
+    toOmit = scoring.read_removed(band)
+    out, i = {}, scoring.FIRST_TRAIN_ID[band]
+    for img in y_preds:
+        while i in toOmit:
+            i += 1
+        out[i] = img[:, :, 0].astype(np.uint16)            # test.py's cast, a pixel clipped to 65536 included
+        i += 1
+    return out
+
+
+def main(opt):
+    from probav_amd.parseConfig import parseConfig
+    config = parseConfig(opt.cfg)
+    bands = scoring.BANDS if opt.band == "BOTH" else (opt.band,)
+    norm_path = opt.norm
+    if norm_path is None:
+        cand = os.path.join(config.get("raw_data", ""), "norm.csv")
+        norm_path = cand if config.get("raw_data") and os.path.isfile(cand) else None
+    norm = scoring.read_norm(norm_path) if norm_path else None
+    hr = {b: scoring.load_hr(config, b) for b in bands}
+    removed = {b: scoring.read_removed(b) for b in bands}
+    if opt.model:
+        images = {}
+        for b in bands:
+            images.update(model_images(config, opt.cfg, b))
+    else:
+        images = scoring.load_sr_dir(opt.toCompare)
+    rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
+    bench_rows = None
+    if opt.benchmark is not None:
+        bench_rows, _ = scoring.score_images(scoring.load_sr_dir(opt.benchmark), hr, border=opt.border, formula=opt.formula, removed=removed)
+    summary = scoring.summarize(rows, counts, norm=norm, bench_rows=bench_rows)
+    summary["formula"] = opt.formula
+    summary["norm"] = norm_path
+    os.makedirs(opt.out, exist_ok=True)
+    scoring.write_csv(os.path.join(opt.out, "scores.csv"), rows, norm=norm, bench_rows=bench_rows)
+    if bench_rows is not None:
+        if scoring.plot_comparison(os.path.join(opt.out, "comparison.png"), rows, bench_rows):
+            summary["comparison_png"] = os.path.join(opt.out, "comparison.png")
+        else:
+            logger.info("matplotlib does not import: comparison.png not written")
+    print(scoring.json_line(summary), flush=True)
+    return summary
+
+
+if __name__ == "__main__":
+    main(parser())

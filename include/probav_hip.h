@@ -271,6 +271,24 @@ int probav_prep_xcorr_surface(const uint16_t* pair, float* spec_scratch, float* 
 int probav_prep_patches(const float* frames, const uint8_t* masks, int S, int T, int H, int W, int pad, int win, int stride, float* patches,
                         uint8_t* patch_masks, int32_t* counts, void* stream);
 
+/* ---- scoring (evaluate.py; proba-v_amd/scoring.py), additions of ABI 7 ------------------------------------------------------------- */
+/* The ESA PROBA-V shift-compensated clear PSNR of whole images; it replaces the reference's unfinished evaluate.py:76-87, which calls
+ * Losses.shiftCompensatedcPSNR (models/loss.py:37-53) and so leaves HR unmasked.  Per image, SR and HR uint16 [S][S], mask uint8 [S][S]
+ * (nonzero = clear pixel of HR), border b, L = S - 2b, P = SR[b:b+L, b:b+L]; for every shift (u, v) in [0, 2b]^2, row-major (k = u (2b+1) + v):
+ *     d = HR[u:u+L, v:v+L] - P,  m = mask[u:u+L, v:v+L],  n = sum m,  s1 = sum m d,  s2 = sum m d^2          (exact integers)
+ *     cMSE = (n s2 - s1^2) / n^2,  cPSNR = 10 log10(65535^2 / min cMSE), the first (u, v) attaining the minimum wins.
+ * Kernels, exactness and cost model: csrc/kernels_score.hip.
+ * moments [n_images][(2b+1)^2][3] int64 = (n, s1, s2) of every shift, exact.  Arrays are [n_images][S][S], contiguous.
+ * 1 <= n_images <= 65535, 0 <= b <= 3, 2b < S <= 2048.                    evaluate.py:76-87, models/loss.py:37-53 (with HR masked) */
+int probav_score_moments(const uint16_t* sr, const uint16_t* hr, const uint8_t* mask, int64_t n_images, int S, int border,
+                         int64_t* moments, void* stream);
+/* From the moments: per image cpsnr (fp64; +inf when min cMSE = 0), shift [2] = (u, v) of the first exact minimum of cMSE (n = 0 shifts
+ * skipped), bias = s1 / n of that shift (mean of HR - SR over its clear pixels), n_clear = its n.  An image with n = 0 at every shift
+ * gets cpsnr = bias = NaN, shift = (-1, -1), n_clear = 0.  n s2 - s1^2 is formed in 128-bit integers and shifts are compared exactly
+ * (num_a n_b^2 < num_b n_a^2); only the winner's cMSE is rounded to fp64.                              evaluate.py:76-87, models/loss.py:37-53 */
+int probav_score_select(const int64_t* moments, int64_t n_images, int border, double* cpsnr, int32_t* shift, double* bias,
+                        int64_t* n_clear, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,9 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::optimizer_wn_step(theta, grad, m, v, wcache, engine, lr, ...) -> ()                 the same update fused with the weight normalisation
                                                                             and operand packing of the NEXT step (wdsr_forward's optional `wcache`)
   probav::clip_round(x, lo, hi) -> y                                        tf.clip_by_value + tf.round   test.py:118-119
+  probav::esa_shift_moments(sr, hr, mask, border) -> moments int64 [N, (2b+1)^2, 3]       (n, s1, s2) of every shift, exact
+  probav::esa_shift_cpsnr(sr, hr, mask, border) -> (cpsnr f64[N], shift i32[N,2], bias f64[N], n_clear i64[N])
+                                                                            the ESA cPSNR of whole images   evaluate.py:76-87 (scoring.py)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -306,6 +309,60 @@ def clip_round(x: Tensor, lo: float, hi: float) -> Tensor:
 @clip_round.register_fake
 def _(x, lo, hi):
     return torch.empty_like(x)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# scoring: the ESA shift-compensated clear PSNR of whole images (csrc/kernels_score.hip; the metric is stated in scoring.py).  No
+# autograd: a score, not a loss.  sr / hr: [N, S, S] uint16 (int16 is taken as the same bits); mask: [N, S, S] bool or uint8, nonzero = clear.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _score_args(sr, hr, mask, border):
+    for t, name in ((sr, "sr"), (hr, "hr"), (mask, "mask")):
+        _dev(t, name)
+    if sr.dim() != 3 or sr.shape[1] != sr.shape[2] or hr.shape != sr.shape or mask.shape != sr.shape:
+        raise ValueError("esa_shift_cpsnr: sr, hr, mask must all be [N, S, S]; got %s %s %s" % (tuple(sr.shape), tuple(hr.shape), tuple(mask.shape)))
+    if sr.dtype not in (torch.uint16, torch.int16) or hr.dtype not in (torch.uint16, torch.int16) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("esa_shift_cpsnr: sr / hr must be uint16 (or int16 bits), mask bool or uint8; got %s %s %s" % (sr.dtype, hr.dtype, mask.dtype))
+    if not 0 <= border <= 3:
+        raise ValueError("esa_shift_cpsnr: border must be in 0..3, got %d" % border)
+    return sr.contiguous(), hr.contiguous(), mask.contiguous().view(torch.uint8)
+
+
+@torch.library.custom_op("probav::esa_shift_moments", mutates_args=(), device_types="cuda")
+def esa_shift_moments(sr: Tensor, hr: Tensor, mask: Tensor, border: int) -> Tensor:
+    sr, hr, mask = _score_args(sr, hr, mask, border)
+    ns = 2 * border + 1
+    mom = torch.empty((sr.shape[0], ns * ns, 3), dtype=torch.int64, device=sr.device)
+    if sr.shape[0]:
+        _lib.check(_lib.lib().probav_score_moments(_lib.ptr(sr), _lib.ptr(hr), _lib.ptr(mask), sr.shape[0], sr.shape[1], border, _lib.ptr(mom),
+                                                   _lib.current_stream()), "probav_score_moments")
+    return mom
+
+
+@esa_shift_moments.register_fake
+def _(sr, hr, mask, border):
+    ns = 2 * border + 1
+    return sr.new_empty((sr.shape[0], ns * ns, 3), dtype=torch.int64)
+
+
+@torch.library.custom_op("probav::esa_shift_cpsnr", mutates_args=(), device_types="cuda")
+def esa_shift_cpsnr(sr: Tensor, hr: Tensor, mask: Tensor, border: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    N, dev = sr.shape[0], sr.device
+    mom = esa_shift_moments(sr, hr, mask, border)
+    cpsnr = torch.empty(N, dtype=torch.float64, device=dev)
+    shift = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    bias = torch.empty(N, dtype=torch.float64, device=dev)
+    n_clear = torch.empty(N, dtype=torch.int64, device=dev)
+    if N:
+        _lib.check(_lib.lib().probav_score_select(_lib.ptr(mom), N, border, _lib.ptr(cpsnr), _lib.ptr(shift), _lib.ptr(bias), _lib.ptr(n_clear),
+                                                  _lib.current_stream()), "probav_score_select")
+    return cpsnr, shift, bias, n_clear
+
+
+@esa_shift_cpsnr.register_fake
+def _(sr, hr, mask, border):
+    N = sr.shape[0]
+    return (sr.new_empty((N,), dtype=torch.float64), sr.new_empty((N, 2), dtype=torch.int32), sr.new_empty((N,), dtype=torch.float64),
+            sr.new_empty((N,), dtype=torch.int64))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
