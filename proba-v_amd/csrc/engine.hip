@@ -6,6 +6,7 @@
 #include "../../include/probav_hip.h"
 #include <stdio.h>
 #include <string.h>
+#include <array>
 #include <string>
 #include <vector>
 
@@ -14,20 +15,41 @@ using namespace probav;
 #include "kernels_mfma.h"
 #include "kernels_x6.h"
 
+// MFMA operand fragments: offsets into the workspace's wpack region (-1 = none)
+struct ConvFrags { long f32 = -1, x6 = -1, h3 = -1, h3t = -1; };   // one direction of a 3x3x3 layer; h3t: per-tap H3 fragments of a 25-channel layer
+struct PwFrags { long w1 = -1, w2 = -1, w2b = -1, w1c = -1; };     // one arithmetic of a block's fused pointwise pair: W1, W2 (forward), W2, W1 (backward's operands)
+
 struct LayerRec {
     char name[32];
     WnLayer wn;
     int kh, kw, kt;
+    ConvFrags pk[2];          // forward, backward-data
 };
+
+// what a kernel family (probav_engine_set_impl) may use: 0 direct kernels, 1 MFMA row-tile kernels, 2 MFMA + strip convolution where it
+// applies, 3 = 2 with the x6 kernels (fp32 products as six bf16-piece MFMA products) where they exist, 4 = 3 with the H3 arithmetic (three
+// products of scaled fp16 piece pairs) where it exists
+struct Family {
+    bool mfma;                // MFMA kernels, and the dedicated small kernels (upscale layer, one-channel input, fused residual path, tuned direct backward-filter)
+    bool strip;               // MFMA strip convolution
+    bool x6;                  // split-operand kernels
+    int arith;                // their arithmetic: 0 none, 1 X6, 2 H3
+    bool pw_fused;            // the fused pointwise pair (expConv + ReLU + decConv in one launch each way)
+};
+static Family make_family(int impl, bool pw_mfma)
+{
+    Family f;
+    f.mfma = impl >= 1; f.strip = impl >= 2; f.x6 = impl >= 3; f.arith = impl >= 4 ? 2 : (impl >= 3 ? 1 : 0);
+    f.pw_fused = f.mfma && pw_mfma;
+    return f;
+}
 
 struct probav_engine {
     probav_net_cfg cfg;
     std::vector<LayerRec> layers;
     int64_t nparams = 0, weff_count = 0, cout_total = 0, cin_total = 0;
     WnLayer* d_layers = nullptr;
-    int impl = 4;             // 0 direct kernels, 1 MFMA row-tile kernels, 2 MFMA + strip convolution where it applies,
-                              // 3 = 2 with the x6 kernels (fp32 products as six bf16-piece MFMA products) where they exist,
-                              // 4 = 3 with the H3 arithmetic (three products of scaled fp16 piece pairs) where it exists
+    Family fam = {};
     int iMain = -1, iResid1 = -1, iResid2 = -1, iResid3 = -1, iUp = -1;
     std::vector<int> iExp, iDec, iNorm, iRed;
     ReduceSide side = {};                           // side stream of the slab sums (probav_common.h), created on first use
@@ -36,20 +58,12 @@ struct probav_engine {
     struct RedSpec { int k, p, pt, refl, refl_t; };   // one valid convReducer: kernel size, H/W pad, depth pad, mirrored H/W pad, mirrored depth pad
     std::vector<RedSpec> redSpec;
     int Hin = 0;
-    // MFMA operand fragments: one packing job per (layer, use); offsets into the workspace's wpack region
+    // MFMA operand fragments: one packing job per (layer or block, use, arithmetic); their offsets live in LayerRec::pk and pkBlk
     std::vector<PackJob> jobs;
     PackJob* d_jobs = nullptr;
     int64_t wpack_count = 0;
-    std::vector<long> pkFwd, pkBwd;          // per layer: conv fragments for forward / backward-data (-1 = none)
-    std::vector<long> pkFwd6, pkBwd6;        // per layer: x6 (pre-split bf16) conv fragments, impl 3
-    std::vector<long> pkFwdH, pkBwdH;        // per layer: H3 (scaled fp16 pieces) conv fragments, impl 4
-    std::vector<long> pkFwdHt, pkBwdHt;      // per layer, 25 input channels only: the per-tap (not K-concatenated) H3 fragments of the piece-ring strip kernel
-    std::vector<long> pkW1h, pkW2h, pkW2Kh, pkW1Ch;   // per block: H3 fragments of the fused expand/decay forward / backward
-    std::vector<long> pkW1x6, pkW2x6;        // per block: x6 fragments of the fused expand/decay forward
-    std::vector<long> pkW2Kx6, pkW1Cx6;      // per block: extra x6 fragments of the fused backward
-    std::vector<long> pkW1, pkW2;            // per block: fused expand/decay forward fragments
-    std::vector<long> pkW2B, pkW1C;          // per block: extra fragments of the fused backward
-    bool pw_mfma = false;
+    std::vector<std::array<PwFrags, 3>> pkBlk;   // per residual block, per arithmetic (fp32, X6, H3)
+    bool pw_mfma = false;     // the block geometry has a fused pointwise pair
     bool fwd_amax = false;    // the last training forward filled the amax slots of the saved activations (H3 kernels, impl 4)
     bool fwd_unfused = false; // ... and laid its workspace out for the unfused pointwise pair (impl 0): the backward pass must agree
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg)
@@ -90,8 +104,7 @@ static double geom_macs(const ConvGeom& g)
 
 static int add_layer(probav_engine* e, const std::string& name, int kh, int kw, int kt, int cin, int cout)
 {
-    LayerRec r;
-    memset(&r, 0, sizeof(r));
+    LayerRec r = {};
     snprintf(r.name, sizeof(r.name), "%s", name.c_str());
     r.kh = kh; r.kw = kw; r.kt = kt;
     r.wn.taps = kh * kw * kt; r.wn.Cin = cin; r.wn.Cout = cout; r.wn.K = r.wn.taps * cin;
@@ -121,7 +134,8 @@ struct Plan {
     size_t bamax, dweff2, Hb, dH, gA, gB, gDec, dtail, dr2, dr1, partial;
     size_t fwd_total, bwd_total, total;       // floats: the saved state of a forward pass | the reverse pass's scratch | both
     std::vector<size_t> gblk, gred;
-    std::vector<size_t> part_off;      // slab region of the k-th backward-filter launch of a backward pass (relative to `partial`), in launch order
+    struct Region { size_t off, floats; };
+    std::vector<Region> parts;          // slab region of the k-th backward-filter launch of a backward pass (offset relative to `partial`, size), in launch order
 };
 
 static ConvGeom make_geom(int N, int Hi, int Ti, int Cin, int Ho, int To, int Cout, int kh, int kw, int kt,
@@ -169,20 +183,32 @@ static void reducer_extents(const probav_engine* e, std::vector<int>& hh, std::v
     }
 }
 
-// slab floats of the backward-filter launch conv_wgrad() makes for geometry g under the engine's kernel family (the same decisions)
 // the low-frequency residual path runs as one launch each way (kernels_direct.hip: resid_path_*) in every family but 0, which stays on the generic direct kernels
 static bool resid_path_fused(const probav_engine* e)
 {
-    return e->impl >= 1 && resid_path_supported(e->Hin, e->cfg.in_channels, e->cfg.scale * e->cfg.scale);
+    return e->fam.mfma && resid_path_supported(e->Hin, e->cfg.in_channels, e->cfg.scale * e->cfg.scale);
 }
-static size_t wgrad_need(const probav_engine* e, const ConvGeom& g)
+
+// The kernel that serves a backward-filter launch: the one decision both make_plan (slab region sizes) and conv_wgrad (launch) read.
+// am.x / am.w: per-sample amax slots of x and of dy (the H3 kernel needs both)
+enum class WgradKernel { direct, x6, mfma };
+struct WgradRoute { WgradKernel k; int cls; int arith; };
+static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Amax& am)
 {
     const bool exotic = g.reflect_t || g.ph > 1 || g.pw > 1 || g.pt > 1 || (g.kh != 3 && g.kh != 1);
-    if (exotic || (e->impl >= 1 && conv3d_direct_wgrad_is_tuned(g))) return wgrad_partial_floats(g);
-    if (e->impl >= 3 && x6_wgrad_supported(g)) return x6_wgrad_partial_floats(g);
-    if (e->impl >= 1 && mfma_wgrad_supported(g)) return mfma_wgrad_partial_floats(g);
-    return wgrad_partial_floats(g);
+    if (exotic || (f.mfma && conv3d_direct_wgrad_is_tuned(g))) return {WgradKernel::direct, CLS_CONV3_WGRAD, 0};
+    const bool x6 = f.x6 && x6_wgrad_supported(g);
+    const int cls = g.kh * g.kw * g.kt == 1 ? CLS_PW_WGRAD : (x6 ? CLS_CONV3_WGRAD_X6 : CLS_CONV3_WGRAD);
+    if (x6) return {WgradKernel::x6, cls, f.arith == 2 && am.x && am.w ? 2 : 1};
+    if (f.mfma && mfma_wgrad_supported(g)) return {WgradKernel::mfma, cls, 0};
+    return {WgradKernel::direct, cls, 0};
 }
+// slab floats the routed kernel writes
+static size_t wgrad_slab_floats(const WgradRoute& r, const ConvGeom& g)
+{
+    return r.k == WgradKernel::x6 ? x6_wgrad_partial_floats(g) : (r.k == WgradKernel::mfma ? mfma_wgrad_partial_floats(g) : wgrad_partial_floats(g));
+}
+static size_t wgrad_need(const Family& f, const ConvGeom& g) { return wgrad_slab_floats(wgrad_route(f, g, Amax()), g); }
 
 static Plan make_plan(const probav_engine* e, int B, int training)
 {
@@ -220,7 +246,7 @@ static Plan make_plan(const probav_engine* e, int B, int training)
     p.r2 = take((size_t)B * (Hin - 4) * (Hin - 4) * s2);
     p.r3 = take((size_t)B * P * P * s2);
     // the 256-channel hidden tensor (1 KB per voxel) only exists in memory when the pointwise pair runs UNfused (generic kernels, impl 0)
-    const bool unfused = !(e->impl >= 1 && e->pw_mfma);
+    const bool unfused = !e->fam.pw_fused;
     p.H = take(unfused ? V * E : 0);
     p.fwd_total = off;
     off = 0;
@@ -250,28 +276,29 @@ static Plan make_plan(const probav_engine* e, int B, int training)
         p.dr2 = take((size_t)B * (Hin - 4) * (Hin - 4) * s2);
         p.dr1 = take((size_t)B * (Hin - 2) * (Hin - 2) * s2);
         p.dH = take(unfused ? V * E : 0);
-        // one slab region per backward-filter launch, in the order probav_backward issues them: the slabs of a launch are summed on the
-        // side stream while the main chain has moved on, so no two launches may share a region
+        // one slab region per backward-filter launch, in the order backward_impl issues them (it checks that it takes exactly these, each large
+        // enough): the slabs of a launch are summed on the side stream while the main chain has moved on, so no two launches may share a region
         {
             std::vector<size_t> need;
+            const Family& f = e->fam;
             const int nred = (int)e->iRed.size();
-            need.push_back(wgrad_need(e, make_geom(B, Hin - 4, 1, s2, P, 1, s2, 3, 3, 1, 0, 0, 0, 0)));           // residConv3, 2, 1
+            need.push_back(wgrad_need(f, make_geom(B, Hin - 4, 1, s2, P, 1, s2, 3, 3, 1, 0, 0, 0, 0)));           // residConv3, 2, 1
             if (resid_path_fused(e)) need.back() = std::max(need.back(), resid_path_slab_floats(B, c.in_channels));        // (the fused reverse pass: one slab per patch, in the first region)
-            need.push_back(wgrad_need(e, make_geom(B, Hin - 2, 1, s2, Hin - 4, 1, s2, 3, 3, 1, 0, 0, 0, 0)));
-            need.push_back(wgrad_need(e, make_geom(B, Hin, 1, c.in_channels, Hin - 2, 1, s2, 3, 3, 1, 0, 0, 0, 1)));
-            need.push_back(wgrad_need(e, make_geom(B, p.redH[nred - 1], p.redT[nred - 1], F, P, 1, s2, 3, 3, 3, 0, 0, 0, 0)));   // upscaleConv1
+            need.push_back(wgrad_need(f, make_geom(B, Hin - 2, 1, s2, Hin - 4, 1, s2, 3, 3, 1, 0, 0, 0, 0)));
+            need.push_back(wgrad_need(f, make_geom(B, Hin, 1, c.in_channels, Hin - 2, 1, s2, 3, 3, 1, 0, 0, 0, 1)));
+            need.push_back(wgrad_need(f, make_geom(B, p.redH[nred - 1], p.redT[nred - 1], F, P, 1, s2, 3, 3, 3, 0, 0, 0, 0)));   // upscaleConv1
             for (int k = nred - 1; k >= 0; --k)
-                need.push_back(wgrad_need(e, red_geom(e, B, (size_t)k, k ? p.redH[k - 1] : Hin, k ? p.redT[k - 1] : T, F)));
+                need.push_back(wgrad_need(f, red_geom(e, B, (size_t)k, k ? p.redH[k - 1] : Hin, k ? p.redT[k - 1] : T, F)));
             const ConvGeom ge = make_geom(B, Hin, T, F, Hin, T, E, 1, 1, 1, 0, 0, 0, 1), gd = make_geom(B, Hin, T, E, Hin, T, D, 1, 1, 1, 0, 0, 0, 0);
             const ConvGeom gn = make_geom(B, Hin, T, D, Hin, T, F, 3, 3, 3, 1, 1, 0, 0);
             for (int i = 0; i < R; ++i) {
-                need.push_back(wgrad_need(e, gn));
+                need.push_back(wgrad_need(f, gn));
                 if (!unfused) need.push_back(mfma_pw_backward_slab_floats(D));
-                else { need.push_back(wgrad_need(e, gd)); need.push_back(wgrad_need(e, ge)); }
+                else { need.push_back(wgrad_need(f, gd)); need.push_back(wgrad_need(f, ge)); }
             }
-            need.push_back(wgrad_need(e, make_geom(B, Hin, T, c.in_channels, Hin, T, F, 3, 3, 3, 1, 1, 0, 1)));               // mainConv1
+            need.push_back(wgrad_need(f, make_geom(B, Hin, T, c.in_channels, Hin, T, F, 3, 3, 3, 1, 1, 0, 1)));               // mainConv1
             size_t acc = 0;
-            for (size_t q : need) { p.part_off.push_back(acc); acc += (q + 63) & ~(size_t)63; }
+            for (size_t q : need) { p.parts.push_back({acc, q}); acc += align_up(q); }
             p.partial = take(acc);
         }
     }
@@ -297,6 +324,13 @@ static WcPlan make_wc_plan(const probav_engine* e)
 
 // ---------------------------------------------------------------------------------------------------
 struct Frags { const float* f32 = nullptr; const float* x6 = nullptr; const float* h3 = nullptr; const float* h3t = nullptr; };   // h3t: per-tap H3 fragments of a 25-channel layer
+// the conv fragments of layer li in direction dir (0 forward, 1 backward-data) inside the packed region `wpack`
+static Frags frags(const probav_engine* e, const float* wpack, int li, int dir)
+{
+    const ConvFrags& o = e->layers[li].pk[dir];
+    auto at = [wpack](long off) -> const float* { return off >= 0 ? wpack + off : nullptr; };
+    return {at(o.f32), at(o.x6), at(o.h3), at(o.h3t)};
+}
 
 // amax slot addresses inside the workspace (layout: make_plan)
 struct AmaxSlots {
@@ -315,73 +349,156 @@ struct AmaxSlots {
     unsigned* back(int j) const { return bbase + B * j; }                             // j-th tensor produced by the backward pass
 };
 
-static int conv_fwd_launch(const probav_engine* e, const ConvGeom& g, const float* x, const float* gate, const float* w,
-                           const Frags& wf, const float* bias, const float* skip, float* y, const Amax& am, bool& reported, hipStream_t s)
+// The kernel that serves a convolution launch of the engine (forward, or backward-data when bias == nullptr): with the launch's profiling class,
+// whether the kernel writes am.y itself, and for the MFMA / x6 kernels the filter fragments they read (x6: in arithmetic 1 X6 or 2 H3)
+enum class ConvKernel { direct, up, up_bwd_data, cin1, x6_strip, x6_rowtile, mfma_strip, mfma_rowtile };
+struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; const float* wfrag; };
+static ConvRoute conv_route(const Family& f, const ConvGeom& g, const float* gate, const float* bias, const float* skip, const Frags& wf, const Amax& am)
 {
-    const float* wfrag = wf.f32;
     const bool pw = g.kh * g.kw * g.kt == 1;
     const bool bwd = (bias == nullptr);              // only backward-data launches run without a bias
-    reported = false;                                // does the kernel write am.y itself?
     // the experimental 19-frame reducer: 5x5x5 kernels, pads of 2, mirrored depth pads (and their backward-data forms): generic kernels
     const bool exotic = g.reflect_t || g.ph > 2 || g.pw > 2 || g.pt > 2 || (!pw && g.kh != 3) || (g.reflect_hw && g.ph > 1);
     // upscaleConv1 and its backward-data (0.2 % of the work): dedicated small VALU kernels instead of 32x32 matrix tiles around a 32x9 product
-    if (e->impl >= 1 && !gate && !skip && bwd && conv3d_up_bwd_data_supported(g)) {
-        ProfScope ps(e, CLS_CONV3_BWD_DATA, geom_macs(g), s);
-        reported = true;
-        return conv3d_up_bwd_data(g, x, w, nullptr, y, am.y, s);
-    }
-    if (exotic) { ProfScope ps(e, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, geom_macs(g), s); return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s); }
-    if (e->impl >= 1 && !gate && !skip && bias && !am.y && conv3d_up_forward_supported(g)) {
-        ProfScope ps(e, CLS_CONV3_FWD, geom_macs(g), s);
-        return conv3d_up_forward(g, x, w, bias, y, s);
-    }
-    if (e->impl >= 1 && !gate && !skip && bias && conv3d_cin1_forward_supported(g)) {
-        ProfScope ps(e, CLS_CONV3_FWD, geom_macs(g), s);
-        reported = true;
-        return conv3d_cin1_forward(g, x, w, bias, y, am.y, s);
-    }
-    const bool no_strip = false;
-    const bool h3 = e->impl >= 4 && wf.h3 && am.x && am.w;
+    if (f.mfma && !gate && !skip && bwd && conv3d_up_bwd_data_supported(g)) return {ConvKernel::up_bwd_data, CLS_CONV3_BWD_DATA, true, 0, nullptr};
+    if (exotic) return {ConvKernel::direct, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, false, 0, nullptr};
+    if (f.mfma && !gate && !skip && bias && !am.y && conv3d_up_forward_supported(g)) return {ConvKernel::up, CLS_CONV3_FWD, false, 0, nullptr};
+    if (f.mfma && !gate && !skip && bias && conv3d_cin1_forward_supported(g)) return {ConvKernel::cin1, CLS_CONV3_FWD, true, 0, nullptr};
+    const bool h3 = f.arith == 2 && wf.h3 && am.x && am.w;
     const float* wsplit = h3 ? wf.h3 : wf.x6;
     const int arith = h3 ? 2 : 1;
     const bool pring = h3 && x6_strip_wants_tap_fragments(g, 2);                  // the H3 piece-ring strip kernel serves this geometry
-    const bool x6s = e->impl >= 3 && wsplit && !no_strip && (mfma_conv_strip_supported(g) || pring);
-    const bool x6r = e->impl >= 3 && wsplit && !x6s && x6_conv_rowtile_supported(g);
+    const bool x6s = f.x6 && wsplit && (mfma_conv_strip_supported(g) || pring);
+    const bool x6r = f.x6 && wsplit && !x6s && x6_conv_rowtile_supported(g);
     const bool x6 = x6s || x6r;
-    ProfScope ps(e, pw ? (bwd ? CLS_PW_BWD_DATA : CLS_PW_FWD) : (bwd ? (x6 ? CLS_CONV3_BWD_DATA_X6 : CLS_CONV3_BWD_DATA) : (x6 ? CLS_CONV3_FWD_X6 : CLS_CONV3_FWD)), geom_macs(g), s);
-    if (x6s) {
-        reported = true;
-        const float* wq = (pring && g.Cin == 25 && wf.h3t) ? wf.h3t : wsplit;
-        return x6_conv_strip_forward(g, x, gate, wq, bias, skip, y, arith, am, s);
-    }
-    if (x6r) { reported = true; return x6_conv_rowtile_forward(g, x, gate, wsplit, bias, skip, y, arith, am, s); }
-    if (e->impl >= 2 && wfrag && mfma_conv_strip_supported(g)) { reported = true; return mfma_conv_strip_forward(g, x, gate, wfrag, bias, skip, y, am, s); }
-    if (e->impl >= 1 && wfrag && mfma_conv_supported(g)) { reported = true; return mfma_conv_forward(g, x, gate, wfrag, bias, skip, y, am, s); }
-    return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
+    const int cls = pw ? (bwd ? CLS_PW_BWD_DATA : CLS_PW_FWD) : (bwd ? (x6 ? CLS_CONV3_BWD_DATA_X6 : CLS_CONV3_BWD_DATA) : (x6 ? CLS_CONV3_FWD_X6 : CLS_CONV3_FWD));
+    if (x6s) return {ConvKernel::x6_strip, cls, true, arith, (pring && g.Cin == 25 && wf.h3t) ? wf.h3t : wsplit};
+    if (x6r) return {ConvKernel::x6_rowtile, cls, true, arith, wsplit};
+    if (f.strip && wf.f32 && mfma_conv_strip_supported(g)) return {ConvKernel::mfma_strip, cls, true, 0, wf.f32};
+    if (f.mfma && wf.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, wf.f32};
+    return {ConvKernel::direct, cls, false, 0, nullptr};
 }
 // am.x / am.w: amax slots of x (one per sample) and of the layer's filter columns (H3 kernels); am.y: per-sample slots that must hold the output's amax afterwards
 static int conv_fwd(const probav_engine* e, const ConvGeom& g, const float* x, const float* gate, const float* w,
                     const Frags& wf, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s)
 {
-    bool reported = false;
-    int rc = conv_fwd_launch(e, g, x, gate, w, wf, bias, skip, y, am, reported, s);
-    if (rc == PROBAV_OK && am.y && !reported) rc = amax_tensor(y, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, am.y, s);
+    const ConvRoute r = conv_route(e->fam, g, gate, bias, skip, wf, am);
+    int rc;
+    {
+        ProfScope ps(e, r.cls, geom_macs(g), s);
+        switch (r.k) {
+        case ConvKernel::up_bwd_data: rc = conv3d_up_bwd_data(g, x, w, nullptr, y, am.y, s); break;
+        case ConvKernel::up: rc = conv3d_up_forward(g, x, w, bias, y, s); break;
+        case ConvKernel::cin1: rc = conv3d_cin1_forward(g, x, w, bias, y, am.y, s); break;
+        case ConvKernel::x6_strip: rc = x6_conv_strip_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s); break;
+        case ConvKernel::x6_rowtile: rc = x6_conv_rowtile_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s); break;
+        case ConvKernel::mfma_strip: rc = mfma_conv_strip_forward(g, x, gate, r.wfrag, bias, skip, y, am, s); break;
+        case ConvKernel::mfma_rowtile: rc = mfma_conv_forward(g, x, gate, r.wfrag, bias, skip, y, am, s); break;
+        default: rc = conv3d_direct_forward(g, x, gate, w, bias, skip, y, s); break;
+        }
+    }
+    if (rc == PROBAV_OK && am.y && !r.reports) rc = amax_tensor(y, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, am.y, s);
     return rc;
-}
-// am.x / am.w: per-sample amax slots of x and of dy (H3 backward-filter kernel)
-static int conv_wgrad(const probav_engine* e, const ConvGeom& g, const float* x, const float* dy, const float* gate,
-                      float* dw, float* db, float* partial, const Amax& am, hipStream_t s)
-{
-    const bool exotic = g.reflect_t || g.ph > 1 || g.pw > 1 || g.pt > 1 || (g.kh != 3 && g.kh != 1);
-    if (exotic || (e->impl >= 1 && conv3d_direct_wgrad_is_tuned(g))) { ProfScope ps(e, CLS_CONV3_WGRAD, geom_macs(g), s); return conv3d_direct_wgrad(g, x, dy, gate, dw, db, partial, s); }
-    const bool x6 = e->impl >= 3 && x6_wgrad_supported(g);
-    ProfScope ps(e, g.kh * g.kw * g.kt == 1 ? CLS_PW_WGRAD : (x6 ? CLS_CONV3_WGRAD_X6 : CLS_CONV3_WGRAD), geom_macs(g), s);
-    if (x6) { const bool h3 = e->impl >= 4 && am.x && am.w; return x6_conv_wgrad(g, x, dy, gate, dw, db, partial, h3 ? 2 : 1, am, s); }
-    if (e->impl >= 1 && mfma_wgrad_supported(g)) return mfma_conv_wgrad(g, x, dy, gate, dw, db, partial, s);
-    return conv3d_direct_wgrad(g, x, dy, gate, dw, db, partial, s);
 }
 
 #define CK(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+// a slab region of the backward pass (make_plan: Plan::parts); p == nullptr: the pass asked for more regions than the plan lists
+struct Slab { float* p; size_t floats; };
+static int slab_fits(const Slab& r, size_t need)
+{
+    if (!r.p) { set_error("probav_backward: more backward-filter launches than make_plan laid out slab regions for", hipSuccess); return PROBAV_EINVAL; }
+    if (need > r.floats) { set_error("probav_backward: a backward-filter launch needs a larger slab region than make_plan laid out", hipSuccess); return PROBAV_EINVAL; }
+    return PROBAV_OK;
+}
+static int conv_wgrad(const probav_engine* e, const ConvGeom& g, const float* x, const float* dy, const float* gate,
+                      float* dw, float* db, const Slab& part, const Amax& am, hipStream_t s)
+{
+    const WgradRoute r = wgrad_route(e->fam, g, am);
+    CK(slab_fits(part, wgrad_slab_floats(r, g)));
+    ProfScope ps(e, r.cls, geom_macs(g), s);
+    switch (r.k) {
+    case WgradKernel::x6: return x6_conv_wgrad(g, x, dy, gate, dw, db, part.p, r.arith, am, s);
+    case WgradKernel::mfma: return mfma_conv_wgrad(g, x, dy, gate, dw, db, part.p, s);
+    default: return conv3d_direct_wgrad(g, x, dy, gate, dw, db, part.p, s);
+    }
+}
+
+// What gets packed into MFMA operand fragments: a 3x3x3 filter (of either direction), the per-tap H3 form of a 25-channel one (the piece-ring
+// strip kernel's operand order; the other forms of 25 channels are K-concatenated), and the fused pointwise pair's W1, W2 (forward) and
+// W2, W1 as the operands of its backward
+enum class Operand { conv, conv_taps, pw_w1, pw_w2, pw_w2b, pw_w1c };
+// a filled packing job for `op` of a cin x cout matrix (conv: of the packed direction) in arithmetic `arith` (0 fp32, 1 X6, 2 H3); the caller
+// sets src_off, dst_off, src_is_T and amax_slot.  count == 0: the fp32 MFMA kernels have no fragments for this channel configuration
+static PackJob pack_job(Operand op, int arith, int cin, int cout)
+{
+    PackJob J; memset(&J, 0, sizeof(J));
+    if (op == Operand::conv || op == Operand::conv_taps) {
+        if (arith == 0) { mfma_conv_pack_job(J, cin, cout); return J; }
+        const bool kc = cin == 25;
+        J.Cin = cin; J.Cout = cout; J.taps = 27;
+        if (arith == 1) { J.type = kc ? PACK_X6_CONVK : PACK_X6_CONV; J.count = kc ? X6_CONVK_FRAG_WORDS : X6_CONV_FRAG_WORDS; return J; }
+        J.type = kc ? (op == Operand::conv_taps ? PACK_H3_CONVP : PACK_H3_CONVK) : PACK_H3_CONV;
+        J.count = kc ? H3_CONVK_FRAG_WORDS : H3_CONV_FRAG_WORDS;
+        J.amax_percol = 1; J.ncol = cout;                      // H3: cut per output column of the packed matrix
+        return J;
+    }
+    static const int types[3][4] = {{PACK_PW_A_KCIN, PACK_PW_A_KHCH, PACK_PW_A_KOUT, PACK_PW_A_CIN_KHCH},
+                                    {PACK_X6_PW_W1, PACK_X6_PW_W2, PACK_X6_PW_W2K, PACK_X6_PW_W1C},
+                                    {PACK_H3_PW_W1, PACK_H3_PW_W2, PACK_H3_PW_W2K, PACK_H3_PW_W1C}};
+    J.type = types[arith][(int)op - (int)Operand::pw_w1];
+    J.count = arith == 0 ? 8 * 4 * 64 * 4 : (arith == 1 ? X6_PW_FRAG_WORDS : H3_PW_FRAG_WORDS);
+    J.Cin = cin; J.Cout = cout;
+    // H3: W2 forward is cut per output column d, W1 as the operand of (c) per cin row (= dX column); the other two take one scale for the tensor
+    if (arith == 2 && op == Operand::pw_w2) { J.amax_percol = 1; J.ncol = cout; }
+    if (arith == 2 && op == Operand::pw_w1c) { J.amax_percol = 1; J.ncol = cin; }
+    return J;
+}
+
+// the fused pointwise pair (expConv + ReLU + decConv), one launch each way: the fp32-MFMA kernels (arith 0) or the split-operand ones (1 X6, 2 H3)
+struct PwOps { const float *w1, *w2, *w2b, *w1c; };
+static int pw_forward(int arith, const PwOps& f, const float* x, const float* b1, const float* b2, float* dec, long nvox, long vps, int D,
+                      const PwAmax& am, hipStream_t s, float* hidden = nullptr)
+{
+    if (arith) return x6_pw_forward(x, f.w1, f.w2, b1, b2, dec, nvox, vps, D, arith, am, s, hidden);
+    return mfma_pw_forward(x, f.w1, f.w2, b1, b2, dec, nvox, D, s);
+}
+static int pw_backward(int arith, const PwOps& f, const float* x, const float* dT, const float* dOut, const float* b1, float* dX, float* dW1,
+                       float* dW2, float* db1, float* db2, float* slabs, long nvox, long vps, int D, const PwAmax& am, hipStream_t s)
+{
+    if (arith) return x6_pw_backward(x, dT, dOut, f.w1, f.w2b, f.w1c, b1, dX, dW1, dW2, db1, db2, slabs, nvox, vps, D, arith, am, s);
+    return mfma_pw_backward(x, dT, dOut, f.w1, f.w2b, f.w1c, b1, dX, dW1, dW2, db1, db2, slabs, nvox, D, s);
+}
+// block i's pair in the engine's family: its fragments (in the packed region `wpack`) and, H3, its amax slots
+static PwOps block_frags(const probav_engine* e, const float* wpack, int i)
+{
+    const PwFrags& o = e->pkBlk[i][e->fam.arith];
+    return {wpack + o.w1, wpack + o.w2, wpack + o.w2b, wpack + o.w1c};
+}
+// forward of block i from act[i] (x) into dec; ay: per-sample slots of the output's amax (H3, optional); hidden: test dump of the hidden tile
+static int pw_forward_launch(const probav_engine* e, int i, const float* wpack, const AmaxSlots& A, const float* params, const float* x,
+                             float* dec, long nvox, unsigned* ay, hipStream_t s, float* hidden = nullptr)
+{
+    const int le = e->iExp[i], ld = e->iDec[i];
+    PwAmax m;
+    if (e->fam.arith == 2) { m.x = A.act(i); m.w1 = A.w(le); m.w2 = A.w(ld); m.w2c = A.wcol(ld); m.b1 = A.b(le); m.y = ay; }
+    return pw_forward(e->fam.arith, block_frags(e, wpack, i), x, params + e->layers[le].wn.b_off, params + e->layers[ld].wn.b_off, dec,
+                      nvox, nvox / A.B, e->cfg.dec_channels, m, s, hidden);
+}
+// backward of block i: dT = d loss / d dec_i, dOut = d loss / d act[i+1] (the skip path) -> dX, the weight (into dweff2) and bias (into grads)
+// gradients of expConv_i and decConv_i; adt / ay: amax slots of dT / dX (H3)
+static int pw_backward_launch(const probav_engine* e, int i, const float* wpack, const AmaxSlots& A, const float* params, float* grads,
+                              float* dweff2, const float* x, const float* dT, const float* dOut, float* dX, const Slab& part, long nvox,
+                              unsigned* adt, unsigned* ay, hipStream_t s)
+{
+    const int D = e->cfg.dec_channels;
+    CK(slab_fits(part, mfma_pw_backward_slab_floats(D)));
+    const WnLayer &we = e->layers[e->iExp[i]].wn, &wd = e->layers[e->iDec[i]].wn;
+    PwAmax m;
+    if (e->fam.arith == 2) { m.x = A.act(i); m.w1 = A.w(e->iExp[i]); m.w2 = A.w(e->iDec[i]); m.w1r = A.wrow(e->iExp[i]); m.b1 = A.b(e->iExp[i]); m.dt = adt; m.y = ay; }
+    return pw_backward(e->fam.arith, block_frags(e, wpack, i), x, dT, dOut, params + we.b_off, dX, dweff2 + we.w_off, dweff2 + wd.w_off,
+                       grads + we.b_off, grads + wd.b_off, part.p, nvox, nvox / A.B, D, m, s);
+}
 
 extern "C" {
 
@@ -454,88 +571,49 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
         set_error("probav_engine_create: reducer geometry does not collapse to [P,P,1]", hipSuccess);
         return PROBAV_EINVAL;
     }
-    // MFMA fragment-packing jobs
-    e->pkFwd.assign(e->layers.size(), -1); e->pkBwd.assign(e->layers.size(), -1);
-    e->pkFwd6.assign(e->layers.size(), -1); e->pkBwd6.assign(e->layers.size(), -1);
-    e->pkFwdH.assign(e->layers.size(), -1); e->pkBwdH.assign(e->layers.size(), -1);
-    e->pkFwdHt.assign(e->layers.size(), -1); e->pkBwdHt.assign(e->layers.size(), -1);
+    // MFMA fragment-packing jobs: every family's fragments, packed whenever weights are normalised at impl >= 1
+    const int L2 = 2 * (int)e->layers.size();                      // weight amax slots per column of weff, then per column of weffT (wn_forward's layout)
+    auto add = [&](PackJob J, long src_off, int src_is_T, int amax_slot) -> long {
+        J.src_off = src_off; J.src_is_T = src_is_T; J.amax_slot = amax_slot; J.dst_off = e->wpack_count;
+        e->wpack_count += J.count;
+        e->jobs.push_back(J);
+        return J.dst_off;
+    };
     for (size_t li = 0; li < e->layers.size(); ++li) {
-        const LayerRec& r = e->layers[li];
+        LayerRec& r = e->layers[li];
         if (r.kh != 3 || r.kw != 3 || r.kt != 3) continue;
         for (int dir = 0; dir < 2; ++dir) {
             const int cin = dir ? r.wn.Cout : r.wn.Cin, cout = dir ? r.wn.Cin : r.wn.Cout;
             if ((int)li == e->iMain && dir) continue;               // input-facing: no backward-data
-            if (mfma_conv_wfrag_floats(cin, cout) == 0) continue;
-            PackJob J; memset(&J, 0, sizeof(J));
-            mfma_conv_pack_job(J, cin, cout);
-            J.src_is_T = dir; J.src_off = r.wn.w_off; J.dst_off = e->wpack_count;
-            (dir ? e->pkBwd : e->pkFwd)[li] = J.dst_off;
-            e->wpack_count += J.count;
-            e->jobs.push_back(J);
-            if ((cin == 25 || cin == 32) && cout <= 32) {           // strip-kernel shapes: also the x6 fragments
-                PackJob X; memset(&X, 0, sizeof(X));
-                X.type = cin == 25 ? PACK_X6_CONVK : PACK_X6_CONV; X.src_is_T = dir; X.src_off = r.wn.w_off; X.dst_off = e->wpack_count;
-                X.count = cin == 25 ? X6_CONVK_FRAG_WORDS : X6_CONV_FRAG_WORDS; X.Cin = cin; X.Cout = cout; X.taps = 27;
-                (dir ? e->pkBwd6 : e->pkFwd6)[li] = X.dst_off;
-                e->wpack_count += X.count;
-                e->jobs.push_back(X);
-                X.type += 10; X.dst_off = e->wpack_count;                              // PACK_H3_*: cut per output column of the packed matrix
-                X.amax_percol = 1; X.ncol = cout;                                      // columns of weff = output channels, of weffT = input channels
-                X.amax_slot = 2 * (int)e->layers.size() + (dir ? (int)e->cout_total + r.wn.r_off : r.wn.n_off);
-                X.count = cin == 25 ? H3_CONVK_FRAG_WORDS : H3_CONV_FRAG_WORDS;
-                (dir ? e->pkBwdH : e->pkFwdH)[li] = X.dst_off;
-                e->wpack_count += X.count;
-                e->jobs.push_back(X);
-                if (cin == 25) {
-                    X.type = PACK_H3_CONVP; X.count = H3_CONVK_FRAG_WORDS; X.dst_off = e->wpack_count;
-                    (dir ? e->pkBwdHt : e->pkFwdHt)[li] = X.dst_off;
-                    e->wpack_count += X.count;
-                    e->jobs.push_back(X);
-                }
+            const PackJob J = pack_job(Operand::conv, 0, cin, cout);
+            if (J.count == 0) continue;
+            ConvFrags& o = r.pk[dir];
+            o.f32 = add(J, r.wn.w_off, dir, 0);
+            if ((cin == 25 || cin == 32) && cout <= 32) {           // strip-kernel shapes: also the split-operand fragments
+                const int wcols = L2 + (dir ? (int)e->cout_total + r.wn.r_off : r.wn.n_off);   // H3: the packed matrix' columns
+                o.x6 = add(pack_job(Operand::conv, 1, cin, cout), r.wn.w_off, dir, 0);
+                o.h3 = add(pack_job(Operand::conv, 2, cin, cout), r.wn.w_off, dir, wcols);
+                if (cin == 25) o.h3t = add(pack_job(Operand::conv_taps, 2, cin, cout), r.wn.w_off, dir, wcols);
             }
         }
     }
     e->pw_mfma = mfma_pw_supported(F, E, D);
-    if (e->pw_mfma) {
-        for (int i = 0; i < cfg->num_res_blocks; ++i) {
-            PackJob J; memset(&J, 0, sizeof(J));
-            J.type = PACK_PW_A_KCIN; J.src_is_T = 0; J.src_off = e->layers[e->iExp[i]].wn.w_off; J.dst_off = e->wpack_count;
-            J.count = 8 * 4 * 64 * 4; J.Cin = F; J.Cout = E;
-            e->pkW1.push_back(J.dst_off); e->wpack_count += J.count; e->jobs.push_back(J);
-            J.type = PACK_PW_A_KHCH; J.src_off = e->layers[e->iDec[i]].wn.w_off; J.dst_off = e->wpack_count;
-            J.Cin = E; J.Cout = D;
-            e->pkW2.push_back(J.dst_off); e->wpack_count += J.count; e->jobs.push_back(J);
-            J.type = PACK_PW_A_KOUT; J.dst_off = e->wpack_count;                      // backward (b): dH^T = W2 dT^T
-            e->pkW2B.push_back(J.dst_off); e->wpack_count += J.count; e->jobs.push_back(J);
-            J.type = PACK_PW_A_CIN_KHCH; J.src_off = e->layers[e->iExp[i]].wn.w_off; J.dst_off = e->wpack_count;
-            J.Cin = F; J.Cout = E;                                                    // backward (c): dX^T += W1 dH'^T
-            e->pkW1C.push_back(J.dst_off); e->wpack_count += J.count; e->jobs.push_back(J);
-            PackJob X; memset(&X, 0, sizeof(X));
-            X.type = PACK_X6_PW_W1; X.src_off = e->layers[e->iExp[i]].wn.w_off; X.dst_off = e->wpack_count;
-            X.count = X6_PW_FRAG_WORDS; X.Cin = F; X.Cout = E;
-            e->pkW1x6.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.type = PACK_X6_PW_W2; X.src_off = e->layers[e->iDec[i]].wn.w_off; X.dst_off = e->wpack_count;
-            X.Cin = E; X.Cout = D;
-            e->pkW2x6.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.type = PACK_X6_PW_W2K; X.dst_off = e->wpack_count;
-            e->pkW2Kx6.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.type = PACK_X6_PW_W1C; X.src_off = e->layers[e->iExp[i]].wn.w_off; X.dst_off = e->wpack_count;
-            X.Cin = F; X.Cout = E;
-            e->pkW1Cx6.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.count = H3_PW_FRAG_WORDS;
-            X.type = PACK_H3_PW_W1; X.src_off = e->layers[e->iExp[i]].wn.w_off; X.dst_off = e->wpack_count;
-            const int L2 = 2 * (int)e->layers.size();
-            X.Cin = F; X.Cout = E; X.amax_slot = e->iExp[i]; X.amax_percol = 0; X.ncol = 0;         // (a): one scale for the tensor
-            e->pkW1h.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.type = PACK_H3_PW_W1C; X.dst_off = e->wpack_count;                                        // (c): cut per cin row = per dX column
-            X.amax_percol = 1; X.ncol = F; X.amax_slot = L2 + (int)e->cout_total + e->layers[e->iExp[i]].wn.r_off;
-            e->pkW1Ch.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.type = PACK_H3_PW_W2; X.src_off = e->layers[e->iDec[i]].wn.w_off; X.dst_off = e->wpack_count;
-            X.Cin = E; X.Cout = D; X.amax_percol = 1; X.ncol = D; X.amax_slot = L2 + e->layers[e->iDec[i]].wn.n_off;   // forward: cut per output column d
-            e->pkW2h.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
-            X.type = PACK_H3_PW_W2K; X.dst_off = e->wpack_count; X.amax_percol = 0; X.ncol = 0; X.amax_slot = e->iDec[i];       // (b): one scale for the tensor
-            e->pkW2Kh.push_back(X.dst_off); e->wpack_count += X.count; e->jobs.push_back(X);
+    for (int i = 0; e->pw_mfma && i < cfg->num_res_blocks; ++i) {
+        const int le = e->iExp[i], ld = e->iDec[i];
+        const long w1 = e->layers[le].wn.w_off, w2 = e->layers[ld].wn.w_off;
+        std::array<PwFrags, 3> b;
+        for (int a = 0; a < 2; ++a) {                               // fp32, X6: no amax
+            b[a].w1 = add(pack_job(Operand::pw_w1, a, F, E), w1, 0, 0);
+            b[a].w2 = add(pack_job(Operand::pw_w2, a, E, D), w2, 0, 0);
+            b[a].w2b = add(pack_job(Operand::pw_w2b, a, E, D), w2, 0, 0);
+            b[a].w1c = add(pack_job(Operand::pw_w1c, a, F, E), w1, 0, 0);
         }
+        // H3 (in this order): W1 and W2-backward scaled by their tensors' slots, W1-backward per cin row, W2 per output column
+        b[2].w1 = add(pack_job(Operand::pw_w1, 2, F, E), w1, 0, le);
+        b[2].w1c = add(pack_job(Operand::pw_w1c, 2, F, E), w1, 0, L2 + (int)e->cout_total + e->layers[le].wn.r_off);
+        b[2].w2 = add(pack_job(Operand::pw_w2, 2, E, D), w2, 0, L2 + e->layers[ld].wn.n_off);
+        b[2].w2b = add(pack_job(Operand::pw_w2b, 2, E, D), w2, 0, ld);
+        e->pkBlk.push_back(b);
     }
     if (!e->jobs.empty()) {
         hipError_t perr = hipMalloc((void**)&e->d_jobs, e->jobs.size() * sizeof(PackJob));
@@ -547,7 +625,8 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
     hipError_t err = hipMalloc((void**)&e->d_layers, h.size() * sizeof(WnLayer));
     if (err == hipSuccess) err = hipMemcpy(e->d_layers, h.data(), h.size() * sizeof(WnLayer), hipMemcpyHostToDevice);
     if (err != hipSuccess) { set_error("probav_engine_create: layer table upload", err); delete e; return PROBAV_EHIP; }
-    if (const char* env = getenv("PROBAV_IMPL")) e->impl = atoi(env);
+    const char* env = getenv("PROBAV_IMPL");
+    e->fam = make_family(env ? atoi(env) : 4, e->pw_mfma);
     *out = e;
     return PROBAV_OK;
 }
@@ -624,7 +703,7 @@ int probav_layer_info(const probav_engine* e, int i, char name[32], int64_t* g_o
 int probav_engine_set_impl(probav_engine* e, int impl)
 {
     if (!e || impl < 0 || impl > 4) { set_error("probav_engine_set_impl: bad argument", hipSuccess); return PROBAV_EINVAL; }
-    e->impl = impl;
+    e->fam = make_family(impl, e->pw_mfma);
     return PROBAV_OK;
 }
 
@@ -682,25 +761,18 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     const int Hin = e->Hin, P = c.patch_size_lr, s2 = c.scale * c.scale;
     auto weff = [&](int li) { return Wweff + e->layers[li].wn.w_off; };
     auto bias = [&](int li) { return params + e->layers[li].wn.b_off; };
-    auto frag = [&](int li) -> Frags {
-        Frags f;
-        if (e->pkFwd[li] >= 0) f.f32 = Wpack + e->pkFwd[li];
-        if (e->pkFwd6[li] >= 0) f.x6 = Wpack + e->pkFwd6[li];
-        if (e->pkFwdH[li] >= 0) f.h3 = Wpack + e->pkFwdH[li];
-        if (e->pkFwdHt[li] >= 0) f.h3t = Wpack + e->pkFwdHt[li];
-        return f;
-    };
+    auto frag = [&](int li) { return frags(e, Wpack, li, 0); };
     // amax slots (H3 arithmetic, impl 4): every tensor an H3 kernel reads has its largest magnitude in a slot by then
-    const bool h3 = e->impl >= 4;
+    const bool h3 = e->fam.arith == 2;
     const AmaxSlots A(e, p, W, R, WC ? reinterpret_cast<unsigned*>(const_cast<float*>(WC + wc.amax)) : nullptr);
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wcol(li); m.y = ay; } return m; };
     // (the per-sample amax slots -- the atomicMax targets -- are cleared by head_kernel below; the weight slots in front of them are plain stores of wn_forward_kernel /
     // wn_rowmax_kernel, every one of them written before anything reads it)
-    if (training) { e->fwd_amax = h3; e->fwd_unfused = !(e->impl >= 1 && e->pw_mfma); }
+    if (training) { e->fwd_amax = h3; e->fwd_unfused = !e->fam.pw_fused; }
 
     if (!WC) {
         { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, W + p.weff, W + p.weffT, W + p.invn, h3 ? A.base : nullptr, s)); }
-        if (e->impl >= 1) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), W + p.weff, W + p.weffT, W + p.wpack, A.base, s)); }
+        if (e->fam.mfma) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), W + p.weff, W + p.weffT, W + p.wpack, A.base, s)); }
     }
     CK(head_forward(x, W + p.xn, W + p.mn, B * Hin * Hin, T, c.in_channels, c.mean, c.std, s, h3 ? A.base + p.amax_fwd : nullptr, h3 ? p.amax_bwd - p.amax_fwd : 0));
     // the low-frequency residual path (three small 2-D convolutions on the temporal mean) meets the main path only in tail_forward: it runs
@@ -719,20 +791,11 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     }
     CK(conv_fwd(e, make_geom(B, Hin, T, c.in_channels, Hin, T, F, 3, 3, 3, 1, 1, 0, 1), W + p.xn, nullptr, weff(e->iMain), frag(e->iMain), bias(e->iMain), nullptr, W + p.act[0], amx(nullptr, e->iMain, A.act(0)), s));
     for (int i = 0; i < R; ++i) {
-        if (e->impl >= 1 && e->pw_mfma) {
+        if (e->fam.pw_fused) {
             // fused expConv + ReLU + decConv: the 256-channel tensor never leaves the accumulators
             const long nvox = (long)B * Hin * Hin * T;
-            ProfScope ps(e, e->impl >= 3 ? CLS_PW_FWD_X6 : CLS_PW_FWD, (double)nvox * ((double)F * E + (double)E * D), s);
-            if (h3) {
-                PwAmax m; m.x = A.act(i); m.w1 = A.w(e->iExp[i]); m.w2 = A.w(e->iDec[i]); m.w2c = A.wcol(e->iDec[i]); m.b1 = A.b(e->iExp[i]); m.y = A.dec(i);
-                CK(x6_pw_forward(W + p.act[i], Wpack + e->pkW1h[i], Wpack + e->pkW2h[i], bias(e->iExp[i]), bias(e->iDec[i]),
-                                 W + p.dec[i], nvox, nvox / B, D, 2, m, s));
-            } else if (e->impl >= 3) {
-                CK(x6_pw_forward(W + p.act[i], Wpack + e->pkW1x6[i], Wpack + e->pkW2x6[i], bias(e->iExp[i]), bias(e->iDec[i]),
-                                 W + p.dec[i], nvox, nvox / B, D, 1, PwAmax(), s));
-            } else
-                CK(mfma_pw_forward(W + p.act[i], Wpack + e->pkW1[i], Wpack + e->pkW2[i], bias(e->iExp[i]), bias(e->iDec[i]),
-                                   W + p.dec[i], nvox, D, s));
+            ProfScope ps(e, e->fam.x6 ? CLS_PW_FWD_X6 : CLS_PW_FWD, (double)nvox * ((double)F * E + (double)E * D), s);
+            CK(pw_forward_launch(e, i, Wpack, A, params, W + p.act[i], W + p.dec[i], nvox, A.dec(i), s));
         } else {
             CK(conv_fwd(e, make_geom(B, Hin, T, F, Hin, T, E, 1, 1, 1, 0, 0, 0, 1), W + p.act[i], nullptr, weff(e->iExp[i]), frag(e->iExp[i]), bias(e->iExp[i]), nullptr, W + p.H, Amax(), s));
             CK(conv_fwd(e, make_geom(B, Hin, T, E, Hin, T, D, 1, 1, 1, 0, 0, 0, 0), W + p.H, nullptr, weff(e->iDec[i]), frag(e->iDec[i]), bias(e->iDec[i]), nullptr, W + p.dec[i], amx(nullptr, e->iDec[i], A.dec(i)), s));
@@ -786,21 +849,14 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     const int F = c.num_filters, E = F * c.exp_rate, D = c.dec_channels, T = c.num_img_lr, R = c.num_res_blocks;
     const int Hin = e->Hin, P = c.patch_size_lr, s2 = c.scale * c.scale;
     auto weffT = [&](int li) { return WweffT + e->layers[li].wn.w_off; };
-    auto fragT = [&](int li) -> Frags {
-        Frags f;
-        if (e->pkBwd[li] >= 0) f.f32 = Wpack + e->pkBwd[li];
-        if (e->pkBwd6[li] >= 0) f.x6 = Wpack + e->pkBwd6[li];
-        if (e->pkBwdH[li] >= 0) f.h3 = Wpack + e->pkBwdH[li];
-        if (e->pkBwdHt[li] >= 0) f.h3t = Wpack + e->pkBwdHt[li];
-        return f;
-    };
+    auto fragT = [&](int li) { return frags(e, Wpack, li, 1); };
     // amax slots of the gradient tensors, in launch order (the forward pass left those of the weights and activations)
-    const bool h3 = e->impl >= 4;
+    const bool h3 = e->fam.arith == 2;
     const AmaxSlots A(e, p, W, R, WC ? reinterpret_cast<unsigned*>(const_cast<float*>(WC + wc.amax)) : nullptr, S);
     int nback = 0;
     auto new_slot = [&]() -> unsigned* { return h3 ? A.back(nback++) : nullptr; };
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wrow(li); m.y = ay; } return m; };   // backward-data: the matrix' columns are the layer's INPUT channels
-    if (e->fwd_unfused != !(e->impl >= 1 && e->pw_mfma)) {
+    if (e->fwd_unfused != !e->fam.pw_fused) {
         set_error("probav_backward: the kernel family changed between forward and backward in a way that changes the workspace layout (impl 0 <-> >= 1)", hipSuccess);
         return PROBAV_EINVAL;
     }
@@ -811,8 +867,12 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     // (the reverse pass's per-sample amax slots are cleared by tail_bwd_kernel, its first launch)
     auto dweff = [&](int li) { return S + p.dweff2 + e->layers[li].wn.w_off; };
     auto dbias = [&](int li) { return grads + e->layers[li].wn.b_off; };
-    int npart = 0;
-    auto next_part = [&]() -> float* { const size_t k = (size_t)npart < p.part_off.size() ? (size_t)npart : p.part_off.size() - 1; ++npart; return S + p.partial + p.part_off[k]; };
+    // the slab regions of the backward-filter launches, in the plan's order (past its end: none, and the launch that asks fails)
+    size_t npart = 0;
+    auto next_part = [&]() -> Slab {
+        const size_t k = npart++;
+        return k < p.parts.size() ? Slab{S + p.partial + p.parts[k].off, p.parts[k].floats} : Slab{nullptr, 0};
+    };
     // (defer: the slab sums and the small launches that only the weight-norm backward waits for are queued and leave in a few flushes -- one event record
     // on the launch stream per flush instead of one per launch, probav_common.h)
     SideGuard side_guard((side_stream_disabled() || e->side_mode == 0) ? nullptr : engine_side(e), s, 1);
@@ -821,7 +881,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     // low-frequency residual path (models/modelsTF.py:45-53), last layer first: beside the main chain, nothing below depends on it until the weight-norm
     // backward -- queued (its slab regions are taken now, in the plan's launch order) and launched at the first flush, when the launch stream has its next kernels
     {
-        float* const rp0 = next_part(); float* const rp1 = next_part(); float* const rp2 = next_part();
+        const Slab rp0 = next_part(), rp1 = next_part(), rp2 = next_part();
         // (the queued launch runs later, from reduce_flush: everything it needs is captured BY VALUE -- pointers and extents, nothing of this frame)
         const float *r2 = W + p.r2, *r1 = W + p.r1, *mn = W + p.mn, *wT3 = weffT(e->iResid3), *wT2 = weffT(e->iResid2);
         const Frags fT3 = fragT(e->iResid3), fT2 = fragT(e->iResid2);
@@ -829,10 +889,11 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         float *dw3 = dweff(e->iResid3), *db3 = dbias(e->iResid3), *dw2 = dweff(e->iResid2), *db2 = dbias(e->iResid2), *dw1 = dweff(e->iResid1), *db1 = dbias(e->iResid1);
         const int inch = c.in_channels;
         const float *w2r = Wweff + e->layers[e->iResid2].wn.w_off, *w3r = Wweff + e->layers[e->iResid3].wn.w_off;
-        if (resid_path_fused(e))
+        if (resid_path_fused(e)) {
+            CK(slab_fits(rp0, resid_path_slab_floats(B, inch)));
             CK(reduce_later(s, [=](hipStream_t rs) -> int {    // one launch + one slab sum (rp0 holds the patches' slabs: make_plan sized it)
-                return resid_path_backward(B, Hin, inch, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp0, rs); }));
-        else
+                return resid_path_backward(B, Hin, inch, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp0.p, rs); }));
+        } else
         CK(reduce_later(s, [=](hipStream_t rs) -> int {
             const ConvGeom g3 = make_geom(B, Hin - 4, 1, s2, P, 1, s2, 3, 3, 1, 0, 0, 0, 0);
             CK(conv_wgrad(e, g3, r2, dtail, nullptr, dw3, db3, rp0, Amax(), rs));
@@ -848,12 +909,12 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     // upscale + reducers (models/modelsTF.py:152-164)
     const int nred = (int)e->iRed.size();
     float* cur = S + p.gA;
-    float* oth = S + p.gB;
+    float* oth = S + p.gB;                          // (the unfused block path below ping-pongs between `cur` and this)
     unsigned* acur = new_slot();                    // amax slot of the tensor `cur` holds
     {
         const int h = p.redH[nred - 1], t = p.redT[nred - 1];
         const ConvGeom gu = make_geom(B, h, t, F, P, 1, s2, 3, 3, 3, 0, 0, 0, 0);
-        float* const up_part = next_part();
+        const Slab up_part = next_part();
         const float* const upx = W + p.red[nred - 1];
         float *const updy = S + p.dtail, *const updw = dweff(e->iUp), *const updb = dbias(e->iUp);
         CK(reduce_later(s, [=](hipStream_t rs) -> int {       // (only the weight-norm backward reads it; captured by value: it runs from a later flush)
@@ -887,7 +948,6 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
             acur = aoth;
         }
     }
-    oth = S + p.gB;                                 // (the unfused block path below ping-pongs between `cur` and this)
     // residual blocks (models/modelsTF.py:177-189), last first.  cur = d loss / d act[i+1]
     const ConvGeom ge = make_geom(B, Hin, T, F, Hin, T, E, 1, 1, 1, 0, 0, 0, 1);
     const ConvGeom gd = make_geom(B, Hin, T, E, Hin, T, D, 1, 1, 1, 0, 0, 0, 0);
@@ -899,7 +959,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         float* dH = S + p.dH;
         const int le = e->iExp[i], ld = e->iDec[i], ln = e->iNorm[i];
         // normConv_i: d loss/d w, then d loss/d dec_i
-        const bool fusedp = e->impl >= 1 && e->pw_mfma;
+        const bool fusedp = e->fam.pw_fused;
         { Amax m; if (h3) { m.x = A.dec(i); m.w = acur; }
           // (from the second block on, the last thing enqueued on s was the previous block's pointwise backward, whose slab sums forked right behind it)
           CK(conv_wgrad(e, gn, W + p.dec[i], cur, nullptr, dweff(ln), dbias(ln), next_part(), m,
@@ -907,22 +967,13 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         if (fusedp) oth = S + p.gblk[i];                   // this block's dX goes to its own buffer: `cur` stays intact for the late backward-filter
         unsigned* agdec = new_slot();
         CK(conv_fwd(e, bwd_data_geom(gn), cur, nullptr, weffT(ln), fragT(ln), nullptr, nullptr, gDec, amx(acur, ln, agdec), s));
-        if (e->impl >= 1 && e->pw_mfma) {
+        if (fusedp) {
             // fused: H recompute, dH, ReLU gate, dX (+ skip), dW1, dW2, db1, db2 -- nothing 256-wide touches HBM
             const long nvox = (long)B * Hin * Hin * T;
             unsigned* anew = new_slot();                     // amax slot of dX
             {   // (the class's bracket ends HERE: the flush below launches the batched slab sums on this stream, and they are no part of this class)
-            ProfScope ps(e, e->impl >= 3 ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, (double)nvox * (2.0 * F * E + 2.0 * E * D), s);   // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work
-            if (h3) {
-                PwAmax m; m.x = A.act(i); m.w1 = A.w(le); m.w2 = A.w(ld); m.w1r = A.wrow(le); m.b1 = A.b(le); m.dt = agdec; m.y = anew;
-                CK(x6_pw_backward(W + p.act[i], gDec, cur, Wpack + e->pkW1h[i], Wpack + e->pkW2Kh[i], Wpack + e->pkW1Ch[i],
-                                  params + e->layers[le].wn.b_off, oth, dweff(le), dweff(ld), dbias(le), dbias(ld), next_part(), nvox, nvox / B, D, 2, m, s));
-            } else if (e->impl >= 3)
-                CK(x6_pw_backward(W + p.act[i], gDec, cur, Wpack + e->pkW1x6[i], Wpack + e->pkW2Kx6[i], Wpack + e->pkW1Cx6[i],
-                                  params + e->layers[le].wn.b_off, oth, dweff(le), dweff(ld), dbias(le), dbias(ld), next_part(), nvox, nvox / B, D, 1, PwAmax(), s));
-            else
-                CK(mfma_pw_backward(W + p.act[i], gDec, cur, Wpack + e->pkW1[i], Wpack + e->pkW2B[i], Wpack + e->pkW1C[i],
-                                    params + e->layers[le].wn.b_off, oth, dweff(le), dweff(ld), dbias(le), dbias(ld), next_part(), nvox, D, s));
+            ProfScope ps(e, e->fam.x6 ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, (double)nvox * (2.0 * F * E + 2.0 * E * D), s);   // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work
+            CK(pw_backward_launch(e, i, Wpack, A, params, grads, S + p.dweff2, W + p.act[i], gDec, cur, oth, next_part(), nvox, agdec, anew, s));
             }
             float* tmp2 = cur; cur = oth; oth = tmp2;
             acur = anew;
@@ -954,6 +1005,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         reduce_side_activate(ctx);
         if (rc) return rc;
     }
+    if (npart != p.parts.size()) { set_error("probav_backward: the pass used fewer slab regions than make_plan laid out", hipSuccess); return PROBAV_EINVAL; }
     CK(reduce_join(s));                                                       // every slab sum has landed in dweff / the bias gradients
     { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_backward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, params, S + p.dweff2, Winvn, grads, s)); }
     return PROBAV_OK;
@@ -1046,12 +1098,12 @@ int probav_workspace_view(const probav_engine* e, int batch, int training, int k
 int probav_debug_hidden(probav_engine* e, const float* params, const void* ws, size_t ws_bytes, int B, int block, float* hidden, float* dec_scratch, const void* wcache, void* stream)
 {
     if (!e || !params || !ws || !hidden || !dec_scratch || B < 1 || block < 0 || block >= e->cfg.num_res_blocks) { set_error("probav_debug_hidden: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
-    if (e->impl < 3 || !e->pw_mfma) { set_error("probav_debug_hidden: only the split-operand kernel families (impl 3, 4) expose their hidden tile", hipSuccess); return PROBAV_EINVAL; }
+    if (!e->fam.x6 || !e->fam.pw_fused) { set_error("probav_debug_hidden: only the split-operand kernel families (impl 3, 4) expose their hidden tile", hipSuccess); return PROBAV_EINVAL; }
     const Plan p = make_plan(e, B, 1);
     if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_debug_hidden: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
     const float* W = (const float*)ws;
     const probav_net_cfg& c = e->cfg;
-    const int D = c.dec_channels, R = c.num_res_blocks, i = block;
+    const int R = c.num_res_blocks;
     const long nvox = (long)B * e->Hin * e->Hin * c.num_img_lr;
     const WcPlan wc = make_wc_plan(e);
     const float* WC = (const float*)wcache;                           // the forward pass ran from the weight cache: its fragments and weight slots live there
@@ -1059,12 +1111,7 @@ int probav_debug_hidden(probav_engine* e, const float* params, const void* ws, s
     const AmaxSlots A(e, p, W, R, WC ? reinterpret_cast<unsigned*>(const_cast<float*>(WC + wc.amax)) : nullptr);
     // the forward launch of block i again, into the caller's scratch output (the saved state is only read), with the hidden tile written out;
     // no amax report (the slots of the saved tensors stay as the forward pass left them)
-    PwAmax m;
-    const bool h3 = e->impl >= 4;
-    if (h3) { m.x = A.act(i); m.w1 = A.w(e->iExp[i]); m.w2 = A.w(e->iDec[i]); m.w2c = A.wcol(e->iDec[i]); m.b1 = A.b(e->iExp[i]); }
-    return x6_pw_forward(W + p.act[i], Wpack + (h3 ? e->pkW1h[i] : e->pkW1x6[i]), Wpack + (h3 ? e->pkW2h[i] : e->pkW2x6[i]),
-                         params + e->layers[e->iExp[i]].wn.b_off, params + e->layers[e->iDec[i]].wn.b_off, dec_scratch, nvox, nvox / B, D, h3 ? 2 : 1, m,
-                         (hipStream_t)stream, hidden);
+    return pw_forward_launch(e, block, Wpack, A, params, W + p.act[block], dec_scratch, nvox, nullptr, (hipStream_t)stream, hidden);
 }
 
 int probav_debug_hidden_from_forward_kernel(int on) { x6_pw_dump_from_forward_kernel(on); return PROBAV_OK; }
@@ -1086,61 +1133,59 @@ static bool geom_ok(const ConvGeom& g)
     return true;
 }
 
-// scratch owned by the library for the single-operator entry points (parity tests): packing raw Keras-layout
-// weights into MFMA fragments needs a device buffer, allocated on first use -- the engine path never does this.
-static float* g_op_frag = nullptr;
-static PackJob* g_op_job = nullptr;
-static unsigned* g_op_amax = nullptr;    // amax slots of a single-operator call with H3 arithmetic (the engine gets them from the producing kernels)
-static size_t g_op_amax_cap = 0;
+// Scratch owned by the library for the single-operator entry points (parity tests), allocated on first use -- the engine path never does this.
+// Packing raw Keras-layout weights into MFMA fragments needs a device buffer (a conv area, then the pointwise pair's four fragments) and a job
+// table; an H3 call needs amax slots (the engine gets them from the producing kernels).
+constexpr size_t OP_CONV_FLOATS = (size_t)1 << 20, OP_PW_FLOATS = 4 * X6_PW_FRAG_WORDS;     // (X6: the largest pointwise fragments)
+static struct { float* frag; PackJob* jobs; unsigned* amax; size_t amax_cap; } g_op;
 static int op_scratch()
 {
-    if (g_op_frag) return PROBAV_OK;
-    hipError_t err = hipMalloc((void**)&g_op_frag, (size_t)4 << 20);
-    if (err == hipSuccess) err = hipMalloc((void**)&g_op_job, 4 * sizeof(PackJob));
+    hipError_t err = hipSuccess;
+    if (!g_op.frag) err = hipMalloc((void**)&g_op.frag, (OP_CONV_FLOATS + OP_PW_FLOATS) * sizeof(float));
+    if (err == hipSuccess && !g_op.jobs) err = hipMalloc((void**)&g_op.jobs, 4 * sizeof(PackJob));
     if (err != hipSuccess) { set_error("single-operator scratch allocation", err); return PROBAV_EHIP; }
     return PROBAV_OK;
 }
-// `count` zeroed slots in g_op_amax
+// `count` zeroed slots in g_op.amax
 static int op_amax_reserve(size_t count, hipStream_t s)
 {
-    if (count > g_op_amax_cap) {
+    if (count > g_op.amax_cap) {
         hipError_t err = hipStreamSynchronize(s);
-        if (err == hipSuccess && g_op_amax) err = hipFree(g_op_amax);
-        g_op_amax = nullptr; g_op_amax_cap = 0;
-        if (err == hipSuccess) err = hipMalloc((void**)&g_op_amax, (count + 1024) * sizeof(unsigned));
+        if (err == hipSuccess && g_op.amax) err = hipFree(g_op.amax);
+        g_op.amax = nullptr; g_op.amax_cap = 0;
+        if (err == hipSuccess) err = hipMalloc((void**)&g_op.amax, (count + 1024) * sizeof(unsigned));
         if (err != hipSuccess) { set_error("single-operator amax allocation", err); return PROBAV_EHIP; }
-        g_op_amax_cap = count + 1024;
+        g_op.amax_cap = count + 1024;
     }
-    if (hipMemsetAsync(g_op_amax, 0, count * sizeof(unsigned), s) != hipSuccess) { set_error("single-operator amax reset", hipGetLastError()); return PROBAV_EHIP; }
+    if (hipMemsetAsync(g_op.amax, 0, count * sizeof(unsigned), s) != hipSuccess) { set_error("single-operator amax reset", hipGetLastError()); return PROBAV_EHIP; }
     return PROBAV_OK;
 }
 // convolution operands: slots [0, N) = x per sample, [N, 2N) = output / dY per sample, [2N, 2N + cols) = filter per output column
 static int op_amax_conv(const ConvGeom& g, const float* x, const float* w, const float* dy, hipStream_t s)
 {
     int rc = op_amax_reserve((size_t)2 * g.N + 256, s);
-    if (!rc) rc = amax_tensor(x, (size_t)g.Hi * g.Wi * g.Ti * g.Cin, g.N, g_op_amax, s);
-    if (!rc && dy) rc = amax_tensor(dy, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, g_op_amax + g.N, s);
-    if (!rc && w) rc = amax_columns(w, (long)g.kh * g.kw * g.kt * g.Cin, g.Cout, g_op_amax + 2 * g.N, s);
+    if (!rc) rc = amax_tensor(x, (size_t)g.Hi * g.Wi * g.Ti * g.Cin, g.N, g_op.amax, s);
+    if (!rc && dy) rc = amax_tensor(dy, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, g_op.amax + g.N, s);
+    if (!rc && w) rc = amax_columns(w, (long)g.kh * g.kw * g.kt * g.Cin, g.Cout, g_op.amax + 2 * g.N, s);
     return rc;
 }
-static int op_pack(const ConvGeom& g, const float* w, hipStream_t s, int split = 0, bool per_tap = false)   // split: 0 fp32 fragments, 1 X6, 2 H3
+// packs `n` jobs into g_op.frag once the stream has drained (the previous call may still read the fragments)
+static int op_pack_jobs(const PackJob* J, int n, const float* weff, const float* weffT, hipStream_t s, const char* what)
 {
-    const size_t n = split ? (size_t)X6_CONV_FRAG_WORDS : mfma_conv_wfrag_floats(g.Cin, g.Cout);
-    if (n == 0) { set_error("probav_conv3d_forward: channel configuration not supported by the MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
-    int rc = op_scratch();
-    if (rc) return rc;
-    if (n * sizeof(float) > ((size_t)4 << 20)) { set_error("probav_conv3d_forward: fragment scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
-    PackJob J; memset(&J, 0, sizeof(J));
-    if (split) {
-        const bool kc = g.Cin == 25 && !per_tap;                            // K-concatenated form (per_tap: the H3 piece-ring strip kernel)
-        J.type = kc ? PACK_X6_CONVK : PACK_X6_CONV; J.count = kc ? X6_CONVK_FRAG_WORDS : X6_CONV_FRAG_WORDS; J.Cin = g.Cin; J.Cout = g.Cout; J.taps = 27;
-        if (split == 2) { J.type += 10; J.count = kc ? H3_CONVK_FRAG_WORDS : H3_CONV_FRAG_WORDS; J.amax_percol = 1; J.ncol = g.Cout; J.amax_slot = 2 * g.N; }
-        if (split == 2 && g.Cin == 25 && per_tap) { J.type = PACK_H3_CONVP; J.count = H3_CONVK_FRAG_WORDS; }
-    } else mfma_conv_pack_job(J, g.Cin, g.Cout);
     hipError_t err = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = hipMemcpy(g_op_job, &J, sizeof(J), hipMemcpyHostToDevice);
-    if (err != hipSuccess) { set_error("probav_conv3d_forward: job upload", err); return PROBAV_EHIP; }
-    return mfma_pack(g_op_job, 1, w, w, g_op_frag, g_op_amax, s);
+    if (err == hipSuccess) err = hipMemcpy(g_op.jobs, J, n * sizeof(PackJob), hipMemcpyHostToDevice);
+    if (err != hipSuccess) { set_error(what, err); return PROBAV_EHIP; }
+    return mfma_pack(g_op.jobs, n, weff, weffT, g_op.frag, g_op.amax, s);
+}
+// the filter of a convolution in arithmetic `arith` (per_tap: the per-tap H3 form of 25 channels) -> g_op.frag
+static int op_pack(const ConvGeom& g, const float* w, hipStream_t s, int arith, bool per_tap)
+{
+    PackJob J = pack_job(per_tap ? Operand::conv_taps : Operand::conv, arith, g.Cin, g.Cout);
+    if (J.count == 0) { set_error("probav_conv3d_forward: channel configuration not supported by the MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
+    CK(op_scratch());
+    if ((size_t)J.count > OP_CONV_FLOATS) { set_error("probav_conv3d_forward: fragment scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
+    if (arith == 2) J.amax_slot = 2 * g.N;
+    return op_pack_jobs(&J, 1, w, w, s, "probav_conv3d_forward: job upload");
 }
 
 int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* gate, const float* w, const float* bias,
@@ -1150,31 +1195,30 @@ int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* g
     const ConvGeom g = geom_from(geom);
     if (!geom_ok(g)) { set_error("probav_conv3d_forward: bad geometry", hipSuccess); return PROBAV_EINVAL; }
     if (impl < 0 || impl > 4) { set_error("probav_conv3d_forward: impl must be 0..4", hipSuccess); return PROBAV_EINVAL; }
+    const hipStream_t s = (hipStream_t)stream;
     // (what the engine does for these two geometries in every kernel family but 0)
-    if (impl >= 1 && !gate && !skip && bias && conv3d_up_forward_supported(g)) return conv3d_up_forward(g, x, w, bias, y, (hipStream_t)stream);
-    if (impl >= 1 && !gate && !skip && !g.relu && conv3d_up_bwd_data_supported(g)) return conv3d_up_bwd_data(g, x, w, bias, y, nullptr, (hipStream_t)stream);
-    if (impl >= 1) {
-        const bool pstrip = impl == 4 && x6_strip_wants_tap_fragments(g, 2);
-        const bool x6row = impl >= 3 && !mfma_conv_strip_supported(g) && !pstrip && x6_conv_rowtile_supported(g);
-        const bool okk = x6row || pstrip || (impl >= 2 ? mfma_conv_strip_supported(g) : mfma_conv_supported(g));
-        if (!okk) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
-        int rc = op_scratch();
-        if (rc) return rc;
-        Amax am;
-        if (impl == 4) {
-            if (g.Cout > 256) { set_error("probav_conv3d_forward: Cout > 256", hipSuccess); return PROBAV_EINVAL; }
-            rc = op_amax_conv(g, x, w, nullptr, (hipStream_t)stream);
-            if (rc) return rc;
-            am.x = g_op_amax; am.w = g_op_amax + 2 * g.N; am.y = g_op_amax + g.N;
-        }
-        rc = op_pack(g, w, (hipStream_t)stream, impl >= 3 ? impl - 2 : 0, pstrip);
-        if (rc) return rc;
-        if (x6row) return x6_conv_rowtile_forward(g, x, gate, g_op_frag, bias, skip, y, impl - 2, am, (hipStream_t)stream);
-        if (impl >= 3) return x6_conv_strip_forward(g, x, gate, g_op_frag, bias, skip, y, impl - 2, am, (hipStream_t)stream);
-        if (impl == 2) return mfma_conv_strip_forward(g, x, gate, g_op_frag, bias, skip, y, am, (hipStream_t)stream);
-        return mfma_conv_forward(g, x, gate, g_op_frag, bias, skip, y, am, (hipStream_t)stream);
+    if (impl >= 1 && !gate && !skip && bias && conv3d_up_forward_supported(g)) return conv3d_up_forward(g, x, w, bias, y, s);
+    if (impl >= 1 && !gate && !skip && !g.relu && conv3d_up_bwd_data_supported(g)) return conv3d_up_bwd_data(g, x, w, bias, y, nullptr, s);
+    if (impl == 0) return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
+    // impl 1 the MFMA row-tile kernel, 2 the strip kernel, 3 / 4 the x6 strip kernel (X6 / H3; the piece-ring form where it applies) or, where
+    // the strip kernels do not apply, its row-tile form; a geometry the chosen kernel does not cover is refused
+    const int arith = impl >= 3 ? impl - 2 : 0;
+    const bool pstrip = impl == 4 && x6_strip_wants_tap_fragments(g, 2);
+    const bool x6row = impl >= 3 && !mfma_conv_strip_supported(g) && !pstrip && x6_conv_rowtile_supported(g);
+    const bool okk = x6row || pstrip || (impl >= 2 ? mfma_conv_strip_supported(g) : mfma_conv_supported(g));
+    if (!okk) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
+    CK(op_scratch());
+    Amax am;
+    if (impl == 4) {
+        if (g.Cout > 256) { set_error("probav_conv3d_forward: Cout > 256", hipSuccess); return PROBAV_EINVAL; }
+        CK(op_amax_conv(g, x, w, nullptr, s));
+        am.x = g_op.amax; am.w = g_op.amax + 2 * g.N; am.y = g_op.amax + g.N;
     }
-    return conv3d_direct_forward(g, x, gate, w, bias, skip, y, (hipStream_t)stream);
+    CK(op_pack(g, w, s, arith, pstrip));
+    if (x6row) return x6_conv_rowtile_forward(g, x, gate, g_op.frag, bias, skip, y, arith, am, s);
+    if (arith) return x6_conv_strip_forward(g, x, gate, g_op.frag, bias, skip, y, arith, am, s);
+    if (impl == 2) return mfma_conv_strip_forward(g, x, gate, g_op.frag, bias, skip, y, am, s);
+    return mfma_conv_forward(g, x, gate, g_op.frag, bias, skip, y, am, s);
 }
 
 size_t probav_conv3d_wgrad_scratch_bytes(const int32_t geom[17], int impl)
@@ -1197,10 +1241,9 @@ int probav_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy,
         if (scratch_bytes < x6_wgrad_partial_floats(g) * sizeof(float)) { set_error("probav_conv3d_wgrad: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
         Amax am;
         if (impl == 4) {
-            int rc = op_scratch();
-            if (!rc) rc = op_amax_conv(g, x, nullptr, dy, (hipStream_t)stream);
-            if (rc) return rc;
-            am.x = g_op_amax; am.w = g_op_amax + g.N;
+            CK(op_scratch());
+            CK(op_amax_conv(g, x, nullptr, dy, (hipStream_t)stream));
+            am.x = g_op.amax; am.w = g_op.amax + g.N;
         }
         return x6_conv_wgrad(g, x, dy, gate, dw, db, (float*)scratch, impl == 4 ? 2 : 1, am, (hipStream_t)stream);
     }
@@ -1213,57 +1256,25 @@ int probav_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy,
     return conv3d_direct_wgrad(g, x, dy, gate, dw, db, (float*)scratch, (hipStream_t)stream);
 }
 
-// fused pointwise pair, single-operator form (packs the Keras-layout weights into MFMA fragments in library scratch)
-static int op_pack_pw(const float* w1, const float* w2, int D, hipStream_t s, const float** f1, const float** f2, const float** f2b, const float** f1c)
+// the fused pointwise pair, single-operator form: its four fragments of W1 [32][256], W2 [256][D] in arithmetic `arith`, behind the conv area
+// of g_op.frag.  H3: the weights' amax must already be in the slots op_amax_pw lays out (wbase = index of the first weight slot)
+static int op_pack_pw(const float* w1, const float* w2, int D, int arith, int wbase, hipStream_t s, PwOps& f)
 {
-    { int rc0 = op_scratch(); if (rc0) return rc0; }
-    static PackJob* d_jobs4 = nullptr;
-    if (!d_jobs4) { hipError_t err = hipMalloc((void**)&d_jobs4, 4 * sizeof(PackJob)); if (err != hipSuccess) { set_error("probav_pw: job allocation", err); return PROBAV_EHIP; } }
-    PackJob J[4]; memset(J, 0, sizeof(J));
-    const int types[4] = {PACK_PW_A_KCIN, PACK_PW_A_KHCH, PACK_PW_A_KOUT, PACK_PW_A_CIN_KHCH};
+    CK(op_scratch());
+    const Operand ops[4] = {Operand::pw_w1, Operand::pw_w2, Operand::pw_w2b, Operand::pw_w1c};
+    const int slot[4] = {wbase + 0, wbase + 8, wbase + 1, wbase + 40};
+    const float* out[4];
+    PackJob J[4];
     for (int k = 0; k < 4; ++k) {
-        J[k].type = types[k]; J[k].count = 8192; J[k].dst_off = 262144 + 8192 * k;       // behind the conv fragment area
-        const bool from_w1 = (k == 0 || k == 3);
-        J[k].src_is_T = from_w1 ? 0 : 1;                                                  // weff := w1, weffT := w2
-        J[k].Cin = from_w1 ? 32 : 256; J[k].Cout = from_w1 ? 256 : D;
+        const bool from_w1 = ops[k] == Operand::pw_w1 || ops[k] == Operand::pw_w1c;
+        J[k] = pack_job(ops[k], arith, from_w1 ? 32 : 256, from_w1 ? 256 : D);
+        J[k].src_is_T = from_w1 ? 0 : 1;                                                 // weff := w1, weffT := w2
+        J[k].dst_off = (long)(OP_CONV_FLOATS + k * X6_PW_FRAG_WORDS);
+        if (arith == 2) J[k].amax_slot = slot[k];
+        out[k] = g_op.frag + J[k].dst_off;
     }
-    hipError_t err = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = hipMemcpy(d_jobs4, J, sizeof(J), hipMemcpyHostToDevice);
-    if (err != hipSuccess) { set_error("probav_pw: job upload", err); return PROBAV_EHIP; }
-    *f1 = g_op_frag + J[0].dst_off; *f2 = g_op_frag + J[1].dst_off; *f2b = g_op_frag + J[2].dst_off; *f1c = g_op_frag + J[3].dst_off;
-    return mfma_pack(d_jobs4, 4, w1, w2, g_op_frag, nullptr, s);
-}
-
-// h3: PACK_H3_* fragments; the weights' amax must already be in the slots op_amax_pw lays out (wbase = index of the first weight slot)
-static int op_pack_pw_x6(const float* w1, const float* w2, int D, hipStream_t s, const float** f1, const float** f2,
-                         const float** f2k = nullptr, const float** f1c = nullptr, bool h3 = false, int wbase = 0)
-{
-    static float* frag = nullptr;
-    static PackJob* d_jobs = nullptr;
-    if (!frag) {
-        hipError_t err = hipMalloc((void**)&frag, (size_t)4 * X6_PW_FRAG_WORDS * 4);
-        if (err == hipSuccess) err = hipMalloc((void**)&d_jobs, 4 * sizeof(PackJob));
-        if (err != hipSuccess) { set_error("probav_pw (x6): scratch allocation", err); return PROBAV_EHIP; }
-    }
-    PackJob J[4]; memset(J, 0, sizeof(J));
-    J[2].type = PACK_X6_PW_W2K; J[2].src_is_T = 1; J[2].dst_off = 2 * X6_PW_FRAG_WORDS; J[2].count = X6_PW_FRAG_WORDS; J[2].Cin = 256; J[2].Cout = D;
-    J[3].type = PACK_X6_PW_W1C; J[3].src_is_T = 0; J[3].dst_off = 3 * X6_PW_FRAG_WORDS; J[3].count = X6_PW_FRAG_WORDS; J[3].Cin = 32; J[3].Cout = 256;
-    J[0].type = PACK_X6_PW_W1; J[0].src_is_T = 0; J[0].dst_off = 0; J[0].count = X6_PW_FRAG_WORDS; J[0].Cin = 32; J[0].Cout = 256;
-    J[1].type = PACK_X6_PW_W2; J[1].src_is_T = 1; J[1].dst_off = X6_PW_FRAG_WORDS; J[1].count = X6_PW_FRAG_WORDS; J[1].Cin = 256; J[1].Cout = D;
-    if (h3) {
-        for (int k = 0; k < 4; ++k) { J[k].type += 10; J[k].count = H3_PW_FRAG_WORDS; }
-        J[0].amax_slot = wbase + 0;                                              // W1 as the operand of (a): one scale
-        J[2].amax_slot = wbase + 1;                                              // W2 as the operand of (b): one scale
-        J[1].amax_percol = 1; J[1].ncol = D; J[1].amax_slot = wbase + 8;         // W2 forward: per output column d
-        J[3].amax_percol = 1; J[3].ncol = 32; J[3].amax_slot = wbase + 40;       // W1 as the operand of (c): per cin row
-    }
-    hipError_t err = hipStreamSynchronize(s);
-    if (err == hipSuccess) err = hipMemcpy(d_jobs, J, sizeof(J), hipMemcpyHostToDevice);
-    if (err != hipSuccess) { set_error("probav_pw (x6): job upload", err); return PROBAV_EHIP; }
-    *f1 = frag; *f2 = frag + X6_PW_FRAG_WORDS;
-    if (f2k) *f2k = frag + 2 * X6_PW_FRAG_WORDS;
-    if (f1c) *f1c = frag + 3 * X6_PW_FRAG_WORDS;
-    return mfma_pack(d_jobs, 4, w1, w2, frag, g_op_amax, s);
+    f = {out[0], out[1], out[2], out[3]};
+    return op_pack_jobs(J, 4, w1, w2, s, "probav_pw: job upload");
 }
 // amax of the operands of a single-operator call of the fused pointwise pair, ns samples: [0, ns) x, [ns, 2ns) d_dec, [2ns, 3ns) output;
 // wbase = 3 ns: +0 w1, +1 w2, +2 b1 (whole tensors), +8 .. w2 per output column, +40 .. w1 per input row
@@ -1273,18 +1284,20 @@ static int op_amax_pw(const float* x, const float* w1, const float* w2, const fl
     if (rc) return rc;
     const int ns = (int)(nvox / vps), wb = 3 * ns;
     rc = op_amax_reserve((size_t)wb + 80, s);
-    if (!rc) rc = amax_tensor(x, (size_t)vps * 32, ns, g_op_amax, s);
-    if (!rc && d_dec) rc = amax_tensor(d_dec, (size_t)vps * D, ns, g_op_amax + ns, s);
-    if (!rc) rc = amax_tensor(w1, 32 * 256, 1, g_op_amax + wb + 0, s);
-    if (!rc) rc = amax_tensor(w2, (size_t)256 * D, 1, g_op_amax + wb + 1, s);
-    if (!rc) rc = amax_tensor(b1, 256, 1, g_op_amax + wb + 2, s);
-    if (!rc) rc = amax_columns(w2, 256, D, g_op_amax + wb + 8, s);
-    if (!rc) rc = amax_tensor(w1, 256, 32, g_op_amax + wb + 40, s);              // rows of W1 [32][256]
-    m.x = g_op_amax; m.dt = g_op_amax + ns; m.y = g_op_amax + 2 * ns;
-    m.w1 = g_op_amax + wb; m.w2 = g_op_amax + wb + 1; m.b1 = g_op_amax + wb + 2; m.w2c = g_op_amax + wb + 8; m.w1r = g_op_amax + wb + 40;
+    unsigned* a = g_op.amax;
+    if (!rc) rc = amax_tensor(x, (size_t)vps * 32, ns, a, s);
+    if (!rc && d_dec) rc = amax_tensor(d_dec, (size_t)vps * D, ns, a + ns, s);
+    if (!rc) rc = amax_tensor(w1, 32 * 256, 1, a + wb + 0, s);
+    if (!rc) rc = amax_tensor(w2, (size_t)256 * D, 1, a + wb + 1, s);
+    if (!rc) rc = amax_tensor(b1, 256, 1, a + wb + 2, s);
+    if (!rc) rc = amax_columns(w2, 256, D, a + wb + 8, s);
+    if (!rc) rc = amax_tensor(w1, 256, 32, a + wb + 40, s);              // rows of W1 [32][256]
+    m.x = a; m.dt = a + ns; m.y = a + 2 * ns;
+    m.w1 = a + wb; m.w2 = a + wb + 1; m.b1 = a + wb + 2; m.w2c = a + wb + 8; m.w1r = a + wb + 40;
     return rc;
 }
 
+// impl 2: the fp32-MFMA kernels, 3 / 4: the split-operand ones (X6 / H3)
 int probav_pw_forward(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* dec,
                       int64_t nvox, int64_t vox_per_sample, int D, int impl, void* stream)
 {
@@ -1292,21 +1305,12 @@ int probav_pw_forward(const float* x, const float* w1, const float* b1, const fl
     if (!mfma_pw_supported(32, 256, D)) { set_error("probav_pw_forward: needs F=32, E=256, D<=26", hipSuccess); return PROBAV_EINVAL; }
     long vps = vox_per_sample > 0 ? (long)vox_per_sample : (long)nvox;
     if (nvox % vps) { set_error("probav_pw_forward: nvox is not a multiple of vox_per_sample", hipSuccess); return PROBAV_EINVAL; }
-    if (impl >= 3) {
-        const float *g1, *g2;
-        PwAmax am;
-        if (impl == 4) {
-            int rc = op_amax_pw(x, w1, w2, b1, nullptr, (long)nvox, vps, D, (hipStream_t)stream, am);
-            if (rc) return rc;
-        }
-        int rc = op_pack_pw_x6(w1, w2, D, (hipStream_t)stream, &g1, &g2, nullptr, nullptr, impl == 4, 3 * (int)(nvox / vps));
-        if (rc) return rc;
-        return x6_pw_forward(x, g1, g2, b1, b2, dec, (long)nvox, vps, D, impl - 2, am, (hipStream_t)stream);
-    }
-    const float *f1, *f2, *f2b, *f1c;
-    int rc = op_pack_pw(w1, w2, D, (hipStream_t)stream, &f1, &f2, &f2b, &f1c);
-    if (rc) return rc;
-    return mfma_pw_forward(x, f1, f2, b1, b2, dec, (long)nvox, D, (hipStream_t)stream);
+    const hipStream_t s = (hipStream_t)stream;
+    PwAmax am;
+    if (impl == 4) CK(op_amax_pw(x, w1, w2, b1, nullptr, (long)nvox, vps, D, s, am));
+    PwOps f;
+    CK(op_pack_pw(w1, w2, D, impl - 2, 3 * (int)(nvox / vps), s, f));
+    return pw_forward(impl - 2, f, x, b1, b2, dec, (long)nvox, vps, D, am, s);
 }
 
 size_t probav_pw_backward_scratch_bytes(int D) { return mfma_pw_backward_slab_floats(D) * sizeof(float); }
@@ -1322,20 +1326,12 @@ int probav_pw_backward(const float* x, const float* d_dec, const float* d_skip, 
     if (scratch_bytes < probav_pw_backward_scratch_bytes(D)) { set_error("probav_pw_backward: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
     long vps = vox_per_sample > 0 ? (long)vox_per_sample : (long)nvox;
     if (nvox % vps) { set_error("probav_pw_backward: nvox is not a multiple of vox_per_sample", hipSuccess); return PROBAV_EINVAL; }
-    const float *f1, *f2, *f2b, *f1c;
-    if (impl >= 3) {
-        PwAmax am;
-        if (impl == 4) {
-            int rc = op_amax_pw(x, w1, w2, b1, d_dec, (long)nvox, vps, D, (hipStream_t)stream, am);
-            if (rc) return rc;
-        }
-        int rc = op_pack_pw_x6(w1, w2, D, (hipStream_t)stream, &f1, &f2, &f2b, &f1c, impl == 4, 3 * (int)(nvox / vps));
-        if (rc) return rc;
-        return x6_pw_backward(x, d_dec, d_skip, f1, f2b, f1c, b1, dx, dw1, dw2, db1, db2, (float*)scratch, (long)nvox, vps, D, impl - 2, am, (hipStream_t)stream);
-    }
-    int rc = op_pack_pw(w1, w2, D, (hipStream_t)stream, &f1, &f2, &f2b, &f1c);
-    if (rc) return rc;
-    return mfma_pw_backward(x, d_dec, d_skip, f1, f2b, f1c, b1, dx, dw1, dw2, db1, db2, (float*)scratch, (long)nvox, D, (hipStream_t)stream);
+    const hipStream_t s = (hipStream_t)stream;
+    PwAmax am;
+    if (impl == 4) CK(op_amax_pw(x, w1, w2, b1, d_dec, (long)nvox, vps, D, s, am));
+    PwOps f;
+    CK(op_pack_pw(w1, w2, D, impl - 2, 3 * (int)(nvox / vps), s, f));
+    return pw_backward(impl - 2, f, x, d_dec, d_skip, b1, dx, dw1, dw2, db1, db2, (float*)scratch, (long)nvox, vps, D, am, s);
 }
 
 int probav_wn_forward(probav_engine* e, const float* params, float* weff, float* weffT, float* inv_norm, void* stream)
