@@ -289,6 +289,20 @@ int probav_score_moments(const uint16_t* sr, const uint16_t* hr, const uint8_t* 
 int probav_score_select(const int64_t* moments, int64_t n_images, int border, double* cpsnr, int32_t* shift, double* bias,
                         int64_t* n_clear, void* stream);
 
+/* ---- batch augmentation (proba-v_amd/augment.py), an addition of ABI 7 ------------------------------------------------------------- */
+/* One launch builds a training batch from the device-resident UN-augmented patches: lr [n_base][H][H][T][C] fp32, hr [n_base][S][S] fp32,
+ * mask [n_base][S][S] uint8 (copied as bytes).  recipe [batch][3 + T] int32, row b = {i, f, k, perm[0..T)}: base sample i, flip code f
+ * (0 none, 1 axis 0, 2 axis 1, 3 both), k counter-clockwise quarter turns, frame permutation perm.  In numpy terms, on one sample:
+ *     lr_b[b] = rot90(flip(lr[i][:, :, perm], FL[f]), k)    hr_b[b] = rot90(flip(hr[i], FL[f]), k)    mask_b[b] likewise
+ * (flip first, then rotate).  Outputs lr_b [batch][H][H][T][C], hr_b / mask_b [batch][S][S]; bits are moved, never computed with.
+ * A row with i outside [0, n_base), f or k outside 0..3 or a perm entry outside [0, T) is skipped (its outputs are left as they were):
+ * nothing is read outside the base arrays.  1 <= T <= 64, 1 <= C <= 16, H, S <= 1024 and one sample of each tensor must fit 64 KiB of
+ * LDS beside a row table.  Kernel: csrc/kernels_augment.hip.
+ *                                         replaces augmentByShufflingLRImgs / augmentByFlipping / augmentByRotating and the 320 x data
+ *                                         set they materialise                                        utils/dataGenerator.py:227-273 */
+int probav_augment_batch(const float* lr, const float* hr, const uint8_t* mask, int64_t n_base, int H, int T, int C, int S,
+                         const int32_t* recipe, int64_t batch, float* lr_b, float* hr_b, uint8_t* mask_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,9 @@ SIGNATURES = {
     # scoring (csrc/kernels_score.hip)
     "probav_score_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "probav_score_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # batch augmentation (csrc/kernels_augment.hip)
+    "probav_augment_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
 }
 
 _lib = None

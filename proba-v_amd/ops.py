@@ -17,6 +17,8 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::esa_shift_moments(sr, hr, mask, border) -> moments int64 [N, (2b+1)^2, 3]       (n, s1, s2) of every shift, exact
   probav::esa_shift_cpsnr(sr, hr, mask, border) -> (cpsnr f64[N], shift i32[N,2], bias f64[N], n_clear i64[N])
                                                                             the ESA cPSNR of whole images   evaluate.py:76-87 (scoring.py)
+  probav::augment_batch(lr, hr, mask, recipe) -> (lr_b, hr_b, mask_b)      a training batch from the un-augmented patches: frame permutation,
+                                                                            flip, quarter turns per sample   utils/dataGenerator.py:227-273 (augment.py)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -363,6 +365,52 @@ def _(sr, hr, mask, border):
     N = sr.shape[0]
     return (sr.new_empty((N,), dtype=torch.float64), sr.new_empty((N, 2), dtype=torch.int32), sr.new_empty((N,), dtype=torch.float64),
             sr.new_empty((N,), dtype=torch.int64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# batch augmentation (csrc/kernels_augment.hip; the recipes are made and validated in augment.py).  No autograd: it moves input bits.
+# lr [N, H, H, T, C] fp32, hr [N, S, S, 1] fp32, mask [N, S, S, 1] bool or uint8, recipe [B, 3 + T] int32 rows {i, f, k, perm}.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _augment_args(lr, hr, mask, recipe):
+    if lr.dim() != 5 or hr.dim() != 4 or mask.shape != hr.shape or hr.shape[3] != 1 or hr.shape[0] != lr.shape[0] or recipe.dim() != 2:
+        raise ValueError("augment_batch: lr [N, H, H, T, C], hr / mask [N, S, S, 1], recipe [B, 3 + T]; got %s %s %s %s"
+                         % (tuple(lr.shape), tuple(hr.shape), tuple(mask.shape), tuple(recipe.shape)))
+    if lr.shape[1] != lr.shape[2] or hr.shape[1] != hr.shape[2]:
+        raise ValueError("augment_batch: square patches only (a quarter turn needs them); got lr %s, hr %s" % (tuple(lr.shape), tuple(hr.shape)))
+    if lr.dtype != torch.float32 or hr.dtype != torch.float32 or mask.dtype not in (torch.bool, torch.uint8) or recipe.dtype != torch.int32:
+        raise ValueError("augment_batch: lr / hr must be float32, mask bool or uint8, recipe int32; got %s %s %s %s"
+                         % (lr.dtype, hr.dtype, mask.dtype, recipe.dtype))
+    if recipe.shape[1] != 3 + lr.shape[3]:
+        raise ValueError("augment_batch: a recipe row is {i, f, k, perm[%d]}; got %d columns" % (lr.shape[3], recipe.shape[1]))
+    if lr.shape[0] < 1:
+        raise ValueError("augment_batch: empty base set")
+
+
+@torch.library.custom_op("probav::augment_batch", mutates_args=(), device_types="cuda")
+def augment_batch(lr: Tensor, hr: Tensor, mask: Tensor, recipe: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """(lr_b [B, H, H, T, C], hr_b [B, S, S, 1], mask_b [B, S, S, 1]): out[b] = rot90(flip(x[i][:, :, perm] if LR else x[i], FL[f]), k) for
+    recipe[b] = {i, f, k, perm}: one launch for the three tensors.  The kernel skips a row it could not apply without reading outside the base
+    arrays; callers validate recipes on the host (augment.DeviceDataset does)."""
+    _augment_args(lr, hr, mask, recipe)
+    for t, name in ((lr, "lr"), (hr, "hr"), (mask, "mask"), (recipe, "recipe")):
+        _dev(t, name)
+    lr, hr, mask, recipe = lr.contiguous(), hr.contiguous(), mask.contiguous(), recipe.contiguous()
+    B = recipe.shape[0]
+    lr_b = torch.empty((B,) + tuple(lr.shape[1:]), dtype=lr.dtype, device=lr.device)
+    hr_b = torch.empty((B,) + tuple(hr.shape[1:]), dtype=hr.dtype, device=lr.device)
+    mask_b = torch.empty((B,) + tuple(mask.shape[1:]), dtype=mask.dtype, device=lr.device)
+    if B:
+        _lib.check(_lib.lib().probav_augment_batch(_lib.ptr(lr), _lib.ptr(hr), _lib.ptr(mask), lr.shape[0], lr.shape[1], lr.shape[3], lr.shape[4],
+                                                   hr.shape[1], _lib.ptr(recipe), B, _lib.ptr(lr_b), _lib.ptr(hr_b), _lib.ptr(mask_b),
+                                                   _lib.current_stream()), "probav_augment_batch")
+    return lr_b, hr_b, mask_b
+
+
+@augment_batch.register_fake
+def _(lr, hr, mask, recipe):
+    _augment_args(lr, hr, mask, recipe)
+    B = recipe.shape[0]
+    return lr.new_empty((B,) + tuple(lr.shape[1:])), hr.new_empty((B,) + tuple(hr.shape[1:])), mask.new_empty((B,) + tuple(mask.shape[1:]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

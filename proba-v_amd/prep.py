@@ -344,7 +344,10 @@ def augmentByRotating(patches):
 
 
 # ---- driver (utils/dataGenerator.py:33-273) ---------------------------------------------------------------------------------------
-def main(config, band, rng=None):
+def main(config, band, rng=None, online_aug=False):
+    """online_aug: stage 5 draws the frame permutations as ever (same rng, same order) but SAVES them beside the un-augmented training
+    arrays instead of applying them -- TRAINbasepatches{LR,HR}_<band>.npy and TRAINaugperms_<band>.npy, what `train.py --online-aug` reads
+    (probav_amd.augment).  The TRAINVAL dumps do not depend on it."""
     log = logging.getLogger("dataGenerator")
     if band not in ('NIR', 'RED'):
         raise ValueError("band must be NIR or RED, got %r" % band)
@@ -417,6 +420,13 @@ def main(config, band, rng=None):
         lr, lrVal, hr, hrVal = splitPatches(lr, hr, config)
         lrVal.dump(path('augmentedPatchesDir', 'TRAINVALpatchesLR'), protocol=4)
         hrVal.dump(path('augmentedPatchesDir', 'TRAINVALpatchesHR'), protocol=4)
+        if online_aug:
+            from .augment import draw_perms
+            perms = draw_perms(config['num_low_res_permute'], lr.shape[3], rng)      # the draws augmentByShufflingLRImgs would make
+            lr.dump(path('augmentedPatchesDir', 'TRAINbasepatchesLR'), protocol=4)
+            hr.dump(path('augmentedPatchesDir', 'TRAINbasepatchesHR'), protocol=4)
+            np.save(path('augmentedPatchesDir', 'TRAINaugperms'), perms)
+            return
         lr = augmentByShufflingLRImgs(lr, numPermute=config['num_low_res_permute'], rng=rng)
         if config['to_flip']:
             lr = augmentByFlipping(lr)

@@ -608,11 +608,13 @@ class ModelTrainer:
 
     # -- training loop (models/trainClass.py:61-122) ---------------------------------------------------
     def fitTrainData(self, X, y, globalBatchSize, epochs, valData, bufferSize=256, valSteps=64,
-                     saveBestOnly=True, initEpoch=0, seed=0):
+                     saveBestOnly=True, initEpoch=0, seed=0, augment=None):
+        """augment: an augment.AugmentSpec -- X, y are then the UN-augmented arrays; they are uploaded once and every batch is built on the device
+        from the virtual augmented set the spec describes (augment.py), over the index stream the materialised set would be walked by."""
         logger.info("[ INFO ] Loading data set to buffer cache...")
         yHR, yMask = y[0], y[1]
         rank, world = self._rank(), self._world()
-        if world > 1 and self.multiGPU:
+        if world > 1 and self.multiGPU and augment is None:        # (augment: the shard is taken on the VIRTUAL indices below)
             # per-replica batch = cfg batch (debug/trainClassMultiGPU0.py:67-73).  Every rank gets EXACTLY len(X) // world samples
             # (the tail of an indivisible data set is dropped): equal shard lengths give every rank the same number of batches, so the
             # per-step gradient all-reduce never waits for a rank that has already finished.
@@ -621,6 +623,11 @@ class ModelTrainer:
         rng = np.random.default_rng(seed + rank)                 # training order: consumed by the prefetch thread only
         vrng = np.random.default_rng(seed + 7919)                # validation order: its own stream, the same on every rank
         dataSetLength = len(X)
+        if augment is not None:
+            from . import augment as aug
+            sharded = world > 1 and self.multiGPU
+            dataSetLength, virtual = aug.virtual_index_batches(len(X) * augment.multiplicity, rank if sharded else 0, world if sharded else 1,
+                                                               epochs, globalBatchSize, bufferSize, rng)
         totalSteps = int(dataSetLength / globalBatchSize)           # tf.cast(len/batch, int64) truncates (:75)
         if totalSteps < 1:
             raise ValueError("data set (%d) smaller than one batch (%d)" % (dataSetLength, globalBatchSize))
@@ -628,9 +635,15 @@ class ModelTrainer:
         step = globalStep % totalSteps
         epoch = initEpoch
         logger.info("[ INFO ] Begin training...")
-        mask_dtype = torch.as_tensor(np.asarray(yMask[:1])).dtype
-        batches = BatchPrefetcher((X, yHR, yMask), (torch.float32, torch.float32, mask_dtype),
-                                  shuffle_repeat_batch(dataSetLength, epochs, globalBatchSize, bufferSize, rng), self._device())
+        if augment is not None:
+            dataset = aug.DeviceDataset(X, yHR, yMask, self._device())
+            logger.info("[ INFO ] %d un-augmented samples on the device (%d bytes), augmented per batch: %d virtual samples", len(dataset), dataset.nbytes,
+                        len(dataset) * augment.multiplicity)
+            batches = dataset.batches(virtual, augment)
+        else:
+            mask_dtype = torch.as_tensor(np.asarray(yMask[:1])).dtype
+            batches = BatchPrefetcher((X, yHR, yMask), (torch.float32, torch.float32, mask_dtype),
+                                      shuffle_repeat_batch(dataSetLength, epochs, globalBatchSize, bufferSize, rng), self._device())
 
         def emit(vals, meta):
             ep, st, gs = meta

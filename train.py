@@ -30,6 +30,8 @@ def parser():
     p.add_argument("--cfg", default="cfg/yourcfg.cfg", type=str)
     p.add_argument("--band", type=str, default="NIR")
     p.add_argument("--modelType", type=str, default="patchNet")
+    p.add_argument("--online-aug", dest="online_aug", action="store_true",
+                   help="train from the un-augmented patches of `utils/dataGenerator.py --online-aug`: every batch is augmented on the GPU")
     return p.parse_args()
 
 
@@ -45,8 +47,15 @@ def patchNet(config, opt):
     logger.info("[ INFO ] Loading data...")
     dataDir = os.path.join(config["preprocessing_out"], "augmentedPatchesDir")
     load = lambda n: np.load(os.path.join(dataDir, n % opt.band), allow_pickle=True)
-    X_train, X_val = load("TRAINpatchesLR_%s.npy"), load("TRAINVALpatchesLR_%s.npy")
-    y_train, y_val = load("TRAINpatchesHR_%s.npy"), load("TRAINVALpatchesHR_%s.npy")
+    augment = None
+    if opt.online_aug:
+        # the un-augmented arrays and the permutation table stage 5 saved: the augmented set stays virtual (probav_amd/augment.py)
+        from probav_amd.augment import AugmentSpec
+        X_train, y_train = load("TRAINbasepatchesLR_%s.npy"), load("TRAINbasepatchesHR_%s.npy")
+        augment = AugmentSpec.from_config(config, load("TRAINaugperms_%s.npy"))
+    else:
+        X_train, y_train = load("TRAINpatchesLR_%s.npy"), load("TRAINpatchesHR_%s.npy")
+    X_val, y_val = load("TRAINVALpatchesLR_%s.npy"), load("TRAINVALpatchesHR_%s.npy")
     y_train_mask, y_val_mask = ~np.ma.getmaskarray(y_train), ~np.ma.getmaskarray(y_val)      # True = clear pixel
     mean, std = BAND_STATS["NIR" if opt.band == "NIR" else "RED"]
     X_train, X_val, y_train, y_val = (np.array(a) for a in (X_train, X_val, y_train, y_val))
@@ -68,7 +77,7 @@ def patchNet(config, opt):
     trainer = ModelTrainer(model=model, loss=type_loss, metric=loss.shiftCompensatedcPSNR, optimizer=optimizer,
                            ckptDir=ckptDir, logDir=logDir)
     trainer.fitTrainData(X_train, [y_train, y_train_mask], config["batch_size"], config["epochs"],
-                         [X_val, y_val, y_val_mask], saveBestOnly=False, initEpoch=0)
+                         [X_val, y_val, y_val_mask], saveBestOnly=False, initEpoch=0, augment=augment)
     logger.info("[ SUCCESS ] Model checkpoint can be found in %s." % ckptDir)
     logger.info("[ SUCCESS ] Model logs can be found in %s." % logDir)
 

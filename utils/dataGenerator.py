@@ -3,7 +3,10 @@ train.py and test.py read.  Runs on the GPU (probav_amd.prep); the same cfg keys
 reference.  --seed N seeds the frame picking and LR shuffling (equal to the reference after np.random.seed(N)); without it the run is
 unseeded, as the reference's is.
 
-    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0]
+    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0] [--online-aug]
+
+--online-aug: stage 5 writes the un-augmented training patches and the frame permutations it drew (TRAINbasepatches{LR,HR}_<band>.npy,
+TRAINaugperms_<band>.npy) instead of the augmented set; `train.py --online-aug` augments every batch on the GPU from them.
 """
 import argparse
 import logging
@@ -23,6 +26,9 @@ def parser(argv=None):
     p.add_argument('--cfg', default='cfg/FINALv2.cfg', type=str)
     p.add_argument('--band', default='NIR', type=str, choices=['NIR', 'RED'])
     p.add_argument('--seed', default=None, type=int)
+    p.add_argument('--online-aug', dest='online_aug', action='store_true',
+                   help='stage 5 saves the un-augmented training patches and the frame permutations instead of the augmented set '
+                        '(for train.py --online-aug)')
     return p.parse_args(argv)
 
 
@@ -31,4 +37,4 @@ if __name__ == '__main__':
     opt = parser()
     logging.info(f'[ CFG - INFO ] Using {opt.cfg} as config file...')
     rng = None if opt.seed is None else np.random.RandomState(opt.seed)
-    prep.main(parseConfig(opt.cfg), opt.band, rng)
+    prep.main(parseConfig(opt.cfg), opt.band, rng, online_aug=opt.online_aug)
