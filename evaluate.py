@@ -3,11 +3,13 @@
 
     python evaluate.py --cfg C --toCompare DIR [--benchmark DIR] [--band NIR|RED|both] [--norm PATH] [--formula esa|reference] [--out DIR]
     python evaluate.py --cfg C --band NIR --model          # the cfg's latest checkpoint on the TRAIN sets, no PNGs written
+    python evaluate.py --cfg C --band NIR --model --ensemble d8 [--ensemble-permute P --ensemble-seed s]     # ... its test-time self-ensemble
 
 --toCompare scores the imgsetNNNN.png of a folder (test.py's output) against resolverDir/TRAINimgHR_<band>.npy, matching by id: train ids
 below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted, skipped).  --model resolves resolverDir/TRAINpatchesLR_<band>.npy
 with the latest checkpoint exactly as `test.py --totest TRAIN` does (same ids, removedTrainSets<BAND>.txt skipped, the same uint16 cast) and
-scores the images on the device.  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
+scores the images on the device; with --ensemble d8 the images are the self-ensemble `test.py --ensemble d8` writes (same three flags,
+probav_amd/ensemble.py), so a checkpoint is scored with and without it in one place.  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
 Losses.shiftCompensatedcPSNR instead (HR unmasked, what the reference's script computes).  The score is mean(N_i / cPSNR_i) with N_i from
 norm.csv (default <raw_data>/norm.csv when present; lower is better).
 
@@ -39,6 +41,10 @@ def parser(argv=None):
     p.add_argument("--formula", type=str, default="esa", choices=("esa", "reference"))
     p.add_argument("--model", action="store_true", help="score the cfg's latest checkpoint on resolverDir/TRAINpatchesLR_<band>.npy")
     p.add_argument("--out", type=str, default=".", help="folder for scores.csv and comparison.png")
+    p.add_argument("--ensemble", type=str, default="none", choices=("none", "d8"), help="with --model: score the test-time self-ensemble "
+                   "(d8 = the mean over 4 quarter turns x 2 flips of every patch), as test.py --ensemble writes it")
+    p.add_argument("--ensemble-permute", type=int, default=0, help="with --ensemble d8: P further frame orders (8 (P + 1) members, at most 256)")
+    p.add_argument("--ensemble-seed", type=int, default=0, help="seed of the frame orders")
     p.add_argument("--border", type=int, default=3, help=argparse.SUPPRESS)
     opt = p.parse_args(argv)
     opt.band = opt.band.upper()
@@ -46,6 +52,10 @@ def parser(argv=None):
         p.error("--band must be NIR, RED or both, got %r" % opt.band)
     if opt.model == (opt.toCompare is not None):
         p.error("give exactly one of --toCompare DIR and --model")
+    if opt.ensemble != "none" and not opt.model:
+        p.error("--ensemble applies to --model (a folder of PNGs is scored as it is)")
+    if opt.ensemble == "none" and opt.ensemble_permute:
+        p.error("--ensemble-permute needs --ensemble d8")
     for name in ("toCompare", "benchmark"):
         d = getattr(opt, name)
         if d is not None and not os.path.isdir(d):
@@ -59,8 +69,9 @@ def parser(argv=None):
     return opt
 
 
-def model_images(config, cfg_path, band):
-    """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN, without the PNGs."""
+def model_images(config, cfg_path, band, ensemble=None):
+    """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN, without the PNGs.
+    ensemble: an EnsembleSpec for the self-ensemble images test.py --ensemble writes (None: the plain prediction)."""
     import torch
     from probav_amd.modelsTF import WDSRConv3D
     from probav_amd.testClass import evaluate_device
@@ -80,7 +91,7 @@ def model_images(config, cfg_path, band):
         trainer = ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, band))
     if trainer.latest_checkpoint is None and trainer._tf_latest() is None:
         raise SystemExit("evaluate.py --model: no checkpoint under %s" % ckptDir)
-    y_preds = evaluate_device(model, patchLR)
+    y_preds = evaluate_device(model, patchLR) if ensemble is None else evaluate_device(model, patchLR, ensemble=ensemble, final="round")
     del model, trainer
     torch.cuda.empty_cache()
     toOmit = scoring.read_removed(band)
@@ -105,9 +116,13 @@ def main(opt):
     hr = {b: scoring.load_hr(config, b) for b in bands}
     removed = {b: scoring.read_removed(b) for b in bands}
     if opt.model:
+        spec = None
+        if opt.ensemble != "none":
+            from probav_amd.ensemble import EnsembleSpec
+            spec = EnsembleSpec(opt.ensemble, permute=opt.ensemble_permute, seed=opt.ensemble_seed)
         images = {}
         for b in bands:
-            images.update(model_images(config, opt.cfg, b))
+            images.update(model_images(config, opt.cfg, b, ensemble=spec))
     else:
         images = scoring.load_sr_dir(opt.toCompare)
     rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
@@ -116,6 +131,8 @@ def main(opt):
         bench_rows, _ = scoring.score_images(scoring.load_sr_dir(opt.benchmark), hr, border=opt.border, formula=opt.formula, removed=removed)
     summary = scoring.summarize(rows, counts, norm=norm, bench_rows=bench_rows)
     summary["formula"] = opt.formula
+    if opt.ensemble != "none":
+        summary["ensemble"] = {"geometry": opt.ensemble, "permute": opt.ensemble_permute, "seed": opt.ensemble_seed}
     summary["norm"] = norm_path
     os.makedirs(opt.out, exist_ok=True)
     scoring.write_csv(os.path.join(opt.out, "scores.csv"), rows, norm=norm, bench_rows=bench_rows)

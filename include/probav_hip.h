@@ -303,6 +303,25 @@ int probav_score_select(const int64_t* moments, int64_t n_images, int border, do
 int probav_augment_batch(const float* lr, const float* hr, const uint8_t* mask, int64_t n_base, int H, int T, int C, int S,
                          const int32_t* recipe, int64_t batch, float* lr_b, float* hr_b, uint8_t* mask_b, void* stream);
 
+/* ---- test-time self-ensemble (proba-v_amd/ensemble.py), additions of ABI 7 ---------------------------------------------------------- */
+/* E(x) = (1 / V) sum_v G_v^-1( round( clip( net(A_v(x)), lo, hi ) ) ): the mean over V variants of one patch, every member clipped and rounded
+ * before the mean as resolveBySampleAveraging does through resolve (test.py:137-146), with flips and quarter turns beside its frame orders.
+ * A variant is a recipe row {i, f, k, perm[0..T)} in the convention of probav_augment_batch; row n V + v is variant v of base patch n.
+ * Kernels: csrc/kernels_ensemble.hip.
+ *
+ * Expand: lr [n_base][H][H][T][C] fp32, recipe [rows][3 + T] int32 -> out [rows][H][H][T][C], out[b] = rot90(flip(lr[i][:, :, perm], FL[f]), k):
+ * the LR tensor of probav_augment_batch alone (same limits, same skipping of a row that points outside the base array).   test.py:137-146 */
+int probav_ensemble_expand(const float* lr, int64_t n_base, int H, int T, int C, const int32_t* recipe, int64_t rows, float* out, void* stream);
+/* Reduce: sr [n_base V][S][S] fp32 (raw network output), recipe [n_base V][3 + T] ->
+ *     out[n] = (1 / V) sum_{v < V} flip(rot90(rint(clip(sr[n V + v], lo, hi)), -k_v), FL[f_v])        (rint: half to even, as probav_clip_round)
+ * summed in fp32 for v = 0 .. V - 1 (exact: 1 <= V <= 256 members of at most 2^16), divided once by V with the correctly rounded fp32
+ * division, and rounded half to even once more when final_round != 0.  grid = 0: out [n_base][S][S]; grid = g >= 1: the stitched images
+ * [n_base / g^2][g S][g S] of test.py:149-160 (patch n is block ((n / g) % g, n % g) of image n / g^2; n_base a multiple of g^2).
+ * PROBAV_EINVAL, nothing launched: V outside 1..256, S over 90 (a prediction and its accumulator must fit 64 KiB of LDS), lo > hi.
+ * A base patch with an f or k outside 0..3 among its rows is skipped (its output is left as it was).                   test.py:137-146 */
+int probav_ensemble_reduce(const float* sr, const int32_t* recipe, int64_t n_base, int V, int T, int S, float lo, float hi, int final_round,
+                           int grid, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

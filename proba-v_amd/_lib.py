@@ -87,6 +87,9 @@ SIGNATURES = {
     # batch augmentation (csrc/kernels_augment.hip)
     "probav_augment_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    # test-time self-ensemble (csrc/kernels_ensemble.hip)
+    "probav_ensemble_expand": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "probav_ensemble_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -27,85 +27,22 @@
 // Safety.  A recipe row whose base index, code or permutation entry is out of range is skipped by all three of its workgroups before
 // anything is read (the decision is uniform across the workgroup): a bad recipe cannot read outside the base arrays.  The host
 // validates recipes before launching (augment.py); this guard is the second line.
+//
+// The per-sample part (augment_part and its index helpers) lives in augment_part.h: kernels_ensemble.hip uses it for the LR variants of
+// inference patches.
 #include "probav_common.h"
+#include "augment_part.h"
 #include "../../include/probav_hip.h"
 
 namespace probav {
 
 namespace {
 
-constexpr int AUG_THREADS = 256, AUG_MAX_T = 64, AUG_MAX_SIDE = 1024, AUG_MAX_C = 16;
-constexpr size_t AUG_LDS_LIMIT = 64 * 1024;
-
 struct AugGeom {
     int64_t n_base;
     int H, T, C, S;
     int lr_vec, hr_vec, mask_vec;       // 1: the sample's byte size is a multiple of 16 and the arrays are 16-byte aligned
 };
-
-inline size_t aug_round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// staged sample + table of one workgroup
-inline size_t aug_part_lds(int side, int TC, size_t elem_bytes)
-{
-    return aug_round16((size_t)side * side * TC * elem_bytes) + (size_t)side * TC * sizeof(int);
-}
-
-// source pixel (row-major index) of output pixel (y, x): flip f, then k quarter turns
-__device__ __forceinline__ int aug_src_pixel(int y, int x, int side, int f, int k)
-{
-    const int n = side - 1;
-    int a = y, b = x;
-    if (k == 1) { a = x; b = n - y; }
-    else if (k == 2) { a = n - y; b = n - x; }
-    else if (k == 3) { a = n - x; b = y; }
-    if (f & 1) a = n - a;
-    if (f & 2) b = n - b;
-    return a * side + b;
-}
-
-template <typename E, int V>
-struct alignas(sizeof(E) * V) AugVec { E v[V]; };
-
-// one sample of one tensor: src [side][side][TC] -> dst, TC = frames x channels (1 for HR / mask), perm = the recipe's frame
-// permutation in global memory (null: identity)
-template <typename E, int V>
-__device__ __forceinline__ void augment_part(const E* __restrict__ src, E* __restrict__ dst, int side, int TC, int C,
-                                             const int32_t* __restrict__ perm, int f, int k, unsigned char* smem)
-{
-    const int row = side * TC, elems = side * row;
-    E* tile = reinterpret_cast<E*>(smem);
-    int* tab = reinterpret_cast<int*>(smem + (((size_t)elems * sizeof(E) + 15) & ~(size_t)15));
-    if (V > 1) {
-        const uint4* s16 = reinterpret_cast<const uint4*>(src);
-        uint4* t16 = reinterpret_cast<uint4*>(smem);
-        const int n16 = (int)((size_t)elems * sizeof(E) / 16);
-        for (int q = threadIdx.x; q < n16; q += AUG_THREADS) t16[q] = s16[q];
-    } else {
-        for (int q = threadIdx.x; q < elems; q += AUG_THREADS) tile[q] = src[q];
-    }
-    const int P0 = aug_src_pixel(0, 0, side, f, k);
-    const int PI = aug_src_pixel(1, 0, side, f, k) - P0, PJ = aug_src_pixel(0, 1, side, f, k) - P0;
-    for (int j = threadIdx.x; j < row; j += AUG_THREADS) {
-        const int x = j / TC, e = j - x * TC, t = e / C, c = e - t * C;
-        tab[j] = TC * x * PJ + (perm ? perm[t] : t) * C + c;
-    }
-    __syncthreads();
-    const int rowstep = TC * PI;
-    for (int q = threadIdx.x; q < elems / V; q += AUG_THREADS) {
-        const int o = q * V;
-        int y = o / row, j = o - y * row;
-        int base = TC * P0 + y * rowstep;
-        AugVec<E, V> out;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            if (j == row) { j = 0; base += rowstep; }
-            out.v[v] = tile[base + tab[j]];
-            ++j;
-        }
-        *reinterpret_cast<AugVec<E, V>*>(dst + o) = out;
-    }
-}
 
 __global__ __launch_bounds__(AUG_THREADS) void augment_batch_kernel(const float* __restrict__ lr, const float* __restrict__ hr,
                                                                      const uint8_t* __restrict__ mask, const int32_t* __restrict__ recipe,
@@ -133,8 +70,6 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_batch_kernel(const float*
         else augment_part<uint8_t, 1>(mask + (size_t)i * n, mask_b + b * n, g.S, 1, 1, nullptr, f, k, aug_smem);
     }
 }
-
-inline bool aug_aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 }  // namespace
 

@@ -19,6 +19,10 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
                                                                             the ESA cPSNR of whole images   evaluate.py:76-87 (scoring.py)
   probav::augment_batch(lr, hr, mask, recipe) -> (lr_b, hr_b, mask_b)      a training batch from the un-augmented patches: frame permutation,
                                                                             flip, quarter turns per sample   utils/dataGenerator.py:227-273 (augment.py)
+  probav::ensemble_expand(lr, recipe) -> lr_v                              the LR variants of inference patches (flip, quarter turns, frame order)
+  probav::ensemble_reduce(sr, recipe, V, lo, hi, final_round, sets, grid) -> patches [N, S, S] | images [sets, grid S, grid S]
+                                                                            the mean of the V clipped, rounded predictions of every patch, each turned
+                                                                            back, optionally stitched   test.py:137-146, 149-160 (ensemble.py)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -411,6 +415,85 @@ def _(lr, hr, mask, recipe):
     _augment_args(lr, hr, mask, recipe)
     B = recipe.shape[0]
     return lr.new_empty((B,) + tuple(lr.shape[1:])), hr.new_empty((B,) + tuple(hr.shape[1:])), mask.new_empty((B,) + tuple(mask.shape[1:]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# test-time self-ensemble (csrc/kernels_ensemble.hip; the variant tables and the definition are in ensemble.py).  No autograd: inference.
+# lr [N, H, H, T, C] fp32; recipe [N V, 3 + T] int32 rows {i, f, k, perm}, row n V + v = variant v of patch n; sr [N V, S, S] or [N V, S, S, 1].
+# ---------------------------------------------------------------------------------------------------------------------------------
+ENSEMBLE_MAX_V = 256          # members are integers in [0, 2**16]: 256 of them sum to at most 2**24, exactly, in fp32 in any order
+
+
+def _expand_args(lr, recipe):
+    if lr.dim() != 5 or recipe.dim() != 2 or lr.shape[1] != lr.shape[2]:
+        raise ValueError("ensemble_expand: lr [N, H, H, T, C] (square: a quarter turn needs it), recipe [B, 3 + T]; got %s %s"
+                         % (tuple(lr.shape), tuple(recipe.shape)))
+    if lr.dtype != torch.float32 or recipe.dtype != torch.int32:
+        raise ValueError("ensemble_expand: lr must be float32, recipe int32; got %s %s" % (lr.dtype, recipe.dtype))
+    if recipe.shape[1] != 3 + lr.shape[3]:
+        raise ValueError("ensemble_expand: a recipe row is {i, f, k, perm[%d]}; got %d columns" % (lr.shape[3], recipe.shape[1]))
+    if lr.shape[0] < 1:
+        raise ValueError("ensemble_expand: no patches")
+
+
+@torch.library.custom_op("probav::ensemble_expand", mutates_args=(), device_types="cuda")
+def ensemble_expand(lr: Tensor, recipe: Tensor) -> Tensor:
+    """[B, H, H, T, C]: out[b] = rot90(flip(lr[i][:, :, perm], FL[f]), k) for recipe[b] = {i, f, k, perm} -- augment_batch's LR tensor alone.
+    The kernel skips a row it could not apply without reading outside `lr`; callers validate recipes on the host (ensemble.py does)."""
+    _expand_args(lr, recipe)
+    _dev(lr, "lr"), _dev(recipe, "recipe")
+    lr, recipe = lr.contiguous(), recipe.contiguous()
+    B = recipe.shape[0]
+    out = torch.empty((B,) + tuple(lr.shape[1:]), dtype=lr.dtype, device=lr.device)
+    if B:
+        _lib.check(_lib.lib().probav_ensemble_expand(_lib.ptr(lr), lr.shape[0], lr.shape[1], lr.shape[3], lr.shape[4], _lib.ptr(recipe), B,
+                                                     _lib.ptr(out), _lib.current_stream()), "probav_ensemble_expand")
+    return out
+
+
+@ensemble_expand.register_fake
+def _(lr, recipe):
+    _expand_args(lr, recipe)
+    return lr.new_empty((recipe.shape[0],) + tuple(lr.shape[1:]))
+
+
+def _reduce_args(sr, recipe, V, sets, grid):
+    """-> (N, S) after the checks the real and the fake kernel share."""
+    if sr.dim() == 4 and sr.shape[3] == 1:
+        sr = sr[..., 0]
+    if sr.dim() != 3 or sr.shape[1] != sr.shape[2] or recipe.dim() != 2 or recipe.shape[1] < 4:
+        raise ValueError("ensemble_reduce: sr [N V, S, S] (or [N V, S, S, 1]), recipe [N V, 3 + T]; got %s %s" % (tuple(sr.shape), tuple(recipe.shape)))
+    if sr.dtype != torch.float32 or recipe.dtype != torch.int32:
+        raise ValueError("ensemble_reduce: sr must be float32, recipe int32; got %s %s" % (sr.dtype, recipe.dtype))
+    if not 1 <= V <= ENSEMBLE_MAX_V:
+        raise ValueError("ensemble_reduce: V = %d members; 1 <= V <= %d (each member is an integer up to 2**16: %d of them sum exactly in fp32, "
+                         "more need not)" % (V, ENSEMBLE_MAX_V, ENSEMBLE_MAX_V))
+    if sr.shape[0] < V or sr.shape[0] % V or recipe.shape[0] != sr.shape[0]:
+        raise ValueError("ensemble_reduce: %d predictions and %d recipe rows do not make whole groups of V = %d" % (sr.shape[0], recipe.shape[0], V))
+    N = sr.shape[0] // V
+    if (grid == 0) != (sets == 0) or grid < 0 or sets < 0 or (grid and sets * grid * grid != N):
+        raise ValueError("ensemble_reduce: sets = grid = 0 for patches, or sets * grid * grid == N = %d for stitched images; got sets %d, grid %d"
+                         % (N, sets, grid))
+    return N, sr.shape[1]
+
+
+@torch.library.custom_op("probav::ensemble_reduce", mutates_args=(), device_types="cuda")
+def ensemble_reduce(sr: Tensor, recipe: Tensor, V: int, lo: float, hi: float, final_round: bool, sets: int, grid: int) -> Tensor:
+    """mean over v < V of flip(rot90(rint(clip(sr[n V + v], lo, hi)), -k_v), FL[f_v]) -- exact fp32 sum, one correctly rounded division, rounded
+    half to even once more if `final_round` -> [N, S, S] (sets = grid = 0) or the stitched [sets, grid S, grid S] of testClass.stitch_device."""
+    N, S = _reduce_args(sr, recipe, V, sets, grid)
+    _dev(sr, "sr"), _dev(recipe, "recipe")
+    sr, recipe = sr.contiguous(), recipe.contiguous()
+    out = torch.empty((sets, grid * S, grid * S) if grid else (N, S, S), dtype=torch.float32, device=sr.device)
+    _lib.check(_lib.lib().probav_ensemble_reduce(_lib.ptr(sr), _lib.ptr(recipe), N, V, recipe.shape[1] - 3, S, lo, hi, 1 if final_round else 0, grid,
+                                                 _lib.ptr(out), _lib.current_stream()), "probav_ensemble_reduce")
+    return out
+
+
+@ensemble_reduce.register_fake
+def _(sr, recipe, V, lo, hi, final_round, sets, grid):
+    N, S = _reduce_args(sr, recipe, V, sets, grid)
+    return sr.new_empty((sets, grid * S, grid * S) if grid else (N, S, S), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops            # noqa: F401  (ops registers torch.ops.probav.*)
+from .ensemble import EnsembleSpec, ensemble_reduce_numpy, validate_ensemble_recipe      # noqa: F401  (re-exported)
 
 
 def _device_of(model):
@@ -83,6 +84,41 @@ def resolveBySampleAveraging(model, lr_batch, rng=None):
         sr = resolve_device(model, x.contiguous())
         acc = sr.double() if acc is None else acc + sr.double()
     return (acc / 20.0).float()
+
+
+def _ensemble_launch_sets(model, flat, spec, final, launch_batch, grid=0):
+    """The ensemble of `flat` [N, H, H, T, C] in launch sets of max(1, launch_batch // V) WHOLE base patches (the members of one patch are
+    never split, and the forward workspace is no larger than the plain path's): expand -> the engine's forward -> reduce, all on the
+    device.  grid = g: launch sets are whole images of g * g patches and every yielded tensor is [images, g S, g S]; grid = 0: [n, S, S]."""
+    if final not in ("mean", "round"):
+        raise ValueError("final must be 'mean' or 'round', got %r" % (final,))
+    dev = _device_of(model)
+    if dev.type != "cuda":
+        raise RuntimeError("the model lives on %s: the self-ensemble runs as HIP kernels on a gfx950 device (no CPU fallback)" % dev)
+    N, T, V = flat.shape[0], flat.shape[3], spec.V
+    per = max(1, (LAUNCH_BATCH if launch_batch is None else launch_batch) // V)
+    if grid:
+        per -= per % (grid * grid)
+    recipe = spec.recipe(min(per, N), T)
+    validate_ensemble_recipe(recipe, min(per, N), V, T)
+    rec = torch.from_numpy(recipe).to(dev)
+    for i in range(0, N, per):
+        x = torch.as_tensor(flat[i:i + per]).to(device=dev, dtype=torch.float32)
+        r = rec[:x.shape[0] * V]
+        with torch.no_grad():
+            sr = model(torch.ops.probav.ensemble_expand(x, r), training=False)
+            out = torch.ops.probav.ensemble_reduce(sr, r, V, 0.0, float(2 ** 16), final == "round", x.shape[0] // (grid * grid) if grid else 0, grid)
+        yield out
+
+
+def resolve_ensemble(model, lr_batch, spec, final="mean", launch_batch=None):
+    """The self-ensemble prediction of every patch of `lr_batch` [b, H, H, T, C] (ensemble.py states it): the mean over the spec's V variants
+    of the clipped, rounded prediction of each, turned back -- test.py:137-146's sample averaging with flips and quarter turns beside the
+    frame orders, reproducible from the spec.  final = "mean": the fp32 mean, as the reference's helper returns it; "round": rounded half
+    to even once more (the uint16-range form).  Returns a device tensor [b, 3P, 3P, 1]."""
+    flat = np.ascontiguousarray(lr_batch) if isinstance(lr_batch, np.ndarray) else lr_batch
+    outs = list(_ensemble_launch_sets(model, flat, spec, final, launch_batch))
+    return (outs[0] if len(outs) == 1 else torch.cat(outs)).unsqueeze(-1)
 
 
 def reconstruct_from_patches(images):
@@ -160,18 +196,28 @@ def stitch_device(sr, sets):
     return sr.reshape(sets, n, n, ps, ps).permute(0, 1, 3, 2, 4).reshape(sets, n * ps, n * ps)
 
 
-def resolve_images(model, patches, micro_batch=2048, launch_batch=None):
+def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round"):
     """All image sets at once: patches [sets, n*n, P+s, P+s, T, 1] -> uint16-range images [sets, 3nP, 3nP] (device tensor).
     Samples are independent in every kernel family (models/modelsTF.py:15-43 has no cross-sample term; the H3 kernels scale their
     operands per sample), so any micro-batch gives bit-identical pixels to the reference's batches of 16
     (tests/test_gpu_h3_range.py::test_forward_is_bitwise_independent_of_the_batch).
     `micro_batch` is the reference-visible slicing (test.py:125: 16); `launch_batch` is how many patches one launch set of the engine takes:
     None (default) coalesces whole micro-batches up to max(micro_batch, LAUNCH_BATCH); `launch_batch=micro_batch` launches every micro-batch
-    on its own, as the reference's loop does (the parity tests compare the two bit for bit)."""
+    on its own, as the reference's loop does (the parity tests compare the two bit for bit).
+    `ensemble` (an EnsembleSpec; None = the plain path, untouched): every patch is predicted in the spec's V variants and the images are the
+    self-ensemble of `resolve_ensemble` in the form `final` ("round" = uint16-range, what a PNG takes; "mean" = the fp32 mean).  A launch set
+    then holds launch_batch // V whole patches -- whole images, reduced and stitched by one kernel, when that many fit; `micro_batch` plays
+    no part."""
     dev = _device_of(model)
     p = torch.as_tensor(patches)
     sets = p.shape[0]
     flat = p.reshape((-1,) + tuple(p.shape[2:]))
+    if ensemble is not None:
+        n = int(round(p.shape[1] ** 0.5))
+        whole = n * n == p.shape[1] and (LAUNCH_BATCH if launch_batch is None else launch_batch) // ensemble.V >= n * n
+        outs = list(_ensemble_launch_sets(model, flat, ensemble, final, launch_batch, grid=n if whole else 0))
+        out = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return out if whole else stitch_device(out.unsqueeze(-1), sets)
     if launch_batch is None:
         launch_batch = max(micro_batch, LAUNCH_BATCH)
     per = max(1, launch_batch // max(1, micro_batch)) * max(1, micro_batch)
@@ -181,9 +227,14 @@ def resolve_images(model, patches, micro_batch=2048, launch_batch=None):
     return stitch_device(torch.cat(outs) if len(outs) > 1 else outs[0], sets)
 
 
-def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None):
+def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round"):
     """test.py:103-111 through the device pipeline: every image set in micro-batches of `micro_batch` patches (16 = the reference's
     resolveByBatch; coalesced into launch sets unless `launch_batch` says otherwise), clip / round and the 8 x 8 stitch on the device, ONE
-    copy back.  Returns a list of [384, 384, 1] float64 arrays, element for element what the reference's `evaluate` returns."""
-    imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch).cpu().numpy().astype(np.float64)
+    copy back.  Returns a list of [384, 384, 1] float64 arrays, element for element what the reference's `evaluate` returns.
+    `ensemble`, `final`: the self-ensemble of `resolve_images` instead of the plain prediction (None: today's path and bytes)."""
+    if ensemble is None:
+        imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch)
+    else:
+        imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch, ensemble=ensemble, final=final)
+    imgs = imgs.cpu().numpy().astype(np.float64)
     return [im[:, :, None] for im in imgs]

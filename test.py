@@ -5,6 +5,10 @@ Loads <preprocessing_out>/resolverDir/<TEST|TRAIN>patchesLR_<band>.npy ([sets, 6
 checkpoint, resolves every image set patch-wise on the MI355X engine (all sets in micro-batches of --micro-batch patches; forward, clip to
 [0, 2**16], round half to even and the 8 x 8 stitch into 384 x 384 stay on the device) and writes uint16 PNGs named imgsetNNNN.png, skipping the ids in
 removedTrainSets<band>.txt exactly as the reference does.
+
+--ensemble d8 [--ensemble-permute P --ensemble-seed s] writes the test-time self-ensemble instead (probav_amd/ensemble.py): every
+patch predicted in 8 (P + 1) flipped / turned / frame-shuffled variants, the clipped and rounded predictions turned back and averaged on the
+device, the mean rounded half to even for the PNG.  It costs that many forward passes.  --ensemble none (default) is the path above, byte for byte.
 """
 import argparse
 import logging
@@ -26,7 +30,7 @@ BAND_STATS = {"NIR": (8075.2045, 3160.7272), "RED": (5266.2245, 3431.8614)}
 FIRST_ID = {("TEST", "NIR"): 1306, ("TEST", "RED"): 1160, ("TRAIN", "NIR"): 594, ("TRAIN", "RED"): 0}    # test.py:79-90
 
 
-def parser():
+def parser(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--cfg", default="cfg/FINAL.cfg", type=str)
     p.add_argument("--band", type=str, default="RED")
@@ -35,7 +39,25 @@ def parser():
                    "Samples are independent, so the images do not depend on it")
     p.add_argument("--reference-loop", action="store_true", help="launch every micro-batch of 16 patches on its own, as the reference's loop does "
                    "(test.py:125-134; 3x slower, same pixels); by default the micro-batches are coalesced into launch sets")
-    return p.parse_args()
+    p.add_argument("--ensemble", type=str, default="none", choices=("none", "d8"), help="test-time self-ensemble: d8 = the mean over the 4 quarter "
+                   "turns x 2 flips of every patch (8 forward passes per patch); none = the plain prediction")
+    p.add_argument("--ensemble-permute", type=int, default=0, help="with --ensemble d8: P further frame orders, crossed with the 8 geometric variants "
+                   "(8 (P + 1) members, at most 256)")
+    p.add_argument("--ensemble-seed", type=int, default=0, help="seed of the frame orders: the same seed gives the same images")
+    opt = p.parse_args(argv)
+    if opt.ensemble == "none" and opt.ensemble_permute:
+        p.error("--ensemble-permute needs --ensemble d8")
+    if opt.ensemble != "none" and opt.reference_loop:
+        p.error("--reference-loop is the reference's plain loop: it cannot be combined with --ensemble")
+    return opt
+
+
+def ensemble_spec(opt):
+    """The EnsembleSpec the three --ensemble flags ask for (None: the plain path)."""
+    if opt.ensemble == "none":
+        return None
+    from probav_amd.ensemble import EnsembleSpec
+    return EnsembleSpec(opt.ensemble, permute=opt.ensemble_permute, seed=opt.ensemble_seed)
 
 
 def main(config, opt):
@@ -53,8 +75,13 @@ def main(config, opt):
     ckptDir = os.path.join(config["model_out"], "ckpt_%s" % basename, opt.band)
     ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, opt.band))   # restores the latest checkpoint
     logger.info("[ INFO ] Generating predictions...")
-    y_preds = (evaluate_device(model, patchLR, micro_batch=16, launch_batch=16) if opt.reference_loop
-               else evaluate_device(model, patchLR, micro_batch=opt.micro_batch))
+    spec = ensemble_spec(opt)
+    if spec is not None:
+        logger.info("[ INFO ] Self-ensemble of %d members per patch" % spec.V)
+        y_preds = evaluate_device(model, patchLR, ensemble=spec, final="round")
+    else:
+        y_preds = (evaluate_device(model, patchLR, micro_batch=16, launch_batch=16) if opt.reference_loop
+                   else evaluate_device(model, patchLR, micro_batch=opt.micro_batch))
 
     band = opt.band.upper()
     toOmit = []
