@@ -4,12 +4,14 @@
     python evaluate.py --cfg C --toCompare DIR [--benchmark DIR] [--band NIR|RED|both] [--norm PATH] [--formula esa|reference] [--out DIR]
     python evaluate.py --cfg C --band NIR --model          # the cfg's latest checkpoint on the TRAIN sets, no PNGs written
     python evaluate.py --cfg C --band NIR --model --ensemble d8 [--ensemble-permute P --ensemble-seed s]     # ... its test-time self-ensemble
+    python evaluate.py --cfg C --band NIR --model --tile-stride 8 [--tile-window hat|box]                    # ... its overlapped, blended tiles
 
 --toCompare scores the imgsetNNNN.png of a folder (test.py's output) against resolverDir/TRAINimgHR_<band>.npy, matching by id: train ids
 below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted, skipped).  --model resolves resolverDir/TRAINpatchesLR_<band>.npy
 with the latest checkpoint exactly as `test.py --totest TRAIN` does (same ids, removedTrainSets<BAND>.txt skipped, the same uint16 cast) and
 scores the images on the device; with --ensemble d8 the images are the self-ensemble `test.py --ensemble d8` writes (same three flags,
-probav_amd/ensemble.py), so a checkpoint is scored with and without it in one place.  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
+probav_amd/ensemble.py), so a checkpoint is scored with and without it in one place; with --tile-stride s the images are the blended overlapping
+tiles `test.py --tile-stride s` writes (read from trimmedArrayDir/TRAINimgLR_<band>.npy, same set order and ids; probav_amd/tiles.py).  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
 Losses.shiftCompensatedcPSNR instead (HR unmasked, what the reference's script computes).  The score is mean(N_i / cPSNR_i) with N_i from
 norm.csv (default <raw_data>/norm.csv when present; lower is better).
 
@@ -45,6 +47,9 @@ def parser(argv=None):
                    "(d8 = the mean over 4 quarter turns x 2 flips of every patch), as test.py --ensemble writes it")
     p.add_argument("--ensemble-permute", type=int, default=0, help="with --ensemble d8: P further frame orders (8 (P + 1) members, at most 256)")
     p.add_argument("--ensemble-seed", type=int, default=0, help="seed of the frame orders")
+    p.add_argument("--tile-stride", type=int, default=0, help="with --model: score the blend of overlapping tiles at this LR stride, as "
+                   "test.py --tile-stride writes it; 0 = disjoint patches")
+    p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
     p.add_argument("--border", type=int, default=3, help=argparse.SUPPRESS)
     opt = p.parse_args(argv)
     opt.band = opt.band.upper()
@@ -56,6 +61,8 @@ def parser(argv=None):
         p.error("--ensemble applies to --model (a folder of PNGs is scored as it is)")
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
+    if opt.tile_stride and not opt.model:
+        p.error("--tile-stride applies to --model (a folder of PNGs is scored as it is)")
     for name in ("toCompare", "benchmark"):
         d = getattr(opt, name)
         if d is not None and not os.path.isdir(d):
@@ -64,21 +71,27 @@ def parser(argv=None):
         p.error("--norm: no such file %r" % opt.norm)
     if not os.path.isfile(opt.cfg):
         p.error("--cfg: no such file %r" % opt.cfg)
+    from probav_amd.tiles import cli_tile_args
+    cli_tile_args(p, opt)
     if not 0 <= opt.border <= 3:
         p.error("--border must be in 0..3")
     return opt
 
 
-def model_images(config, cfg_path, band, ensemble=None):
+def model_images(config, cfg_path, band, ensemble=None, tiles=None):
     """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN, without the PNGs.
-    ensemble: an EnsembleSpec for the self-ensemble images test.py --ensemble writes (None: the plain prediction)."""
+    ensemble: an EnsembleSpec for the self-ensemble images test.py --ensemble writes (None: the plain prediction).
+    tiles: a TileSpec for the blended overlapping tiles test.py --tile-stride writes (None: disjoint patches)."""
     import torch
     from probav_amd.modelsTF import WDSRConv3D
-    from probav_amd.testClass import evaluate_device
+    from probav_amd.testClass import evaluate_device, evaluate_tiled_frames
     from probav_amd.trainClass import ModelTrainer
-    dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
-    patchLR = np.load(os.path.join(dataDir, "TRAINpatchesLR_%s.npy" % band), allow_pickle=True)
-    patchLR = np.array(patchLR).transpose((0, 1, 4, 5, 2, 3))
+    if tiles is not None:
+        framesLR = np.load(os.path.join(config["preprocessing_out"], "trimmedArrayDir", "TRAINimgLR_%s.npy" % band), allow_pickle=True)
+    else:
+        dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
+        patchLR = np.load(os.path.join(dataDir, "TRAINpatchesLR_%s.npy" % band), allow_pickle=True)
+        patchLR = np.array(patchLR).transpose((0, 1, 4, 5, 2, 3))
     mean, std = BAND_STATS[band]
     k = config["kernel_size"]
     model = WDSRConv3D(name="superResolutionNet", band=band, mean=mean, std=std, maxShift=config["max_shift"]).build(
@@ -91,7 +104,10 @@ def model_images(config, cfg_path, band, ensemble=None):
         trainer = ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, band))
     if trainer.latest_checkpoint is None and trainer._tf_latest() is None:
         raise SystemExit("evaluate.py --model: no checkpoint under %s" % ckptDir)
-    y_preds = evaluate_device(model, patchLR) if ensemble is None else evaluate_device(model, patchLR, ensemble=ensemble, final="round")
+    if tiles is not None:
+        y_preds = evaluate_tiled_frames(model, framesLR, tiles, config, ensemble=ensemble)
+    else:
+        y_preds = evaluate_device(model, patchLR) if ensemble is None else evaluate_device(model, patchLR, ensemble=ensemble, final="round")
     del model, trainer
     torch.cuda.empty_cache()
     toOmit = scoring.read_removed(band)
@@ -120,9 +136,13 @@ def main(opt):
         if opt.ensemble != "none":
             from probav_amd.ensemble import EnsembleSpec
             spec = EnsembleSpec(opt.ensemble, permute=opt.ensemble_permute, seed=opt.ensemble_seed)
+        tiles = None
+        if opt.tile_stride:
+            from probav_amd.tiles import TileSpec
+            tiles = TileSpec(opt.tile_stride, opt.tile_window)
         images = {}
         for b in bands:
-            images.update(model_images(config, opt.cfg, b, ensemble=spec))
+            images.update(model_images(config, opt.cfg, b, ensemble=spec, tiles=tiles))
     else:
         images = scoring.load_sr_dir(opt.toCompare)
     rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
@@ -133,6 +153,8 @@ def main(opt):
     summary["formula"] = opt.formula
     if opt.ensemble != "none":
         summary["ensemble"] = {"geometry": opt.ensemble, "permute": opt.ensemble_permute, "seed": opt.ensemble_seed}
+    if opt.tile_stride:
+        summary["tiles"] = {"stride": opt.tile_stride, "window": opt.tile_window}
     summary["norm"] = norm_path
     os.makedirs(opt.out, exist_ok=True)
     scoring.write_csv(os.path.join(opt.out, "scores.csv"), rows, norm=norm, bench_rows=bench_rows)

@@ -322,6 +322,23 @@ int probav_ensemble_expand(const float* lr, int64_t n_base, int H, int T, int C,
 int probav_ensemble_reduce(const float* sr, const int32_t* recipe, int64_t n_base, int V, int T, int S, float lo, float hi, int final_round,
                            int grid, float* out, void* stream);
 
+/* ---- overlapped-tile inference (proba-v_amd/tiles.py), an addition of ABI 7 ------------------------------------------------------------- */
+/* The blend of overlapping tile predictions into whole images ('Overlapped tiles').  sr [n_images n n][S][S] fp32: the
+ * predictions of the n x n tiles of every image in row-major order, raw network output or members that are already rounded; tile (a, c) has
+ * its origin at (a hr_stride, c hr_stride).  w [S] int32, device: a window of positive integers, W2[i][j] = w[i] w[j].  For every pixel (y, x) of
+ * out [n_images][G][G], G = (n - 1) hr_stride + S, over the tiles t = (a, c) that cover it, with p = rint(clip(sr, lo, hi)) (rint: half to
+ * even, as probav_clip_round):
+ *     N = sum_t W2[y - o_a][x - o_c] p_t[y - o_a][x - o_c],  D = sum_t W2[y - o_a][x - o_c],  out[y][x] = N / D rounded half to even
+ * in exact 64-bit integer arithmetic (q = floor(N / D); q + 1 when 2 (N - q D) > D, or == D and q odd).  Nothing is floating point after the
+ * rint, so the image does not depend on the launch, and with hr_stride = S it is the plain stitch of test.py:149-160.
+ * Range: at most ceil(S / hr_stride)^2 <= S^2 tiles cover a pixel, so |N| <= S^2 max(w)^2 max|p|.  The callers keep every w[i] in [1, 1024]
+ * (tiles.py checks the window before it is uploaded; the library cannot see device memory) and p in [0, 2^16]: with S <= 90, S^2 < 2^13 and
+ * |N| < 2^13 2^20 2^16 = 2^49, far below 2^63.  In general S^2 max(w)^2 max(|lo|, |hi|) must stay below 2^62.
+ * PROBAV_EINVAL, nothing launched: a null pointer, n_images, n or S below 1, hr_stride outside 1..S (a gap between tiles would leave D = 0),
+ * lo > hi, clip bounds beyond +-2^24 (the result is stored as fp32), G over 32767.  Kernel: csrc/kernels_tile.hip.
+ *                                         replaces reconstruct_from_patches for overlapping tiles         test.py:149-160 */
+int probav_tile_blend(const float* sr, const int32_t* w, int64_t n_images, int n, int S, int hr_stride, float lo, float hi, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

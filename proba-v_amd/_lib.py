@@ -90,6 +90,8 @@ SIGNATURES = {
     # test-time self-ensemble (csrc/kernels_ensemble.hip)
     "probav_ensemble_expand": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "probav_ensemble_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
+    # overlapped-tile inference (csrc/kernels_tile.hip)
+    "probav_tile_blend": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,120 @@
+// Overlapped-tile inference (gfx950): the blend of the tile predictions into whole images.  proba-v_amd/tiles.py states it in numpy int64
+// (tile_blend_numpy) and drives this kernel; INTEGRATION.md, 'Overlapped tiles', has the definition.
+//
+// sr [n_images n n][S][S] holds the predictions of the n x n tiles of every image, row-major; tile (a, c) has its origin at
+// (a hr_stride, c hr_stride) of the image, G = (n - 1) hr_stride + S pixels a side.  With p = rint(clip(sr, lo, hi)) (probav_clip_round's
+// arithmetic, idempotent on members that are already integers) and the separable window W2[i][j] = w[i] w[j], for output pixel (y, x)
+//     N = sum_t W2[y - o_a][x - o_c] p_t[y - o_a][x - o_c],   D = sum_t W2[y - o_a][x - o_c]   over the tiles t = (a, c) that cover it,
+//     out[y][x] = N / D rounded half to even: q = floor(N / D), r = N - q D, q + 1 when 2 r > D or when 2 r == D and q is odd.
+// Everything after the rint is 64-bit integer arithmetic, so the image depends on nothing but its inputs.
+//
+// Gather form.  A thread owns Wd consecutive pixels of one output row and loops over the tiles that cover them: rows a in
+// [y < S ? 0 : (y - S) / hr_stride + 1,  min(n - 1, y / hr_stride)], which is exactly the set with 0 <= y - a hr_stride < S, and the same along x.
+// At most ceil(S / hr_stride) tiles cover a pixel per axis.  One writer per output element, no atomics, no scratch, no hand-off between
+// workgroups.  Consecutive threads own consecutive pixel groups of the flattened [n_images][G][G] output, so a wave stores 64 Wd
+// consecutive floats of an output row, and its loads from a tile row are the consecutive floats of that row which fall under them; every tile
+// pixel is read exactly once.  Wd = 4 (16-byte loads and stores) when S, hr_stride (hence G and every tile origin) are multiples of 4 and the
+// arrays are 16-byte aligned: the four pixels of a group then lie under the same tiles.  Wd = 1 otherwise.
+#include "probav_common.h"
+#include "../../include/probav_hip.h"
+
+namespace probav {
+
+namespace {
+
+constexpr int TILE_THREADS = 256;
+
+struct TileGeom {
+    int n, S, hs, G;                    // tiles per axis, side of a prediction, HR stride between tile origins, side of an image
+    float lo, hi;
+};
+
+struct alignas(16) TileVec4 { float v[4]; };
+
+__device__ __forceinline__ float tile_round_div(long long N, long long D)
+{
+    long long q = N / D, r = N % D;     // D > 0; C++ truncates, the definition floors
+    if (r < 0) { r += D; q -= 1; }
+    if (2 * r > D || (2 * r == D && (q & 1))) q += 1;
+    return (float)q;
+}
+
+template <int Wd>
+__global__ __launch_bounds__(TILE_THREADS) void tile_blend_kernel(const float* __restrict__ sr, const int32_t* __restrict__ w, TileGeom g, size_t groups,
+                                                                   float* __restrict__ out)
+{
+    const size_t q = (size_t)blockIdx.x * TILE_THREADS + threadIdx.x;
+    if (q >= groups) return;
+    const size_t e = q * Wd, GG = (size_t)g.G * g.G, img = e / GG;
+    const int rem = (int)(e - img * GG), y = rem / g.G, x = rem - y * g.G;
+    const int a0 = y < g.S ? 0 : (y - g.S) / g.hs + 1, a1 = min(g.n - 1, y / g.hs);
+    const int c0 = x < g.S ? 0 : (x - g.S) / g.hs + 1, c1 = min(g.n - 1, x / g.hs);
+    const size_t px = (size_t)g.S * g.S;
+    long long N[Wd], D[Wd];
+#pragma unroll
+    for (int j = 0; j < Wd; ++j) N[j] = D[j] = 0;
+    for (int a = a0; a <= a1; ++a) {
+        const int dy = y - a * g.hs;                                // 0 <= dy < S by the choice of a0, a1
+        const long long wy = w[dy];
+        for (int c = c0; c <= c1; ++c) {
+            const int dx = x - c * g.hs;                            // 0 <= dx, dx + Wd - 1 < S
+            const float* src = sr + ((img * g.n + a) * g.n + c) * px + (size_t)dy * g.S + dx;
+            float m[Wd];
+            if (Wd == 4) {
+                const TileVec4 in = *reinterpret_cast<const TileVec4*>(src);
+#pragma unroll
+                for (int j = 0; j < Wd; ++j) m[j] = in.v[j];
+            } else {
+                m[0] = src[0];
+            }
+#pragma unroll
+            for (int j = 0; j < Wd; ++j) {
+                const long long w2 = wy * w[dx + j];
+                N[j] += w2 * (long long)rintf(fminf(fmaxf(m[j], g.lo), g.hi));      // probav_clip_round's arithmetic
+                D[j] += w2;
+            }
+        }
+    }
+    if (Wd == 4) {
+        TileVec4 o;
+#pragma unroll
+        for (int j = 0; j < Wd; ++j) o.v[j] = tile_round_div(N[j], D[j]);
+        *reinterpret_cast<TileVec4*>(out + e) = o;
+    } else {
+        out[e] = tile_round_div(N[0], D[0]);
+    }
+}
+
+}  // namespace
+
+}  // namespace probav
+
+using namespace probav;
+
+extern "C" int probav_tile_blend(const float* sr, const int32_t* w, int64_t n_images, int n, int S, int hr_stride, float lo, float hi, float* out, void* stream)
+{
+    if (!sr || !w || !out || n_images < 1 || n < 1 || S < 1 || hr_stride < 1 || hr_stride > S || !(lo <= hi)) {
+        set_error("probav_tile_blend: null/invalid argument (n_images, n, S >= 1; 1 <= hr_stride <= S, a gap between tiles would leave pixels without a "
+                  "weight; lo <= hi)", hipSuccess);
+        return PROBAV_EINVAL;
+    }
+    const int64_t G = (int64_t)(n - 1) * hr_stride + S;
+    if (G > 0x7fff || (int64_t)n * n * n_images > 0x7fffffff || !(fabsf(lo) <= 16777216.f && fabsf(hi) <= 16777216.f)) {
+        set_error("probav_tile_blend: an image side over 32767, more than 2^31 - 1 tiles, or clip bounds beyond +-2^24 (the result must be an integer "
+                  "that fp32 holds)", hipSuccess);
+        return PROBAV_EINVAL;
+    }
+    TileGeom g;
+    g.n = n; g.S = S; g.hs = hr_stride; g.G = (int)G; g.lo = lo; g.hi = hi;
+    const size_t pixels = (size_t)n_images * G * G;
+    const bool vec = S % 4 == 0 && hr_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(sr) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
+    const size_t groups = vec ? pixels / 4 : pixels;
+    const size_t blocks = (groups + TILE_THREADS - 1) / TILE_THREADS;
+    if (blocks > 0x7fffffff) {
+        set_error("probav_tile_blend: too many output pixels for one launch: blend fewer images per call", hipSuccess);
+        return PROBAV_EINVAL;
+    }
+    if (vec) hipLaunchKernelGGL(tile_blend_kernel<4>, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, (hipStream_t)stream, sr, w, g, groups, out);
+    else hipLaunchKernelGGL(tile_blend_kernel<1>, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, (hipStream_t)stream, sr, w, g, groups, out);
+    return check_launch("tile_blend_kernel");
+}

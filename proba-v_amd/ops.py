@@ -23,6 +23,9 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::ensemble_reduce(sr, recipe, V, lo, hi, final_round, sets, grid) -> patches [N, S, S] | images [sets, grid S, grid S]
                                                                             the mean of the V clipped, rounded predictions of every patch, each turned
                                                                             back, optionally stitched   test.py:137-146, 149-160 (ensemble.py)
+  probav::tile_blend(sr, w, n_images, n, hr_stride, lo, hi) -> images [n_images, G, G]
+                                                                            overlapping tile predictions blended by an integer window, exact
+                                                                            64-bit arithmetic, rounded half to even   test.py:149-160 (tiles.py)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -494,6 +497,49 @@ def ensemble_reduce(sr: Tensor, recipe: Tensor, V: int, lo: float, hi: float, fi
 def _(sr, recipe, V, lo, hi, final_round, sets, grid):
     N, S = _reduce_args(sr, recipe, V, sets, grid)
     return sr.new_empty((sets, grid * S, grid * S) if grid else (N, S, S), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# overlapped-tile inference (csrc/kernels_tile.hip; the definition and the numpy statement are in tiles.py).  No autograd: inference.
+# sr [n_images n n, S, S] or [..., S, S, 1] fp32: the tiles of every image in row-major order; w [S] int32, every entry in [1, 1024].
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _tile_blend_args(sr, w, n_images, n, hr_stride, lo, hi):
+    """-> (S, G) after the checks the real and the fake kernel share."""
+    if sr.dim() == 4 and sr.shape[3] == 1:
+        sr = sr[..., 0]
+    if sr.dim() != 3 or sr.shape[1] != sr.shape[2] or w.dim() != 1:
+        raise ValueError("tile_blend: sr [n_images n n, S, S] (or [..., S, S, 1]), w [S]; got %s %s" % (tuple(sr.shape), tuple(w.shape)))
+    if sr.dtype != torch.float32 or w.dtype != torch.int32:
+        raise ValueError("tile_blend: sr must be float32, w int32; got %s %s" % (sr.dtype, w.dtype))
+    S = sr.shape[1]
+    if n_images < 1 or n < 1 or S < 1 or sr.shape[0] != n_images * n * n or w.shape[0] != S:
+        raise ValueError("tile_blend: %d predictions of side %d and a window of %d do not make %d images of %d x %d tiles"
+                         % (sr.shape[0], S, w.shape[0], n_images, n, n))
+    if not 1 <= hr_stride <= S:
+        raise ValueError("tile_blend: hr_stride = %d; 1 <= hr_stride <= S = %d (a gap between tiles would leave pixels without a weight)" % (hr_stride, S))
+    if not lo <= hi:
+        raise ValueError("tile_blend: lo = %r > hi = %r" % (lo, hi))
+    return S, (n - 1) * hr_stride + S
+
+
+@torch.library.custom_op("probav::tile_blend", mutates_args=(), device_types="cuda")
+def tile_blend(sr: Tensor, w: Tensor, n_images: int, n: int, hr_stride: int, lo: float, hi: float) -> Tensor:
+    """out[y, x] = (sum_t W2 p_t) / (sum_t W2) over the tiles that cover (y, x), rounded half to even in exact 64-bit integer arithmetic;
+    p = rint(clip(sr, lo, hi)), W2[i, j] = w[i] w[j], tile (a, c) at (a hr_stride, c hr_stride) -> [n_images, G, G], G = (n - 1) hr_stride + S.
+    The window must hold integers in [1, 1024] (tiles.validate_window: callers check it on the host before the upload)."""
+    S, G = _tile_blend_args(sr, w, n_images, n, hr_stride, lo, hi)
+    _dev(sr, "sr"), _dev(w, "w")
+    sr, w = sr.contiguous(), w.contiguous()
+    out = torch.empty((n_images, G, G), dtype=torch.float32, device=sr.device)
+    _lib.check(_lib.lib().probav_tile_blend(_lib.ptr(sr), _lib.ptr(w), n_images, n, S, hr_stride, lo, hi, _lib.ptr(out), _lib.current_stream()),
+               "probav_tile_blend")
+    return out
+
+
+@tile_blend.register_fake
+def _(sr, w, n_images, n, hr_stride, lo, hi):
+    S, G = _tile_blend_args(sr, w, n_images, n, hr_stride, lo, hi)
+    return sr.new_empty((n_images, G, G), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -109,8 +109,9 @@ def device_xcorr_surface(ref, img):
     return surf.cpu().numpy(), {"B": float(i[0]), "c_ref": int(i[1]), "c_img": int(i[2]), "max": float(i[3])}
 
 
-def device_patches(frames, masks, pad, win, stride):
-    """frames [S,T,H,W] (cast to fp32), masks [S,T,H,W] -> patches [S,P,T,win,win] fp32, masks bool, counts [S,P,T] int32."""
+def _device_patches(frames, masks, pad, win, stride):
+    """`device_patches` without the copy to the host: (patches [S,P,T,win,win] fp32, masks uint8, counts [S,P,T] int32) as device tensors
+    (tiles.build_tiles keeps the patches where they are and brings only the counts back)."""
     import torch
     from . import _lib
     dev = _dev()
@@ -124,6 +125,12 @@ def device_patches(frames, masks, pad, win, stride):
     pc = torch.empty(S, P, T, dtype=torch.int32, device=dev)
     _lib.check(_lib.lib().probav_prep_patches(_lib.ptr(fr), _lib.ptr(mk), S, T, H, W, pad, win, stride, _lib.ptr(pt), _lib.ptr(pm),
                                               _lib.ptr(pc), _lib.current_stream()), "probav_prep_patches")
+    return pt, pm, pc
+
+
+def device_patches(frames, masks, pad, win, stride):
+    """frames [S,T,H,W] (cast to fp32), masks [S,T,H,W] -> patches [S,P,T,win,win] fp32, masks bool, counts [S,P,T] int32."""
+    pt, pm, pc = _device_patches(frames, masks, pad, win, stride)
     return pt.cpu().numpy(), pm.cpu().numpy().astype(bool), pc.cpu().numpy()
 
 
@@ -266,16 +273,15 @@ def _mask_counts(patches):
     return m.reshape(*m.shape[:-3], -1).sum(-1)
 
 
-def removeAndReplaceDirtyFrames(imgSet, k, clarityThreshold, counts=None):
-    """imgSet [P, T, C, H, W]: per patch, the frames that pass the threshold (all of them if none does), tiled to at least k, sorted by
-    masked-pixel count (np.argsort of the tiled counts, as the reference), first k."""
-    P, T, C, H, W = imgSet.shape
-    counts = _mask_counts(imgSet) if counts is None else counts
+def clearFrameSelection(counts, pixels, k, clarityThreshold):
+    """The index half of removeAndReplaceDirtyFrames: counts [P, T] masked pixels of every frame of every patch (`pixels` each) ->
+    (sel [P, k] frame indices, count, countNotReplaced).  tiles.build_tiles applies `sel` to patches that stay on the device."""
+    P, T = np.shape(counts)
     sel = np.empty((P, k), np.int64)
     count = countNotReplaced = 0
     for i in range(P):
         cnt = np.asarray(counts[i], np.int64)
-        idx = np.nonzero(cnt / (H * W) < (1 - clarityThreshold))[0]
+        idx = np.nonzero(cnt / pixels < (1 - clarityThreshold))[0]
         if len(idx) == 0:
             idx = np.arange(T)
             count += T
@@ -284,6 +290,15 @@ def removeAndReplaceDirtyFrames(imgSet, k, clarityThreshold, counts=None):
             count += T - len(idx)
         tiled = np.tile(idx, math.ceil(k / len(idx)))
         sel[i] = tiled[np.argsort(cnt[tiled])][:k]
+    return sel, count, countNotReplaced
+
+
+def removeAndReplaceDirtyFrames(imgSet, k, clarityThreshold, counts=None):
+    """imgSet [P, T, C, H, W]: per patch, the frames that pass the threshold (all of them if none does), tiled to at least k, sorted by
+    masked-pixel count (np.argsort of the tiled counts, as the reference), first k."""
+    P, T, C, H, W = imgSet.shape
+    counts = _mask_counts(imgSet) if counts is None else counts
+    sel, count, countNotReplaced = clearFrameSelection(counts, H * W, k, clarityThreshold)
     out = imgSet[np.arange(P)[:, None], sel]
     return np.ma.masked_array(np.ma.getdata(out), mask=np.ma.getmaskarray(out)), count, countNotReplaced
 

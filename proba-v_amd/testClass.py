@@ -11,6 +11,8 @@ import torch
 
 from . import _lib, ops            # noqa: F401  (ops registers torch.ops.probav.*)
 from .ensemble import EnsembleSpec, ensemble_reduce_numpy, validate_ensemble_recipe      # noqa: F401  (re-exported)
+from . import tiles as _tiles
+from .tiles import TileSpec, tile_blend_numpy      # noqa: F401  (re-exported)
 
 
 def _device_of(model):
@@ -196,7 +198,65 @@ def stitch_device(sr, sets):
     return sr.reshape(sets, n, n, ps, ps).permute(0, 1, 3, 2, 4).reshape(sets, n * ps, n * ps)
 
 
-def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round"):
+def resolve_tiled(model, tiles, spec, ensemble=None, launch_batch=None):
+    """Overlapping tiles [images, n n, P+s, P+s, T, 1] (tiles.build_tiles at spec.stride; the chunk of images the caller chose) -> the blended
+    uint16-range images [images, G, G] (device tensor), G = scale * ((n - 1) * stride + P): tiles.py states the blend.  The forward passes
+    run in launch sets of at most `launch_batch` tiles (default LAUNCH_BATCH), with an `ensemble` (EnsembleSpec) in launch sets of
+    launch_batch // V tiles through `resolve_ensemble`'s kernels, every tile rounded (final="round"); then ONE blend kernel, which clips and
+    rounds the raw predictions itself.  Integer arithmetic from there on: the images do not depend on the launch sets."""
+    dev = _device_of(model)
+    if dev.type != "cuda":
+        raise RuntimeError("the model lives on %s: the tile blend runs as a HIP kernel on a gfx950 device (no CPU fallback)" % dev)
+    t = torch.as_tensor(tiles)
+    images, nn_ = t.shape[0], t.shape[1]
+    n = int(round(nn_ ** 0.5))
+    if t.dim() != 6 or n * n != nn_:
+        raise ValueError("tiles must be [images, n * n, win, win, T, 1], got %s" % (tuple(t.shape),))
+    P, r = model.patchSizeLR, model.scale
+    if not 1 <= spec.stride <= P:
+        raise ValueError("tile stride %d outside 1..%d" % (spec.stride, P))
+    S = r * P
+    w = torch.from_numpy(spec.weights(S)).to(dev)                    # validated on the host: every weight in [1, 1024]
+    flat = t.reshape((-1,) + tuple(t.shape[2:]))
+    sr = torch.empty((flat.shape[0], S, S), dtype=torch.float32, device=dev)
+    if ensemble is not None:
+        i = 0
+        for out in _ensemble_launch_sets(model, flat, ensemble, "round", launch_batch):
+            sr[i:i + out.shape[0]] = out
+            i += out.shape[0]
+    else:
+        per = max(1, LAUNCH_BATCH if launch_batch is None else launch_batch)
+        with torch.no_grad():
+            for i in range(0, flat.shape[0], per):
+                x = flat[i:i + per].to(device=dev, dtype=torch.float32)
+                sr[i:i + x.shape[0]] = model(x, training=False)[..., 0]
+    return torch.ops.probav.tile_blend(sr, w, images, n, r * spec.stride, 0.0, float(2 ** 16))
+
+
+def resolve_tiled_frames(model, imgsLR_masked, spec, config, ensemble=None, launch_batch=None, budget=None):
+    """The registered LR frames of whole image sets (trimmedArrayDir/<TEST|TRAIN>imgLR_<band>.npy, masked [images, T_pre, 1, H, H]) -> the
+    blended images [images, G, G] on the device: tiles.build_tiles + resolve_tiled in chunks of whole images sized so that neither the
+    unfolded tiles nor the predictions of a chunk exceed `budget` bytes (default tiles.CHUNK_BYTES, 1 GiB each)."""
+    H, T_pre = imgsLR_masked.shape[3], imgsLR_masked.shape[1]
+    spec.validate(int(config["patch_size"]), H)
+    per = _tiles.images_per_chunk(spec, config, H, T_pre, _tiles.CHUNK_BYTES if budget is None else budget)
+    dev = _device_of(model)
+    outs = []
+    for i in range(0, imgsLR_masked.shape[0], per):
+        t = _tiles.build_tiles(imgsLR_masked[i:i + per], spec, config, dev)
+        outs.append(resolve_tiled(model, t, spec, ensemble=ensemble, launch_batch=launch_batch))
+        del t
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+def evaluate_tiled_frames(model, imgsLR_masked, spec, config, ensemble=None, launch_batch=None, budget=None):
+    """`resolve_tiled_frames` in the form `evaluate_device` returns: a list of [G, G, 1] float64 arrays, one copy back."""
+    imgs = resolve_tiled_frames(model, imgsLR_masked, spec, config, ensemble=ensemble, launch_batch=launch_batch, budget=budget)
+    imgs = imgs.cpu().numpy().astype(np.float64)
+    return [im[:, :, None] for im in imgs]
+
+
+def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round", tiles=None):
     """All image sets at once: patches [sets, n*n, P+s, P+s, T, 1] -> uint16-range images [sets, 3nP, 3nP] (device tensor).
     Samples are independent in every kernel family (models/modelsTF.py:15-43 has no cross-sample term; the H3 kernels scale their
     operands per sample), so any micro-batch gives bit-identical pixels to the reference's batches of 16
@@ -207,7 +267,13 @@ def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble
     `ensemble` (an EnsembleSpec; None = the plain path, untouched): every patch is predicted in the spec's V variants and the images are the
     self-ensemble of `resolve_ensemble` in the form `final` ("round" = uint16-range, what a PNG takes; "mean" = the fp32 mean).  A launch set
     then holds launch_batch // V whole patches -- whole images, reduced and stitched by one kernel, when that many fit; `micro_batch` plays
-    no part."""
+    no part.
+    `tiles` (a TileSpec; None = the paths above, untouched): `patches` are the overlapping tiles of tiles.build_tiles at that stride and the
+    images are their blend, `resolve_tiled` (always the rounded form; `micro_batch` plays no part)."""
+    if tiles is not None:
+        if final != "round":
+            raise ValueError("blended tiles are integers: final must be 'round', got %r" % (final,))
+        return resolve_tiled(model, patches, tiles, ensemble=ensemble, launch_batch=launch_batch)
     dev = _device_of(model)
     p = torch.as_tensor(patches)
     sets = p.shape[0]
@@ -227,12 +293,15 @@ def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble
     return stitch_device(torch.cat(outs) if len(outs) > 1 else outs[0], sets)
 
 
-def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round"):
+def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round", tiles=None):
     """test.py:103-111 through the device pipeline: every image set in micro-batches of `micro_batch` patches (16 = the reference's
     resolveByBatch; coalesced into launch sets unless `launch_batch` says otherwise), clip / round and the 8 x 8 stitch on the device, ONE
     copy back.  Returns a list of [384, 384, 1] float64 arrays, element for element what the reference's `evaluate` returns.
-    `ensemble`, `final`: the self-ensemble of `resolve_images` instead of the plain prediction (None: today's path and bytes)."""
-    if ensemble is None:
+    `ensemble`, `final`: the self-ensemble of `resolve_images` instead of the plain prediction (None: today's path and bytes).
+    `tiles`: a TileSpec when X_test_patches are overlapping tiles to be blended (`resolve_images`; None: today's path and bytes)."""
+    if tiles is not None:
+        imgs = resolve_images(model, X_test_patches, launch_batch=launch_batch, ensemble=ensemble, final=final, tiles=tiles)
+    elif ensemble is None:
         imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch)
     else:
         imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch, ensemble=ensemble, final=final)

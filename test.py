@@ -9,6 +9,12 @@ removedTrainSets<band>.txt exactly as the reference does.
 --ensemble d8 [--ensemble-permute P --ensemble-seed s] writes the test-time self-ensemble instead (probav_amd/ensemble.py): every
 patch predicted in 8 (P + 1) flipped / turned / frame-shuffled variants, the clipped and rounded predictions turned back and averaged on the
 device, the mean rounded half to even for the PNG.  It costs that many forward passes.  --ensemble none (default) is the path above, byte for byte.
+
+--tile-stride s [--tile-window hat|box] writes the blend of overlapping tiles instead (probav_amd/tiles.py): the registered frames
+of <preprocessing_out>/trimmedArrayDir/<TEST|TRAIN>imgLR_<band>.npy are unfolded at LR stride s, the frames of every tile chosen as the dataset
+builder chooses them, every tile predicted, and the predictions blended by an integer window in exact arithmetic on the device.  The set order,
+hence the PNG names and the omitted ids, is the same.  ((128 - P) / s + 1)^2 / 64 times the forward passes (3.5 x at s = 8); combines with
+--ensemble.  --tile-stride 0 (default) is the path above, byte for byte.
 """
 import argparse
 import logging
@@ -20,7 +26,8 @@ import torch
 from probav_amd.modelsTF import WDSRConv3D
 from probav_amd.parseConfig import parseConfig
 from probav_amd.pngio import imsave_uint16
-from probav_amd.testClass import evaluate, evaluate_device
+from probav_amd.testClass import evaluate, evaluate_device, evaluate_tiled_frames
+from probav_amd.tiles import cli_tile_args
 from probav_amd.trainClass import ModelTrainer
 
 logging.basicConfig(format="%(asctime)s - %(message)s", level=logging.INFO)
@@ -44,12 +51,26 @@ def parser(argv=None):
     p.add_argument("--ensemble-permute", type=int, default=0, help="with --ensemble d8: P further frame orders, crossed with the 8 geometric variants "
                    "(8 (P + 1) members, at most 256)")
     p.add_argument("--ensemble-seed", type=int, default=0, help="seed of the frame orders: the same seed gives the same images")
+    p.add_argument("--tile-stride", type=int, default=0, help="predict overlapping tiles at this LR stride and blend them on the device "
+                   "(it must divide 128 - patch_size and be at most patch_size; 8 = 3.5 x the forward passes); 0 = disjoint patches placed side by side")
+    p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
     opt = p.parse_args(argv)
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
     if opt.ensemble != "none" and opt.reference_loop:
         p.error("--reference-loop is the reference's plain loop: it cannot be combined with --ensemble")
+    if opt.tile_stride and opt.reference_loop:
+        p.error("--reference-loop is the reference's plain loop: it cannot be combined with --tile-stride")
+    cli_tile_args(p, opt)
     return opt
+
+
+def tile_spec(opt):
+    """The TileSpec the two --tile flags ask for (None: disjoint patches)."""
+    if not opt.tile_stride:
+        return None
+    from probav_amd.tiles import TileSpec
+    return TileSpec(opt.tile_stride, opt.tile_window)
 
 
 def ensemble_spec(opt):
@@ -62,9 +83,13 @@ def ensemble_spec(opt):
 
 def main(config, opt):
     logger.info("[ INFO ] Loading data...")
-    dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
-    patchLR = np.load(os.path.join(dataDir, "%spatchesLR_%s.npy" % (opt.totest, opt.band)), allow_pickle=True)
-    patchLR = np.array(patchLR).transpose((0, 1, 4, 5, 2, 3))                    # -> [sets, 64, 22, 22, T, 1] (test.py:38)
+    tiles = tile_spec(opt)
+    if tiles is not None:
+        framesLR = np.load(os.path.join(config["preprocessing_out"], "trimmedArrayDir", "%simgLR_%s.npy" % (opt.totest, opt.band)), allow_pickle=True)
+    else:
+        dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
+        patchLR = np.load(os.path.join(dataDir, "%spatchesLR_%s.npy" % (opt.totest, opt.band)), allow_pickle=True)
+        patchLR = np.array(patchLR).transpose((0, 1, 4, 5, 2, 3))                    # -> [sets, 64, 22, 22, T, 1] (test.py:38)
     mean, std = BAND_STATS["NIR" if opt.band == "NIR" else "RED"]
     k = config["kernel_size"]
     model = WDSRConv3D(name="superResolutionNet", band=opt.band, mean=mean, std=std, maxShift=config["max_shift"]).build(
@@ -76,7 +101,10 @@ def main(config, opt):
     ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, opt.band))   # restores the latest checkpoint
     logger.info("[ INFO ] Generating predictions...")
     spec = ensemble_spec(opt)
-    if spec is not None:
+    if tiles is not None:
+        logger.info("[ INFO ] Overlapping tiles at stride %d, %s window%s" % (tiles.stride, tiles.window, "" if spec is None else ", self-ensemble of %d members per tile" % spec.V))
+        y_preds = evaluate_tiled_frames(model, framesLR, tiles, config, ensemble=spec)
+    elif spec is not None:
         logger.info("[ INFO ] Self-ensemble of %d members per patch" % spec.V)
         y_preds = evaluate_device(model, patchLR, ensemble=spec, final="round")
     else:
