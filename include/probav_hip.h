@@ -10,8 +10,10 @@
  *   - activations [N][H][W][T][C], C innermost (the reference's layout; models/modelsTF.py:19);
  *     kernels [kh][kw][kt][Cin][Cout] (Keras).  All buffers contiguous, 16-byte aligned.
  *   - every call only ENQUEUES work on `stream` and returns; it never synchronises, allocates or
- *     frees device memory (so calls can be captured in a hipGraph).  probav_engine_create /
- *     _destroy are the only functions that allocate (a few KB for the layer table).
+ *     frees device memory (so calls can be captured in a hipGraph).  The one exception is an engine's
+ *     first call that launches with its layer table (a pass, a weight-norm or optimizer call): it uploads
+ *     that table, a few KB, once -- make it outside a graph capture.  probav_engine_create itself touches
+ *     no device: the size and layout queries of a configuration answer on a host without one.
  *     probav_forward / probav_backward additionally fork work that is off the critical path (the
  *     low-frequency residual path, the sums of the backward-filter slabs) onto one engine-owned side
  *     stream by event and join it back into `stream` before returning: the caller sees plain

@@ -615,19 +615,31 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
         b[2].w2b = add(pack_job(Operand::pw_w2b, 2, E, D), w2, 0, ld);
         e->pkBlk.push_back(b);
     }
-    if (!e->jobs.empty()) {
-        hipError_t perr = hipMalloc((void**)&e->d_jobs, e->jobs.size() * sizeof(PackJob));
-        if (perr == hipSuccess) perr = hipMemcpy(e->d_jobs, e->jobs.data(), e->jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice);
-        if (perr != hipSuccess) { set_error("probav_engine_create: pack table upload", perr); delete e; return PROBAV_EHIP; }
-    }
-    std::vector<WnLayer> h;
-    for (auto& r : e->layers) h.push_back(r.wn);
-    hipError_t err = hipMalloc((void**)&e->d_layers, h.size() * sizeof(WnLayer));
-    if (err == hipSuccess) err = hipMemcpy(e->d_layers, h.data(), h.size() * sizeof(WnLayer), hipMemcpyHostToDevice);
-    if (err != hipSuccess) { set_error("probav_engine_create: layer table upload", err); delete e; return PROBAV_EHIP; }
+    // (the layer and packing tables go to the device with the first call that launches with them: device_tables)
     const char* env = getenv("PROBAV_IMPL");
     e->fam = make_family(env ? atoi(env) : 4, e->pw_mfma);
     *out = e;
+    return PROBAV_OK;
+}
+
+// The layer table and the packing jobs on the device, uploaded by the first call that launches with them (like the side stream, created on the engine's
+// first pass: make that call outside a graph capture).  probav_engine_create itself touches no device, so the size and layout queries of a configuration
+// answer on a host without one.
+static int device_tables(probav_engine* e)
+{
+    if (e->d_layers) return PROBAV_OK;
+    if (!e->jobs.empty() && !e->d_jobs) {
+        hipError_t perr = hipMalloc((void**)&e->d_jobs, e->jobs.size() * sizeof(PackJob));
+        if (perr == hipSuccess) perr = hipMemcpy(e->d_jobs, e->jobs.data(), e->jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice);
+        if (perr != hipSuccess) { if (e->d_jobs) (void)hipFree(e->d_jobs); e->d_jobs = nullptr; set_error("probav_engine: pack table upload", perr); return PROBAV_EHIP; }
+    }
+    std::vector<WnLayer> h;
+    for (auto& r : e->layers) h.push_back(r.wn);
+    WnLayer* d = nullptr;
+    hipError_t err = hipMalloc((void**)&d, h.size() * sizeof(WnLayer));
+    if (err == hipSuccess) err = hipMemcpy(d, h.data(), h.size() * sizeof(WnLayer), hipMemcpyHostToDevice);
+    if (err != hipSuccess) { if (d) (void)hipFree(d); set_error("probav_engine: layer table upload", err); return PROBAV_EHIP; }
+    e->d_layers = d;
     return PROBAV_OK;
 }
 
@@ -751,6 +763,7 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     hipStream_t s = (hipStream_t)stream;
     const Plan p = make_plan(e, B, training);
     if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_forward: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
+    CK(device_tables(e));
     float* W = (float*)ws;
     const WcPlan wc = make_wc_plan(e);
     // where the parameter-derived tensors live: inside the workspace (recomputed by this call) or in the caller's weight cache
@@ -838,6 +851,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     const Plan p = make_plan(e, B, 1);
     if (ws_bytes < (scratch ? p.fwd_total : p.total) * sizeof(float)) { set_error("probav_backward: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
     if (scratch && scratch_bytes < p.bwd_total * sizeof(float)) { set_error("probav_backward: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
+    CK(device_tables(e));
     const float* W = (const float*)ws;
     float* S = scratch ? (float*)scratch : const_cast<float*>(W) + p.fwd_total;
     const WcPlan wc = make_wc_plan(e);
@@ -1045,6 +1059,7 @@ int probav_optimizer_step_fused(probav_engine* e, float* params, const float* gr
     if (!e || !params || !grads || !m || !v || !wcache) { set_error("probav_optimizer_step_fused: null argument", hipSuccess); return PROBAV_EINVAL; }
     const WcPlan wc = make_wc_plan(e);
     if (wcache_bytes < wc.total * sizeof(float)) { set_error("probav_optimizer_step_fused: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
+    CK(device_tables(e));
     hipStream_t s = (hipStream_t)stream;
     float* C = (float*)wcache;
     unsigned* wam = reinterpret_cast<unsigned*>(C + wc.amax);
@@ -1064,6 +1079,7 @@ int probav_weight_cache_build(probav_engine* e, const float* params, void* wcach
     if (!e || !params || !wcache) { set_error("probav_weight_cache_build: null argument", hipSuccess); return PROBAV_EINVAL; }
     const WcPlan wc = make_wc_plan(e);
     if (wcache_bytes < wc.total * sizeof(float)) { set_error("probav_weight_cache_build: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
+    CK(device_tables(e));
     hipStream_t s = (hipStream_t)stream;
     float* C = (float*)wcache;
     unsigned* wam = reinterpret_cast<unsigned*>(C + wc.amax);
@@ -1337,11 +1353,13 @@ int probav_pw_backward(const float* x, const float* d_dec, const float* d_skip, 
 int probav_wn_forward(probav_engine* e, const float* params, float* weff, float* weffT, float* inv_norm, void* stream)
 {
     if (!e || !params || !weff || !weffT || !inv_norm) { set_error("probav_wn_forward: null argument", hipSuccess); return PROBAV_EINVAL; }
+    CK(device_tables(e));
     return wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, weff, weffT, inv_norm, nullptr, (hipStream_t)stream);
 }
 int probav_wn_backward(probav_engine* e, const float* params, const float* dweff, const float* inv_norm, float* grads, void* stream)
 {
     if (!e || !params || !dweff || !inv_norm || !grads) { set_error("probav_wn_backward: null argument", hipSuccess); return PROBAV_EINVAL; }
+    CK(device_tables(e));
     return wn_backward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, params, dweff, inv_norm, grads, (hipStream_t)stream);
 }
 

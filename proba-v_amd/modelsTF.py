@@ -50,6 +50,7 @@ class WDSRModel(torch.nn.Module):
             flat[L.g_off:L.v_off] = v.double().reshape(-1, vs[-1]).pow(2).sum(0).sqrt().float()
         self.flat = torch.nn.Parameter(flat)
         self._engine = None
+        self._impl = None
         self._ws = {}
         self._wcache, self._wcache_version = None, None
 
@@ -156,6 +157,12 @@ class WDSRModel(torch.nn.Module):
         4 (default) = the same kernels with the H3 arithmetic (three products of fp16 piece pairs, operands scaled by a power
         of two per sample / per filter column).  Every family computes a sample independently of its batch mates, bit for bit."""
         _lib.check(_lib.lib().probav_engine_set_impl(self._handle(), int(impl)), "probav_engine_set_impl")
+        self._impl = int(impl)
+
+    @property
+    def impl(self):
+        """The engine's kernel family: what `set_impl` chose, else the engine's own default (PROBAV_IMPL in the environment, else 4)."""
+        return self._impl if self._impl is not None else int(os.environ.get("PROBAV_IMPL", 4))
 
     def set_side_stream_mode(self, mode):
         """probav_engine_side_stream: 0 = everything on the caller's stream; 1 = the slab sums, the residual path and the upscale layer's backward-filter on the
