@@ -5,6 +5,7 @@
     python evaluate.py --cfg C --band NIR --model          # the cfg's latest checkpoint on the TRAIN sets, no PNGs written
     python evaluate.py --cfg C --band NIR --model --ensemble d8 [--ensemble-permute P --ensemble-seed s]     # ... its test-time self-ensemble
     python evaluate.py --cfg C --band NIR --model --tile-stride 8 [--tile-window hat|box]                    # ... its overlapped, blended tiles
+    python evaluate.py --cfg C --band NIR --model --weights ema                                              # ... its EMA weights (train.py --ema-momentum)
 
 --toCompare scores the imgsetNNNN.png of a folder (test.py's output) against resolverDir/TRAINimgHR_<band>.npy, matching by id: train ids
 below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted, skipped).  --model resolves resolverDir/TRAINpatchesLR_<band>.npy
@@ -50,6 +51,8 @@ def parser(argv=None):
     p.add_argument("--tile-stride", type=int, default=0, help="with --model: score the blend of overlapping tiles at this LR stride, as "
                    "test.py --tile-stride writes it; 0 = disjoint patches")
     p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
+    p.add_argument("--weights", type=str, default="raw", choices=("raw", "ema"), help="with --model: score the checkpoint's raw weights (default) or "
+                   "the moving average saved by train.py --ema-momentum; ema on a checkpoint without one is an error")
     p.add_argument("--border", type=int, default=3, help=argparse.SUPPRESS)
     opt = p.parse_args(argv)
     opt.band = opt.band.upper()
@@ -61,6 +64,8 @@ def parser(argv=None):
         p.error("--ensemble applies to --model (a folder of PNGs is scored as it is)")
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
+    if opt.weights != "raw" and not opt.model:
+        p.error("--weights applies to --model (a folder of PNGs is scored as it is)")
     if opt.tile_stride and not opt.model:
         p.error("--tile-stride applies to --model (a folder of PNGs is scored as it is)")
     for name in ("toCompare", "benchmark"):
@@ -78,10 +83,11 @@ def parser(argv=None):
     return opt
 
 
-def model_images(config, cfg_path, band, ensemble=None, tiles=None):
+def model_images(config, cfg_path, band, ensemble=None, tiles=None, weights="raw"):
     """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN, without the PNGs.
     ensemble: an EnsembleSpec for the self-ensemble images test.py --ensemble writes (None: the plain prediction).
-    tiles: a TileSpec for the blended overlapping tiles test.py --tile-stride writes (None: disjoint patches)."""
+    tiles: a TileSpec for the blended overlapping tiles test.py --tile-stride writes (None: disjoint patches).
+    weights: "raw" or "ema" -- the checkpoint entry test.py --weights predicts with."""
     import torch
     from probav_amd.modelsTF import WDSRConv3D
     from probav_amd.testClass import evaluate_device, evaluate_tiled_frames
@@ -101,7 +107,12 @@ def model_images(config, cfg_path, band, ensemble=None, tiles=None):
     basename = os.path.basename(cfg_path).split(".")[0]
     ckptDir = os.path.join(config["model_out"], "ckpt_%s" % basename, band)
     with contextlib.redirect_stdout(sys.stderr):            # the restore messages: stdout carries the JSON line only
-        trainer = ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, band))
+        try:
+            trainer = ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, band), weights=weights)
+        except ValueError as exc:
+            if weights != "ema":
+                raise
+            raise SystemExit("evaluate.py --model --weights ema: %s" % exc)
     if trainer.latest_checkpoint is None and trainer._tf_latest() is None:
         raise SystemExit("evaluate.py --model: no checkpoint under %s" % ckptDir)
     if tiles is not None:
@@ -142,7 +153,7 @@ def main(opt):
             tiles = TileSpec(opt.tile_stride, opt.tile_window)
         images = {}
         for b in bands:
-            images.update(model_images(config, opt.cfg, b, ensemble=spec, tiles=tiles))
+            images.update(model_images(config, opt.cfg, b, ensemble=spec, tiles=tiles, weights=opt.weights))
     else:
         images = scoring.load_sr_dir(opt.toCompare)
     rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
@@ -153,6 +164,8 @@ def main(opt):
     summary["formula"] = opt.formula
     if opt.ensemble != "none":
         summary["ensemble"] = {"geometry": opt.ensemble, "permute": opt.ensemble_permute, "seed": opt.ensemble_seed}
+    if opt.weights != "raw":
+        summary["weights"] = opt.weights
     if opt.tile_stride:
         summary["tiles"] = {"stride": opt.tile_stride, "window": opt.tile_window}
     summary["norm"] = norm_path

@@ -165,6 +165,38 @@ int probav_revssim_backward(const float* hr, const uint8_t* mask, const float* p
  * three optimizers of train.py:77-83 are one fused launch.                                                           */
 int probav_nadam_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                       float eps, float c_g, float c_m, float c_v, void* stream);
+/* ---- optimizer options on the device: global-norm clip, non-finite guard, weight EMA (additions made UNDER ABI 7: purely additive, the
+ * version number stays) ---------------------------------------------------------------------------------------------------------------
+ * replaces  the Keras optimizer arguments `global_clipnorm` (= tf.clip_by_global_norm over all gradient tensors), `use_ema` / `ema_momentum`
+ *           (optimizer_v2 of train.py:77-83), and adds a guard Keras does not have: a step whose gradient holds an inf or a NaN is dropped.
+ * probav_grad_guard: two launches.  (1) the sum of squares of the flat gradient in fp64, fixed grid, fixed order, one fp64 partial per
+ * workgroup in `scratch` (probav_grad_guard_scratch_bytes; no floating-point atomics: the same gradient gives the same bits).  (2) one
+ * workgroup sums the partials in index order and writes the control block:
+ *     total = sum g^2 (fp64);  norm = sqrt(total);  scale = clipnorm / max(norm, clipnorm) in fp64, rounded once to fp32 (1 when clipnorm <= 0)
+ *     skip  = 1 when skip_nonfinite != 0 and total is not finite (squares of finite fp32 values cannot overflow an fp64 sum: total is
+ *             non-finite exactly when some element is), else 0;  skipped_total += skip  (the caller zeroes the block once, before the first step)
+ * A non-finite total with clipping on and the guard off gives scale = NaN, as tf.clip_by_global_norm does.  One call = one step's decision.
+ * The *_guarded steps read the block on the device: g' = g * scale enters the update rule of probav_nadam_step; with skip set params, m, v
+ * and ema are left untouched (the fused step still normalises and packs the unchanged parameters: the weight cache stays valid).  With
+ * ema != NULL, after the update:  ema = ema_momentum * ema + (1 - ema_momentum) * params   (Keras's rule, no de-biasing; the caller
+ * initialises ema to the initial parameters).  ctl == NULL: no scaling and no skip (EMA only).  With ctl->scale == 1, skip == 0 and
+ * ema == NULL the guarded steps leave the bits of the plain ones.  Nothing here is read by the host.                                     */
+typedef struct probav_guard_ctl {
+    float scale;              /* what every gradient element is multiplied by */
+    uint32_t skip;            /* 1: this step is dropped */
+    uint32_t skipped_total;   /* running count of dropped steps */
+    float norm;               /* global L2 norm of the gradient, fp64 rounded to fp32 */
+} probav_guard_ctl;
+size_t probav_grad_guard_scratch_bytes(int64_t n);
+int probav_grad_guard(const float* grads, int64_t n, float clipnorm /* <= 0: off */, int skip_nonfinite, void* scratch, size_t scratch_bytes,
+                      probav_guard_ctl* ctl /* device */, void* stream);
+int probav_nadam_step_guarded(float* params, const float* grads, float* m, float* v, float* ema /* or NULL */, int64_t n, float lr,
+                              float beta1, float beta2, float eps, float c_g, float c_m, float c_v, float ema_momentum,
+                              const probav_guard_ctl* ctl /* device, or NULL: EMA only */, void* stream);
+int probav_optimizer_step_fused_guarded(probav_engine* e, float* params, const float* grads, float* m, float* v, float lr, float beta1,
+                                        float beta2, float eps, float c_g, float c_m, float c_v, void* wcache, size_t wcache_bytes,
+                                        float* ema /* or NULL */, float ema_momentum, const probav_guard_ctl* ctl /* device, or NULL */,
+                                        void* stream);
 /* replaces tf.clip_by_value(sr, 0, 2**16); tf.round(sr)                 test.py:118-119             */
 int probav_clip_round(const float* in, float* out, size_t n, float lo, float hi, void* stream);
 

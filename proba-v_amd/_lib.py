@@ -21,6 +21,11 @@ class NetCfg(ctypes.Structure):
                 ("max_shift", c_int32), ("mean", c_float), ("std", c_float), ("in_channels", c_int32)]
 
 
+class GuardCtl(ctypes.Structure):
+    """struct probav_guard_ctl (include/probav_hip.h): the device control block of a guarded optimizer step, 16 bytes."""
+    _fields_ = [("scale", c_float), ("skip", ctypes.c_uint32), ("skipped_total", ctypes.c_uint32), ("norm", c_float)]
+
+
 # every symbol include/probav_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "probav_abi_version": (c_int, []),
@@ -50,6 +55,13 @@ SIGNATURES = {
     "probav_clip_round": (c_int, [c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p]),
     "probav_nadam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                   c_float, c_float, c_float, c_void_p]),
+    # optimizer options on the device (csrc/kernels_small.hip): added under ABI 7
+    "probav_grad_guard_scratch_bytes": (c_size_t, [c_int64]),
+    "probav_grad_guard": (c_int, [c_void_p, c_int64, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "probav_nadam_step_guarded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+                                          c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "probav_optimizer_step_fused_guarded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float,
+                                                    c_float, c_void_p, c_size_t, c_void_p, c_float, c_void_p, c_void_p]),
     "probav_conv3d_forward": (c_int, [POINTER(c_int32 * 17), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int, c_void_p]),
     "probav_conv3d_wgrad_scratch_bytes": (c_size_t, [POINTER(c_int32 * 17), c_int]),

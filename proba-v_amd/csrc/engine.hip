@@ -1073,6 +1073,27 @@ int probav_optimizer_step_fused(probav_engine* e, float* params, const float* gr
     return PROBAV_OK;
 }
 
+int probav_optimizer_step_fused_guarded(probav_engine* e, float* params, const float* grads, float* m, float* v, float lr, float beta1, float beta2,
+                                        float eps, float c_g, float c_m, float c_v, void* wcache, size_t wcache_bytes, float* ema, float ema_momentum,
+                                        const probav_guard_ctl* ctl, void* stream)
+{
+    if (!e || !params || !grads || !m || !v || !wcache) { set_error("probav_optimizer_step_fused_guarded: null argument", hipSuccess); return PROBAV_EINVAL; }
+    if (ema && !(ema_momentum >= 0.f && ema_momentum <= 1.f)) { set_error("probav_optimizer_step_fused_guarded: ema_momentum outside [0, 1]", hipSuccess); return PROBAV_EINVAL; }
+    const WcPlan wc = make_wc_plan(e);
+    if (wcache_bytes < wc.total * sizeof(float)) { set_error("probav_optimizer_step_fused_guarded: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
+    CK(device_tables(e));
+    hipStream_t s = (hipStream_t)stream;
+    float* C = (float*)wcache;
+    unsigned* wam = reinterpret_cast<unsigned*>(C + wc.amax);
+    if (hipMemsetAsync(wam, 0, (size_t)wc.n_wamax * sizeof(unsigned), s) != hipSuccess) { set_error("probav_optimizer_step_fused_guarded: amax reset", hipGetLastError()); return PROBAV_EHIP; }
+    // probav_optimizer_step_fused with the control block and the EMA buffer handed to the update half; on a skipped step the same launches rebuild the
+    // cache of the unchanged parameters
+    { ProfScope ps(e, CLS_WN, 0.0, s);
+      CK(optimizer_wn_step_guarded(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, grads, m, v, lr, beta1, beta2, eps, c_g, c_m, c_v,
+                                   C + wc.weff, C + wc.weffT, C + wc.invn, wam, ema, ema_momentum, ctl, s)); }
+    if (!e->jobs.empty()) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), C + wc.weff, C + wc.weffT, C + wc.wpack, wam, s)); }
+    return PROBAV_OK;
+}
 
 int probav_weight_cache_build(probav_engine* e, const float* params, void* wcache, size_t wcache_bytes, void* stream)
 {
@@ -1412,6 +1433,22 @@ int probav_nadam_step(float* params, const float* grads, float* m, float* v, int
 {
     if (!params || !grads || !m || !v || n < 0) { set_error("probav_nadam_step: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
     return nadam_step(params, grads, m, v, (long)n, lr, beta1, beta2, eps, c_g, c_m, c_v, (hipStream_t)stream);
+}
+size_t probav_grad_guard_scratch_bytes(int64_t n) { return n < 0 ? 0 : grad_guard_scratch_bytes(); }
+int probav_grad_guard(const float* grads, int64_t n, float clipnorm, int skip_nonfinite, void* scratch, size_t scratch_bytes, probav_guard_ctl* ctl, void* stream)
+{
+    if (!grads || !scratch || !ctl || n < 0) { set_error("probav_grad_guard: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    if (clipnorm != clipnorm) { set_error("probav_grad_guard: clipnorm is NaN", hipSuccess); return PROBAV_EINVAL; }
+    if (scratch_bytes < grad_guard_scratch_bytes()) { set_error("probav_grad_guard: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
+    if (((uintptr_t)scratch & 7u) != 0) { set_error("probav_grad_guard: scratch must be 8-byte aligned", hipSuccess); return PROBAV_EINVAL; }
+    return grad_guard(grads, (long)n, clipnorm, skip_nonfinite, (double*)scratch, ctl, (hipStream_t)stream);
+}
+int probav_nadam_step_guarded(float* params, const float* grads, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                              float eps, float c_g, float c_m, float c_v, float ema_momentum, const probav_guard_ctl* ctl, void* stream)
+{
+    if (!params || !grads || !m || !v || n < 0) { set_error("probav_nadam_step_guarded: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    if (ema && !(ema_momentum >= 0.f && ema_momentum <= 1.f)) { set_error("probav_nadam_step_guarded: ema_momentum outside [0, 1]", hipSuccess); return PROBAV_EINVAL; }
+    return nadam_step_guarded(params, grads, m, v, ema, (long)n, lr, beta1, beta2, eps, c_g, c_m, c_v, ema_momentum, ctl, (hipStream_t)stream);
 }
 
 int probav_clip_round(const float* in, float* out, size_t n, float lo, float hi, void* stream)

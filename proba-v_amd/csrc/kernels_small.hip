@@ -6,6 +6,7 @@
 //   clip + round-half-even                              (test.py:117-119, models/testClass.py:27-28)
 //   shift-compensated L1 / L2 / cPSNR fwd + bwd         (models/loss.py:37-84, 140-187, 226-238)
 #include "probav_common.h"
+#include "../../include/probav_hip.h"
 #include <cstdlib>
 #include <atomic>
 #include <vector>
@@ -84,16 +85,52 @@ __device__ __forceinline__ float opt_update(float theta, float g, float& m, floa
     return theta - c.lr * (c.c_g * g + c.c_m * m) / (sqrtf(v * c.c_v) + c.eps);
 }
 
+// opt_update with every rounding written out, for the GUARD kernels.  The guarded step with scale == 1, no skip and no EMA must leave the plain
+// step's bits, and which of opt_update's multiply-adds the compiler fuses in the plain kernel is decided per inlined copy (the vectoriser pairs
+// the products of the column loop before fusion sees them): two differently shaped kernels do not get the same choices by themselves.  These are
+// the two forms wn_forward_kernel<true> is compiled to -- COLUMN = false: the gain / bias copy (m, v and the numerator each one fused
+// multiply-add); COLUMN = true: the column loop (m fused, v and the numerator two rounded products and a sum).  Contraction is off in here, so
+// the form does not depend on the caller.  tests/test_gpu_optim_guard.py compares the two kernels bit for bit: a compiler that chooses
+// otherwise for the plain kernel shows there.
+template <bool COLUMN>
+__device__ __forceinline__ float opt_update_exact(float theta, float g, float& m, float& v, const OptCoef& c)
+{
+#pragma clang fp contract(off)
+    const float gm = (1.f - c.b1) * g;
+    m = __builtin_fmaf(c.b1, m, gm);
+    const float gv = ((1.f - c.b2) * g) * g;
+    float num;
+    if constexpr (COLUMN) {
+        const float bv = c.b2 * v;
+        v = bv + gv;
+        const float ng = c.c_g * g, nm = c.c_m * m;
+        num = ng + nm;
+    } else {
+        v = __builtin_fmaf(c.b2, v, gv);
+        const float nm = c.c_m * m;
+        num = __builtin_fmaf(c.c_g, g, nm);
+    }
+    const float up = c.lr * num;
+    const float den = sqrtf(v * c.c_v) + c.eps;
+    return theta - up / den;
+}
+
 // UPDATE: the optimizer step of this column's parameters (g[co], bias[co], v[:, co]) runs first, in the same wave, and the
 // reparameterisation that follows is that of the UPDATED parameters: the next forward pass finds its effective weights ready
 // (reference: optimizer.apply_gradients, then WeightNormalization's kernel recomputed at the next call --
 // models/trainClass.py:132, models/modelsTF.py:191-197).  The arithmetic of every element is the one of nadam_kernel.
-template <bool UPDATE>
-__global__ __launch_bounds__(64) void wn_forward_kernel(const WnLayer* __restrict__ layers, int nl,
-                                                       float* __restrict__ params, float* __restrict__ weff,
-                                                       float* __restrict__ weffT, float* __restrict__ inv_norm,
-                                                       unsigned* __restrict__ amax, const float* __restrict__ grad,
-                                                       float* __restrict__ om, float* __restrict__ ov, OptCoef oc)
+// GUARD (include/probav_hip.h, 'optimizer options on the device'): the update reads the step's control block -- every gradient element is
+// multiplied by ctl->scale before opt_update, and with ctl->skip set the whole update half is left out (params, m, v, ema untouched; the
+// reparameterisation below then runs on the unchanged parameters) -- and, with an EMA buffer, follows every updated parameter with
+// ema = mom * ema + (1 - mom) * theta_new.  ctl and ema are wave-uniform (scalar loads, uniform branches).  The two kernels below share this
+// body: with GUARD = false the guard arguments are compile-time dead and the plain kernel is the code it always was.
+template <bool UPDATE, bool GUARD>
+__device__ __forceinline__ void wn_forward_body(const WnLayer* __restrict__ layers, int nl,
+                                                float* __restrict__ params, float* __restrict__ weff,
+                                                float* __restrict__ weffT, float* __restrict__ inv_norm,
+                                                unsigned* __restrict__ amax, const float* __restrict__ grad,
+                                                float* __restrict__ om, float* __restrict__ ov, const OptCoef& oc,
+                                                const probav_guard_ctl* __restrict__ ctl, float* __restrict__ ema, float ema_mom)
 {
     int co;
     const int li = find_layer(layers, nl, blockIdx.x, co);
@@ -101,7 +138,37 @@ __global__ __launch_bounds__(64) void wn_forward_kernel(const WnLayer* __restric
     float* v = params + L.v_off;
     const int lane = threadIdx.x;
     float gain = params[L.g_off + co];
-    if constexpr (UPDATE) {
+    if constexpr (UPDATE && GUARD) {
+        const float gs = ctl ? ctl->scale : 1.f;
+        const bool skip = ctl && ctl->skip != 0u;
+        if (!skip) {
+            {   // as below: every lane computes the gain and the bias, lanes 0 and 1 store them (and their averages)
+                const int ig = L.g_off + co, ib = L.b_off + co;
+                float mg = om[ig], vg = ov[ig], mb = om[ib], vb = ov[ib];
+                gain = opt_update_exact<false>(gain, grad[ig] * gs, mg, vg, oc);
+                const float bnew = opt_update_exact<false>(params[ib], grad[ib] * gs, mb, vb, oc);
+                if (lane == 0) { params[ig] = gain; om[ig] = mg; ov[ig] = vg; if (ema) ema[ig] = ema_mom * ema[ig] + (1.f - ema_mom) * gain; }
+                if (lane == 1) { params[ib] = bnew; om[ib] = mb; ov[ib] = vb; if (ema) ema[ib] = ema_mom * ema[ib] + (1.f - ema_mom) * bnew; }
+            }
+            if (ema) {
+                for (int k = lane; k < L.K; k += 64) {
+                    const int i = L.v_off + k * L.Cout + co;
+                    float mi = om[i], vi = ov[i];
+                    const float e = ema[i];
+                    const float t = opt_update_exact<true>(params[i], grad[i] * gs, mi, vi, oc);
+                    params[i] = t; om[i] = mi; ov[i] = vi;
+                    ema[i] = ema_mom * e + (1.f - ema_mom) * t;
+                }
+            } else {
+                for (int k = lane; k < L.K; k += 64) {
+                    const int i = L.v_off + k * L.Cout + co;
+                    float mi = om[i], vi = ov[i];
+                    params[i] = opt_update_exact<true>(params[i], grad[i] * gs, mi, vi, oc);
+                    om[i] = mi; ov[i] = vi;
+                }
+            }
+        }
+    } else if constexpr (UPDATE) {
         {   // the gain g[co] and the bias[co]: every lane computes both (the values are needed below), lanes 0 and 1 store them
             const int ig = L.g_off + co, ib = L.b_off + co;
             float mg = om[ig], vg = ov[ig], mb = om[ib], vb = ov[ib];
@@ -163,6 +230,25 @@ __global__ __launch_bounds__(64) void wn_forward_kernel(const WnLayer* __restric
         // three cache lines queued for 24 us -- tools/atomic_probe.hip: 3 ns apiece, one after the other)
         if (lane == 0) amax[2 * nl + L.n_off + co] = __float_as_uint(wmax);
     }
+}
+template <bool UPDATE>
+__global__ __launch_bounds__(64) void wn_forward_kernel(const WnLayer* __restrict__ layers, int nl,
+                                                       float* __restrict__ params, float* __restrict__ weff,
+                                                       float* __restrict__ weffT, float* __restrict__ inv_norm,
+                                                       unsigned* __restrict__ amax, const float* __restrict__ grad,
+                                                       float* __restrict__ om, float* __restrict__ ov, OptCoef oc)
+{
+    wn_forward_body<UPDATE, false>(layers, nl, params, weff, weffT, inv_norm, amax, grad, om, ov, oc, nullptr, nullptr, 0.f);
+}
+// wn_forward_kernel<true> with GUARD: the guarded fused step (probav_optimizer_step_fused_guarded)
+__global__ __launch_bounds__(64) void wn_forward_guard_kernel(const WnLayer* __restrict__ layers, int nl,
+                                                             float* __restrict__ params, float* __restrict__ weff,
+                                                             float* __restrict__ weffT, float* __restrict__ inv_norm,
+                                                             unsigned* __restrict__ amax, const float* __restrict__ grad,
+                                                             float* __restrict__ om, float* __restrict__ ov, OptCoef oc,
+                                                             const probav_guard_ctl* __restrict__ ctl, float* __restrict__ ema, float ema_mom)
+{
+    wn_forward_body<true, true>(layers, nl, params, weff, weffT, inv_norm, amax, grad, om, ov, oc, ctl, ema, ema_mom);
 }
 
 // largest |effective weight| per INPUT channel (the output columns of the backward-data matrices weffT, and the rows of W1 the fused
@@ -307,6 +393,17 @@ int optimizer_wn_step(const WnLayer* d_layers, int nlayers, int cout_total, int 
     OptCoef oc = {lr, b1, b2, eps, c_g, c_m, c_v};
     hipLaunchKernelGGL(wn_forward_kernel<true>, dim3(cout_total), dim3(64), 0, s, d_layers, nlayers, params, weff, weffT, inv_norm, amax, grad, m, v, oc);
     int rc = check_launch("optimizer_wn_step");
+    if (rc || !amax) return rc;
+    hipLaunchKernelGGL(wn_rowmax_kernel, dim3(cin_total), dim3(64), 0, s, d_layers, nlayers, weff, amax + 2 * nlayers + cout_total, amax, params);
+    return check_launch("wn_rowmax");
+}
+int optimizer_wn_step_guarded(const WnLayer* d_layers, int nlayers, int cout_total, int cin_total, float* params, const float* grad, float* m, float* v,
+                              float lr, float b1, float b2, float eps, float c_g, float c_m, float c_v,
+                              float* weff, float* weffT, float* inv_norm, unsigned* amax, float* ema, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s)
+{
+    OptCoef oc = {lr, b1, b2, eps, c_g, c_m, c_v};
+    hipLaunchKernelGGL(wn_forward_guard_kernel, dim3(cout_total), dim3(64), 0, s, d_layers, nlayers, params, weff, weffT, inv_norm, amax, grad, m, v, oc, ctl, ema, ema_mom);
+    int rc = check_launch("optimizer_wn_step_guarded");
     if (rc || !amax) return rc;
     hipLaunchKernelGGL(wn_rowmax_kernel, dim3(cin_total), dim3(64), 0, s, d_layers, nlayers, weff, amax + 2 * nlayers + cout_total, amax, params);
     return check_launch("wn_rowmax");
@@ -1353,17 +1450,58 @@ int revssim_backward(const float* hr, const uint8_t* mask, const float* pred, co
 // The step-dependent scalars (c_g = (1-mu_t)/(1-Pi_t), c_m = mu_{t+1}/(1-Pi_t mu_{t+1}), c_v = 1/(1-b2^t)) are computed by the
 // host in double and passed by value.
 // ---------------------------------------------------------------------------------------------------
+// GUARD: as in wn_forward_body -- g' = g * ctl->scale, nothing written when ctl->skip is set, the EMA after the update.  One body for both
+// kernels: with GUARD = false it is the plain kernel's arithmetic, text and order unchanged (the rule of opt_update).
+template <bool GUARD>
+__device__ __forceinline__ void nadam_body(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m,
+                                           float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                           float c_g, float c_m, float c_v, const probav_guard_ctl* __restrict__ ctl,
+                                           float* __restrict__ ema, float ema_mom)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (GUARD) {
+        float g = grad[i];
+        if (ctl) {
+            if (ctl->skip != 0u) return;
+            g *= ctl->scale;
+        }
+        float t;
+        {   // the plain kernel below is compiled to products and sums, none fused: written out with contraction off, so that scale == 1 leaves its bits
+            // (see opt_update_exact)
+#pragma clang fp contract(off)
+            const float bm = b1 * m[i], gm = (1.f - b1) * g;
+            const float mi = bm + gm;
+            const float bv = b2 * v[i], gv = ((1.f - b2) * g) * g;
+            const float vi = bv + gv;
+            m[i] = mi; v[i] = vi;
+            const float ng = c_g * g, nm = c_m * mi;
+            const float up = lr * (ng + nm);
+            const float den = sqrtf(vi * c_v) + eps;
+            t = theta[i] - up / den;
+        }
+        theta[i] = t;
+        if (ema) ema[i] = ema_mom * ema[i] + (1.f - ema_mom) * t;
+    } else {
+        const float g = grad[i];
+        const float mi = b1 * m[i] + (1.f - b1) * g;
+        const float vi = b2 * v[i] + (1.f - b2) * g * g;
+        m[i] = mi; v[i] = vi;
+        theta[i] -= lr * (c_g * g + c_m * mi) / (sqrtf(vi * c_v) + eps);
+    }
+}
 __global__ __launch_bounds__(256) void nadam_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m,
                                                    float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
                                                    float c_g, float c_m, float c_v)
 {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float g = grad[i];
-    const float mi = b1 * m[i] + (1.f - b1) * g;
-    const float vi = b2 * v[i] + (1.f - b2) * g * g;
-    m[i] = mi; v[i] = vi;
-    theta[i] -= lr * (c_g * g + c_m * mi) / (sqrtf(vi * c_v) + eps);
+    nadam_body<false>(theta, grad, m, v, n, lr, b1, b2, eps, c_g, c_m, c_v, nullptr, nullptr, 0.f);
+}
+__global__ __launch_bounds__(256) void nadam_guard_kernel(float* __restrict__ theta, const float* __restrict__ grad, float* __restrict__ m,
+                                                         float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                                         float c_g, float c_m, float c_v, const probav_guard_ctl* __restrict__ ctl,
+                                                         float* __restrict__ ema, float ema_mom)
+{
+    nadam_body<true>(theta, grad, m, v, n, lr, b1, b2, eps, c_g, c_m, c_v, ctl, ema, ema_mom);
 }
 int nadam_step(float* theta, const float* grad, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                float c_g, float c_m, float c_v, hipStream_t s)
@@ -1371,6 +1509,72 @@ int nadam_step(float* theta, const float* grad, float* m, float* v, long n, floa
     if (n <= 0) return PROBAV_OK;
     hipLaunchKernelGGL(nadam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, theta, grad, m, v, n, lr, b1, b2, eps, c_g, c_m, c_v);
     return check_launch("nadam");
+}
+int nadam_step_guarded(float* theta, const float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
+                       float c_g, float c_m, float c_v, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s)
+{
+    if (n <= 0) return PROBAV_OK;
+    hipLaunchKernelGGL(nadam_guard_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, theta, grad, m, v, n, lr, b1, b2, eps, c_g, c_m, c_v, ctl, ema, ema_mom);
+    return check_launch("nadam_guarded");
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The gradient's global norm and the step's control block (include/probav_hip.h, 'optimizer options on the device'; Keras global_clipnorm =
+// tf.clip_by_global_norm).  grad_sumsq_kernel: GUARD_BLOCKS workgroups of 256 threads whatever the device; thread t of the grid accumulates
+// (double)g * g over i = t, t + GUARD_BLOCKS * 256, ... in that order; a butterfly over the wave (every lane ends with the same bits), the four
+// waves' sums added in wave order, one fp64 partial per workgroup.  No floating-point atomics: the same gradient gives the same partials on
+// every run and on every device.  guard_finish_kernel: one wave adds the partials in index order and derives the block.  It is a launch of its
+// own, not a prologue of every consumer wave: the 3 920 waves of the fused step would each repeat an fp64 square root and a division and one
+// of them would still have to publish the block for the host's log; as a launch the consumers read two words.
+// The squares of finite fp32 values are below 2^256 and at most 2^31 of them are added: the fp64 total is non-finite exactly when an element is.
+// ---------------------------------------------------------------------------------------------------
+constexpr int GUARD_BLOCKS = 128;
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ grad, long n, double* __restrict__ partial)
+{
+    const long stride = (long)GUARD_BLOCKS * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    double acc = 0.0;
+    for (; i + 3 * stride < n; i += 4 * stride) {                       // four independent loads in flight, added in index order
+        const float a = grad[i], b = grad[i + stride], c = grad[i + 2 * stride], d = grad[i + 3 * stride];
+        acc += (double)a * a; acc += (double)b * b; acc += (double)c * c; acc += (double)d * d;
+    }
+    for (; i < n; i += stride) { const float a = grad[i]; acc += (double)a * a; }
+    acc = wave_sum(acc);
+    __shared__ double ws[4];
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+__global__ __launch_bounds__(64) void guard_finish_kernel(const double* __restrict__ partial, float clipnorm, int skip_nonfinite,
+                                                         probav_guard_ctl* __restrict__ ctl)
+{
+    __shared__ double p[GUARD_BLOCKS];
+    for (int k = threadIdx.x; k < GUARD_BLOCKS; k += 64) p[k] = partial[k];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double total = 0.0;
+    for (int k = 0; k < GUARD_BLOCKS; ++k) total += p[k];
+    const bool finite = total == total && total <= 1.7976931348623157e308;
+    const double norm = sqrt(total);
+    float scale = 1.f;
+    if (clipnorm > 0.f) {
+        const double c = (double)clipnorm;
+        scale = finite ? (float)(c / (norm > c ? norm : c)) : __builtin_nanf("");
+    }
+    const unsigned skip = (skip_nonfinite && !finite) ? 1u : 0u;
+    ctl->scale = scale;
+    ctl->skip = skip;
+    ctl->skipped_total = ctl->skipped_total + skip;
+    ctl->norm = (float)norm;
+}
+size_t grad_guard_scratch_bytes() { return (size_t)GUARD_BLOCKS * sizeof(double); }
+int grad_guard(const float* grad, long n, float clipnorm, int skip_nonfinite, double* partial, probav_guard_ctl* ctl, hipStream_t s)
+{
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GUARD_BLOCKS), dim3(256), 0, s, grad, n, partial);
+    int rc = check_launch("grad_sumsq");
+    if (rc) return rc;
+    hipLaunchKernelGGL(guard_finish_kernel, dim3(1), dim3(64), 0, s, partial, clipnorm, skip_nonfinite, ctl);
+    return check_launch("guard_finish");
 }
 
 }  // namespace probav

@@ -27,6 +27,8 @@ struct ConvGeom {
     int reflect_t;      // the depth pad mirrors too (only the experimental 19-frame reducer, models/modelsTF.py:76-121; direct kernels only)
 };
 
+struct probav_guard_ctl;         // include/probav_hip.h: the control block of a guarded optimizer step
+
 namespace probav {
 
 // amax slots of one launch (H3 arithmetic, x6_device.h): bit patterns of largest magnitudes (non-negative floats), kept in device memory.
@@ -149,5 +151,14 @@ int revssim_backward(const float* hr, const uint8_t* mask, const float* pred, co
 
 int nadam_step(float* theta, const float* grad, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                float c_g, float c_m, float c_v, hipStream_t s);
+// optimizer options on the device (include/probav_hip.h): the gradient's global norm -> control block (two launches; partial: grad_guard_scratch_bytes()),
+// and the two update launches reading it (ctl / ema may be null)
+size_t grad_guard_scratch_bytes();
+int grad_guard(const float* grad, long n, float clipnorm, int skip_nonfinite, double* partial, probav_guard_ctl* ctl, hipStream_t s);
+int nadam_step_guarded(float* theta, const float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
+                       float c_g, float c_m, float c_v, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s);
+int optimizer_wn_step_guarded(const WnLayer* d_layers, int nlayers, int cout_total, int cin_total, float* params, const float* grad, float* m, float* v,
+                              float lr, float b1, float b2, float eps, float c_g, float c_m, float c_v,
+                              float* weff, float* weffT, float* inv_norm, unsigned* amax, float* ema, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s);
 
 }  // namespace probav

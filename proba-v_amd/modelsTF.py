@@ -9,6 +9,7 @@ libprobav_hip.so (csrc/); torch only owns the device memory, the stream and the 
 torch custom op, `torch.ops.probav.wdsr_forward`, whose registered autograd formula is `torch.ops.probav.wdsr_backward`
 (the engine's reverse pass) -- probav_amd/ops.py.
 """
+import contextlib
 import ctypes
 import os
 import weakref
@@ -53,6 +54,7 @@ class WDSRModel(torch.nn.Module):
         self._impl = None
         self._ws = {}
         self._wcache, self._wcache_version = None, None
+        self._alt, self._alt_wcache = None, None            # weights_from: (flat buffer, its weight cache) while a scope is open
 
     # -- reference-facing surface ------------------------------------------------------------------
     @property
@@ -111,6 +113,12 @@ class WDSRModel(torch.nn.Module):
         if self.flat.device != x.device:
             raise RuntimeError("model parameters are on %s but the input is on %s" % (self.flat.device, x.device))
         x = x.contiguous().float()
+        if self._alt is not None:                          # inside `weights_from`: another flat buffer with a weight cache of its own, inference only
+            if bool(training) and torch.is_grad_enabled():
+                raise RuntimeError("model(x, training=True) with gradients inside weights_from(): the scope runs forward passes only")
+            flat, wc = self._alt
+            y, ws = torch.ops.probav.wdsr_forward(flat, x, int(self._handle().value), self.scale * self.patchSizeLR, False, wc)
+            return y
         need_grad = bool(training) and torch.is_grad_enabled() and self.flat.requires_grad
         wc = self.weight_cache()
         if wc is None and not need_grad:
@@ -228,6 +236,36 @@ class WDSRModel(torch.nn.Module):
                                        "(flat.data / raw pointer / broadcast) without model.invalidate_weight_cache()")
             return self._wcache
         return None
+
+    @contextlib.contextmanager
+    def weights_from(self, flat):
+        """Run forward passes from ANOTHER flat parameter buffer -- the optimizer's moving average (`optimizer.ema_buffer()`), a snapshot -- without
+        touching the model's own parameters or their weight cache:
+
+            with model.weights_from(ema):
+                y = model(x)                                # the prediction of the EMA weights
+
+        flat: float32, contiguous, `param_count` values in the model's layout, on the model's device.  On entry its weight normalisation and operand
+        packing are built once (probav_weight_cache_build) into a cache that belongs to the scope, so every pass inside starts at its first
+        convolution and is bit for bit the pass of a model loaded with those values.  The buffer must not change while the scope is open.  Forward
+        only: a pass that would need gradients raises.  Scopes nest; on exit the model is back on `self.flat` and its untouched cache."""
+        flat = _lib.require_device(flat, "weights_from buffer").detach()
+        if flat.dtype != torch.float32 or flat.numel() != self.flat.numel() or not flat.is_contiguous() or flat.device != self.flat.device:
+            raise ValueError("weights_from: a contiguous float32 buffer of %d values on %s, got %s %s on %s"
+                             % (self.flat.numel(), self.flat.device, flat.dtype, tuple(flat.shape), flat.device))
+        flat = flat.reshape(-1)
+        n = _lib.lib().probav_weight_cache_bytes(self._handle())
+        cache = self._alt_wcache if self._alt is None else None          # (a nested scope gets a buffer of its own)
+        if cache is None or cache.device != flat.device:
+            cache = torch.empty((n + 3) // 4, dtype=torch.float32, device=flat.device)
+            if self._alt is None:
+                self._alt_wcache = cache
+        torch.ops.probav.weight_cache_build(flat, cache, int(self._handle().value))
+        prev, self._alt = self._alt, (flat, cache)
+        try:
+            yield self
+        finally:
+            self._alt = prev
 
     def _workspace(self, batch, training):
         """The workspace the LAST forward call of this (batch, training) shape produced (every call gets its own: an output of

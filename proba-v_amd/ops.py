@@ -13,6 +13,10 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::nadam_step(theta, grad, m, v, lr, b1, b2, eps, c_g, c_m, c_v) -> ()                 optimizer.apply_gradients   trainClass.py:132
   probav::optimizer_wn_step(theta, grad, m, v, wcache, engine, lr, ...) -> ()                 the same update fused with the weight normalisation
                                                                             and operand packing of the NEXT step (wdsr_forward's optional `wcache`)
+  probav::grad_guard(grad, ctl, scratch, clipnorm, skip_nonfinite) -> ()                     tf.clip_by_global_norm's norm + the non-finite guard: the step's
+                                                                            control block {scale, skip, skipped_total, norm}, on the device
+  probav::nadam_step_guarded(theta, grad, m, v, ema?, ctl?, lr, ..., ema_momentum) -> ()      nadam_step with Keras global_clipnorm / use_ema + the guard
+  probav::optimizer_wn_step_guarded(theta, grad, m, v, wcache, ema?, ctl?, engine, ...) -> () optimizer_wn_step with the same
   probav::clip_round(x, lo, hi) -> y                                        tf.clip_by_value + tf.round   test.py:118-119
   probav::esa_shift_moments(sr, hr, mask, border) -> moments int64 [N, (2b+1)^2, 3]       (n, s1, s2) of every shift, exact
   probav::esa_shift_cpsnr(sr, hr, mask, border) -> (cpsnr f64[N], shift i32[N,2], bias f64[N], n_clear i64[N])
@@ -291,6 +295,74 @@ def optimizer_wn_step(theta: Tensor, grad: Tensor, m: Tensor, v: Tensor, wcache:
 
 @optimizer_wn_step.register_fake
 def _(theta, grad, m, v, wcache, engine, lr, beta_1, beta_2, eps, c_g, c_m, c_v):
+    return None
+
+
+GUARD_CTL_WORDS = 4           # struct probav_guard_ctl as an int32 tensor: [scale (f32 bits), skip, skipped_total, norm (f32 bits)]
+
+
+def guard_scratch_doubles(n):
+    """float64 elements of the scratch probav::grad_guard needs for a gradient of n floats (probav_grad_guard_scratch_bytes)."""
+    return (_lib.lib().probav_grad_guard_scratch_bytes(int(n)) + 7) // 8
+
+
+def _guard_args(ctl, ema, theta):
+    if ctl is not None and (ctl.dtype != torch.int32 or ctl.numel() != GUARD_CTL_WORDS or not ctl.is_contiguous()):
+        raise ValueError("guard control block: a contiguous int32 tensor of %d words (struct probav_guard_ctl), got %s %s" % (GUARD_CTL_WORDS, ctl.dtype, tuple(ctl.shape)))
+    if ema is not None and (ema.dtype != torch.float32 or ema.numel() != theta.numel() or not ema.is_contiguous()):
+        raise ValueError("EMA buffer: a contiguous float32 tensor of the parameters' size, got %s %s" % (ema.dtype, tuple(ema.shape)))
+
+
+@torch.library.custom_op("probav::grad_guard", mutates_args=("ctl", "scratch"), device_types="cuda")
+def grad_guard(grad: Tensor, ctl: Tensor, scratch: Tensor, clipnorm: float, skip_nonfinite: bool) -> None:
+    """The step's control block from the flat gradient (Keras global_clipnorm = tf.clip_by_global_norm, plus the non-finite guard): fp64 sum of
+    squares in a fixed order -> ctl = {scale = clipnorm / max(norm, clipnorm) (1 when clipnorm <= 0), skip, skipped_total += skip, norm}.  Two
+    launches; nothing comes back to the host.  ctl: int32 [4], zeroed once by the caller; scratch: float64 [guard_scratch_doubles(n)]."""
+    _dev(grad, "gradient")
+    _guard_args(ctl, None, grad)
+    if grad.dtype != torch.float32 or not grad.is_contiguous() or scratch.dtype != torch.float64:
+        raise ValueError("grad_guard: a contiguous float32 gradient and a float64 scratch; got %s, %s" % (grad.dtype, scratch.dtype))
+    _lib.check(_lib.lib().probav_grad_guard(_lib.ptr(grad), grad.numel(), clipnorm, 1 if skip_nonfinite else 0, _lib.ptr(scratch), scratch.numel() * 8,
+                                            _lib.ptr(ctl), _lib.current_stream()), "probav_grad_guard")
+
+
+@grad_guard.register_fake
+def _(grad, ctl, scratch, clipnorm, skip_nonfinite):
+    return None
+
+
+@torch.library.custom_op("probav::nadam_step_guarded", mutates_args=("theta", "m", "v", "ema"), device_types="cuda")
+def nadam_step_guarded(theta: Tensor, grad: Tensor, m: Tensor, v: Tensor, ema: Optional[Tensor], ctl: Optional[Tensor], lr: float, beta_1: float,
+                       beta_2: float, eps: float, c_g: float, c_m: float, c_v: float, ema_momentum: float) -> None:
+    """nadam_step on g * ctl.scale, dropped when ctl.skip is set, followed by ema = ema_momentum * ema + (1 - ema_momentum) * theta (Keras use_ema)."""
+    _dev(theta, "parameter")
+    _guard_args(ctl, ema, theta)
+    _lib.check(_lib.lib().probav_nadam_step_guarded(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), _lib.ptr(ema), theta.numel(), lr, beta_1,
+                                                    beta_2, eps, c_g, c_m, c_v, ema_momentum, _lib.ptr(ctl), _lib.current_stream()),
+               "probav_nadam_step_guarded")
+
+
+@nadam_step_guarded.register_fake
+def _(theta, grad, m, v, ema, ctl, lr, beta_1, beta_2, eps, c_g, c_m, c_v, ema_momentum):
+    return None
+
+
+@torch.library.custom_op("probav::optimizer_wn_step_guarded", mutates_args=("theta", "m", "v", "wcache", "ema"), device_types="cuda")
+def optimizer_wn_step_guarded(theta: Tensor, grad: Tensor, m: Tensor, v: Tensor, wcache: Tensor, ema: Optional[Tensor], ctl: Optional[Tensor],
+                              engine: int, lr: float, beta_1: float, beta_2: float, eps: float, c_g: float, c_m: float, c_v: float,
+                              ema_momentum: float) -> None:
+    """optimizer_wn_step under the control block and with the EMA buffer: on a skipped step the parameters, both moments and the EMA are left as
+    they were and `wcache` is rebuilt from the unchanged parameters (it stays valid)."""
+    _dev(theta, "parameter")
+    _guard_args(ctl, ema, theta)
+    _lib.check(_lib.lib().probav_optimizer_step_fused_guarded(c_void_p(engine), _lib.ptr(theta), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), lr, beta_1,
+                                                              beta_2, eps, c_g, c_m, c_v, _lib.ptr(wcache), wcache.numel() * 4, _lib.ptr(ema),
+                                                              ema_momentum, _lib.ptr(ctl), _lib.current_stream()),
+               "probav_optimizer_step_fused_guarded")
+
+
+@optimizer_wn_step_guarded.register_fake
+def _(theta, grad, m, v, wcache, ema, ctl, engine, lr, beta_1, beta_2, eps, c_g, c_m, c_v, ema_momentum):
     return None
 
 

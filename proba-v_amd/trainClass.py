@@ -234,6 +234,16 @@ class GradBucket:
         return tail[0], tail[1]
 
 
+class _DeviceScalar:
+    """A device scalar in the shape _LateScalars takes a Keras `Mean` in: (value, 1)."""
+
+    def __init__(self, t):
+        self.t = t
+
+    def snapshot(self):
+        return self.t, 1
+
+
 class _LateScalars:
     """Per-step log lines and summary scalars WITHOUT a host sync per step: the running sums of the two train metrics are copied to a
     pinned host buffer on the compute stream (non-blocking) with an event behind them, and the line of step k is emitted once that
@@ -278,6 +288,8 @@ def load_nadam_state(optimizer, step, momentum_cache, m, v):
     vt = torch.as_tensor(v, dtype=torch.float32).reshape(p.shape).to(p.device)
     if isinstance(optimizer, HipNadam):
         optimizer.state[p] = {"step": int(step), "momentum_cache": float(momentum_cache), "m": mt.clone(), "v": vt.clone()}
+        if optimizer.guard is not None and optimizer.guard["use_ema"]:      # a TensorFlow bundle carries no average: it starts at the restored weights
+            optimizer.state[p]["ema"] = p.detach().clone()
     elif isinstance(optimizer, torch.optim.NAdam):
         optimizer.state[p] = {"step": torch.tensor(float(step)), "mu_product": torch.tensor(float(momentum_cache)),
                               "exp_avg": mt.clone(), "exp_avg_sq": vt.clone()}
@@ -296,15 +308,111 @@ def _fused_update(model, p, g, st, lr, b1, b2, eps, c_g, c_m, c_v):
         torch.ops.probav.nadam_step(p, g, st["m"], st["v"], lr, b1, b2, eps, c_g, c_m, c_v)
 
 
-class HipNadam(torch.optim.Optimizer):
+class _GuardedOptions:
+    """Keras's `global_clipnorm`, `use_ema` / `ema_momentum` and a non-finite guard for the three optimizers below, on the device (INTEGRATION.md,
+    'Optimizer options on the device'; the fp64 statement is optim_numpy.py).  With every option at its default `guard` is None and `step()` is the
+    plain path.  Otherwise a step is: probav::grad_guard on the flat gradient (two launches: fp64 sum of squares in a fixed order, then the control
+    block {scale, skip, skipped_total, norm} -- skipped when only the EMA is on), then the guarded update launch, which multiplies every gradient
+    element by `scale`, leaves parameters, m, v and the EMA untouched when `skip` is set, and follows the update with
+    ema = ema_momentum * ema + (1 - ema_momentum) * theta.  The host reads nothing back: the step count and Nadam's momentum schedule therefore
+    ADVANCE ON A SKIPPED STEP TOO (the host cannot know a step was skipped without the synchronisation this exists to avoid).  Under data
+    parallelism the norm is taken on the all-reduced gradient (the trainer reduces before `step()`): every rank derives the same bits and the
+    same decision, with no second collective.  The norm is global over ONE flat parameter (the model's): several parameters are refused."""
+
+    def _init_guard(self, model, global_clipnorm, skip_nonfinite, use_ema, ema_momentum):
+        self.model = model
+        self.guard = None
+        self._ctl = self._scratch = None
+        self._skipped_restored = 0
+        if global_clipnorm is not None and not float(global_clipnorm) > 0.0:
+            raise ValueError("global_clipnorm must be positive (None: no clipping), got %r" % (global_clipnorm,))
+        if not 0.0 <= float(ema_momentum) <= 1.0:
+            raise ValueError("ema_momentum must be in [0, 1], got %r" % (ema_momentum,))
+        if global_clipnorm is not None or skip_nonfinite or use_ema:
+            self.guard = {"global_clipnorm": None if global_clipnorm is None else float(global_clipnorm), "skip_nonfinite": bool(skip_nonfinite),
+                          "use_ema": bool(use_ema), "ema_momentum": float(ema_momentum)}
+            if (global_clipnorm is not None or skip_nonfinite) and sum(len(g["params"]) for g in self.param_groups) != 1:
+                raise ValueError("global_clipnorm / skip_nonfinite take the norm of ONE flat gradient (the model's single parameter); got several parameters")
+
+    def _has_ctl(self):
+        return self.guard is not None and (self.guard["global_clipnorm"] is not None or self.guard["skip_nonfinite"])
+
+    def _guard_buffers(self, p):
+        from . import ops
+        if self._ctl is None or self._ctl.device != p.device:
+            self._ctl = torch.zeros(ops.GUARD_CTL_WORDS, dtype=torch.int32, device=p.device)
+            self._ctl[2] = int(self._skipped_restored)
+            self._scratch = torch.empty(ops.guard_scratch_doubles(p.numel()), dtype=torch.float64, device=p.device)
+        return self._ctl, self._scratch
+
+    def _guarded_update(self, p, g, st, lr, b1, b2, eps, c_g, c_m, c_v):
+        """_fused_update with the options: at most two launches more than the plain step."""
+        o = self.guard
+        ctl = None
+        if self._has_ctl():
+            ctl, scratch = self._guard_buffers(p)
+            torch.ops.probav.grad_guard(g, ctl, scratch, o["global_clipnorm"] or 0.0, o["skip_nonfinite"])
+        ema = None
+        if o["use_ema"]:
+            if "ema" not in st:
+                st["ema"] = p.detach().clone()                 # Keras: the average starts at the initial values
+            ema = st["ema"]
+        model = self.model
+        if model is not None and p is model.flat:
+            torch.ops.probav.optimizer_wn_step_guarded(p, g, st["m"], st["v"], model.weight_cache_buffer(), ema, ctl, int(model._handle().value),
+                                                       lr, b1, b2, eps, c_g, c_m, c_v, o["ema_momentum"])
+            model.mark_weight_cache()
+        else:
+            torch.ops.probav.nadam_step_guarded(p, g, st["m"], st["v"], ema, ctl, lr, b1, b2, eps, c_g, c_m, c_v, o["ema_momentum"])
+
+    def guard_stats(self):
+        """{"norm", "scale", "skipped_total"} of the last step as DEVICE tensors (views of the control block: copy them before the next step), or
+        None when neither clipping nor the guard is on (or no step has run)."""
+        if not self._has_ctl() or self._ctl is None:
+            return None
+        f = self._ctl.view(torch.float32)
+        return {"norm": f[3], "scale": f[0], "skipped_total": self._ctl[2]}
+
+    def ema_buffer(self):
+        """The EMA of the flat parameter (None: EMA off, or no step yet)."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                e = self.state.get(p, {}).get("ema")
+                if e is not None:
+                    return e
+        return None
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.guard is not None:                             # (the EMA buffer is per-parameter state and travels with m and v)
+            sd["guard"] = {"options": dict(self.guard), "skipped_total": int(self._ctl[2]) if self._ctl is not None else int(self._skipped_restored)}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        state_dict = dict(state_dict)
+        saved = state_dict.pop("guard", None)
+        super().load_state_dict(state_dict)
+        if saved is not None and self.guard is not None:
+            if saved["options"] != self.guard:
+                logger.warning("[ WARN ] optimizer options differ from the checkpoint's (%s): this run's (%s) apply", saved["options"], self.guard)
+            self._skipped_restored = int(saved["skipped_total"])
+            if self._ctl is not None:
+                self._ctl[2] = self._skipped_restored
+        if self.guard is None or not self.guard["use_ema"]:
+            for st in self.state.values():
+                st.pop("ema", None)
+
+
+class HipNadam(_GuardedOptions, torch.optim.Optimizer):
     """Keras ``Nadam`` (optimizer_v2 defaults: beta_1 0.9, beta_2 0.999, epsilon 1e-7, schedule_decay 0.004)
     as ONE fused HIP launch per parameter tensor (the model has a single flat one).  The momentum schedule
     (mu_t, the running product Pi_t = `momentum_cache`) is tracked on the host in double, like Keras tracks it in
     variables; `state_dict()` carries step, momentum cache and the two slots, so checkpoints resume exactly."""
 
-    def __init__(self, params, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule_decay=0.004, model=None):
+    def __init__(self, params, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, schedule_decay=0.004, model=None,
+                 global_clipnorm=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99):
         super().__init__(params, dict(lr=lr, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon, schedule_decay=schedule_decay))
-        self.model = model
+        self._init_guard(model, global_clipnorm, skip_nonfinite, use_ema, ema_momentum)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -329,17 +437,21 @@ class HipNadam(torch.optim.Optimizer):
                 c_m = mu_t1 / (1.0 - pi_t * mu_t1)
                 c_v = 1.0 / (1.0 - b2 ** t)
                 g = p.grad.contiguous()
-                _fused_update(self.model, p, g, st, group["lr"], b1, b2, group["epsilon"], c_g, c_m, c_v)
+                if self.guard is None:
+                    _fused_update(self.model, p, g, st, group["lr"], b1, b2, group["epsilon"], c_g, c_m, c_v)
+                else:
+                    self._guarded_update(p, g, st, group["lr"], b1, b2, group["epsilon"], c_g, c_m, c_v)
 
 
-class HipAdam(torch.optim.Optimizer):
+class HipAdam(_GuardedOptions, torch.optim.Optimizer):
     """Keras ``Adam`` (optimizer_v2 defaults, amsgrad off): lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); theta -= lr_t m / (sqrt(v) + eps), eps
     outside the bias correction.  Same fused launch as HipNadam (the kernel computes
     theta -= lr (c_g g + c_m m) / (sqrt(c_v v) + eps); here c_g = 0, c_m = sqrt(1 - b2^t) / (1 - b1^t), c_v = 1)."""
 
-    def __init__(self, params, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, model=None):
+    def __init__(self, params, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, model=None,
+                 global_clipnorm=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99):
         super().__init__(params, dict(lr=lr, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon))
-        self.model = model
+        self._init_guard(model, global_clipnorm, skip_nonfinite, use_ema, ema_momentum)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -357,15 +469,18 @@ class HipAdam(torch.optim.Optimizer):
                 st["step"] += 1
                 t = st["step"]
                 c_m = (1.0 - b2 ** t) ** 0.5 / (1.0 - b1 ** t)
-                _fused_update(self.model, p, p.grad.contiguous(), st, group["lr"], b1, b2, group["epsilon"], 0.0, c_m, 1.0)
+                if self.guard is None:
+                    _fused_update(self.model, p, p.grad.contiguous(), st, group["lr"], b1, b2, group["epsilon"], 0.0, c_m, 1.0)
+                else:
+                    self._guarded_update(p, p.grad.contiguous(), st, group["lr"], b1, b2, group["epsilon"], 0.0, c_m, 1.0)
 
 
-class HipSGD(torch.optim.Optimizer):
+class HipSGD(_GuardedOptions, torch.optim.Optimizer):
     """Keras ``SGD`` without momentum through the same fused launch (c_g = 1, c_m = 0, c_v = 0, eps = 1: theta -= lr g)."""
 
-    def __init__(self, params, lr=1e-2, model=None):
+    def __init__(self, params, lr=1e-2, model=None, global_clipnorm=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99):
         super().__init__(params, dict(lr=lr))
-        self.model = model
+        self._init_guard(model, global_clipnorm, skip_nonfinite, use_ema, ema_momentum)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -378,20 +493,26 @@ class HipSGD(torch.optim.Optimizer):
                 st = self.state[p]
                 if not st:
                     st["m"], st["v"] = torch.zeros_like(p), torch.zeros_like(p)
-                _fused_update(self.model, p, p.grad.contiguous(), st, group["lr"], 0.0, 0.0, 1.0, 1.0, 0.0, 0.0)
+                if self.guard is None:
+                    _fused_update(self.model, p, p.grad.contiguous(), st, group["lr"], 0.0, 0.0, 1.0, 1.0, 0.0, 0.0)
+                else:
+                    self._guarded_update(p, p.grad.contiguous(), st, group["lr"], 0.0, 0.0, 1.0, 1.0, 0.0, 0.0)
 
 
-def make_optimizer(name, model, learning_rate):
+def make_optimizer(name, model, learning_rate, global_clipnorm=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99):
     """train.py:77-83: 'adam' -> Keras Adam, 'nadam' -> Keras Nadam, anything else -> SGD, with the Keras
     defaults restated (epsilon 1e-7; Nadam schedule_decay 0.004 -- SURVEY.md A.5), each ONE fused HIP launch over the model's
-    flat parameter buffer.  There is no CPU implementation: `step()` on parameters that do not live on a HIP device raises."""
+    flat parameter buffer.  There is no CPU implementation: `step()` on parameters that do not live on a HIP device raises.
+    global_clipnorm, use_ema, ema_momentum: the Keras optimizer arguments of those names; skip_nonfinite: drop a step whose gradient holds an
+    inf or a NaN (_GuardedOptions).  All off by default: the plain step."""
     params = list(model.parameters())
     fused = model if hasattr(model, "weight_cache_buffer") else None
+    opts = dict(global_clipnorm=global_clipnorm, skip_nonfinite=skip_nonfinite, use_ema=use_ema, ema_momentum=ema_momentum)
     if name == "adam":
-        return HipAdam(params, lr=learning_rate, model=fused)
+        return HipAdam(params, lr=learning_rate, model=fused, **opts)
     if name == "nadam":
-        return HipNadam(params, lr=learning_rate, model=fused)
-    return HipSGD(params, lr=learning_rate, model=fused)
+        return HipNadam(params, lr=learning_rate, model=fused, **opts)
+    return HipSGD(params, lr=learning_rate, model=fused, **opts)
 
 
 class _SideStreamTuner:
@@ -460,7 +581,15 @@ class _SideStreamTuner:
 class ModelTrainer:
     """models/trainClass.py:17-143."""
 
-    def __init__(self, model, loss, metric, optimizer, ckptDir, logDir, multiGPU=True, evalStep=1000):
+    def __init__(self, model, loss, metric, optimizer, ckptDir, logDir, multiGPU=True, evalStep=1000, validate_on="raw", weights="raw"):
+        """validate_on: "raw" (default) or "ema" -- the weights `testStep` and the validation of `fitTrainData` run on (the optimizer's moving
+        average, through WDSRModel.weights_from).  weights: "raw" (default) or "ema" -- which entry of a checkpoint `restore` loads into the
+        model (inference: test.py / evaluate.py --weights); "ema" on a checkpoint without one is an error."""
+        if validate_on not in ("raw", "ema") or weights not in ("raw", "ema"):
+            raise ValueError("validate_on / weights must be 'raw' or 'ema', got %r / %r" % (validate_on, weights))
+        if validate_on == "ema" and (optimizer is None or getattr(optimizer, "guard", None) is None or not optimizer.guard["use_ema"]):
+            raise ValueError("validate_on='ema' needs an optimizer made with use_ema=True")
+        self.validate_on, self.weights = validate_on, weights
         os.makedirs(ckptDir, exist_ok=True)
         os.makedirs(logDir, exist_ok=True)
         self._model, self.optimizer = model, optimizer
@@ -532,6 +661,8 @@ class ModelTrainer:
         path = self.latest_checkpoint                   # checkpoints of this trainer are newer than a TF bundle in the same directory
         tf_prefix = self._tf_latest() if not (path and os.path.exists(path)) else None
         if tf_prefix is not None:                       # weights trained by the reference (tf.train.Checkpoint bundle)
+            if self.weights == "ema":
+                raise ValueError("weights='ema': %s is a TensorFlow bundle of the reference, which carries no EMA weights" % tf_prefix)
             from .tfckpt import load_reference_checkpoint, load_reference_optimizer
             step = load_reference_checkpoint(self._model, tf_prefix)
             self.step = int(step or 0)
@@ -549,7 +680,9 @@ class ModelTrainer:
             return
         if path and os.path.exists(path):
             state = torch.load(path, map_location="cpu")
-            self._model.load_variables(state["model"])
+            if self.weights == "ema" and state.get("ema") is None:
+                raise ValueError("weights='ema': checkpoint %s holds no EMA weights (it was trained without --ema-momentum / use_ema)" % path)
+            self._model.load_variables(state["ema" if self.weights == "ema" else "model"])
             if self.optimizer is not None and state.get("optimizer") is not None:
                 self.optimizer.load_state_dict(state["optimizer"])
             self.step, self.psnr = int(state["step"]), float(state["psnr"])
@@ -568,9 +701,16 @@ class ModelTrainer:
         for n, t in zip(names, tensors):
             layer, key = n.split("/")
             model_state.setdefault(layer, {})[key] = t
-        torch.save({"model": model_state, "optimizer": self.optimizer.state_dict() if self.optimizer else None,
-                    "step": self.step, "psnr": self.psnr, "save_counter": self.save_counter},
-                   os.path.join(self.ckptDir, name))
+        state = {"model": model_state, "optimizer": self.optimizer.state_dict() if self.optimizer else None,
+                 "step": self.step, "psnr": self.psnr, "save_counter": self.save_counter}
+        ema = self._ema()
+        if ema is not None:                             # the moving average in the layout of "model" ("model" stays the raw weights)
+            flat = ema.detach().cpu()
+            state["ema"] = {}
+            for L in self._model.layers:
+                state["ema"][L.name] = {"g": flat[L.g_off:L.v_off].clone(), "v": flat[L.v_off:L.b_off].view(L.vshape).clone(),
+                                        "bias": flat[L.b_off:L.b_off + L.cout].clone()}
+        torch.save(state, os.path.join(self.ckptDir, name))
         kept = before + [name]
         for old in kept[:-self.max_to_keep]:
             try:
@@ -580,6 +720,19 @@ class ModelTrainer:
         with open(self._index_path(), "w") as fh:
             fh.write("\n".join(kept[-self.max_to_keep:]) + "\n")
         return name
+
+    def _ema(self):
+        """The optimizer's EMA of the model's flat parameter, or None."""
+        fn = getattr(self.optimizer, "ema_buffer", None)
+        return fn() if fn is not None else None
+
+    def _eval_scope(self):
+        """The scope validation runs in: the EMA weights with validate_on='ema' (before the first optimizer step the average IS the parameters)."""
+        import contextlib
+        if self.validate_on != "ema" or getattr(self._model, "_alt", None) is not None:
+            return contextlib.nullcontext()
+        ema = self._ema()
+        return contextlib.nullcontext() if ema is None else self._model.weights_from(ema)
 
     # -- summaries ---------------------------------------------------------------------------------
     def _scalar(self, tag, value, step):
@@ -647,9 +800,16 @@ class ModelTrainer:
 
         def emit(vals, meta):
             ep, st, gs = meta
-            logger.info(f"[ EPOCH {ep}/{epochs} ] - [ STEP {st}/{int(totalSteps)} ] Loss: {vals[0]:.6f}, cPSNR: {vals[1]:.3f}")
+            if len(vals) > 2:                               # clipping or the guard is on: the step's norm and the running count ride along
+                logger.info(f"[ EPOCH {ep}/{epochs} ] - [ STEP {st}/{int(totalSteps)} ] Loss: {vals[0]:.6f}, cPSNR: {vals[1]:.3f}, "
+                            f"Grad norm: {vals[2]:.6g}, Skipped steps: {int(vals[3])}")
+            else:
+                logger.info(f"[ EPOCH {ep}/{epochs} ] - [ STEP {st}/{int(totalSteps)} ] Loss: {vals[0]:.6f}, cPSNR: {vals[1]:.3f}")
             self._scalar("Train PSNR", vals[1], gs)
             self._scalar("Train loss", vals[0], gs)
+            if len(vals) > 2:
+                self._scalar("Grad norm", vals[2], gs)
+                self._scalar("Skipped steps", vals[3], gs)
         late = _LateScalars(emit, self._device())
         tuner = _SideStreamTuner(self.model) if getattr(self, "tune_side_stream", True) else None       # (set trainer.tune_side_stream = False to keep the engine's mode)
         # The host is at most one step (134 launches) ahead of the device: a generation-2 sweep of the interpreter's collector is a 10-20 ms hole in the launch
@@ -686,7 +846,11 @@ class ModelTrainer:
             globalStep += 1
             self.trainStep(xb, hb, mb)
             self.step += 1
-            late.push((self.trainLoss, self.trainPSNR), (epoch, step, globalStep))      # the reference's per-step line, one step late, no sync
+            stats = self.optimizer.guard_stats() if hasattr(self.optimizer, "guard_stats") else None
+            if stats is None:
+                late.push((self.trainLoss, self.trainPSNR), (epoch, step, globalStep))      # the reference's per-step line, one step late, no sync
+            else:                                           # (the same late, sync-free path; the running means stay the reference's)
+                late.push((self.trainLoss, self.trainPSNR, _DeviceScalar(stats["norm"]), _DeviceScalar(stats["skipped_total"])), (epoch, step, globalStep))
 
             if step != 0 and (step % self.evalStep) == 0:
                 late.flush()
@@ -695,11 +859,12 @@ class ModelTrainer:
                 gc.collect()
                 self.testLoss.reset_states()
                 self.testPSNR.reset_states()
-                for k, vidx in enumerate(shuffle_repeat_batch(len(valData[0]), 1, globalBatchSize, bufferSize, vrng, repeat=False)):
-                    if k >= valSteps:                   # .take(valSteps) (utils/utils.py:37-39)
-                        break
-                    self.testStep(self._to_dev(valData[0][vidx], torch.float32), self._to_dev(valData[1][vidx], torch.float32),
-                                  self._to_dev(valData[2][vidx]))
+                with self._eval_scope():                # (validate_on='ema': one weight-cache build for the whole validation)
+                    for k, vidx in enumerate(shuffle_repeat_batch(len(valData[0]), 1, globalBatchSize, bufferSize, vrng, repeat=False)):
+                        if k >= valSteps:                   # .take(valSteps) (utils/utils.py:37-39)
+                            break
+                        self.testStep(self._to_dev(valData[0][vidx], torch.float32), self._to_dev(valData[1][vidx], torch.float32),
+                                      self._to_dev(valData[2][vidx]))
                 testLoss, testPSNR = self.testLoss.result(), self.testPSNR.result()
                 self._scalar("Test loss", testLoss, globalStep)
                 self._scalar("Test PSNR", testPSNR, globalStep)
@@ -735,7 +900,7 @@ class ModelTrainer:
         self.trainPSNR(metric)
 
     def testStep(self, patchLR, patchHR, maskHR):
-        with torch.no_grad():
+        with torch.no_grad(), self._eval_scope():
             predPatchHR = self._model(patchLR, training=False)
             loss = self.loss(patchHR, maskHR, predPatchHR)
             metric = self.metric(patchHR, maskHR, predPatchHR)

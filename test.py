@@ -15,6 +15,9 @@ of <preprocessing_out>/trimmedArrayDir/<TEST|TRAIN>imgLR_<band>.npy are unfolded
 builder chooses them, every tile predicted, and the predictions blended by an integer window in exact arithmetic on the device.  The set order,
 hence the PNG names and the omitted ids, is the same.  ((128 - P) / s + 1)^2 / 64 times the forward passes (3.5 x at s = 8); combines with
 --ensemble.  --tile-stride 0 (default) is the path above, byte for byte.
+
+--weights ema predicts with the moving average of the weights that `train.py --ema-momentum M` keeps and saves beside the raw weights (the
+checkpoint's "ema" entry); --weights raw (default) is the path above.  A checkpoint without an "ema" entry is refused, not silently read raw.
 """
 import argparse
 import logging
@@ -54,6 +57,8 @@ def parser(argv=None):
     p.add_argument("--tile-stride", type=int, default=0, help="predict overlapping tiles at this LR stride and blend them on the device "
                    "(it must divide 128 - patch_size and be at most patch_size; 8 = 3.5 x the forward passes); 0 = disjoint patches placed side by side")
     p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
+    p.add_argument("--weights", type=str, default="raw", choices=("raw", "ema"), help="which weights of the checkpoint to predict with: raw (default) or "
+                   "the moving average a run with train.py --ema-momentum saved; ema on a checkpoint without one is an error")
     opt = p.parse_args(argv)
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
@@ -98,7 +103,12 @@ def main(config, opt):
         patchSizeLR=config["patch_size"], isGrayScale=config["is_grayscale"]).to("cuda")
     basename = os.path.basename(opt.cfg).split(".")[0]
     ckptDir = os.path.join(config["model_out"], "ckpt_%s" % basename, opt.band)
-    ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, opt.band))   # restores the latest checkpoint
+    try:
+        ModelTrainer(model, None, None, None, ckptDir, os.path.join(config["model_out"], "logs_%s" % basename, opt.band), weights=opt.weights)   # restores the latest checkpoint
+    except ValueError as exc:
+        if opt.weights != "ema":
+            raise
+        raise SystemExit("test.py --weights ema: %s" % exc)
     logger.info("[ INFO ] Generating predictions...")
     spec = ensemble_spec(opt)
     if tiles is not None:

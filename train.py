@@ -25,14 +25,30 @@ logger = logging.getLogger("probav_amd")
 BAND_STATS = {"NIR": (8075.2045, 3160.7272), "RED": (5266.2245, 3431.8614)}      # train.py:47-52
 
 
-def parser():
+def parser(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--cfg", default="cfg/yourcfg.cfg", type=str)
     p.add_argument("--band", type=str, default="NIR")
     p.add_argument("--modelType", type=str, default="patchNet")
     p.add_argument("--online-aug", dest="online_aug", action="store_true",
                    help="train from the un-augmented patches of `utils/dataGenerator.py --online-aug`: every batch is augmented on the GPU")
-    return p.parse_args()
+    # optimizer options on the device (probav_amd/trainClass.py: _GuardedOptions).  Flags, not cfg keys: the cfg is the reference's format
+    p.add_argument("--global-clipnorm", dest="global_clipnorm", type=float, default=None,
+                   help="Keras global_clipnorm: scale the whole gradient so that its global L2 norm is at most this (tf.clip_by_global_norm)")
+    p.add_argument("--skip-nonfinite", dest="skip_nonfinite", action="store_true",
+                   help="drop a step whose gradient holds an inf or a NaN (parameters, moments and EMA untouched; counted as 'Skipped steps')")
+    p.add_argument("--ema-momentum", dest="ema_momentum", type=float, default=None,
+                   help="Keras use_ema / ema_momentum: keep a moving average of the weights with this momentum (e.g. 0.99); checkpoints gain an 'ema' entry")
+    p.add_argument("--validate-on", dest="validate_on", type=str, default="raw", choices=("raw", "ema"),
+                   help="the weights the validation runs on (ema needs --ema-momentum); default raw")
+    opt = p.parse_args(argv)
+    if opt.global_clipnorm is not None and not opt.global_clipnorm > 0:
+        p.error("--global-clipnorm must be positive")
+    if opt.ema_momentum is not None and not 0.0 <= opt.ema_momentum <= 1.0:
+        p.error("--ema-momentum must be in [0, 1]")
+    if opt.validate_on == "ema" and opt.ema_momentum is None:
+        p.error("--validate-on ema needs --ema-momentum")
+    return opt
 
 
 def patchNet(config, opt):
@@ -66,7 +82,12 @@ def patchNet(config, opt):
         scale=config["scale"], numFilters=config["num_filters"], kernelSize=(k, k, k), numResBlocks=config["num_res_blocks"],
         expRate=config["exp_rate"], decayRate=config["decay_rate"], numImgLR=config["num_low_res_imgs"],
         patchSizeLR=config["patch_size"], isGrayScale=config["is_grayscale"], seed=0).to(torch.device("cuda", local))
-    optimizer = make_optimizer(config["optimizer"], model, config["learning_rate"])
+    if opt.global_clipnorm is None and not opt.skip_nonfinite and opt.ema_momentum is None:
+        optimizer = make_optimizer(config["optimizer"], model, config["learning_rate"])
+    else:
+        optimizer = make_optimizer(config["optimizer"], model, config["learning_rate"], global_clipnorm=opt.global_clipnorm,
+                                   skip_nonfinite=opt.skip_nonfinite, use_ema=opt.ema_momentum is not None,
+                                   ema_momentum=0.99 if opt.ema_momentum is None else opt.ema_momentum)
     target = config["scale"] * config["patch_size"]
     loss = Losses(targetShape=(target, target, 1))
     type_loss = {"l1": loss.shiftCompensatedL1Loss, "l2": loss.shiftCompensatedL2Loss,
@@ -75,7 +96,7 @@ def patchNet(config, opt):
     ckptDir = os.path.join(config["model_out"], "ckpt_%s" % basename, opt.band)
     logDir = os.path.join(config["model_out"], "logs_%s" % basename, opt.band)
     trainer = ModelTrainer(model=model, loss=type_loss, metric=loss.shiftCompensatedcPSNR, optimizer=optimizer,
-                           ckptDir=ckptDir, logDir=logDir)
+                           ckptDir=ckptDir, logDir=logDir, validate_on=opt.validate_on)
     trainer.fitTrainData(X_train, [y_train, y_train_mask], config["batch_size"], config["epochs"],
                          [X_val, y_val, y_val_mask], saveBestOnly=False, initEpoch=0, augment=augment)
     logger.info("[ SUCCESS ] Model checkpoint can be found in %s." % ckptDir)
