@@ -127,7 +127,18 @@ int probav_forward_wc(probav_engine* e, const float* params, const float* x, flo
 int probav_backward_wc(probav_engine* e, const float* params, const float* dy, float* grads, void* ws, size_t ws_bytes, int batch,
                        const void* wcache, size_t wcache_bytes, void* stream);
 
-/* ---- loss / metric ------------------------------------------------------------------------------ */
+/* ---- loss / metric ------------------------------------------------------------------------------
+ * Common to the three losses below (tests/test_gpu_losses.py holds each point to the fp64 oracle):
+ *  - shapes: size > 2 * border for L1 / L2 / cPSNR; crop = size - 2 * border in [3, 100] for sobel_l1_mix and in [2, 140] for l1msssim
+ *    (their backward kernels hold the crop in LDS, (3 L^2 + (L + 2)^2) floats and (5 L + L^2) doubles, within the device's 160 KiB).  A shape outside
+ *    is PROBAV_EINVAL from the FORWARD as from the backward, with the limit in probav_last_error(); nothing is launched.
+ *  - ties: among candidates that tie exactly the FIRST in shift order (smallest i * (2 * border + 1) + j) is selected, and the backward
+ *    differentiates that one shift.  tf.reduce_min, which the reference uses, splits the gradient equally among the tied shifts.
+ *  - no clear pixel: a shift under which a sample has no clear pixel (n = 0) is no candidate; the minimum is over the others (as in
+ *    probav_score_select).  A sample with no clear pixel under ANY shift has l1 = l2 = cpsnr = loss = NaN and arg 0, the batch means are
+ *    then NaN, and its gradient is NaN inside the crop (0 on the border ring); the gradients of the other samples are unaffected.  For
+ *    l1msssim, one scalar for the batch, any such sample makes loss NaN and arg 0; its gradient is then unspecified (not for use).
+ *  - the gradient is written for every element of dpred: exactly 0 on the border ring.                                               */
 /* replaces Losses.shiftCompensatedL1Loss / L2Loss / cPSNR               models/loss.py:37-84
  * hr, pred [B,S,S,1] f32; mask [B,S,S,1] uint8 (non-zero = clear pixel).  Outputs (device):
  * l1[B], l2[B] minima over the (2*border+1)^2 shifts, cpsnr[B] maximum, arg_l1[B]/arg_l2[B] the

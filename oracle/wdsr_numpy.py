@@ -235,3 +235,209 @@ def shift_l1_grad(hr, mask, pred, cropBorder=3):
             gk = -(M / n) * (sg - (sg * M).sum() / n)
             g[bi, c:c + L, c:c + L] += gk / (len(ties) * B)
     return g[..., None]
+
+
+# ----------------------------------------------------------------------------------------------
+# per-candidate tables, per-sample minima and the gradient of ONE given shift, for all three cfg losses.
+# The device differentiates the shift it selected (first minimum in shift order), not tf.reduce_min's equal
+# split among exact ties: `*_grad_at(arg)` is the closed-form gradient of candidate `arg` alone.
+# A shift under which a sample has no clear pixel (n = 0) is NaN in the tables and is no candidate.
+# ----------------------------------------------------------------------------------------------
+def shift_tables(hr, mask, pred, cropBorder=3):
+    """(l1[ns^2, B], l2[ns^2, B]) of every candidate registration (models/loss.py:140-180, 226-232), (i outer, j inner)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return _shift_terms(hr, mask, pred, cropBorder)
+
+
+def select_min(table):
+    """Column-wise minimum over the non-NaN rows and the FIRST row that attains it; a column of NaNs only gives (NaN, 0)."""
+    table = np.asarray(table, F64)
+    if table.ndim == 1:
+        v, a = select_min(table[:, None])
+        return v[0], a[0]
+    arg = np.where(np.isnan(table), np.inf, table).argmin(axis=0)
+    return table[arg, np.arange(table.shape[1])], arg.astype(np.int32)
+
+
+def second_best_gap(table):
+    """Column-wise (second smallest - smallest) / max(|second smallest|, tiny) over the non-NaN rows (inf with fewer than two)."""
+    t = np.sort(np.where(np.isnan(np.asarray(table, F64).reshape(len(table), -1)), np.inf, np.asarray(table, F64).reshape(len(table), -1)), axis=0)
+    if t.shape[0] < 2:
+        return np.full(t.shape[1], np.inf)
+    with np.errstate(invalid="ignore"):
+        gap = (t[1] - t[0]) / np.maximum(np.abs(t[1]), 1e-300)
+    return np.where(np.isfinite(t[1]), gap, np.inf)
+
+
+def shift_per_sample(hr, mask, pred, cropBorder=3, bitDepth=16):
+    """dict(l1[B], l2[B], cpsnr[B], arg_l1[B], arg_l2[B]): what one device launch returns per sample."""
+    t1, t2 = shift_tables(hr, mask, pred, cropBorder)
+    l1, a1 = select_min(t1)
+    l2, a2 = select_min(t2)
+    nb = 2.0 ** bitDepth - 1.0
+    with np.errstate(divide="ignore"):
+        cpsnr = 10.0 * (np.log(nb * nb / l2) / np.log(10.0))       # the maximum over the shifts is the cPSNR of the smallest l2
+    return {"l1": l1, "l2": l2, "cpsnr": cpsnr, "arg_l1": a1, "arg_l2": a2}
+
+
+def _crop_at(hr, mask, pred, arg, c):
+    """H, M [B,L,L] at each sample's own shift arg[b], P [B,L,L], n [B], bias [B]."""
+    hr64 = np.asarray(hr, F64)[..., 0]
+    m = (np.asarray(mask)[..., 0] != 0).astype(F64)
+    p = np.asarray(pred, F64)[..., 0]
+    B, S = hr64.shape[0], hr64.shape[1]
+    L, ns = S - 2 * c, 2 * c + 1
+    arg = np.broadcast_to(np.asarray(arg), (B,))
+    H = np.stack([hr64[b, arg[b] // ns:arg[b] // ns + L, arg[b] % ns:arg[b] % ns + L] for b in range(B)])
+    M = np.stack([m[b, arg[b] // ns:arg[b] // ns + L, arg[b] % ns:arg[b] % ns + L] for b in range(B)])
+    P = p[:, c:c + L, c:c + L]
+    n = M.sum(axis=(1, 2))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bias = (H - P * M).sum(axis=(1, 2)) / n
+    return H, M, P, n, bias
+
+
+def _embed(g, S, c):
+    out = np.zeros((g.shape[0], S, S, 1), F64)
+    out[:, c:S - c, c:S - c, 0] = g
+    return out
+
+
+def shift_grad_at(hr, mask, pred, arg, cropBorder=3, which=1, upstream=1.0):
+    """d(upstream * mean_B candidate arg[b])/d(pred) for the L1 (which=1) or L2 (which=2) term:
+    dP = -(M/n) (s - sum(s M)/n),  s = sign(H - C) or 2 (H - C); zero on the border ring."""
+    H, M, P, n, bias = _crop_at(hr, mask, pred, arg, cropBorder)
+    B = H.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = H - (P + bias[:, None, None]) * M
+        s = np.sign(e) if which == 1 else 2.0 * e
+        nn = n[:, None, None]
+        g = -(M / nn) * (s - (s * M).sum(axis=(1, 2), keepdims=True) / nn) * (upstream / B)
+    return _embed(g, np.asarray(hr).shape[1], cropBorder)
+
+
+def sobel_edges(D):
+    """tf.image.sobel_edges on [B,L,L]: 3x3 cross-correlations with [[-1,-2,-1],[0,0,0],[1,2,1]] (Gy) and its transpose (Gx) of the
+    REFLECT-padded image."""
+    Dp = np.pad(np.asarray(D, F64), [(0, 0), (1, 1), (1, 1)], mode="reflect")
+    gy = (Dp[:, 2:, :-2] + 2.0 * Dp[:, 2:, 1:-1] + Dp[:, 2:, 2:]) - (Dp[:, :-2, :-2] + 2.0 * Dp[:, :-2, 1:-1] + Dp[:, :-2, 2:])
+    gx = (Dp[:, :-2, 2:] + 2.0 * Dp[:, 1:-1, 2:] + Dp[:, 2:, 2:]) - (Dp[:, :-2, :-2] + 2.0 * Dp[:, 1:-1, :-2] + Dp[:, 2:, :-2])
+    return gy, gx
+
+
+def shift_l1edge_table(hr, mask, pred, cropBorder=3, pi=0.7):
+    """[ns^2, B] candidates of shiftCompensatedL1EdgeLoss (models/loss.py:86-97, 126-137, 214-219):
+    pi * sum|D|/n + (1 - pi) * sum(|Gy| + |Gx|)/n with D = H - C; sobel_edges is linear, so edges(H) - edges(C) = edges(D)."""
+    B, S = np.asarray(hr).shape[0], np.asarray(hr).shape[1]
+    ns = 2 * cropBorder + 1
+    out = []
+    for s in range(ns * ns):
+        H, M, P, n, bias = _crop_at(hr, mask, pred, np.full(B, s), cropBorder)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            D = H - (P + bias[:, None, None]) * M
+            gy, gx = sobel_edges(D)
+            out.append((pi * np.abs(D).sum(axis=(1, 2)) + (1.0 - pi) * (np.abs(gy) + np.abs(gx)).sum(axis=(1, 2))) / n)
+    return np.stack(out)
+
+
+def shift_l1edge_sobel_at(hr, mask, pred, arg, cropBorder=3):
+    """(D, Gy, Gx) [B,L,L] at each sample's shift arg[b]."""
+    H, M, P, n, bias = _crop_at(hr, mask, pred, arg, cropBorder)
+    D = H - (P + bias[:, None, None]) * M
+    return (D,) + sobel_edges(D)
+
+
+def shift_l1edge_grad_at(hr, mask, pred, arg, cropBorder=3, pi=0.7, upstream=1.0):
+    """Gradient of upstream * mean_B candidate arg[b] of the edge loss:
+    G = [pi sign(D) + (1 - pi) Sobel^T(sign Gy, sign Gx)] / n,  dP = -M (G - sum(G M)/n); Sobel^T scatters every output's taps onto the
+    padded crop and folds the mirrored pad back (pad row -1 onto row 1, pad row L onto row L-2; likewise the columns)."""
+    H, M, P, n, bias = _crop_at(hr, mask, pred, arg, cropBorder)
+    B, L = H.shape[0], H.shape[1]
+    D = H - (P + bias[:, None, None]) * M
+    gy, gx = sobel_edges(D)
+    sy, sx = np.sign(gy), np.sign(gx)
+    ky = np.array([[-1.0, -2.0, -1.0], [0.0, 0.0, 0.0], [1.0, 2.0, 1.0]])
+    gp = np.zeros((B, L + 2, L + 2), F64)
+    for a in range(3):
+        for b in range(3):
+            gp[:, a:a + L, b:b + L] += ky[a, b] * sy + ky[b, a] * sx
+    rows = gp[:, 1:-1, :].copy()
+    rows[:, 1, :] += gp[:, 0, :]
+    rows[:, L - 2, :] += gp[:, L + 1, :]
+    A = rows[:, :, 1:-1].copy()
+    A[:, :, 1] += rows[:, :, 0]
+    A[:, :, L - 2] += rows[:, :, L + 1]
+    nn = n[:, None, None]
+    G = (pi * np.sign(D) + (1.0 - pi) * A) / nn
+    g = -M * (G - (G * M).sum(axis=(1, 2), keepdims=True) / nn) * (upstream / B)
+    return _embed(g, np.asarray(hr).shape[1], cropBorder)
+
+
+_RS_SIGMA = (0.5, 1.0, 2.0, 4.0, 8.0)
+
+
+def _revssim_parts(hr, mask, pred, s, c, bit_depth):
+    """Everything of candidate s: H, Cc, M [B,L,L], n [B], normalised windows w [5,B,L,L] and the moment terms [5,B]."""
+    B = np.asarray(hr).shape[0]
+    H, M, P, n, bias = _crop_at(hr, mask, pred, np.full(B, s), c)
+    L = H.shape[1]
+    nb = 2.0 ** bit_depth - 1.0
+    C1, C3 = (0.01 * nb) ** 2, (0.03 * nb) ** 2 / 2.0
+    x = np.linspace(-L / 2.0, L / 2.0, L)
+    Cc = (P + bias[:, None, None]) * M
+    w = []
+    for sig in _RS_SIGMA:
+        w1 = np.exp(-x / (2.0 * sig * sig))                             # the reference's window: x is NOT squared
+        ww = np.outer(w1, w1)[None] * M
+        w.append(ww / ww.sum(axis=(1, 2), keepdims=True))
+    w = np.stack(w)
+    t = {"muH": (w * H).sum(axis=(2, 3)), "muS": (w * Cc).sum(axis=(2, 3))}
+    t["sH"] = (w * H * H).sum(axis=(2, 3)) - t["muH"] ** 2
+    t["sS"] = (w * Cc * Cc).sum(axis=(2, 3)) - t["muS"] ** 2
+    t["cov"] = (w * H * Cc).sum(axis=(2, 3)) - t["muS"] * t["muH"]
+    t["lum"] = (2 * t["muH"] * t["muS"] + C1) / (t["muH"] ** 2 + t["muS"] ** 2 + C1)
+    t["con"] = (2 * t["sH"] * t["sS"] + C1) / (t["sH"] ** 2 + t["sS"] ** 2 + C1)
+    t["str"] = (2 * t["cov"] + C3) / (t["sH"] * t["sS"] + C3)
+    t["l1"] = (w * np.abs(H - Cc)).sum(axis=(2, 3))
+    return H, Cc, M, n, w, t, nb, C1, C3
+
+
+def shift_revssim_table(hr, mask, pred, cropBorder=3, bit_depth=16, eta=0.25):
+    """[ns^2] candidates of shiftCompensatedRevSSIM (models/loss.py:99-124, 189-212): ONE scalar per shift for the whole batch."""
+    B = np.asarray(hr).shape[0]
+    ns = 2 * cropBorder + 1
+    out = []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for s in range(ns * ns):
+            _, _, _, _, _, t, nb, _, _ = _revssim_parts(hr, mask, pred, s, cropBorder, bit_depth)
+            ssim = 1.0 - (t["lum"] * (t["con"] * t["str"]).prod(axis=0)).sum() / B
+            out.append(eta * ssim + (1.0 - eta) * (t["l1"].sum() / B) / nb)
+    return np.array(out)
+
+
+def shift_revssim_grad_at(hr, mask, pred, arg, cropBorder=3, bit_depth=16, eta=0.25, upstream=1.0):
+    """Gradient of upstream * candidate `arg` (one shift for the batch).  With T_b = (sum_s lum_s) prod_s con_s str_s and the window
+    weights held fixed, d muS/dC_k = w_k, d sS/dC_k = 2 w_k (C_k - muS), d cov/dC_k = w_k (H_k - muH), d|H - C|/dC = -sign(H - C);
+    then C = (P + bias) M gives dP = M (g - sum(g M)/n)."""
+    B = np.asarray(hr).shape[0]
+    H, Cc, M, n, w, t, nb, C1, C3 = _revssim_parts(hr, mask, pred, int(arg), cropBorder, bit_depth)
+    cs = t["con"] * t["str"]                                            # [5,B]
+    lsum = t["lum"].sum(axis=0)
+    pcs = cs.prod(axis=0)
+    g = np.zeros_like(H)
+    for s in range(len(_RS_SIGMA)):
+        pex = np.prod(np.delete(cs, s, axis=0), axis=0)
+        muH, muS, sH, sS, cov = (t[k][s] for k in ("muH", "muS", "sH", "sS", "cov"))
+        dl = muH ** 2 + muS ** 2 + C1
+        dlum = (2 * muH * dl - (2 * muH * muS + C1) * 2 * muS) / dl ** 2
+        dc = sH ** 2 + sS ** 2 + C1
+        dcon = (2 * sH * dc - (2 * sH * sS + C1) * 2 * sS) / dc ** 2
+        ds = sH * sS + C3
+        dstr_cov, dstr_sS = 2.0 / ds, -(2 * cov + C3) * sH / ds ** 2
+        a = (pcs * dlum)[:, None, None]
+        bq = (lsum * pex * t["str"][s] * dcon + lsum * pex * t["con"][s] * dstr_sS)[:, None, None]
+        cq = (lsum * pex * t["con"][s] * dstr_cov)[:, None, None]
+        g += -(eta / B) * w[s] * (a + 2 * bq * (Cc - muS[:, None, None]) + cq * (H - muH[:, None, None]))
+        g += -((1.0 - eta) / (nb * B)) * w[s] * np.sign(H - Cc)
+    d = M * (g - (g * M).sum(axis=(1, 2), keepdims=True) / n[:, None, None]) * upstream
+    return _embed(d, np.asarray(hr).shape[1], cropBorder)

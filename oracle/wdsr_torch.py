@@ -90,8 +90,13 @@ def wdsr_forward(x, params, mean, std, numResBlocks=12, numImgLR=9, scale=3, gat
     return (main + depth_to_space(r, scale)) * std + mean      # :38, :41
 
 
-def _shift_terms(hr, mask, pred, cropBorder=3):
-    """models/loss.py:140-180 scaffolding -> l1[49,B], mse[49,B]."""
+def _shift_ids(border, only):
+    ns = 2 * border + 1
+    return [divmod(int(s), ns) for s in (range(ns * ns) if only is None else only)]
+
+
+def _shift_terms(hr, mask, pred, cropBorder=3, only=None):
+    """models/loss.py:140-180 scaffolding -> l1[49,B], mse[49,B] (only: the listed shift ids instead of all, in that order)."""
     dt = pred.dtype
     hr = hr.to(dt)[..., 0]
     m = mask.to(dt)[..., 0]
@@ -101,16 +106,36 @@ def _shift_terms(hr, mask, pred, cropBorder=3):
     L = S - 2 * c
     P = p[:, c:c + L, c:c + L]
     l1, l2 = [], []
-    for i in range(2 * c + 1):
-        for j in range(2 * c + 1):
-            H = hr[:, i:i + L, j:j + L]
-            M = m[:, i:i + L, j:j + L]
-            n = M.sum(dim=(1, 2))
-            b = (1.0 / n) * (H - P * M).sum(dim=(1, 2))
-            C = (P + b[:, None, None]) * M
-            l1.append((1.0 / n) * (H - C).abs().sum(dim=(1, 2)))
-            l2.append((1.0 / n) * (H - C).square().sum(dim=(1, 2)))
+    for i, j in _shift_ids(c, only):
+        H = hr[:, i:i + L, j:j + L]
+        M = m[:, i:i + L, j:j + L]
+        n = M.sum(dim=(1, 2))
+        b = (1.0 / n) * (H - P * M).sum(dim=(1, 2))
+        C = (P + b[:, None, None]) * M
+        l1.append((1.0 / n) * (H - C).abs().sum(dim=(1, 2)))
+        l2.append((1.0 / n) * (H - C).square().sum(dim=(1, 2)))
     return torch.stack(l1), torch.stack(l2)
+
+
+def shift_tables(hr, mask, pred, cropBorder=3, only=None):
+    """(l1, l2) [shifts, B]: every candidate registration, or the listed shift ids."""
+    return _shift_terms(hr, mask, pred, cropBorder, only)
+
+
+def candidate_grad(table_fn, pred, arg, upstream=1.0):
+    """Autograd through candidate `arg` alone: d(upstream * mean_B table[arg[b], b])/d(pred), or d(upstream * table[arg])/d(pred) for a
+    batch-level table.  table_fn(pred, only) evaluates the listed shift ids only (nothing of any other candidate enters the graph).  This is
+    what the device differentiates: the shift it selected, not tf.reduce_min's equal split among exact ties."""
+    pt = torch.as_tensor(pred).detach().to(torch.float64).clone().requires_grad_(True)
+    arg = [int(a) for a in (arg.reshape(-1).tolist() if hasattr(arg, "reshape") else ([arg] if isinstance(arg, int) else list(arg)))]
+    ids = sorted(set(arg))
+    t = table_fn(pt, ids)
+    if t.dim() == 1:
+        loss = t[ids.index(arg[0])]
+    else:
+        loss = torch.stack([t[ids.index(a), b] for b, a in enumerate(arg)]).mean()
+    (upstream * loss).backward()
+    return pt.grad.numpy()
 
 
 def shift_l1_loss(hr, mask, pred, cropBorder=3):
@@ -153,7 +178,12 @@ def train_step_grads(x, hr, mask, params, mean, std, **kw):
 
 
 def shift_l1edge_loss(hr, mask, pred, border=3, pi=0.7):
-    """cfg loss = sobel_l1_mix (models/loss.py:86-97, 126-137, 214-219): min over the shifts of
+    """models/loss.py:86-97: the per-sample minimum over the candidates of shift_l1edge_table, batch mean."""
+    return shift_l1edge_table(hr, mask, pred, border, pi).min(dim=0).values.mean()
+
+
+def shift_l1edge_table(hr, mask, pred, border=3, pi=0.7, only=None):
+    """[shifts, B] candidates of cfg loss = sobel_l1_mix (models/loss.py:86-97, 126-137, 214-219): min over the shifts of
     pi * L1 + (1 - pi) * sum |tf.image.sobel_edges(HR) - sobel_edges(corrected SR)| / n, batch mean.
     tf.image.sobel_edges = depthwise 3x3 cross-correlation of the REFLECT-padded image with
     [[-1,-2,-1],[0,0,0],[1,2,1]] (dy) and its transpose (dx)."""
@@ -170,20 +200,24 @@ def shift_l1edge_loss(hr, mask, pred, border=3, pi=0.7):
 
     cp = pred[:, border:border + L, border:border + L]
     cands = []
-    for i in range(2 * border + 1):
-        for j in range(2 * border + 1):
-            h, mm = hr[:, i:i + L, j:j + L], m[:, i:i + L, j:j + L]
-            n = mm.sum(dim=(1, 2, 3))
-            b = ((h - cp * mm).sum(dim=(1, 2, 3)) / n).reshape(-1, 1, 1, 1)
-            c = (cp + b) * mm
-            l1 = (h - c).abs().sum(dim=(1, 2, 3)) / n
-            sob = (sobel(h) - sobel(c)).abs().sum(dim=(1, 2, 3)) / n
-            cands.append(pi * l1 + (1 - pi) * sob)
-    return torch.stack(cands).min(dim=0).values.mean()
+    for i, j in _shift_ids(border, only):
+        h, mm = hr[:, i:i + L, j:j + L], m[:, i:i + L, j:j + L]
+        n = mm.sum(dim=(1, 2, 3))
+        b = ((h - cp * mm).sum(dim=(1, 2, 3)) / n).reshape(-1, 1, 1, 1)
+        c = (cp + b) * mm
+        l1 = (h - c).abs().sum(dim=(1, 2, 3)) / n
+        sob = (sobel(h) - sobel(c)).abs().sum(dim=(1, 2, 3)) / n
+        cands.append(pi * l1 + (1 - pi) * sob)
+    return torch.stack(cands)
 
 
 def shift_revssim_loss(hr, mask, pred, border=3, bit_depth=16, eta=0.25):
-    """cfg loss = l1msssim (models/loss.py:99-124, 189-212), with the reference's quirks: exponential (not Gaussian) windows
+    """models/loss.py:99-110: the minimum over the batch-level candidates of shift_revssim_table."""
+    return shift_revssim_table(hr, mask, pred, border, bit_depth, eta).min()
+
+
+def shift_revssim_table(hr, mask, pred, border=3, bit_depth=16, eta=0.25, only=None):
+    """[shifts] candidates of cfg loss = l1msssim (models/loss.py:99-124, 189-212), with the reference's quirks: exponential (not Gaussian) windows
     exp(-x / (2 sigma^2)) over x = linspace(-L/2, L/2, L); C1 in the contrast term; variances (not standard deviations) called sigma;
     one scalar per shift for the WHOLE batch, minimum over the shifts."""
     hr, pred = hr.to(torch.float64), pred.to(torch.float64)
@@ -195,28 +229,27 @@ def shift_revssim_loss(hr, mask, pred, border=3, bit_depth=16, eta=0.25):
     x = torch.linspace(-L / 2, L / 2, L, dtype=torch.float64)
     cp = pred[:, border:border + L, border:border + L]
     cands = []
-    for i in range(2 * border + 1):
-        for j in range(2 * border + 1):
-            h, mm = hr[:, i:i + L, j:j + L], m[:, i:i + L, j:j + L]
-            n = mm.sum(dim=(1, 2, 3))
-            b = ((h - cp * mm).sum(dim=(1, 2, 3)) / n).reshape(-1, 1, 1, 1)
-            c = (cp + b) * mm
-            ws = []
-            for sig in (0.5, 1.0, 2.0, 4.0, 8.0):
-                w1 = torch.exp(-x / (2 * sig ** 2))
-                w = torch.outer(w1, w1).reshape(1, L, L, 1) * mm
-                ws.append(w / w.sum(dim=(1, 2, 3), keepdim=True))
-            w = torch.stack(ws)                                          # [5,B,L,L,1]
-            mu_h = (w * h).sum(dim=(2, 3), keepdim=True)
-            mu_s = (w * c).sum(dim=(2, 3), keepdim=True)
-            s_h = (w * h ** 2).sum(dim=(2, 3), keepdim=True) - mu_h ** 2
-            s_s = (w * c ** 2).sum(dim=(2, 3), keepdim=True) - mu_s ** 2
-            cov = (w * h * c).sum(dim=(2, 3), keepdim=True) - mu_s * mu_h
-            lum = (2 * mu_h * mu_s + C1) / (mu_h ** 2 + mu_s ** 2 + C1)
-            con = (2 * s_h * s_s + C1) / (s_h ** 2 + s_s ** 2 + C1)
-            stc = (2 * cov + C3) / (s_h * s_s + C3)
-            pcs = (con * stc).prod(dim=0)
-            loss = 1 - (lum * pcs).sum() / B
-            l1w = ((h - c).abs() * w).sum() / B
-            cands.append(eta * loss + (1 - eta) * l1w / nb)
-    return torch.stack(cands).min()
+    for i, j in _shift_ids(border, only):
+        h, mm = hr[:, i:i + L, j:j + L], m[:, i:i + L, j:j + L]
+        n = mm.sum(dim=(1, 2, 3))
+        b = ((h - cp * mm).sum(dim=(1, 2, 3)) / n).reshape(-1, 1, 1, 1)
+        c = (cp + b) * mm
+        ws = []
+        for sig in (0.5, 1.0, 2.0, 4.0, 8.0):
+            w1 = torch.exp(-x / (2 * sig ** 2))
+            w = torch.outer(w1, w1).reshape(1, L, L, 1) * mm
+            ws.append(w / w.sum(dim=(1, 2, 3), keepdim=True))
+        w = torch.stack(ws)                                          # [5,B,L,L,1]
+        mu_h = (w * h).sum(dim=(2, 3), keepdim=True)
+        mu_s = (w * c).sum(dim=(2, 3), keepdim=True)
+        s_h = (w * h ** 2).sum(dim=(2, 3), keepdim=True) - mu_h ** 2
+        s_s = (w * c ** 2).sum(dim=(2, 3), keepdim=True) - mu_s ** 2
+        cov = (w * h * c).sum(dim=(2, 3), keepdim=True) - mu_s * mu_h
+        lum = (2 * mu_h * mu_s + C1) / (mu_h ** 2 + mu_s ** 2 + C1)
+        con = (2 * s_h * s_s + C1) / (s_h ** 2 + s_s ** 2 + C1)
+        stc = (2 * cov + C3) / (s_h * s_s + C3)
+        pcs = (con * stc).prod(dim=0)
+        loss = 1 - (lum * pcs).sum() / B
+        l1w = ((h - c).abs() * w).sum() / B
+        cands.append(eta * loss + (1 - eta) * l1w / nb)
+    return torch.stack(cands)

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <vector>
 #include <functional>
+#include <mutex>
 #include <stdio.h>
 #include <string.h>
 
@@ -889,7 +890,12 @@ __global__ __launch_bounds__(64) void batch_mean_kernel(const float* __restrict_
     if (threadIdx.x == 0) { *ma = (float)(s1 / n); *mb = (float)(s2 / n); }
 }
 
-// per-sample minima over the shifts (ascending shift order, strict <: the first minimum wins ties); one thread per sample
+// per-sample minima over the shifts (ascending shift order, strict <: the first minimum wins ties); one thread per sample.
+// A shift under which the sample has no clear pixel has n = 0 and NaN candidates: `v < best` is false for it, so it is no candidate (as in
+// probav_score_select).  A sample with no candidate at all keeps best = 1e300: it is reported as NaN (loss, cPSNR; arg 0), not as the
+// sentinel -- (float)1e300 is +inf and 10 log10(max^2 / 1e300) a finite -2 900 dB that a validation mean would swallow.  Samples with a
+// candidate are untouched: the same bits as before.
+#define SHIFT_NO_CANDIDATE __builtin_nan("")
 // One workgroup of up to 1024 threads: the batch means (batch_mean_kernel's sums, in its order: a wave's lanes take the samples 64 apart, then the butterfly)
 // are taken in the same launch -- a 6-us launch less between the forward and the backward pass.
 __global__ __launch_bounds__(1024) void shift_select_mean_kernel(const double* __restrict__ cand, int B, int nshift, float max_val,
@@ -908,6 +914,8 @@ __global__ __launch_bounds__(1024) void shift_select_mean_kernel(const double* _
             if (v.x < best1) { best1 = v.x; a1 = sft; }
             if (v.y < best2) { best2 = v.y; a2 = sft; }
         }
+        if (!(best1 < 1e300)) best1 = SHIFT_NO_CANDIDATE;
+        if (!(best2 < 1e300)) best2 = SHIFT_NO_CANDIDATE;
         sl1[b] = l1_out[b] = (float)best1;
         sl2[b] = l2_out[b] = (float)best2;
         cpsnr_out[b] = (float)(10.0 * log10((double)max_val * (double)max_val / best2));
@@ -938,6 +946,8 @@ __global__ __launch_bounds__(64) void shift_select_kernel(const double* __restri
         if (v.x < best1) { best1 = v.x; a1 = sft; }
         if (v.y < best2) { best2 = v.y; a2 = sft; }
     }
+    if (!(best1 < 1e300)) best1 = SHIFT_NO_CANDIDATE;
+    if (!(best2 < 1e300)) best2 = SHIFT_NO_CANDIDATE;
     l1_out[b] = (float)best1;
     l2_out[b] = (float)best2;
     cpsnr_out[b] = (float)(10.0 * log10((double)max_val * (double)max_val / best2));
@@ -949,7 +959,7 @@ int shift_loss_forward(const float* hr, const uint8_t* mask, const float* pred, 
                        float* l1, float* l2, float* cpsnr, int* arg_l1, int* arg_l2, float* mean_l1, float* mean_l2,
                        float max_val, hipStream_t s)
 {
-    if (B <= 0 || S <= 2 * border) { set_error("shift_loss_forward: bad shape", hipSuccess); return PROBAV_EINVAL; }
+    if (B <= 0 || border < 0 || S <= 2 * border) { set_error("shift_loss_forward: bad shape (size must exceed 2 * border)", hipSuccess); return PROBAV_EINVAL; }
     const int ns = 2 * border + 1;
     // candidate table owned by the library, grown on demand (never inside a captured region: the first call of a shape allocates)
     static double* cand = nullptr;
@@ -1030,6 +1040,7 @@ int shift_loss_backward(const float* hr, const uint8_t* mask, const float* pred,
                         int border, int which, const float* upstream, float* dpred, hipStream_t s)
 {
     if (which != 1 && which != 2) { set_error("shift_loss_backward: which must be 1 (L1) or 2 (L2)", hipSuccess); return PROBAV_EINVAL; }
+    if (B <= 0 || border < 0 || S <= 2 * border) { set_error("shift_loss_backward: bad shape (size must exceed 2 * border)", hipSuccess); return PROBAV_EINVAL; }
     hipLaunchKernelGGL(shift_loss_bwd_kernel, dim3(B), dim3(256), 0, s, hr, mask, pred, arg, S, border, which, upstream, 1.0f / (float)B, dpred);
     return check_launch("shift_loss_backward");
 }
@@ -1100,6 +1111,7 @@ __global__ __launch_bounds__(256) void shift_l1edge_fwd_kernel(
         const double loss = ((double)pi * s1 + (1.0 - (double)pi) * sg) / cnt;
         if (loss < best) { best = loss; abest = sft; }              // first minimum in shift order wins ties
     }
+    if (!(best < 1e300)) best = SHIFT_NO_CANDIDATE;                 // no clear pixel under any shift (see shift_select_mean_kernel)
     if (tid == 0) { loss_out[b] = (float)best; arg_out[b] = abest; }
 }
 
@@ -1196,10 +1208,39 @@ __global__ __launch_bounds__(256) void shift_l1edge_bwd_kernel(
     }
 }
 
+// Both kernels keep the crop in dynamic LDS.  The forward holds C [L][L] fp32 (at most 40 000 bytes, within the default limit); the backward holds
+// D, sign(Gy), sign(Gx) [L][L] and the padded gradient [L+2][L+2], fp32, and its limit is raised once per process.  The device has 160 KiB of
+// LDS for static + dynamic together and the backward also has static LDS (the reduction slots), so the limit asked for is what the largest
+// accepted crop needs (161 616 bytes), not the whole 160 KiB: crop <= 100.  The forward checks the same bound, so that a training step never
+// finds the limit after its forward has run.
+constexpr size_t LOSS_LDS_MAX = 160 * 1024;   // the device's LDS per workgroup, static + dynamic
+constexpr int L1EDGE_MAX_CROP = 100;          // (3 L^2 + (L + 2)^2) * 4 + the static slots <= 160 KiB
+static size_t l1edge_bwd_lds(int L) { return ((size_t)3 * L * L + (size_t)(L + 2) * (L + 2)) * sizeof(float); }
+static_assert(((size_t)3 * L1EDGE_MAX_CROP * L1EDGE_MAX_CROP + (size_t)(L1EDGE_MAX_CROP + 2) * (L1EDGE_MAX_CROP + 2)) * sizeof(float) + 64 <= LOSS_LDS_MAX, "edge-loss crop bound");
+static_assert(((size_t)3 * (L1EDGE_MAX_CROP + 1) * (L1EDGE_MAX_CROP + 1) + (size_t)(L1EDGE_MAX_CROP + 3) * (L1EDGE_MAX_CROP + 3)) * sizeof(float) > LOSS_LDS_MAX, "edge-loss crop bound is the largest");
+static void l1edge_raise_lds()
+{
+    static std::once_flag once;
+    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(shift_l1edge_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1edge_bwd_lds(L1EDGE_MAX_CROP))); });
+}
+static int l1edge_check(const char* who, int B, int S, int border)
+{
+    const int L = S - 2 * border;
+    if (B <= 0 || border < 0 || L < 3) {
+        char msg[160]; snprintf(msg, sizeof(msg), "%s: bad shape (crop = size - 2 * border must be at least 3)", who);
+        set_error(msg, hipSuccess); return PROBAV_EINVAL;
+    }
+    if (L > L1EDGE_MAX_CROP) {
+        char msg[200]; snprintf(msg, sizeof(msg), "%s: crop %d exceeds the limit of %d pixels (size - 2 * border <= %d: the crop is held in LDS)", who, L, L1EDGE_MAX_CROP, L1EDGE_MAX_CROP);
+        set_error(msg, hipSuccess); return PROBAV_EINVAL;
+    }
+    return PROBAV_OK;
+}
 int shift_l1edge_forward(const float* hr, const uint8_t* mask, const float* pred, int B, int S, int border, float pi,
                          float* loss, int* arg, float* mean, float* scratch_mean2, hipStream_t s)
 {
-    if (B <= 0 || S <= 2 * border + 2) { set_error("shift_l1edge_forward: bad shape", hipSuccess); return PROBAV_EINVAL; }
+    { const int rc = l1edge_check("shift_l1edge_forward", B, S, border); if (rc) return rc; }
+    l1edge_raise_lds();                                                              // (so that a refused raise is reported here, not after the forward)
     const int L = S - 2 * border;
     hipLaunchKernelGGL(shift_l1edge_fwd_kernel, dim3(B), dim3(256), (size_t)L * L * sizeof(float), s, hr, mask, pred, S, border, pi, loss, arg);
     hipLaunchKernelGGL(batch_mean_kernel, dim3(1), dim3(64), 0, s, loss, loss, mean, scratch_mean2, B);
@@ -1208,10 +1249,10 @@ int shift_l1edge_forward(const float* hr, const uint8_t* mask, const float* pred
 int shift_l1edge_backward(const float* hr, const uint8_t* mask, const float* pred, const int* arg, int B, int S, int border, float pi,
                           const float* upstream, float* dpred, hipStream_t s)
 {
+    { const int rc = l1edge_check("shift_l1edge_backward", B, S, border); if (rc) return rc; }
+    l1edge_raise_lds();
     const int L = S - 2 * border;
-    const size_t lds = ((size_t)3 * L * L + (size_t)(L + 2) * (L + 2)) * sizeof(float);
-    if (B <= 0 || L < 3 || lds > 64 * 1024) { set_error("shift_l1edge_backward: bad shape", hipSuccess); return PROBAV_EINVAL; }
-    hipLaunchKernelGGL(shift_l1edge_bwd_kernel, dim3(B), dim3(256), lds, s, hr, mask, pred, arg, S, border, pi, upstream, 1.0f / (float)B, dpred);
+    hipLaunchKernelGGL(shift_l1edge_bwd_kernel, dim3(B), dim3(256), l1edge_bwd_lds(L), s, hr, mask, pred, arg, S, border, pi, upstream, 1.0f / (float)B, dpred);
     return check_launch("shift_l1edge_backward");
 }
 
@@ -1332,6 +1373,7 @@ __global__ __launch_bounds__(64) void revssim_select_kernel(const double* __rest
     if (lane == 0) {
         for (int k = 1; k < 64; ++k)
             if (sl[k] < mine || (sl[k] == mine && sa[k] < marg)) { mine = sl[k]; marg = sa[k]; }
+        if (!(mine < 1e300)) mine = SHIFT_NO_CANDIDATE;             // every shift leaves some sample without a clear pixel
         loss_out[0] = (float)mine;
         arg_out[0] = marg;
     }
@@ -1424,11 +1466,37 @@ __global__ __launch_bounds__(256) void revssim_bwd_kernel(
 
 size_t revssim_scratch_bytes(int B, int border) { const int ns = 2 * border + 1; return (size_t)ns * ns * B * RS_NS * RS_NM * sizeof(double); }
 
+// The backward keeps the five windows [5][L] and dLoss/dC [L][L] in dynamic LDS as fp64: its limit is raised once per process to what the
+// largest accepted crop needs (162 400 bytes; the static reduction slots share the device's 160 KiB), which bounds the crop at 140.  The
+// forward checks the same bound (see the edge loss above).
+constexpr int REVSSIM_MAX_CROP = 140;        // (5 L + L^2) * 8 + the static slots <= 160 KiB
+static size_t revssim_bwd_lds(int L) { return ((size_t)RS_NS * L + (size_t)L * L) * sizeof(double); }
+static_assert(((size_t)RS_NS * REVSSIM_MAX_CROP + (size_t)REVSSIM_MAX_CROP * REVSSIM_MAX_CROP) * sizeof(double) + 512 <= LOSS_LDS_MAX, "l1msssim crop bound");
+static_assert(((size_t)RS_NS * (REVSSIM_MAX_CROP + 1) + (size_t)(REVSSIM_MAX_CROP + 1) * (REVSSIM_MAX_CROP + 1)) * sizeof(double) > LOSS_LDS_MAX, "l1msssim crop bound is the largest");
+static void revssim_raise_lds()
+{
+    static std::once_flag once;
+    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(revssim_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)revssim_bwd_lds(REVSSIM_MAX_CROP))); });
+}
+static int revssim_check(const char* who, int B, int S, int border)
+{
+    const int L = S - 2 * border;
+    if (B <= 0 || border < 0 || L < 2) {
+        char msg[160]; snprintf(msg, sizeof(msg), "%s: bad shape (crop = size - 2 * border must be at least 2)", who);
+        set_error(msg, hipSuccess); return PROBAV_EINVAL;
+    }
+    if (L > REVSSIM_MAX_CROP) {
+        char msg[200]; snprintf(msg, sizeof(msg), "%s: crop %d exceeds the limit of %d pixels (size - 2 * border <= %d: the crop's gradient is held in LDS)", who, L, REVSSIM_MAX_CROP, REVSSIM_MAX_CROP);
+        set_error(msg, hipSuccess); return PROBAV_EINVAL;
+    }
+    return PROBAV_OK;
+}
 int revssim_forward(const float* hr, const uint8_t* mask, const float* pred, int B, int S, int border, float max_val, float eta,
                     double* scratch, float* loss, int* arg, hipStream_t s)
 {
+    { const int rc = revssim_check("revssim_forward", B, S, border); if (rc) return rc; }
     const int L = S - 2 * border, ns = 2 * border + 1;
-    if (B <= 0 || L < 2) { set_error("revssim_forward: bad shape", hipSuccess); return PROBAV_EINVAL; }
+    revssim_raise_lds();                                                             // (so that a refused raise is reported here, not after the forward)
     hipLaunchKernelGGL(revssim_moments_kernel, dim3(B, ns * ns), dim3(256), (size_t)RS_NS * L * sizeof(double), s, hr, mask, pred, S, border, scratch, B);
     hipLaunchKernelGGL(revssim_select_kernel, dim3(1), dim3(64), 0, s, scratch, B, ns * ns, max_val, eta, loss, arg);
     return check_launch("revssim_forward");
@@ -1436,10 +1504,10 @@ int revssim_forward(const float* hr, const uint8_t* mask, const float* pred, int
 int revssim_backward(const float* hr, const uint8_t* mask, const float* pred, const int* arg, const double* scratch, int B, int S,
                      int border, float max_val, float eta, const float* upstream, float* dpred, hipStream_t s)
 {
+    { const int rc = revssim_check("revssim_backward", B, S, border); if (rc) return rc; }
+    revssim_raise_lds();
     const int L = S - 2 * border;
-    const size_t lds = ((size_t)RS_NS * L + (size_t)L * L) * sizeof(double);
-    if (B <= 0 || L < 2 || lds > 64 * 1024) { set_error("revssim_backward: bad shape", hipSuccess); return PROBAV_EINVAL; }
-    hipLaunchKernelGGL(revssim_bwd_kernel, dim3(B), dim3(256), lds, s, hr, mask, pred, arg, scratch, S, border, B, max_val, eta, upstream, dpred);
+    hipLaunchKernelGGL(revssim_bwd_kernel, dim3(B), dim3(256), revssim_bwd_lds(L), s, hr, mask, pred, arg, scratch, S, border, B, max_val, eta, upstream, dpred);
     return check_launch("revssim_backward");
 }
 

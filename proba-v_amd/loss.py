@@ -85,8 +85,18 @@ class _RevSSIM(torch.autograd.Function):
         return dpred, None, None, None, None, None
 
 
+# Largest crop (targetShape - 2 * cropBorder) of the two losses whose kernels hold the crop in LDS (include/probav_hip.h): 160 KiB of
+# (3 L^2 + (L + 2)^2) floats for sobel_l1_mix, of (5 L + L^2) doubles for l1msssim.  Patch sizes 16, 24 and 32 (crops 42, 66, 90) fit both.
+L1EDGE_MAX_CROP = 100
+REVSSIM_MAX_CROP = 140
+
+
 class Losses:
-    """models/loss.py:8-35: all losses / metrics in one object; constants follow the reference."""
+    """models/loss.py:8-35: all losses / metrics in one object; constants follow the reference.
+
+    Where this differs from the reference, by decision (include/probav_hip.h, 'loss / metric'): among shifts that tie exactly the FIRST in
+    shift order is selected and differentiated (tf.reduce_min splits the gradient equally among them); a shift under which a sample has no
+    clear pixel is no candidate, and a sample without a clear pixel under any shift has NaN losses and cPSNR (arg 0)."""
 
     def __init__(self, targetShape=(96, 96, 1), cropBorder=3, bitDepth=16):
         self.targetShapeHeight, self.targetShapeWidth, self.targetShapeChannels = targetShape
@@ -104,6 +114,13 @@ class Losses:
             raise ValueError("Losses(targetShape=%r) got a %dx%d prediction"
                              % ((self.targetShapeHeight, self.targetShapeWidth, self.targetShapeChannels),
                                 pred.shape[1], pred.shape[2]))
+
+    def _check_crop(self, limit, what):
+        """The LDS-bound losses: refuse a too-large targetShape here, by name, before anything is launched."""
+        crop = max(self.cropSizeHeight, self.cropSizeWidth)
+        if crop > limit:
+            raise ValueError("%s: crop %d (targetShape %d - 2 * cropBorder %d) exceeds the limit of %d pixels of this loss"
+                             % (what, crop, max(self.targetShapeHeight, self.targetShapeWidth), self.cropBorder, limit))
 
     def shiftCompensatedL1Loss(self, patchHR, maskHR, predPatchHR):
         """models/loss.py:73-84 -> scalar: mean over the batch of the minimum masked, bias-corrected L1."""
@@ -128,6 +145,7 @@ class Losses:
     def evaluate_all(self, patchHR, maskHR, predPatchHR):
         """One launch, everything it computes: dict(l1[B], l2[B], cpsnr[B], arg_l1[B], arg_l2[B], mean_l1, mean_l2)."""
         hr, m, pred = _prep(patchHR, maskHR, predPatchHR)
+        self._check(pred)
         with torch.no_grad():
             f, arg, means = _launch_forward(hr, m, pred.detach(), self.cropBorder, self.bitDepth)
         return {"l1": f[0], "l2": f[1], "cpsnr": f[2], "arg_l1": arg[0], "arg_l2": arg[1],
@@ -137,10 +155,12 @@ class Losses:
         """models/loss.py:86-97 (cfg loss = sobel_l1_mix): pi * L1 + (1 - pi) * Sobel-edge L1, minimum over the shifts, batch mean."""
         hr, m, pred = _prep(patchHR, maskHR, predPatchHR)
         self._check(pred)
+        self._check_crop(L1EDGE_MAX_CROP, "shiftCompensatedL1EdgeLoss (sobel_l1_mix)")
         return _ShiftL1Edge.apply(pred, hr, m, self.cropBorder, float(self.pi))
 
     def shiftCompensatedRevSSIM(self, patchHR, maskHR, predPatchHR):
         """models/loss.py:99-110 (cfg loss = l1msssim): the batch-level multi-scale SSIM / weighted-L1 mixture, minimum over the shifts."""
         hr, m, pred = _prep(patchHR, maskHR, predPatchHR)
         self._check(pred)
+        self._check_crop(REVSSIM_MAX_CROP, "shiftCompensatedRevSSIM (l1msssim)")
         return _RevSSIM.apply(pred, hr, m, self.cropBorder, self.bitDepth, float(self.eta))

@@ -202,3 +202,65 @@ def test_conv_conventions_equal_torch_conv3d():
     xt = torch.tensor(x).permute(0, 3, 4, 1, 2).reshape(N, T * C, H, W)                       # 2-D reflect pad over (H, W)
     want = F.pad(xt, (1, 1, 1, 1), mode="reflect").reshape(N, T, C, H + 2, W + 2).permute(0, 3, 4, 1, 2).numpy()
     np.testing.assert_array_equal(on.reflect_pad_hw(x), want)
+
+
+# ---- the per-candidate tables and single-shift gradients the loss tests stand on: closed form (numpy) against autograd (torch) ----------
+def _rel(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300))
+
+
+def _loss_case(loss, **want):
+    from tests import loss_cases as lc
+    hits = [c for c in lc.ALL_CASES if c["loss"] == loss and all(c[k] == v for k, v in want.items())]
+    assert hits, want
+    return hits[0], lc.inputs(hits[0])
+
+
+@pytest.mark.parametrize("want", [dict(S=12, border=1), dict(S=8, border=1, B=65), dict(S=16, border=0, kind="random"), dict(kind="tie_lr", seed=25),
+                                  dict(mask="row0")])
+def test_shift_tables_and_single_shift_gradient_two_formulations(want):
+    case, (hr, mask, pred) = _loss_case("shift", **want)
+    c, up = case["border"], case["upstream"]
+    t1, t2 = on.shift_tables(hr, mask, pred, c)
+    r = on.shift_per_sample(hr, mask, pred, c, case["bit_depth"])
+    th, tm = torch.tensor(hr), torch.tensor(mask)
+    for which, t, arg in ((1, t1, r["arg_l1"]), (2, t2, r["arg_l2"])):
+        live = np.flatnonzero(~np.isnan(t).any(axis=1))                # (torch evaluates the listed candidates only: no NaN enters its graph)
+        tt = ot.shift_tables(th, tm, torch.tensor(pred, dtype=torch.float64), c, only=live)[which - 1].numpy()
+        assert _rel(t[live], tt) <= 1e-12
+        g = on.shift_grad_at(hr, mask, pred, arg, c, which, up)
+        # sample by sample: a shift that is a candidate for one sample may leave another without a clear pixel (mask 'row0')
+        ga = np.concatenate([ot.candidate_grad(lambda p, only, b=b: ot.shift_tables(th[b:b + 1], tm[b:b + 1], p, c, only)[which - 1], pred[b:b + 1],
+                                               arg[b:b + 1], up / len(arg)) for b in range(len(arg))])
+        assert _rel(g, ga) <= 1e-12
+    assert _rel(r["cpsnr"], ot.shift_cpsnr(th, tm, torch.tensor(pred, dtype=torch.float64), c, case["bit_depth"]).numpy()) <= 1e-12 or want.get("mask") == "row0"
+    if not want.get("kind", "").startswith("tie") and want.get("mask") != "row0":      # no ties: the split gradient is the single-shift one
+        assert _rel(on.shift_grad_at(hr, mask, pred, r["arg_l1"], c, 1), on.shift_l1_grad(hr, mask, pred, c)) <= 1e-12
+
+
+@pytest.mark.parametrize("want", [dict(S=5), dict(S=6), dict(S=7, B=1), dict(S=20, border=4), dict(kind="tie_lr")])
+def test_edge_loss_table_and_single_shift_gradient_two_formulations(want):
+    case, (hr, mask, pred) = _loss_case("edge", **want)
+    c, up, pi = case["border"], case["upstream"], float(np.float32(case["pi"]))
+    t = on.shift_l1edge_table(hr, mask, pred, c, pi)
+    th, tm = torch.tensor(hr), torch.tensor(mask)
+    assert _rel(t, ot.shift_l1edge_table(th, tm, torch.tensor(pred), c, pi).numpy()) <= 1e-12
+    assert abs(float(ot.shift_l1edge_loss(th, tm, torch.tensor(pred), c, pi)) - on.select_min(t)[0].mean()) <= 1e-12 * on.select_min(t)[0].mean()
+    _, arg = on.select_min(t)
+    g = on.shift_l1edge_grad_at(hr, mask, pred, arg, c, pi, up)
+    ga = ot.candidate_grad(lambda p, only: ot.shift_l1edge_table(th, tm, p, c, pi, only), pred, arg, up)
+    assert _rel(g, ga) <= 1e-12
+
+
+@pytest.mark.parametrize("want", [dict(S=4), dict(S=9, B=5), dict(S=20, border=4, kind="random"), dict(S=12, eta=1.0), dict(kind="tie_cols")])
+def test_l1msssim_table_and_single_shift_gradient_two_formulations(want):
+    case, (hr, mask, pred) = _loss_case("revssim", **want)
+    c, up, eta, bd = case["border"], case["upstream"], float(np.float32(case["eta"])), case["bit_depth"]
+    t = on.shift_revssim_table(hr, mask, pred, c, bd, eta)
+    th, tm = torch.tensor(hr), torch.tensor(mask)
+    assert _rel(t, ot.shift_revssim_table(th, tm, torch.tensor(pred), c, bd, eta).numpy()) <= 1e-12
+    assert abs(float(ot.shift_revssim_loss(th, tm, torch.tensor(pred), c, bd, eta)) - on.select_min(t)[0]) <= 1e-12 * abs(on.select_min(t)[0])
+    _, arg = on.select_min(t)
+    g = on.shift_revssim_grad_at(hr, mask, pred, arg, c, bd, eta, up)
+    ga = ot.candidate_grad(lambda p, only: ot.shift_revssim_table(th, tm, p, c, bd, eta, only), pred, int(arg), up)
+    assert _rel(g, ga) <= 1e-12
