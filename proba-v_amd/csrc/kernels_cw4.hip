@@ -25,7 +25,6 @@
 #include "kernels_x6.h"
 #include "x6_device.h"
 #include <cstdlib>
-#include <mutex>
 #include <algorithm>
 
 namespace probav {
@@ -684,16 +683,9 @@ int cw4_conv_forward(const ConvGeom& g, const float* x, const float* wfrag, cons
     int grid;
     if (!cw4_plan(g, p, lds_bytes, grid)) { set_error("cw4_conv_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (!am.x || !am.w) { set_error("cw4_conv_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
-    static std::once_flag once;
-    std::call_once(once, [] {
     // instances: every (channels, depth) with all three of ReLU / skip / bias compiled in (a layer without one passes 0 / no tensor), and the two layers of the
     // residual blocks without what they do not have: normConv forward (skip + bias, no ReLU), its backward-data (none of the three)
-#define CW4_BIG(C, O, T, R, S, B) (void)hipFuncSetAttribute((const void*)conv3_w4_kernel<C, O, T, R, S, B>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840)
-        CW4_BIG(25, 32, 11, true, true, true); CW4_BIG(32, 25, 11, true, true, true); CW4_BIG(32, 32, 11, true, true, true);
-        CW4_BIG(25, 32, 9, true, true, true); CW4_BIG(32, 25, 9, true, true, true); CW4_BIG(32, 32, 9, true, true, true);
-        CW4_BIG(25, 32, 11, false, true, true); CW4_BIG(32, 25, 11, false, false, false); });
-#undef CW4_BIG
-#define CW4_LAUNCH(C, O, T, R, S, B) hipLaunchKernelGGL((conv3_w4_kernel<C, O, T, R, S, B>), dim3(grid), dim3(256), lds_bytes, s, p, x, (const uint4*)wfrag, bias, skip, y, am)
+#define CW4_LAUNCH(C, O, T, R, S, B) return launch_lds<conv3_w4_kernel<C, O, T, R, S, B>>("conv3_w4", dim3(grid), dim3(256), lds_bytes, s, p, x, (const uint4*)wfrag, bias, skip, y, am)
 #define CW4_LAUNCH_T(C, O) do { if (g.To == 9) CW4_LAUNCH(C, O, 11, true, true, true); else CW4_LAUNCH(C, O, 9, true, true, true); } while (0)
     if (g.Cin == 25 && g.To == 9 && !g.relu && skip && bias) CW4_LAUNCH(25, 32, 11, false, true, true);
     else if (g.Cin == 32 && g.Cout == 25 && g.To == 9 && !g.relu && !skip && !bias) CW4_LAUNCH(32, 25, 11, false, false, false);
@@ -702,7 +694,6 @@ int cw4_conv_forward(const ConvGeom& g, const float* x, const float* wfrag, cons
     else CW4_LAUNCH_T(32, 32);
 #undef CW4_LAUNCH_T
 #undef CW4_LAUNCH
-    return check_launch("conv3_w4");
 }
 
 #ifdef CW4_DIAG

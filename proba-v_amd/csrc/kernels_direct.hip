@@ -11,7 +11,6 @@
 // wave-uniform, so the compiler fetches them through the scalar cache (s_load) and the FMAs take
 // them as SGPR operands -- filter reuse costs no vector memory traffic at all.
 #include "probav_common.h"
-#include <mutex>
 #include "x6_device.h"
 
 namespace probav {
@@ -322,9 +321,7 @@ int conv3d_up_forward(const ConvGeom& g, const float* x, const float* w, const f
 {
     if (!conv3d_up_forward_supported(g)) { set_error("conv3d_up_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     const size_t lds = ((size_t)27 * 32 * 9 + (size_t)3 * g.Wi * 3 * 32) * sizeof(float);
-    static std::once_flag once;
-    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_up_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); });
-    hipLaunchKernelGGL(conv3_up_fwd_kernel, dim3((unsigned)(g.N * g.Ho < 512 ? g.N * g.Ho : 512)), dim3(256), lds, s, g, x, w, bias, y);
+    hipLaunchKernelGGL(conv3_up_fwd_kernel, dim3((unsigned)(g.N * g.Ho < 512 ? g.N * g.Ho : 512)), dim3(256), lds, s, g, x, w, bias, y);      // (Wi == 18: 51 840 bytes, within the default limit)
     return check_launch("conv3_up_fwd");
 }
 // amax: per-sample slots of the output (may be null; zeroed by the caller)
@@ -814,20 +811,14 @@ int resid_path_forward(int N, int Hin, int Cx, const float* mn, const float* w1,
                        float* r1, float* r2, float* r3, hipStream_t s)
 {
     if (!resid_path_supported(Hin, Cx, RP_C) || N < 1) { set_error("resid_path_forward: unsupported shape", hipSuccess); return PROBAV_EINVAL; }
-    static std::once_flag once;
-    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(resid_path_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); });
-    hipLaunchKernelGGL(resid_path_fwd_kernel, dim3((unsigned)N), dim3(512), rp_fwd_lds(Hin, Cx), s, Hin, Cx, mn, w1, b1, w2, b2, w3, b3, r1, r2, r3);
-    return check_launch("resid_path_fwd");
+    return launch_lds<resid_path_fwd_kernel>("resid_path_fwd", dim3((unsigned)N), dim3(512), rp_fwd_lds(Hin, Cx), s, Hin, Cx, mn, w1, b1, w2, b2, w3, b3, r1, r2, r3);
 }
 
 int resid_path_backward(int N, int Hin, int Cx, const float* mn, const float* r1, const float* r2, const float* dtail, const float* w2, const float* w3,
                         float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* slabs, hipStream_t s)
 {
     if (!resid_path_supported(Hin, Cx, RP_C) || N < 1) { set_error("resid_path_backward: unsupported shape", hipSuccess); return PROBAV_EINVAL; }
-    static std::once_flag once;
-    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(resid_path_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); });
-    hipLaunchKernelGGL(resid_path_bwd_kernel, dim3((unsigned)N), dim3(1024), rp_bwd_lds(Hin, Cx), s, Hin, Cx, mn, r1, r2, dtail, w2, w3, slabs);
-    const int rc = check_launch("resid_path_bwd");
+    const int rc = launch_lds<resid_path_bwd_kernel>("resid_path_bwd", dim3((unsigned)N), dim3(1024), rp_bwd_lds(Hin, Cx), s, Hin, Cx, mn, r1, r2, dtail, w2, w3, slabs);
     if (rc) return rc;
     const long nw = 9L * RP_C * RP_C, nw1 = 9L * Cx * RP_C, total = rp_slab_floats(Cx);
     const SlabSumJob jobs[6] = {{slabs, dw3, total, (int)nw, N}, {slabs + nw, db3, total, RP_C, N},

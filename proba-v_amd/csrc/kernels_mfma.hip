@@ -23,7 +23,6 @@
 #include <type_traits>
 #include <cstdint>
 
-#include <mutex>
 
 namespace probav {
 
@@ -699,24 +698,15 @@ void mfma_conv_pack_job(PackJob& J, int Cin, int Cout)
     J.count = (long)mfma_conv_wfrag_floats(Cin, Cout);
 }
 
-template <typename K>
-static void allow_big_lds(K kernel)
-{
-    note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
-}
-
 int mfma_conv_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag, const float* bias,
                       const float* skip, float* y, const Amax& am, hipStream_t s)
 {
     const ConvPlan p = conv_plan(g, false);
     if (!p.ok) { set_error("mfma_conv_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     const dim3 grid((unsigned)(g.N * p.a.ntile_rows)), block(256);
-    static std::once_flag once;
-    std::call_once(once, [] { allow_big_lds(conv3_mfma_kernel<25, 13, 0>); allow_big_lds(conv3_mfma_kernel<16, 8, 0>); allow_big_lds(conv3_mfma_kernel<1, 1, 0>); });
-    if (p.CC == 1) hipLaunchKernelGGL((conv3_mfma_kernel<1, 1, 0>), grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
-    else if (p.CC == 25) hipLaunchKernelGGL((conv3_mfma_kernel<25, 13, 0>), grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
-    else            hipLaunchKernelGGL((conv3_mfma_kernel<16, 8, 0>), grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
-    return check_launch("conv3_mfma");
+    if (p.CC == 1) return launch_lds<conv3_mfma_kernel<1, 1, 0>>("conv3_mfma", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
+    if (p.CC == 25) return launch_lds<conv3_mfma_kernel<25, 13, 0>>("conv3_mfma", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
+    return launch_lds<conv3_mfma_kernel<16, 8, 0>>("conv3_mfma", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
 }
 
 // row-tile kernel with a split-operand tap loop: 32-channel inputs (two 16-channel chunks), any pads / reflect (reducers, upscale)
@@ -732,15 +722,10 @@ int x6_conv_rowtile_forward(const ConvGeom& g, const float* x, const float* gate
     if (!x6_conv_rowtile_supported(g)) { set_error("x6_conv_rowtile_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (arith == 2 && (!am.x || !am.w)) { set_error("x6_conv_rowtile_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
     const dim3 grid((unsigned)(g.N * p.a.ntile_rows)), block(256);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        allow_big_lds(conv3_mfma_kernel<16, 8, 1>); allow_big_lds(conv3_mfma_kernel<25, 13, 1>);
-        allow_big_lds(conv3_mfma_kernel<16, 8, 2>); allow_big_lds(conv3_mfma_kernel<25, 13, 2>); });
-#define PROBAV_RT(C, K, A) hipLaunchKernelGGL((conv3_mfma_kernel<C, K, A>), grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag6, bias, skip, y, am)
+#define PROBAV_RT(C, K, A) return launch_lds<conv3_mfma_kernel<C, K, A>>("conv3_mfma_x6", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag6, bias, skip, y, am)
     if (arith == 2) { if (p.CC == 25) PROBAV_RT(25, 13, 2); else PROBAV_RT(16, 8, 2); }
     else            { if (p.CC == 25) PROBAV_RT(25, 13, 1); else PROBAV_RT(16, 8, 1); }
 #undef PROBAV_RT
-    return check_launch("conv3_mfma_x6");
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2500,47 +2485,25 @@ static int strip_launch(const ConvGeom& g, const float* x, const float* gate, co
         StripPlan pp;
         int rvp = 2;
         if (pp_plan(g, pp, rvp)) {
-            static std::once_flag onceq;
-            std::call_once(onceq, [] {
-                allow_big_lds(conv3_pp_kernel<32, true, 3>);
-                allow_big_lds(conv3_pp_kernel<32, false, 2, true>); allow_big_lds(conv3_pp_kernel<32, true, 2, true>);
-                allow_big_lds(conv3_pp_kernel<32, false, 3, true>);
-                allow_big_lds(conv3_pp_kernel<25, false, 2, true>); allow_big_lds(conv3_pp_kernel<25, false, 3, true>); });
             // the instances that ship: 25 input channels (the forward pass of the residual blocks) in the pair-split form; 32 input channels (backward-data, reducers) in
             // the 16x16x32 MFMA form -- except the gated layer with three staging items per thread (reducers at T = 13), whose new-form instance would spill 42
             // registers: it keeps the one-wave-per-tile 32x32x16 form.  (Rounds 3 / 4 carried the superseded forms behind PROBAV_PP_K16 / PROBAV_PP_OLD25 for A/B runs.)
             if (g.Cin == 25 && gate) { set_error("x6_conv_strip_forward: a gated 25-channel layer has no piece-ring instance (none occurs in the reference's networks)", hipSuccess); return PROBAV_EINVAL; }
-#define PROBAV_PPK(C, G, R) hipLaunchKernelGGL((conv3_pp_kernel<C, G, R, true>), dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
-            if (g.Cin == 25) { if (rvp == 2) PROBAV_PPK(25, false, 2); else PROBAV_PPK(25, false, 3); }
-            else if (gate) {
-                if (rvp == 2) PROBAV_PPK(32, true, 2);
-                else hipLaunchKernelGGL((conv3_pp_kernel<32, true, 3>), dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am);
-            } else { if (rvp == 2) PROBAV_PPK(32, false, 2); else PROBAV_PPK(32, false, 3); }
+#define PROBAV_PPK(...) return launch_lds<conv3_pp_kernel<__VA_ARGS__>>("conv3_pp", dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
+            if (g.Cin == 25) { if (rvp == 2) PROBAV_PPK(25, false, 2, true); else PROBAV_PPK(25, false, 3, true); }
+            else if (gate) { if (rvp == 2) PROBAV_PPK(32, true, 2, true); else PROBAV_PPK(32, true, 3); }
+            else { if (rvp == 2) PROBAV_PPK(32, false, 2, true); else PROBAV_PPK(32, false, 3, true); }
 #undef PROBAV_PPK
-            return check_launch("conv3_pp");
         }
         if (!pstrip_plan(g, pp)) { set_error("x6_conv_strip_forward: no piece-ring plan for this geometry", hipSuccess); return PROBAV_EINVAL; }
-        static std::once_flag oncep;
-        std::call_once(oncep, [] {
-            allow_big_lds(conv3_pstrip_kernel<25, false>); allow_big_lds(conv3_pstrip_kernel<25, true>);
-            allow_big_lds(conv3_pstrip_kernel<32, false>); allow_big_lds(conv3_pstrip_kernel<32, true>); });
-#define PROBAV_PSTRIP(C, G) hipLaunchKernelGGL((conv3_pstrip_kernel<C, G>), dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
+#define PROBAV_PSTRIP(C, G) return launch_lds<conv3_pstrip_kernel<C, G>>("conv3_pstrip", dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
         if (g.Cin == 25) { if (gate) PROBAV_PSTRIP(25, true); else PROBAV_PSTRIP(25, false); }
         else             { if (gate) PROBAV_PSTRIP(32, true); else PROBAV_PSTRIP(32, false); }
 #undef PROBAV_PSTRIP
-        return check_launch("conv3_pstrip");
     }
     const StripPlan p = strip_plan(g);
     if (!p.ok) { set_error("mfma_conv_strip_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
-    static std::once_flag once;
-    std::call_once(once, [] {
-        allow_big_lds(conv3_strip_kernel<25, 13, false, 5, 0>); allow_big_lds(conv3_strip_kernel<25, 13, true, 5, 0>);
-        allow_big_lds(conv3_strip_kernel<32, 16, false, 4, 0>); allow_big_lds(conv3_strip_kernel<32, 16, true, 4, 0>);
-        allow_big_lds(conv3_strip_kernel<25, 13, false, 5, 1>); allow_big_lds(conv3_strip_kernel<25, 13, true, 5, 1>);
-        allow_big_lds(conv3_strip_kernel<32, 16, false, 4, 1>); allow_big_lds(conv3_strip_kernel<32, 16, true, 4, 1>);
-        allow_big_lds(conv3_strip_kernel<25, 13, false, 5, 2>); allow_big_lds(conv3_strip_kernel<25, 13, true, 5, 2>);
-        allow_big_lds(conv3_strip_kernel<32, 16, false, 4, 2>); allow_big_lds(conv3_strip_kernel<32, 16, true, 4, 2>); });
-#define PROBAV_STRIP(C, K, G, S, X) hipLaunchKernelGGL((conv3_strip_kernel<C, K, G, S, X>), dim3(p.grid), dim3(512), p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am)
+#define PROBAV_STRIP(C, K, G, S, X) return launch_lds<conv3_strip_kernel<C, K, G, S, X>>("conv3_strip", dim3(p.grid), dim3(512), p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am)
 #define PROBAV_STRIP_A(X) do { \
         if (p.CC == 25) { if (gate) PROBAV_STRIP(25, 13, true, 5, X); else PROBAV_STRIP(25, 13, false, 5, X); } \
         else            { if (gate) PROBAV_STRIP(32, 16, true, 4, X); else PROBAV_STRIP(32, 16, false, 4, X); } } while (0)
@@ -2549,7 +2512,6 @@ static int strip_launch(const ConvGeom& g, const float* x, const float* gate, co
     else PROBAV_STRIP_A(0);
 #undef PROBAV_STRIP_A
 #undef PROBAV_STRIP
-    return check_launch("conv3_strip");
 }
 
 int mfma_conv_strip_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag, const float* bias,
@@ -2718,17 +2680,12 @@ int mfma_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const fl
     const int grid = wgrad_grid(p, g), total = g.N * p.a.ntile_rows;
     const long nw = (long)27 * g.Cin * g.Cout;
     float* partial_b = partial + (size_t)grid * nw;
-    static std::once_flag once;
-#define PROBAV_WGRAD(CI, GT) hipLaunchKernelGGL((conv3_wgrad_mfma_kernel<CI, GT>), dim3(grid), dim3(256), p.lds_bytes, s, p.a, total, x, dy, gate, partial, partial_b)
-    std::call_once(once, [] {
-        allow_big_lds(conv3_wgrad_mfma_kernel<25, false>); allow_big_lds(conv3_wgrad_mfma_kernel<25, true>);
-        allow_big_lds(conv3_wgrad_mfma_kernel<32, false>); allow_big_lds(conv3_wgrad_mfma_kernel<32, true>);
-        allow_big_lds(conv3_wgrad_mfma_kernel<1, false>); allow_big_lds(conv3_wgrad_mfma_kernel<1, true>); });
+    int rc;
+#define PROBAV_WGRAD(CI, GT) rc = launch_lds<conv3_wgrad_mfma_kernel<CI, GT>>("conv3_wgrad_mfma", dim3(grid), dim3(256), p.lds_bytes, s, p.a, total, x, dy, gate, partial, partial_b)
     if (g.Cin == 1) { if (gate) PROBAV_WGRAD(1, true); else PROBAV_WGRAD(1, false); }
     else if (g.Cin == 25) { if (gate) PROBAV_WGRAD(25, true); else PROBAV_WGRAD(25, false); }
     else { if (gate) PROBAV_WGRAD(32, true); else PROBAV_WGRAD(32, false); }
 #undef PROBAV_WGRAD
-    int rc = check_launch("conv3_wgrad_mfma");
     if (rc) return rc;
     return mfma_wgrad_reduce(partial, partial_b, dw, db, nw, g.Cout, grid, s);
 }
@@ -2811,11 +2768,8 @@ bool mfma_pw_supported(int F, int E, int D) { return F == 32 && E == 256 && D >=
 int mfma_pw_forward(const float* x, const float* w1frag, const float* w2frag, const float* b1, const float* b2, float* dec,
                     long nvox, int D, hipStream_t s)
 {
-    static std::once_flag once;
-    std::call_once(once, [] { allow_big_lds(pw_fwd_mfma_kernel); });
     const size_t lds = (size_t)(2 * 8 * 4 * 64 * 4 + 256 + 32) * sizeof(float);
-    hipLaunchKernelGGL(pw_fwd_mfma_kernel, dim3(512), dim3(256), lds, s, x, (const float4*)w1frag, (const float4*)w2frag, b1, b2, dec, nvox, D);
-    return check_launch("pw_fwd_mfma");
+    return launch_lds<pw_fwd_mfma_kernel>("pw_fwd_mfma", dim3(512), dim3(256), lds, s, x, (const float4*)w1frag, (const float4*)w2frag, b1, b2, dec, nvox, D);
 }
 
 
@@ -3027,13 +2981,10 @@ int mfma_pw_backward(const float* x, const float* dT, const float* dOut, const f
                      const float* w1khch, const float* b1, float* dX, float* dW1, float* dW2, float* db1, float* db2,
                      float* slabs, long nvox, int D, hipStream_t s)
 {
-    static std::once_flag once;
-    std::call_once(once, [] { allow_big_lds(pw_bwd2_mfma_kernel); });
     const size_t lds = (size_t)(2 * PW2_XT + 2 * PW2_DT + PW2_WAVES * 2 * PW2_TB) * sizeof(float);
     const long slab_floats = 8192 + 256 * (long)D + 256 + D;
-    hipLaunchKernelGGL(pw_bwd2_mfma_kernel, dim3(PW_BWD_GRID), dim3(64 * PW2_WAVES), lds, s, x, dT, dOut, (const float4*)w1kcin,
-                       (const float4*)w2kout, (const float4*)w1khch, b1, dX, slabs, nvox, D);
-    int rc = check_launch("pw_bwd2_mfma");
+    const int rc = launch_lds<pw_bwd2_mfma_kernel>("pw_bwd2_mfma", dim3(PW_BWD_GRID), dim3(64 * PW2_WAVES), lds, s, x, dT, dOut, (const float4*)w1kcin,
+                                                   (const float4*)w2kout, (const float4*)w1khch, b1, dX, slabs, nvox, D);
     if (rc) return rc;
     return mfma_pw_backward_reduce(slabs, D, dW1, dW2, db1, db2, s);
 }

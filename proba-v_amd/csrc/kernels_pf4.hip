@@ -18,7 +18,6 @@
 #include "kernels_x6.h"
 #include "x6_device.h"
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace probav {
@@ -362,16 +361,10 @@ int pf4_forward(const float* x, const float* w1frag, const float* w2frag, const 
 {
     if (!pf4_forward_supported(nvox, vps, D)) { set_error("pf4_forward: unsupported shape", hipSuccess); return PROBAV_EINVAL; }
     if (!am.x || !am.w1 || !am.w2c || !am.b1) { set_error("pf4_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)pw_fwd_w4_kernel<false, 25>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)pw_fwd_w4_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)pw_fwd_w4_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     const size_t lds = (size_t)PF4_TAB + (256 + 32 + 32 + 4 * 864) * sizeof(float);
-    if (hdump) hipLaunchKernelGGL((pw_fwd_w4_kernel<true, 0>), dim3(256), dim3(256), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, hdump);
-    else if (D == 25) hipLaunchKernelGGL((pw_fwd_w4_kernel<false, 25>), dim3(256), dim3(256), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
-    else hipLaunchKernelGGL((pw_fwd_w4_kernel<false, 0>), dim3(256), dim3(256), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
-    return check_launch("pw_fwd_w4");
+    if (hdump) return launch_lds<pw_fwd_w4_kernel<true, 0>>("pw_fwd_w4", dim3(256), dim3(256), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, hdump);
+    if (D == 25) return launch_lds<pw_fwd_w4_kernel<false, 25>>("pw_fwd_w4", dim3(256), dim3(256), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
+    return launch_lds<pw_fwd_w4_kernel<false, 0>>("pw_fwd_w4", dim3(256), dim3(256), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
 }
 
 #ifdef PF4_DIAG

@@ -22,7 +22,6 @@
 // probav_prep_xcorr_surface returns e and B for one pair (the bound is checked against the exact surface by tests/test_gpu_prep.py).
 #include "probav_common.h"
 #include "../../include/probav_hip.h"
-#include <atomic>
 
 namespace probav {
 
@@ -341,25 +340,6 @@ __global__ __launch_bounds__(256) void prep_patches_kernel(const float* __restri
     if (threadIdx.x == 0) counts[b] = part[0] + part[1] + part[2] + part[3];
 }
 
-// hipFuncSetAttribute is per device: once per device this process touches (not once per process)
-int prep_lds_attr()
-{
-    static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) { set_error("probav_prep: hipGetDevice", e); return PROBAV_EHIP; }
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load() & bit) return PROBAV_OK;
-    const void* ks[] = {reinterpret_cast<const void*>(prep_ref_spectrum_kernel), reinterpret_cast<const void*>(prep_register_kernel<false>),
-                        reinterpret_cast<const void*>(prep_register_kernel<true>)};
-    for (const void* k : ks) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_LDS);
-        if (e != hipSuccess) { set_error("probav_prep: hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e); return PROBAV_EHIP; }
-    }
-    done.fetch_or(bit);
-    return PROBAV_OK;
-}
-
 }  // namespace
 
 }  // namespace probav
@@ -386,15 +366,12 @@ extern "C" int probav_prep_register(const uint16_t* frames, const uint8_t* masks
         set_error("probav_prep_register: null/invalid argument", hipSuccess);
         return PROBAV_EINVAL;
     }
-    int rc = prep_lds_attr();
-    if (rc != PROBAV_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     float2* spec = reinterpret_cast<float2*>(spec_scratch);
-    hipLaunchKernelGGL(prep_ref_spectrum_kernel, dim3((unsigned)n_sets), dim3(PREP_THREADS), PREP_LDS, s, frames, ref_frame, set_offsets, n_frames, spec);
-    if ((rc = check_launch("prep_ref_spectrum_kernel")) != PROBAV_OK) return rc;
-    hipLaunchKernelGGL(prep_register_kernel<false>, dim3((unsigned)n_frames), dim3(PREP_THREADS), PREP_LDS, s, frames, masks, set_offsets, n_sets,
-                       n_frames, ref_frame, (const float2*)spec, shifts, reg_frames, reg_masks, reg_counts, (float*)nullptr, (double*)nullptr);
-    return check_launch("prep_register_kernel");
+    const int rc = launch_lds<prep_ref_spectrum_kernel>("prep_ref_spectrum_kernel", dim3((unsigned)n_sets), dim3(PREP_THREADS), PREP_LDS, s, frames, ref_frame, set_offsets, n_frames, spec);
+    if (rc != PROBAV_OK) return rc;
+    return launch_lds<prep_register_kernel<false>>("prep_register_kernel", dim3((unsigned)n_frames), dim3(PREP_THREADS), PREP_LDS, s, frames, masks, set_offsets, n_sets,
+                                                   n_frames, ref_frame, (const float2*)spec, shifts, reg_frames, reg_masks, reg_counts, (float*)nullptr, (double*)nullptr);
 }
 
 extern "C" int probav_prep_xcorr_surface(const uint16_t* pair, float* spec_scratch, float* surface, double* info, void* stream)
@@ -403,16 +380,13 @@ extern "C" int probav_prep_xcorr_surface(const uint16_t* pair, float* spec_scrat
         set_error("probav_prep_xcorr_surface: null argument", hipSuccess);
         return PROBAV_EINVAL;
     }
-    int rc = prep_lds_attr();
-    if (rc != PROBAV_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     float2* spec = reinterpret_cast<float2*>(spec_scratch);
-    hipLaunchKernelGGL(prep_ref_spectrum_kernel, dim3(1), dim3(PREP_THREADS), PREP_LDS, s, pair, (const int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)2, spec);
-    if ((rc = check_launch("prep_ref_spectrum_kernel")) != PROBAV_OK) return rc;
-    hipLaunchKernelGGL(prep_register_kernel<true>, dim3(1), dim3(PREP_THREADS), PREP_LDS, s, pair, (const uint8_t*)nullptr,
-                       (const int64_t*)nullptr, 1, (int64_t)2, (const int32_t*)nullptr, (const float2*)spec, (int32_t*)nullptr, (uint16_t*)nullptr, (uint8_t*)nullptr,
-                       (int32_t*)nullptr, surface, info);
-    return check_launch("prep_register_kernel<diag>");
+    const int rc = launch_lds<prep_ref_spectrum_kernel>("prep_ref_spectrum_kernel", dim3(1), dim3(PREP_THREADS), PREP_LDS, s, pair, (const int32_t*)nullptr, (const int64_t*)nullptr, (int64_t)2, spec);
+    if (rc != PROBAV_OK) return rc;
+    return launch_lds<prep_register_kernel<true>>("prep_register_kernel<diag>", dim3(1), dim3(PREP_THREADS), PREP_LDS, s, pair, (const uint8_t*)nullptr,
+                                                  (const int64_t*)nullptr, 1, (int64_t)2, (const int32_t*)nullptr, (const float2*)spec, (int32_t*)nullptr, (uint16_t*)nullptr, (uint8_t*)nullptr,
+                                                  (int32_t*)nullptr, surface, info);
 }
 
 extern "C" int probav_prep_patches(const float* frames, const uint8_t* masks, int S, int T, int H, int W, int pad, int win, int stride,

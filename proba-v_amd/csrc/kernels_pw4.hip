@@ -25,7 +25,6 @@
 #include "kernels_x6.h"
 #include "x6_device.h"
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace probav {
@@ -734,15 +733,12 @@ int pw4_backward(const float* x, const float* dT, const float* dOut, const float
                  const float* b1, float* dX, float* dW1, float* dW2, float* db1, float* db2, float* slabs, long nvox, long vps, int D,
                  const PwAmax& am, hipStream_t s)
 {
-    static std::once_flag once;
-    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_bwd_w4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
     if (!pw4_backward_supported(nvox, vps, D)) { set_error("pw4_backward: unsupported shape", hipSuccess); return PROBAV_EINVAL; }
     if (!am.x || !am.w1 || !am.w2 || !am.b1 || !am.dt || !am.w1r) { set_error("pw4_backward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
     const int grid = mfma_pw_backward_grid(), nsamp = (int)(nvox / vps);
     const int wps = 4 * grid / nsamp;                              // waves per sample (>= 1)
-    hipLaunchKernelGGL(pw_bwd_w4_kernel, dim3(grid), dim3(256), PW4_LDS, s, x, dT, dOut, (const uint4*)w1f, (const uint4*)w2kf, (const uint4*)w1cf,
-                       b1, dX, slabs, nsamp, (int)vps, D, wps, am);
-    int rc = check_launch("pw_bwd_w4");
+    const int rc = launch_lds<pw_bwd_w4_kernel>("pw_bwd_w4", dim3(grid), dim3(256), PW4_LDS, s, x, dT, dOut, (const uint4*)w1f, (const uint4*)w2kf, (const uint4*)w1cf,
+                                                b1, dX, slabs, nsamp, (int)vps, D, wps, am);
     if (rc) return rc;
     return mfma_pw_backward_reduce(slabs, D, dW1, dW2, db1, db2, s);
 }

@@ -8,10 +8,8 @@
 #include "probav_common.h"
 #include "../../include/probav_hip.h"
 #include <cstdlib>
-#include <atomic>
 #include <vector>
 #include <functional>
-#include <mutex>
 #include <stdio.h>
 #include <string.h>
 
@@ -24,18 +22,10 @@ void set_error(const char* what, hipError_t e)
     else snprintf(g_err, sizeof(g_err), "%s", what);
 }
 const char* last_error() { return g_err; }
-static std::atomic<int> g_attr_err{(int)hipSuccess};                 // first failed hipFuncSetAttribute, sticky (process-wide: the attribute is)
-void note_attr_error(hipError_t e)
-{
-    int ok = (int)hipSuccess;
-    if (e != hipSuccess) g_attr_err.compare_exchange_strong(ok, (int)e);
-}
 int check_launch(const char* what)
 {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error(what, e); return PROBAV_EHIP; }
-    const int a = g_attr_err.load();
-    if (a != (int)hipSuccess) { set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for a kernel of this library", (hipError_t)a); return PROBAV_EHIP; }
     return PROBAV_OK;
 }
 
@@ -1209,20 +1199,14 @@ __global__ __launch_bounds__(256) void shift_l1edge_bwd_kernel(
 }
 
 // Both kernels keep the crop in dynamic LDS.  The forward holds C [L][L] fp32 (at most 40 000 bytes, within the default limit); the backward holds
-// D, sign(Gy), sign(Gx) [L][L] and the padded gradient [L+2][L+2], fp32, and its limit is raised once per process.  The device has 160 KiB of
-// LDS for static + dynamic together and the backward also has static LDS (the reduction slots), so the limit asked for is what the largest
-// accepted crop needs (161 616 bytes), not the whole 160 KiB: crop <= 100.  The forward checks the same bound, so that a training step never
-// finds the limit after its forward has run.
-constexpr size_t LOSS_LDS_MAX = 160 * 1024;   // the device's LDS per workgroup, static + dynamic
+// D, sign(Gy), sign(Gx) [L][L] and the padded gradient [L+2][L+2], fp32, and launch_lds raises its limit.  The device has 160 KiB of
+// LDS for static + dynamic together and the backward also has static LDS (the reduction slots), so the largest accepted crop is the one
+// whose 161 616 bytes leave room for them: crop <= 100.  The forward checks the same bound, so that a training step never finds the
+// limit after its forward has run.
 constexpr int L1EDGE_MAX_CROP = 100;          // (3 L^2 + (L + 2)^2) * 4 + the static slots <= 160 KiB
 static size_t l1edge_bwd_lds(int L) { return ((size_t)3 * L * L + (size_t)(L + 2) * (L + 2)) * sizeof(float); }
-static_assert(((size_t)3 * L1EDGE_MAX_CROP * L1EDGE_MAX_CROP + (size_t)(L1EDGE_MAX_CROP + 2) * (L1EDGE_MAX_CROP + 2)) * sizeof(float) + 64 <= LOSS_LDS_MAX, "edge-loss crop bound");
-static_assert(((size_t)3 * (L1EDGE_MAX_CROP + 1) * (L1EDGE_MAX_CROP + 1) + (size_t)(L1EDGE_MAX_CROP + 3) * (L1EDGE_MAX_CROP + 3)) * sizeof(float) > LOSS_LDS_MAX, "edge-loss crop bound is the largest");
-static void l1edge_raise_lds()
-{
-    static std::once_flag once;
-    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(shift_l1edge_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1edge_bwd_lds(L1EDGE_MAX_CROP))); });
-}
+static_assert(((size_t)3 * L1EDGE_MAX_CROP * L1EDGE_MAX_CROP + (size_t)(L1EDGE_MAX_CROP + 2) * (L1EDGE_MAX_CROP + 2)) * sizeof(float) + 64 <= LDS_LIMIT, "edge-loss crop bound");
+static_assert(((size_t)3 * (L1EDGE_MAX_CROP + 1) * (L1EDGE_MAX_CROP + 1) + (size_t)(L1EDGE_MAX_CROP + 3) * (L1EDGE_MAX_CROP + 3)) * sizeof(float) > LDS_LIMIT, "edge-loss crop bound is the largest");
 static int l1edge_check(const char* who, int B, int S, int border)
 {
     const int L = S - 2 * border;
@@ -1240,7 +1224,6 @@ int shift_l1edge_forward(const float* hr, const uint8_t* mask, const float* pred
                          float* loss, int* arg, float* mean, float* scratch_mean2, hipStream_t s)
 {
     { const int rc = l1edge_check("shift_l1edge_forward", B, S, border); if (rc) return rc; }
-    l1edge_raise_lds();                                                              // (so that a refused raise is reported here, not after the forward)
     const int L = S - 2 * border;
     hipLaunchKernelGGL(shift_l1edge_fwd_kernel, dim3(B), dim3(256), (size_t)L * L * sizeof(float), s, hr, mask, pred, S, border, pi, loss, arg);
     hipLaunchKernelGGL(batch_mean_kernel, dim3(1), dim3(64), 0, s, loss, loss, mean, scratch_mean2, B);
@@ -1250,10 +1233,8 @@ int shift_l1edge_backward(const float* hr, const uint8_t* mask, const float* pre
                           const float* upstream, float* dpred, hipStream_t s)
 {
     { const int rc = l1edge_check("shift_l1edge_backward", B, S, border); if (rc) return rc; }
-    l1edge_raise_lds();
     const int L = S - 2 * border;
-    hipLaunchKernelGGL(shift_l1edge_bwd_kernel, dim3(B), dim3(256), l1edge_bwd_lds(L), s, hr, mask, pred, arg, S, border, pi, upstream, 1.0f / (float)B, dpred);
-    return check_launch("shift_l1edge_backward");
+    return launch_lds<shift_l1edge_bwd_kernel>("shift_l1edge_backward", dim3(B), dim3(256), l1edge_bwd_lds(L), s, hr, mask, pred, arg, S, border, pi, upstream, 1.0f / (float)B, dpred);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1466,18 +1447,13 @@ __global__ __launch_bounds__(256) void revssim_bwd_kernel(
 
 size_t revssim_scratch_bytes(int B, int border) { const int ns = 2 * border + 1; return (size_t)ns * ns * B * RS_NS * RS_NM * sizeof(double); }
 
-// The backward keeps the five windows [5][L] and dLoss/dC [L][L] in dynamic LDS as fp64: its limit is raised once per process to what the
-// largest accepted crop needs (162 400 bytes; the static reduction slots share the device's 160 KiB), which bounds the crop at 140.  The
+// The backward keeps the five windows [5][L] and dLoss/dC [L][L] in dynamic LDS as fp64 (launch_lds raises its limit): the
+// largest accepted crop needs 162 400 bytes and the static reduction slots share the device's 160 KiB, which bounds the crop at 140.  The
 // forward checks the same bound (see the edge loss above).
 constexpr int REVSSIM_MAX_CROP = 140;        // (5 L + L^2) * 8 + the static slots <= 160 KiB
 static size_t revssim_bwd_lds(int L) { return ((size_t)RS_NS * L + (size_t)L * L) * sizeof(double); }
-static_assert(((size_t)RS_NS * REVSSIM_MAX_CROP + (size_t)REVSSIM_MAX_CROP * REVSSIM_MAX_CROP) * sizeof(double) + 512 <= LOSS_LDS_MAX, "l1msssim crop bound");
-static_assert(((size_t)RS_NS * (REVSSIM_MAX_CROP + 1) + (size_t)(REVSSIM_MAX_CROP + 1) * (REVSSIM_MAX_CROP + 1)) * sizeof(double) > LOSS_LDS_MAX, "l1msssim crop bound is the largest");
-static void revssim_raise_lds()
-{
-    static std::once_flag once;
-    std::call_once(once, [] { note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(revssim_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)revssim_bwd_lds(REVSSIM_MAX_CROP))); });
-}
+static_assert(((size_t)RS_NS * REVSSIM_MAX_CROP + (size_t)REVSSIM_MAX_CROP * REVSSIM_MAX_CROP) * sizeof(double) + 512 <= LDS_LIMIT, "l1msssim crop bound");
+static_assert(((size_t)RS_NS * (REVSSIM_MAX_CROP + 1) + (size_t)(REVSSIM_MAX_CROP + 1) * (REVSSIM_MAX_CROP + 1)) * sizeof(double) > LDS_LIMIT, "l1msssim crop bound is the largest");
 static int revssim_check(const char* who, int B, int S, int border)
 {
     const int L = S - 2 * border;
@@ -1496,7 +1472,6 @@ int revssim_forward(const float* hr, const uint8_t* mask, const float* pred, int
 {
     { const int rc = revssim_check("revssim_forward", B, S, border); if (rc) return rc; }
     const int L = S - 2 * border, ns = 2 * border + 1;
-    revssim_raise_lds();                                                             // (so that a refused raise is reported here, not after the forward)
     hipLaunchKernelGGL(revssim_moments_kernel, dim3(B, ns * ns), dim3(256), (size_t)RS_NS * L * sizeof(double), s, hr, mask, pred, S, border, scratch, B);
     hipLaunchKernelGGL(revssim_select_kernel, dim3(1), dim3(64), 0, s, scratch, B, ns * ns, max_val, eta, loss, arg);
     return check_launch("revssim_forward");
@@ -1505,10 +1480,8 @@ int revssim_backward(const float* hr, const uint8_t* mask, const float* pred, co
                      int border, float max_val, float eta, const float* upstream, float* dpred, hipStream_t s)
 {
     { const int rc = revssim_check("revssim_backward", B, S, border); if (rc) return rc; }
-    revssim_raise_lds();
     const int L = S - 2 * border;
-    hipLaunchKernelGGL(revssim_bwd_kernel, dim3(B), dim3(256), revssim_bwd_lds(L), s, hr, mask, pred, arg, scratch, S, border, B, max_val, eta, upstream, dpred);
-    return check_launch("revssim_backward");
+    return launch_lds<revssim_bwd_kernel>("revssim_backward", dim3(B), dim3(256), revssim_bwd_lds(L), s, hr, mask, pred, arg, scratch, S, border, B, max_val, eta, upstream, dpred);
 }
 
 // ---------------------------------------------------------------------------------------------------

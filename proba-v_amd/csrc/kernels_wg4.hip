@@ -24,7 +24,6 @@
 #include "kernels_x6.h"
 #include "x6_device.h"
 #include <cstdlib>
-#include <mutex>
 
 // The kernel's ten instances are one unrolled instruction stream each and 6 min 40 s of hipcc in one translation unit: kernels_wg4b.hip / kernels_wg4c.hip include THIS file with
 // WG4_PART = 1 / 2 and instantiate their share of them (WG4_PART1 / WG4_PART2 below); part 0 -- this file compiled for itself -- declares those `extern template`, instantiates the
@@ -624,19 +623,13 @@ int wg4_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const flo
     int grid;
     if (!wg4_plan(g, gate, p, grid)) { set_error("wg4_conv_wgrad: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (!am.x || !am.w) { set_error("wg4_conv_wgrad: H3 arithmetic needs the per-sample amax slots of x (am.x) and dY (am.w)", hipSuccess); return PROBAV_EINVAL; }
-    static std::once_flag once;
-    std::call_once(once, [] {
-#define WG4_BIG(W, TP, RT, C, M) note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_w4_kernel<W, TP, RT, C, M>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840))
-        WG4_BIG(22, 11, WG4_RT, 25, 0); WG4_BIG(22, 9, WG4_RT, 25, 0); WG4_BIG(22, 9, 32, 32, 1); WG4_BIG(22, 7, 32, 32, 1); WG4_BIG(22, 5, 32, 32, 1);
-        WG4_BIG(20, 7, 32, 32, 2); WG4_BIG(18, 5, 32, 32, 2);
-        WG4_BIG(11, 15, WG4_RT, 25, 0); WG4_BIG(11, 13, 32, 32, 1); WG4_BIG(22, 11, 32, 32, 1); });
-#undef WG4_BIG
     const long nw = (long)27 * g.Cin * g.Cout;
     float* partial_b = partial + (size_t)grid * nw;
     const int Tp = g.To + 2;
     const int Wk = g.Wo / p.nsplit;                                        // columns of a workgroup's rows
     const size_t lds_bytes = (size_t)4 * 2 * (Wk + 2) * Tp * 64 + 1024 + (size_t)((Wk * g.To + 15) / 16) * 2048;      // ring, slack, the row's dY fragments
-#define WG4_LAUNCH(W, TP, RT, C, M) hipLaunchKernelGGL((conv3_wgrad_w4_kernel<W, TP, RT, C, M>), dim3(grid), dim3(256), lds_bytes, s, p, x, dy, gate, partial, partial_b, am)
+    int rc;
+#define WG4_LAUNCH(W, TP, RT, C, M) rc = launch_lds<conv3_wgrad_w4_kernel<W, TP, RT, C, M>>("conv3_wgrad_w4", dim3(grid), dim3(256), lds_bytes, s, p, x, dy, gate, partial, partial_b, am)
     if (g.Cin == 25) { if (g.To == 13) WG4_LAUNCH(11, 15, WG4_RT, 25, 0); else if (g.To == 9) WG4_LAUNCH(22, 11, WG4_RT, 25, 0); else WG4_LAUNCH(22, 9, WG4_RT, 25, 0); }
     else if (!g.reflect_hw) { if (g.Wo == 20) WG4_LAUNCH(20, 7, 32, 32, 2); else WG4_LAUNCH(18, 5, 32, 32, 2); }
     else if (g.To == 11) WG4_LAUNCH(11, 13, 32, 32, 1);
@@ -645,7 +638,6 @@ int wg4_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const flo
     else if (g.To == 5) WG4_LAUNCH(22, 7, 32, 32, 1);
     else WG4_LAUNCH(22, 5, 32, 32, 1);
 #undef WG4_LAUNCH
-    int rc = check_launch("conv3_wgrad_w4");
     if (rc) return rc;
     return mfma_wgrad_reduce(partial, partial_b, dw, db, nw, g.Cout, grid, s);
 }

@@ -19,7 +19,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-#include <mutex>
 
 namespace probav {
 
@@ -421,13 +420,6 @@ void x6_pw_dump_from_forward_kernel(int on) { g_pw_dump_h3k = on ? 1 : 0; }
 int x6_pw_forward(const float* x, const float* w1frag, const float* w2frag, const float* b1, const float* b2, float* dec,
                   long nvox, long vps, int D, int arith, const PwAmax& am, hipStream_t s, float* hdump)
 {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_fwd_x6_kernel<X6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_fwd_x6_kernel<X6, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_fwd_x6_kernel<H3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_fwd_h3k_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_fwd_h3k_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
     if (vps <= 0 || vps > nvox) vps = nvox;                          // one "sample"
     if (nvox % vps || vps > 0x7fffffffL) { set_error("x6_pw_forward: nvox must be a multiple of the voxels per sample", hipSuccess); return PROBAV_EINVAL; }
     if (arith == 2) {
@@ -437,18 +429,16 @@ int x6_pw_forward(const float* x, const float* w1frag, const float* w2frag, cons
         // x6_pw_dump_from_forward_kernel(1), from the forward kernel itself
         if (pf4_enabled() && pf4_forward_supported(nvox, vps, D) && (!hdump || g_pw_dump_h3k))          // one wave per SIMD (kernels_pf4.hip); its dump IS "from the forward kernel"
             return pf4_forward(x, w1frag, w2frag, b1, b2, dec, nvox, vps, D, am, s, hdump);
-        if (hdump && g_pw_dump_h3k) hipLaunchKernelGGL(pw_fwd_h3k_kernel<true>, dim3(256 * 2), dim3(512), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, hdump);
-        else if (hdump) hipLaunchKernelGGL((pw_fwd_x6_kernel<H3, true>), dim3(256 * PwfShape<H3>::WGS), dim3(64 * PwfShape<H3>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
-                                      b1, b2, dec, nvox, (int)vps, D, am, hdump);
-        else hipLaunchKernelGGL(pw_fwd_h3k_kernel<false>, dim3(256 * 2), dim3(512), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
-    } else {
-        const size_t lds = (size_t)2 * 8 * 2 * X6::NP * 64 * 16 + (256 + 32 + 32) * sizeof(float);
-        if (hdump) hipLaunchKernelGGL((pw_fwd_x6_kernel<X6, true>), dim3(256 * PwfShape<X6>::WGS), dim3(64 * PwfShape<X6>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
-                                      b1, b2, dec, nvox, (int)vps, D, am, hdump);
-        else hipLaunchKernelGGL((pw_fwd_x6_kernel<X6, false>), dim3(256 * PwfShape<X6>::WGS), dim3(64 * PwfShape<X6>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
-                                b1, b2, dec, nvox, (int)vps, D, am, hdump);
+        if (hdump && g_pw_dump_h3k) return launch_lds<pw_fwd_h3k_kernel<true>>("pw_fwd_x6", dim3(256 * 2), dim3(512), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, hdump);
+        if (hdump) return launch_lds<pw_fwd_x6_kernel<H3, true>>("pw_fwd_x6", dim3(256 * PwfShape<H3>::WGS), dim3(64 * PwfShape<H3>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
+                                                                 b1, b2, dec, nvox, (int)vps, D, am, hdump);
+        return launch_lds<pw_fwd_h3k_kernel<false>>("pw_fwd_x6", dim3(256 * 2), dim3(512), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
     }
-    return check_launch("pw_fwd_x6");
+    const size_t lds = (size_t)2 * 8 * 2 * X6::NP * 64 * 16 + (256 + 32 + 32) * sizeof(float);
+    if (hdump) return launch_lds<pw_fwd_x6_kernel<X6, true>>("pw_fwd_x6", dim3(256 * PwfShape<X6>::WGS), dim3(64 * PwfShape<X6>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
+                                                             b1, b2, dec, nvox, (int)vps, D, am, hdump);
+    return launch_lds<pw_fwd_x6_kernel<X6, false>>("pw_fwd_x6", dim3(256 * PwfShape<X6>::WGS), dim3(64 * PwfShape<X6>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
+                                                   b1, b2, dec, nvox, (int)vps, D, am, hdump);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -889,12 +879,9 @@ int x6_pw_backward(const float* x, const float* dT, const float* dOut, const flo
                    const float* b1, float* dX, float* dW1, float* dW2, float* db1, float* db2, float* slabs, long nvox, long vps, int D,
                    int arith, const PwAmax& am, hipStream_t s)
 {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_bwd_x6_kernel<X6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(pw_bwd_x6_kernel<H3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
     if (vps <= 0 || vps > nvox) vps = nvox;
     if (nvox % vps || vps > 0x7fffffffL) { set_error("x6_pw_backward: nvox must be a multiple of the voxels per sample", hipSuccess); return PROBAV_EINVAL; }
+    int rc;
     if (arith == 2) {
         if (!am.x || !am.w1 || !am.w2 || !am.b1 || !am.dt || !am.w1r) { set_error("x6_pw_backward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
         // round 5: one wave per SIMD, 512 registers, no barrier in the tile loop (kernels_pw4.hip).  pw_bwd_x6_kernel<H3> below is the general form: any
@@ -902,14 +889,13 @@ int x6_pw_backward(const float* x, const float* dT, const float* dOut, const flo
         if (pw4_enabled() && pw4_backward_supported(nvox, vps, D))
             return pw4_backward(x, dT, dOut, w1f, w2kf, w1cf, b1, dX, dW1, dW2, db1, db2, slabs, nvox, vps, D, am, s);
         const size_t lds = (size_t)4 * H3::NP * PB_IMG + ((size_t)16 * PB_TB + 256) * sizeof(float) + (size_t)8 * 2 * H3::NP * PT_IMG;   // (two transpose images per wave)
-        hipLaunchKernelGGL(pw_bwd_x6_kernel<H3>, dim3(mfma_pw_backward_grid()), dim3(512), lds, s, x, dT, dOut, (const uint4*)w1f,
-                           (const uint4*)w2kf, (const uint4*)w1cf, b1, dX, slabs, nvox, (int)vps, D, am);
+        rc = launch_lds<pw_bwd_x6_kernel<H3>>("pw_bwd_x6", dim3(mfma_pw_backward_grid()), dim3(512), lds, s, x, dT, dOut, (const uint4*)w1f,
+                                              (const uint4*)w2kf, (const uint4*)w1cf, b1, dX, slabs, nvox, (int)vps, D, am);
     } else {
         const size_t lds = (size_t)4 * X6::NP * PB_IMG + ((size_t)16 * PB_TB + 256) * sizeof(float) + (size_t)8 * X6::NP * PT_IMG;
-        hipLaunchKernelGGL(pw_bwd_x6_kernel<X6>, dim3(mfma_pw_backward_grid()), dim3(512), lds, s, x, dT, dOut, (const uint4*)w1f,
-                           (const uint4*)w2kf, (const uint4*)w1cf, b1, dX, slabs, nvox, (int)vps, D, am);
+        rc = launch_lds<pw_bwd_x6_kernel<X6>>("pw_bwd_x6", dim3(mfma_pw_backward_grid()), dim3(512), lds, s, x, dT, dOut, (const uint4*)w1f,
+                                              (const uint4*)w2kf, (const uint4*)w1cf, b1, dX, slabs, nvox, (int)vps, D, am);
     }
-    int rc = check_launch("pw_bwd_x6");
     if (rc) return rc;
     return mfma_pw_backward_reduce(slabs, D, dW1, dW2, db1, db2, s);
 }
@@ -1452,14 +1438,8 @@ int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const floa
         const size_t tb = (lds + 15) & ~(size_t)15, tsz = (size_t)(g.Cin == 25 ? 6 : 7) * 512 * 8;
         if (a.nsplit == 1 && tb + tsz <= 160 * 1024) { a.tab = (int)tb; lds = tb + tsz; }
     }
-    static std::once_flag once;
-    std::call_once(once, [] {
-#define PROBAV_WGA(C, G, A) note_attr_error(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_x6_kernel<C, G, A>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        PROBAV_WGA(25, false, X6); PROBAV_WGA(25, true, X6); PROBAV_WGA(32, false, X6); PROBAV_WGA(32, true, X6);
-        PROBAV_WGA(25, false, H3); PROBAV_WGA(25, true, H3); PROBAV_WGA(32, false, H3); PROBAV_WGA(32, true, H3);
-#undef PROBAV_WGA
-    });
-#define PROBAV_WG6(C, G, A) hipLaunchKernelGGL((conv3_wgrad_x6_kernel<C, G, A>), dim3(grid), dim3(512), lds, s, a, x, dy, gate, partial, partial_b, am)
+    int rc;
+#define PROBAV_WG6(C, G, A) rc = launch_lds<conv3_wgrad_x6_kernel<C, G, A>>("conv3_wgrad_x6", dim3(grid), dim3(512), lds, s, a, x, dy, gate, partial, partial_b, am)
     if (arith == 2) {
         if (g.Cin == 25) { if (gate) PROBAV_WG6(25, true, H3); else PROBAV_WG6(25, false, H3); }
         else             { if (gate) PROBAV_WG6(32, true, H3); else PROBAV_WG6(32, false, H3); }
@@ -1468,7 +1448,6 @@ int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const floa
         else             { if (gate) PROBAV_WG6(32, true, X6); else PROBAV_WG6(32, false, X6); }
     }
 #undef PROBAV_WG6
-    int rc = check_launch("conv3_wgrad_x6");
     if (rc) return rc;
     return mfma_wgrad_reduce(partial, partial_b, dw, db, nw, g.Cout, grid, s);
 }

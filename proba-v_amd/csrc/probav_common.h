@@ -4,8 +4,10 @@
 //   kernels      [kh][kw][kt][Cin][Cout]       (Keras layout; models/modelsTF.py:191-197)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <functional>
 #include <stdint.h>
+#include <stdio.h>
 #include <stddef.h>
 
 #define PROBAV_OK 0
@@ -43,12 +45,49 @@ int amax_tensor(const float* x, size_t per_sample, int N, unsigned* slots, hipSt
 int amax_columns(const float* w, long rows, int cols, unsigned* slots, hipStream_t s);
 
 void set_error(const char* what, hipError_t e);
-// check_launch: hipGetLastError after a launch -> PROBAV_OK / PROBAV_EHIP.  It also reports (once set, sticky) a failed
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) of any kernel: note_attr_error() records it from inside the std::call_once
-// blocks that raise the LDS limits, so the failure surfaces as what it is instead of as an opaque launch error later.
-void note_attr_error(hipError_t e);
+// check_launch: hipGetLastError after a launch -> PROBAV_OK / PROBAV_EHIP (the message names `what`)
 int check_launch(const char* what);
 const char* last_error();
+
+// launch_lds: THE launch of every kernel that may need more dynamic LDS than a kernel gets by default.  The limit is an attribute of the
+// kernel ON ONE DEVICE, so each kernel (the template argument) keeps a mask of the devices on which it has been raised; a launch with
+// lds > LDS_DEFAULT on a device whose bit is clear raises it first, to the one value the library uses (LDS_LIMIT less the kernel's static
+// LDS).  A refused raise fails THIS call (PROBAV_EHIP, the message names `what`) and leaves the bit clear: nothing is sticky, no other
+// kernel is affected.
+constexpr size_t LDS_DEFAULT = 64 * 1024;       // dynamic LDS a launch may ask for without the attribute
+constexpr size_t LDS_LIMIT = 160 * 1024;        // gfx950: LDS per workgroup, static + dynamic
+inline int raise_lds_limit(const void* kernel, std::atomic<uint64_t>& done, const char* what)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    const uint64_t bit = uint64_t(1) << (dev & 63);
+    if (e == hipSuccess) {
+        if (done.load() & bit) return PROBAV_OK;
+        hipFuncAttributes fa;                    // LDS_LIMIT holds a kernel's static LDS too (the loss kernels' reduction slots): ask for what is left beside it
+        e = hipFuncGetAttributes(&fa, kernel);
+        if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_LIMIT - fa.sharedSizeBytes));
+    }
+    if (e != hipSuccess) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "%s: raising the kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize)", what);
+        set_error(msg, e);
+        (void)hipGetLastError();                 // (reported here: the next check_launch must not find it)
+        return PROBAV_EHIP;
+    }
+    done.fetch_or(bit);
+    return PROBAV_OK;
+}
+template <auto Kernel, typename... Args>
+int launch_lds(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args)
+{
+    static std::atomic<uint64_t> done{0};        // one per kernel instance: bit d = raised on device d
+    if (lds > LDS_DEFAULT) {
+        const int rc = raise_lds_limit(reinterpret_cast<const void*>(Kernel), done, what);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+    return check_launch(what);
+}
 
 // ---- kernels_direct.hip : generic direct (VALU) convolution, any geometry ------------------------
 // y = act( conv(x * [gate > 0], w) + bias ) + skip        (gate/bias/skip optional)
