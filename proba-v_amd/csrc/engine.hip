@@ -124,18 +124,31 @@ static int add_layer(probav_engine* e, const std::string& name, int kh, int kw, 
 
 static size_t align_up(size_t v) { return (v + 63) & ~(size_t)63; }      // 64 floats = 256 B
 
+// The network's geometry for one (engine, batch): the forward ConvGeom of every layer (a reducer's input extents are its Hi, Ti).  make_net is
+// the one place that states them; the plan, both passes and the introspection calls read them here (backward-data: bwd_data_geom of these)
+struct Net {
+    ConvGeom main, exp, dec, norm, up, resid1, resid2, resid3;      // exp / dec / norm: the same for every block
+    std::vector<ConvGeom> red;
+};
+static size_t in_floats(const ConvGeom& g) { return (size_t)g.N * g.Hi * g.Wi * g.Ti * g.Cin; }
+static size_t out_floats(const ConvGeom& g) { return (size_t)g.N * g.Ho * g.Wo * g.To * g.Cout; }
+static long in_voxels(const ConvGeom& g) { return (long)g.N * g.Hi * g.Wi * g.Ti; }
+
 struct Plan {
+    Net net;
     size_t weff, weffT, invn, xn, mn;
     size_t amax; int n_amax, amax_bwd, amax_fwd, B;   // amax slots (one 32-bit word each, x6_device.h): region offset, count, first slot of the backward / forward per-sample arrays
+    int n_back;                               // per-sample slot arrays the reverse pass takes (new_slot); the region behind amax_bwd holds at least as many
     std::vector<size_t> act, dec, red;
-    std::vector<int> redH, redT;              // output extent of each reducer
     size_t up, r1, r2, r3, H, wpack;
     // --- what only the reverse pass writes (offsets relative to the SCRATCH base: the tail of a one-piece workspace, or the caller's second buffer) ---
     size_t bamax, dweff2, Hb, dH, gA, gB, gDec, dtail, dr2, dr1, partial;
     size_t fwd_total, bwd_total, total;       // floats: the saved state of a forward pass | the reverse pass's scratch | both
     std::vector<size_t> gblk, gred;
-    struct Region { size_t off, floats; };
-    std::vector<Region> parts;          // slab region of the k-th backward-filter launch of a backward pass (offset relative to `partial`, size), in launch order
+    // the slab region of each backward-filter launch of a backward pass, by the layer it serves (offset relative to `partial`, size; off == none:
+    // this plan has no such launch).  pair[i]: the fused pointwise pair of block i; dec[i], exp[i]: its two layers un-fused
+    struct Region { static constexpr size_t none = ~(size_t)0; size_t off = none, floats = 0; };
+    struct { Region resid3, resid2, resid1, up, main; std::vector<Region> red, norm, pair, dec, exp; } slab;
 };
 
 static ConvGeom make_geom(int N, int Hi, int Ti, int Cin, int Ho, int To, int Cout, int kh, int kw, int kt,
@@ -172,15 +185,27 @@ static ConvGeom red_geom(const probav_engine* e, int B, size_t k, int h, int t, 
     return g;
 }
 
-static void reducer_extents(const probav_engine* e, std::vector<int>& hh, std::vector<int>& tt)
+static Net make_net(const probav_engine* e, int B)
 {
-    int h = e->Hin, t = e->cfg.num_img_lr;
-    for (size_t k = 0; k < e->iRed.size(); ++k) {
-        const probav_engine::RedSpec& r = e->redSpec[k];
-        h += 2 * r.p - (r.k - 1);
-        t += 2 * r.pt - (r.k - 1);
-        hh.push_back(h); tt.push_back(t);
+    const probav_net_cfg& c = e->cfg;
+    const int F = c.num_filters, E = F * c.exp_rate, D = c.dec_channels, T = c.num_img_lr, Cx = c.in_channels;
+    const int Hin = e->Hin, P = c.patch_size_lr, s2 = c.scale * c.scale;
+    Net n;
+    //                  N  Hi       Ti Cin Ho       To Cout kh kw kt ph pt reflect relu
+    n.main   = make_geom(B, Hin,     T, Cx, Hin,     T, F,   3, 3, 3, 1, 1, 0, 1);
+    n.exp    = make_geom(B, Hin,     T, F,  Hin,     T, E,   1, 1, 1, 0, 0, 0, 1);
+    n.dec    = make_geom(B, Hin,     T, E,  Hin,     T, D,   1, 1, 1, 0, 0, 0, 0);
+    n.norm   = make_geom(B, Hin,     T, D,  Hin,     T, F,   3, 3, 3, 1, 1, 0, 0);
+    int h = Hin, t = T;
+    for (size_t k = 0; k < e->redSpec.size(); ++k) {
+        n.red.push_back(red_geom(e, B, k, h, t, F));
+        h = n.red[k].Ho; t = n.red[k].To;
     }
+    n.up     = make_geom(B, h,       t, F,  P,       1, s2,  3, 3, 3, 0, 0, 0, 0);
+    n.resid1 = make_geom(B, Hin,     1, Cx, Hin - 2, 1, s2,  3, 3, 1, 0, 0, 0, 1);
+    n.resid2 = make_geom(B, Hin - 2, 1, s2, Hin - 4, 1, s2,  3, 3, 1, 0, 0, 0, 0);
+    n.resid3 = make_geom(B, Hin - 4, 1, s2, P,       1, s2,  3, 3, 1, 0, 0, 0, 0);
+    return n;
 }
 
 // the low-frequency residual path runs as one launch each way (kernels_direct.hip: resid_path_*) in every family but 0, which stays on the generic direct kernels
@@ -213,92 +238,82 @@ static size_t wgrad_need(const Family& f, const ConvGeom& g) { return wgrad_slab
 static Plan make_plan(const probav_engine* e, int B, int training)
 {
     Plan p;
-    const probav_net_cfg& c = e->cfg;
-    const int F = c.num_filters, E = F * c.exp_rate, D = c.dec_channels, T = c.num_img_lr, R = c.num_res_blocks;
-    const int Hin = e->Hin, P = c.patch_size_lr, s2 = c.scale * c.scale;
-    const size_t V = (size_t)B * Hin * Hin * T;
+    p.net = make_net(e, B);
+    const Net& n = p.net;
+    const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
     size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += align_up(n); return o; };
+    auto take = [&](size_t q) { size_t o = off; off += align_up(q); return o; };
     p.weff = take(e->weff_count); p.weffT = take(e->weff_count); p.invn = take(e->cout_total);
     {   // slots: per layer [weights | biases] (whole tensor), per output channel, per input channel (wn_forward's layout); then ONE SLOT PER
-        // SAMPLE for act[0..R], dec[0..R-1], the reducer outputs, and for the backward pass's tensors in launch order
-        const int L = (int)e->layers.size(), nred = (int)e->iRed.size();
+        // SAMPLE for act[0..R], dec[0..R-1], the reducer outputs, and for the backward pass's tensors in launch order: the upscale layer's input
+        // gradient, per reducer its input gradient and (mirrored pads) the folded one, per block those of dec_i and act[i]
+        const int L = (int)e->layers.size();
         p.B = B;
         p.amax_fwd = 2 * L + (int)e->cout_total + (int)e->cin_total;
         p.amax_bwd = p.amax_fwd + B * (2 * R + 1 + nred);
-        p.n_amax = p.amax_bwd + (training ? B * (2 * R + 2 * nred + 8) : 0);
+        p.n_back = 1 + 2 * R;
+        for (const ConvGeom& g : n.red) p.n_back += g.reflect_hw ? 2 : 1;
+        p.n_amax = p.amax_bwd + (training ? B * (2 * R + 2 * nred + 8) : 0);     // (reserved: n_back and a margin that the workspace sizes have always carried)
         p.amax = take((size_t)p.amax_bwd);
     }
     p.wpack = take(e->wpack_count);
-    p.xn = take(V * c.in_channels); p.mn = take((size_t)B * Hin * Hin * c.in_channels);
+    p.xn = take(in_floats(n.main)); p.mn = take(in_floats(n.resid1));
     if (training) {
-        for (int i = 0; i <= R; ++i) p.act.push_back(take(V * F));
-        for (int i = 0; i < R; ++i) p.dec.push_back(take(V * D));
+        for (int i = 0; i <= R; ++i) p.act.push_back(take(out_floats(n.main)));
+        for (int i = 0; i < R; ++i) p.dec.push_back(take(out_floats(n.dec)));
     } else {
-        const size_t a0 = take(V * F), a1 = take(V * F), d0 = take(V * D);
+        const size_t a0 = take(out_floats(n.main)), a1 = take(out_floats(n.main)), d0 = take(out_floats(n.dec));
         for (int i = 0; i <= R; ++i) p.act.push_back((i & 1) ? a1 : a0);
         for (int i = 0; i < R; ++i) p.dec.push_back(d0);
     }
-    reducer_extents(e, p.redH, p.redT);
-    for (size_t k = 0; k < e->iRed.size(); ++k) p.red.push_back(take((size_t)B * p.redH[k] * p.redH[k] * p.redT[k] * F));
-    p.up = take((size_t)B * P * P * s2);
-    p.r1 = take((size_t)B * (Hin - 2) * (Hin - 2) * s2);
-    p.r2 = take((size_t)B * (Hin - 4) * (Hin - 4) * s2);
-    p.r3 = take((size_t)B * P * P * s2);
+    for (const ConvGeom& g : n.red) p.red.push_back(take(out_floats(g)));
+    p.up = take(out_floats(n.up));
+    p.r1 = take(out_floats(n.resid1));
+    p.r2 = take(out_floats(n.resid2));
+    p.r3 = take(out_floats(n.resid3));
     // the 256-channel hidden tensor (1 KB per voxel) only exists in memory when the pointwise pair runs UNfused (generic kernels, impl 0)
     const bool unfused = !e->fam.pw_fused;
-    p.H = take(unfused ? V * E : 0);
+    p.H = take(unfused ? out_floats(n.exp) : 0);
     p.fwd_total = off;
     off = 0;
     p.bamax = p.dweff2 = p.Hb = p.dH = p.gA = p.gB = p.gDec = p.dtail = p.dr2 = p.dr1 = p.partial = 0;
     if (training) {
         p.bamax = take((size_t)(p.n_amax - p.amax_bwd));
         p.dweff2 = take(e->weff_count);
-        p.Hb = take(unfused ? V * E : 0);              // the recomputed hidden tensor of the unfused path (the forward pass's own copy is saved state: read-only here)
-        size_t gmax = (size_t)B * (Hin + 2) * (Hin + 2) * T * F;
-        {   // gradients of the (mirror-padded) reducer inputs
-            int h = Hin, t = T;
-            for (size_t k = 0; k < e->iRed.size(); ++k) {
-                const probav_engine::RedSpec& r = e->redSpec[k];
-                const size_t q = (size_t)B * (h + 2 * r.p) * (h + 2 * r.p) * (t + 2 * r.pt) * F;
-                if (q > gmax) gmax = q;
-                h = p.redH[k]; t = p.redT[k];
-            }
-        }
-        p.gA = take(gmax); p.gB = take(gmax); p.gDec = take(V * D);
+        p.Hb = take(unfused ? out_floats(n.exp) : 0);  // the recomputed hidden tensor of the unfused path (the forward pass's own copy is saved state: read-only here)
+        // gradient buffers of the chain: the largest (mirror-padded) reducer input, and never less than a block-sized tensor padded by one row / column
+        size_t gmax = (size_t)B * (n.main.Ho + 2) * (n.main.Wo + 2) * n.main.To * n.main.Cout;
+        for (const ConvGeom& g : n.red) gmax = std::max(gmax, out_floats(bwd_data_geom(g)));
+        p.gA = take(gmax); p.gB = take(gmax); p.gDec = take(out_floats(n.dec));
         // every block's input gradient in its own buffer: the block's backward-filter (needed only by the weight-norm backward at the very end)
         // runs on the low-priority side stream, filling the tails of the main chain's launches, and must find its dY untouched whenever it runs
-        p.gblk.clear();
-        for (int i = 0; i < R; ++i) p.gblk.push_back(take(V * F));
-        p.gred.clear();                                        // the reducers likewise: backward-data output and (mirrored pads) its folded form
-        for (size_t k = 0; k < 2 * e->iRed.size(); ++k) p.gred.push_back(take(gmax));
-        p.dtail = take((size_t)B * P * P * s2);
-        p.dr2 = take((size_t)B * (Hin - 4) * (Hin - 4) * s2);
-        p.dr1 = take((size_t)B * (Hin - 2) * (Hin - 2) * s2);
-        p.dH = take(unfused ? V * E : 0);
-        // one slab region per backward-filter launch, in the order backward_impl issues them (it checks that it takes exactly these, each large
-        // enough): the slabs of a launch are summed on the side stream while the main chain has moved on, so no two launches may share a region
+        for (int i = 0; i < R; ++i) p.gblk.push_back(take(out_floats(n.main)));
+        for (int k = 0; k < 2 * nred; ++k) p.gred.push_back(take(gmax));   // the reducers likewise: backward-data output and (mirrored pads) its folded form
+        p.dtail = take(out_floats(n.up));
+        p.dr2 = take(out_floats(n.resid2));
+        p.dr1 = take(out_floats(n.resid1));
+        p.dH = take(unfused ? out_floats(n.exp) : 0);
+        // one slab region per backward-filter launch, laid out in the order backward_impl issues them: the slabs of a launch are summed on the side
+        // stream while the main chain has moved on, so no two launches may share a region
         {
-            std::vector<size_t> need;
             const Family& f = e->fam;
-            const int nred = (int)e->iRed.size();
-            need.push_back(wgrad_need(f, make_geom(B, Hin - 4, 1, s2, P, 1, s2, 3, 3, 1, 0, 0, 0, 0)));           // residConv3, 2, 1
-            if (resid_path_fused(e)) need.back() = std::max(need.back(), resid_path_slab_floats(B, c.in_channels));        // (the fused reverse pass: one slab per patch, in the first region)
-            need.push_back(wgrad_need(f, make_geom(B, Hin - 2, 1, s2, Hin - 4, 1, s2, 3, 3, 1, 0, 0, 0, 0)));
-            need.push_back(wgrad_need(f, make_geom(B, Hin, 1, c.in_channels, Hin - 2, 1, s2, 3, 3, 1, 0, 0, 0, 1)));
-            need.push_back(wgrad_need(f, make_geom(B, p.redH[nred - 1], p.redT[nred - 1], F, P, 1, s2, 3, 3, 3, 0, 0, 0, 0)));   // upscaleConv1
-            for (int k = nred - 1; k >= 0; --k)
-                need.push_back(wgrad_need(f, red_geom(e, B, (size_t)k, k ? p.redH[k - 1] : Hin, k ? p.redT[k - 1] : T, F)));
-            const ConvGeom ge = make_geom(B, Hin, T, F, Hin, T, E, 1, 1, 1, 0, 0, 0, 1), gd = make_geom(B, Hin, T, E, Hin, T, D, 1, 1, 1, 0, 0, 0, 0);
-            const ConvGeom gn = make_geom(B, Hin, T, D, Hin, T, F, 3, 3, 3, 1, 1, 0, 0);
-            for (int i = 0; i < R; ++i) {
-                need.push_back(wgrad_need(f, gn));
-                if (!unfused) need.push_back(mfma_pw_backward_slab_floats(D));
-                else { need.push_back(wgrad_need(f, gd)); need.push_back(wgrad_need(f, ge)); }
-            }
-            need.push_back(wgrad_need(f, make_geom(B, Hin, T, c.in_channels, Hin, T, F, 3, 3, 3, 1, 1, 0, 1)));               // mainConv1
             size_t acc = 0;
-            for (size_t q : need) { p.parts.push_back({acc, q}); acc += align_up(q); }
+            auto region = [&](size_t q) { Plan::Region r; r.off = acc; r.floats = q; acc += align_up(q); return r; };
+            size_t resid3 = wgrad_need(f, n.resid3);
+            if (resid_path_fused(e)) resid3 = std::max(resid3, resid_path_slab_floats(B, n.resid1.Cin));     // (the fused reverse pass: one slab per patch, in the first region)
+            p.slab.resid3 = region(resid3);
+            p.slab.resid2 = region(wgrad_need(f, n.resid2));
+            p.slab.resid1 = region(wgrad_need(f, n.resid1));
+            p.slab.up = region(wgrad_need(f, n.up));
+            p.slab.red.resize(nred);
+            for (int k = nred - 1; k >= 0; --k) p.slab.red[k] = region(wgrad_need(f, n.red[k]));
+            p.slab.norm.resize(R); p.slab.pair.resize(R); p.slab.dec.resize(R); p.slab.exp.resize(R);
+            for (int i = R - 1; i >= 0; --i) {
+                p.slab.norm[i] = region(wgrad_need(f, n.norm));
+                if (!unfused) p.slab.pair[i] = region(mfma_pw_backward_slab_floats(n.dec.Cout));
+                else { p.slab.dec[i] = region(wgrad_need(f, n.dec)); p.slab.exp[i] = region(wgrad_need(f, n.exp)); }
+            }
+            p.slab.main = region(wgrad_need(f, n.main));
             p.partial = take(acc);
         }
     }
@@ -332,13 +347,24 @@ static Frags frags(const probav_engine* e, const float* wpack, int li, int dir)
     return {at(o.f32), at(o.x6), at(o.h3), at(o.h3t)};
 }
 
+// Where the parameter-derived tensors of a pass live: in the caller's weight cache (WC), or in the workspace W, where the forward pass recomputes them.
+// wslots: the weights' amax slots (the head of the workspace's amax region, or the cache's)
+struct Derived { const float *weff, *weffT, *invn, *wpack; unsigned* wslots; };
+static Derived derived(const probav_engine* e, const Plan& p, const float* W, const float* WC)
+{
+    auto slots = [](const float* q) { return reinterpret_cast<unsigned*>(const_cast<float*>(q)); };
+    if (!WC) return {W + p.weff, W + p.weffT, W + p.invn, W + p.wpack, slots(W + p.amax)};
+    const WcPlan wc = make_wc_plan(e);
+    return {WC + wc.weff, WC + wc.weffT, WC + wc.invn, WC + wc.wpack, slots(WC + wc.amax)};
+}
+
 // amax slot addresses inside the workspace (layout: make_plan)
 struct AmaxSlots {
     const probav_engine* e; unsigned* base; unsigned* wbase; unsigned* bbase; int L, R, B, fwd;
-    // wslots: where the weights' slots live -- the head of the workspace's amax region, or the weight cache's; S: the reverse pass's scratch (its slots live there)
-    AmaxSlots(const probav_engine* e_, const Plan& p, const float* W, int R_, unsigned* wslots = nullptr, float* S = nullptr)
-        : e(e_), base(reinterpret_cast<unsigned*>(const_cast<float*>(W) + p.amax)), wbase(wslots ? wslots : reinterpret_cast<unsigned*>(const_cast<float*>(W) + p.amax)),
-          bbase(S ? reinterpret_cast<unsigned*>(S + p.bamax) : nullptr), L((int)e_->layers.size()), R(R_), B(p.B), fwd(p.amax_fwd) {}
+    // wslots: where the weights' slots live (Derived); S: the reverse pass's scratch (its slots live there)
+    AmaxSlots(const probav_engine* e_, const Plan& p, const float* W, unsigned* wslots, float* S = nullptr)
+        : e(e_), base(reinterpret_cast<unsigned*>(const_cast<float*>(W) + p.amax)), wbase(wslots),
+          bbase(S ? reinterpret_cast<unsigned*>(S + p.bamax) : nullptr), L((int)e_->layers.size()), R(e_->cfg.num_res_blocks), B(p.B), fwd(p.amax_fwd) {}
     unsigned* w(int li) const { return wbase + li; }                                   // whole weight tensor of layer li
     unsigned* b(int li) const { return wbase + L + li; }                               // its bias
     unsigned* wcol(int li) const { return wbase + 2 * L + e->layers[li].wn.n_off; }     // per output channel (Cout slots): columns of the forward matrices
@@ -403,8 +429,12 @@ static int conv_fwd(const probav_engine* e, const ConvGeom& g, const float* x, c
 
 #define CK(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-// a slab region of the backward pass (make_plan: Plan::parts); p == nullptr: the pass asked for more regions than the plan lists
+// a slab region of the backward pass (make_plan: Plan::slab) inside the scratch S; p == nullptr: the pass asked for a region that the plan did not lay out
 struct Slab { float* p; size_t floats; };
+static Slab slab_at(const Plan& p, float* S, const Plan::Region& r)
+{
+    return r.off == Plan::Region::none ? Slab{nullptr, 0} : Slab{S + p.partial + r.off, r.floats};
+}
 static int slab_fits(const Slab& r, size_t need)
 {
     if (!r.p) { set_error("probav_backward: more backward-filter launches than make_plan laid out slab regions for", hipSuccess); return PROBAV_EINVAL; }
@@ -564,9 +594,8 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
     e->iResid2 = add_layer(e, "residConv2", 3, 3, 1, s2, s2);
     e->iResid3 = add_layer(e, "residConv3", 3, 3, 1, s2, s2);
     // the graph must close: after the reducers one valid 3x3x3 conv lands on [P, P, 1]
-    std::vector<int> hh, tt;
-    reducer_extents(e, hh, tt);
-    if (hh.back() - 2 != cfg->patch_size_lr || tt.back() - 2 != 1) {
+    const ConvGeom up = make_net(e, 1).up;
+    if (up.Hi - 2 != up.Ho || up.Ti - 2 != up.To) {
         delete e;
         set_error("probav_engine_create: reducer geometry does not collapse to [P,P,1]", hipSuccess);
         return PROBAV_EINVAL;
@@ -765,19 +794,16 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_forward: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
     CK(device_tables(e));
     float* W = (float*)ws;
-    const WcPlan wc = make_wc_plan(e);
-    // where the parameter-derived tensors live: inside the workspace (recomputed by this call) or in the caller's weight cache
-    const float* Wweff = WC ? WC + wc.weff : W + p.weff;
-    const float* Wpack = WC ? WC + wc.wpack : W + p.wpack;
+    const Net& n = p.net;
+    const Derived dv = derived(e, p, W, WC);
     const probav_net_cfg& c = e->cfg;
-    const int F = c.num_filters, E = F * c.exp_rate, D = c.dec_channels, T = c.num_img_lr, R = c.num_res_blocks;
-    const int Hin = e->Hin, P = c.patch_size_lr, s2 = c.scale * c.scale;
-    auto weff = [&](int li) { return Wweff + e->layers[li].wn.w_off; };
+    const int R = c.num_res_blocks;
+    auto weff = [&](int li) { return dv.weff + e->layers[li].wn.w_off; };
     auto bias = [&](int li) { return params + e->layers[li].wn.b_off; };
-    auto frag = [&](int li) { return frags(e, Wpack, li, 0); };
+    auto frag = [&](int li) { return frags(e, dv.wpack, li, 0); };
     // amax slots (H3 arithmetic, impl 4): every tensor an H3 kernel reads has its largest magnitude in a slot by then
     const bool h3 = e->fam.arith == 2;
-    const AmaxSlots A(e, p, W, R, WC ? reinterpret_cast<unsigned*>(const_cast<float*>(WC + wc.amax)) : nullptr);
+    const AmaxSlots A(e, p, W, dv.wslots);
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wcol(li); m.y = ay; } return m; };
     // (the per-sample amax slots -- the atomicMax targets -- are cleared by head_kernel below; the weight slots in front of them are plain stores of wn_forward_kernel /
     // wn_rowmax_kernel, every one of them written before anything reads it)
@@ -787,45 +813,43 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
         { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, W + p.weff, W + p.weffT, W + p.invn, h3 ? A.base : nullptr, s)); }
         if (e->fam.mfma) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), W + p.weff, W + p.weffT, W + p.wpack, A.base, s)); }
     }
-    CK(head_forward(x, W + p.xn, W + p.mn, B * Hin * Hin, T, c.in_channels, c.mean, c.std, s, h3 ? A.base + p.amax_fwd : nullptr, h3 ? p.amax_bwd - p.amax_fwd : 0));
+    CK(head_forward(x, W + p.xn, W + p.mn, B * n.main.Hi * n.main.Wi, n.main.Ti, n.main.Cin, c.mean, c.std, s, h3 ? A.base + p.amax_fwd : nullptr, h3 ? p.amax_bwd - p.amax_fwd : 0));
     // the low-frequency residual path (three small 2-D convolutions on the temporal mean) meets the main path only in tail_forward: it runs
     // on the side stream, in the gaps of the chip-filling launches
     SideGuard side_guard((side_stream_disabled() || e->side_mode == 0) ? nullptr : engine_side(e), s);
     {
         hipStream_t rs = reduce_fork(s);
         if (resid_path_fused(e)) {                         // the three layers as one launch (kernels_direct.hip); family 0 keeps the generic direct kernels
-            CK(resid_path_forward(B, Hin, c.in_channels, W + p.mn, weff(e->iResid1), bias(e->iResid1), weff(e->iResid2), bias(e->iResid2), weff(e->iResid3), bias(e->iResid3),
+            CK(resid_path_forward(B, n.resid1.Hi, n.resid1.Cin, W + p.mn, weff(e->iResid1), bias(e->iResid1), weff(e->iResid2), bias(e->iResid2), weff(e->iResid3), bias(e->iResid3),
                                   W + p.r1, W + p.r2, W + p.r3, rs));
         } else {
-        CK(conv_fwd(e, make_geom(B, Hin, 1, c.in_channels, Hin - 2, 1, s2, 3, 3, 1, 0, 0, 0, 1), W + p.mn, nullptr, weff(e->iResid1), frag(e->iResid1), bias(e->iResid1), nullptr, W + p.r1, Amax(), rs));
-        CK(conv_fwd(e, make_geom(B, Hin - 2, 1, s2, Hin - 4, 1, s2, 3, 3, 1, 0, 0, 0, 0), W + p.r1, nullptr, weff(e->iResid2), frag(e->iResid2), bias(e->iResid2), nullptr, W + p.r2, Amax(), rs));
-        CK(conv_fwd(e, make_geom(B, Hin - 4, 1, s2, P, 1, s2, 3, 3, 1, 0, 0, 0, 0), W + p.r2, nullptr, weff(e->iResid3), frag(e->iResid3), bias(e->iResid3), nullptr, W + p.r3, Amax(), rs));
+        CK(conv_fwd(e, n.resid1, W + p.mn, nullptr, weff(e->iResid1), frag(e->iResid1), bias(e->iResid1), nullptr, W + p.r1, Amax(), rs));
+        CK(conv_fwd(e, n.resid2, W + p.r1, nullptr, weff(e->iResid2), frag(e->iResid2), bias(e->iResid2), nullptr, W + p.r2, Amax(), rs));
+        CK(conv_fwd(e, n.resid3, W + p.r2, nullptr, weff(e->iResid3), frag(e->iResid3), bias(e->iResid3), nullptr, W + p.r3, Amax(), rs));
         }
     }
-    CK(conv_fwd(e, make_geom(B, Hin, T, c.in_channels, Hin, T, F, 3, 3, 3, 1, 1, 0, 1), W + p.xn, nullptr, weff(e->iMain), frag(e->iMain), bias(e->iMain), nullptr, W + p.act[0], amx(nullptr, e->iMain, A.act(0)), s));
+    CK(conv_fwd(e, n.main, W + p.xn, nullptr, weff(e->iMain), frag(e->iMain), bias(e->iMain), nullptr, W + p.act[0], amx(nullptr, e->iMain, A.act(0)), s));
     for (int i = 0; i < R; ++i) {
         if (e->fam.pw_fused) {
             // fused expConv + ReLU + decConv: the 256-channel tensor never leaves the accumulators
-            const long nvox = (long)B * Hin * Hin * T;
-            ProfScope ps(e, e->fam.x6 ? CLS_PW_FWD_X6 : CLS_PW_FWD, (double)nvox * ((double)F * E + (double)E * D), s);
-            CK(pw_forward_launch(e, i, Wpack, A, params, W + p.act[i], W + p.dec[i], nvox, A.dec(i), s));
+            const long nvox = in_voxels(n.exp);
+            ProfScope ps(e, e->fam.x6 ? CLS_PW_FWD_X6 : CLS_PW_FWD, geom_macs(n.exp) + geom_macs(n.dec), s);
+            CK(pw_forward_launch(e, i, dv.wpack, A, params, W + p.act[i], W + p.dec[i], nvox, A.dec(i), s));
         } else {
-            CK(conv_fwd(e, make_geom(B, Hin, T, F, Hin, T, E, 1, 1, 1, 0, 0, 0, 1), W + p.act[i], nullptr, weff(e->iExp[i]), frag(e->iExp[i]), bias(e->iExp[i]), nullptr, W + p.H, Amax(), s));
-            CK(conv_fwd(e, make_geom(B, Hin, T, E, Hin, T, D, 1, 1, 1, 0, 0, 0, 0), W + p.H, nullptr, weff(e->iDec[i]), frag(e->iDec[i]), bias(e->iDec[i]), nullptr, W + p.dec[i], amx(nullptr, e->iDec[i], A.dec(i)), s));
+            CK(conv_fwd(e, n.exp, W + p.act[i], nullptr, weff(e->iExp[i]), frag(e->iExp[i]), bias(e->iExp[i]), nullptr, W + p.H, Amax(), s));
+            CK(conv_fwd(e, n.dec, W + p.H, nullptr, weff(e->iDec[i]), frag(e->iDec[i]), bias(e->iDec[i]), nullptr, W + p.dec[i], amx(nullptr, e->iDec[i], A.dec(i)), s));
         }
-        CK(conv_fwd(e, make_geom(B, Hin, T, D, Hin, T, F, 3, 3, 3, 1, 1, 0, 0), W + p.dec[i], nullptr, weff(e->iNorm[i]), frag(e->iNorm[i]), bias(e->iNorm[i]), W + p.act[i], W + p.act[i + 1], amx(A.dec(i), e->iNorm[i], A.act(i + 1)), s));
+        CK(conv_fwd(e, n.norm, W + p.dec[i], nullptr, weff(e->iNorm[i]), frag(e->iNorm[i]), bias(e->iNorm[i]), W + p.act[i], W + p.act[i + 1], amx(A.dec(i), e->iNorm[i], A.act(i + 1)), s));
     }
     const float* cur = W + p.act[R];
     const unsigned* acur = A.act(R);
-    int h = Hin, t = T;
-    for (size_t k = 0; k < e->iRed.size(); ++k) {
-        CK(conv_fwd(e, red_geom(e, B, k, h, t, F), cur, nullptr,
-                    weff(e->iRed[k]), frag(e->iRed[k]), bias(e->iRed[k]), nullptr, W + p.red[k], amx(acur, e->iRed[k], A.red((int)k)), s));
-        cur = W + p.red[k]; acur = A.red((int)k); h = p.redH[k]; t = p.redT[k];
+    for (size_t k = 0; k < n.red.size(); ++k) {
+        CK(conv_fwd(e, n.red[k], cur, nullptr, weff(e->iRed[k]), frag(e->iRed[k]), bias(e->iRed[k]), nullptr, W + p.red[k], amx(acur, e->iRed[k], A.red((int)k)), s));
+        cur = W + p.red[k]; acur = A.red((int)k);
     }
-    CK(conv_fwd(e, make_geom(B, h, t, F, P, 1, s2, 3, 3, 3, 0, 0, 0, 0), cur, nullptr, weff(e->iUp), frag(e->iUp), bias(e->iUp), nullptr, W + p.up, amx(acur, e->iUp, nullptr), s));
+    CK(conv_fwd(e, n.up, cur, nullptr, weff(e->iUp), frag(e->iUp), bias(e->iUp), nullptr, W + p.up, amx(acur, e->iUp, nullptr), s));
     CK(reduce_join(s));                                                       // the residual path has arrived
-    CK(tail_forward(W + p.up, W + p.r3, y, B, P, c.scale, c.mean, c.std, s));
+    CK(tail_forward(W + p.up, W + p.r3, y, B, n.up.Ho, c.scale, c.mean, c.std, s));
     return PROBAV_OK;
 }
 
@@ -854,21 +878,21 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     CK(device_tables(e));
     const float* W = (const float*)ws;
     float* S = scratch ? (float*)scratch : const_cast<float*>(W) + p.fwd_total;
-    const WcPlan wc = make_wc_plan(e);
-    const float* Wweff = WC ? WC + wc.weff : W + p.weff;
-    const float* WweffT = WC ? WC + wc.weffT : W + p.weffT;
-    const float* Winvn = WC ? WC + wc.invn : W + p.invn;
-    const float* Wpack = WC ? WC + wc.wpack : W + p.wpack;
-    const probav_net_cfg& c = e->cfg;
-    const int F = c.num_filters, E = F * c.exp_rate, D = c.dec_channels, T = c.num_img_lr, R = c.num_res_blocks;
-    const int Hin = e->Hin, P = c.patch_size_lr, s2 = c.scale * c.scale;
-    auto weffT = [&](int li) { return WweffT + e->layers[li].wn.w_off; };
-    auto fragT = [&](int li) { return frags(e, Wpack, li, 1); };
+    const Net& n = p.net;
+    const Derived dv = derived(e, p, W, WC);
+    const int R = e->cfg.num_res_blocks;
+    auto weff = [&](int li) { return dv.weff + e->layers[li].wn.w_off; };
+    auto weffT = [&](int li) { return dv.weffT + e->layers[li].wn.w_off; };
+    auto fragT = [&](int li) { return frags(e, dv.wpack, li, 1); };
     // amax slots of the gradient tensors, in launch order (the forward pass left those of the weights and activations)
     const bool h3 = e->fam.arith == 2;
-    const AmaxSlots A(e, p, W, R, WC ? reinterpret_cast<unsigned*>(const_cast<float*>(WC + wc.amax)) : nullptr, S);
+    const AmaxSlots A(e, p, W, dv.wslots, S);
     int nback = 0;
-    auto new_slot = [&]() -> unsigned* { return h3 ? A.back(nback++) : nullptr; };
+    auto new_slot = [&](unsigned*& slot) -> int {
+        if (h3 && nback >= p.n_back) { set_error("probav_backward: the pass takes more per-sample amax slots than make_plan counted", hipSuccess); return PROBAV_EINVAL; }
+        slot = h3 ? A.back(nback++) : nullptr;
+        return PROBAV_OK;
+    };
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wrow(li); m.y = ay; } return m; };   // backward-data: the matrix' columns are the layer's INPUT channels
     if (e->fwd_unfused != !e->fam.pw_fused) {
         set_error("probav_backward: the kernel family changed between forward and backward in a way that changes the workspace layout (impl 0 <-> >= 1)", hipSuccess);
@@ -881,54 +905,45 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     // (the reverse pass's per-sample amax slots are cleared by tail_bwd_kernel, its first launch)
     auto dweff = [&](int li) { return S + p.dweff2 + e->layers[li].wn.w_off; };
     auto dbias = [&](int li) { return grads + e->layers[li].wn.b_off; };
-    // the slab regions of the backward-filter launches, in the plan's order (past its end: none, and the launch that asks fails)
-    size_t npart = 0;
-    auto next_part = [&]() -> Slab {
-        const size_t k = npart++;
-        return k < p.parts.size() ? Slab{S + p.partial + p.parts[k].off, p.parts[k].floats} : Slab{nullptr, 0};
-    };
+    auto slab = [&](const Plan::Region& r) { return slab_at(p, S, r); };
     // (defer: the slab sums and the small launches that only the weight-norm backward waits for are queued and leave in a few flushes -- one event record
     // on the launch stream per flush instead of one per launch, probav_common.h)
     SideGuard side_guard((side_stream_disabled() || e->side_mode == 0) ? nullptr : engine_side(e), s, 1);
 
-    CK(tail_backward(dy, S + p.dtail, B, P, c.scale, c.std, s, h3 ? A.back(0) : nullptr, h3 ? p.n_amax - p.amax_bwd : 0));
+    CK(tail_backward(dy, S + p.dtail, B, n.up.Ho, e->cfg.scale, e->cfg.std, s, h3 ? A.back(0) : nullptr, h3 ? p.n_amax - p.amax_bwd : 0));
     // low-frequency residual path (models/modelsTF.py:45-53), last layer first: beside the main chain, nothing below depends on it until the weight-norm
-    // backward -- queued (its slab regions are taken now, in the plan's launch order) and launched at the first flush, when the launch stream has its next kernels
+    // backward -- queued and launched at the first flush, when the launch stream has its next kernels
     {
-        const Slab rp0 = next_part(), rp1 = next_part(), rp2 = next_part();
-        // (the queued launch runs later, from reduce_flush: everything it needs is captured BY VALUE -- pointers and extents, nothing of this frame)
+        const Slab rp3 = slab(p.slab.resid3), rp2 = slab(p.slab.resid2), rp1 = slab(p.slab.resid1);
+        // (the queued launch runs later, from reduce_flush: everything it needs is captured BY VALUE -- pointers, geometries and extents, nothing of this frame)
+        const ConvGeom g3 = n.resid3, g2 = n.resid2, g1 = n.resid1;
         const float *r2 = W + p.r2, *r1 = W + p.r1, *mn = W + p.mn, *wT3 = weffT(e->iResid3), *wT2 = weffT(e->iResid2);
         const Frags fT3 = fragT(e->iResid3), fT2 = fragT(e->iResid2);
         float *dtail = S + p.dtail, *dr2 = S + p.dr2, *dr1 = S + p.dr1;
         float *dw3 = dweff(e->iResid3), *db3 = dbias(e->iResid3), *dw2 = dweff(e->iResid2), *db2 = dbias(e->iResid2), *dw1 = dweff(e->iResid1), *db1 = dbias(e->iResid1);
-        const int inch = c.in_channels;
-        const float *w2r = Wweff + e->layers[e->iResid2].wn.w_off, *w3r = Wweff + e->layers[e->iResid3].wn.w_off;
+        const float *w2r = weff(e->iResid2), *w3r = weff(e->iResid3);
         if (resid_path_fused(e)) {
-            CK(slab_fits(rp0, resid_path_slab_floats(B, inch)));
-            CK(reduce_later(s, [=](hipStream_t rs) -> int {    // one launch + one slab sum (rp0 holds the patches' slabs: make_plan sized it)
-                return resid_path_backward(B, Hin, inch, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp0.p, rs); }));
+            CK(slab_fits(rp3, resid_path_slab_floats(B, g1.Cin)));
+            CK(reduce_later(s, [=](hipStream_t rs) -> int {    // one launch + one slab sum (residConv3's region holds the patches' slabs: make_plan sized it)
+                return resid_path_backward(B, g1.Hi, g1.Cin, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp3.p, rs); }));
         } else
         CK(reduce_later(s, [=](hipStream_t rs) -> int {
-            const ConvGeom g3 = make_geom(B, Hin - 4, 1, s2, P, 1, s2, 3, 3, 1, 0, 0, 0, 0);
-            CK(conv_wgrad(e, g3, r2, dtail, nullptr, dw3, db3, rp0, Amax(), rs));
+            CK(conv_wgrad(e, g3, r2, dtail, nullptr, dw3, db3, rp3, Amax(), rs));
             CK(conv_fwd(e, bwd_data_geom(g3), dtail, nullptr, wT3, fT3, nullptr, nullptr, dr2, Amax(), rs));
-            const ConvGeom g2 = make_geom(B, Hin - 2, 1, s2, Hin - 4, 1, s2, 3, 3, 1, 0, 0, 0, 0);
-            CK(conv_wgrad(e, g2, r1, dr2, nullptr, dw2, db2, rp1, Amax(), rs));
+            CK(conv_wgrad(e, g2, r1, dr2, nullptr, dw2, db2, rp2, Amax(), rs));
             CK(conv_fwd(e, bwd_data_geom(g2), dr2, nullptr, wT2, fT2, nullptr, nullptr, dr1, Amax(), rs));
-            const ConvGeom g1 = make_geom(B, Hin, 1, inch, Hin - 2, 1, s2, 3, 3, 1, 0, 0, 0, 1);
-            CK(conv_wgrad(e, g1, mn, dr1, r1, dw1, db1, rp2, Amax(), rs));
+            CK(conv_wgrad(e, g1, mn, dr1, r1, dw1, db1, rp1, Amax(), rs));
             return PROBAV_OK;
         }));
     }
     // upscale + reducers (models/modelsTF.py:152-164)
-    const int nred = (int)e->iRed.size();
+    const int nred = (int)n.red.size();
     float* cur = S + p.gA;
     float* oth = S + p.gB;                          // (the unfused block path below ping-pongs between `cur` and this)
-    unsigned* acur = new_slot();                    // amax slot of the tensor `cur` holds
+    unsigned* acur; CK(new_slot(acur));             // amax slot of the tensor `cur` holds
     {
-        const int h = p.redH[nred - 1], t = p.redT[nred - 1];
-        const ConvGeom gu = make_geom(B, h, t, F, P, 1, s2, 3, 3, 3, 0, 0, 0, 0);
-        const Slab up_part = next_part();
+        const ConvGeom gu = n.up;
+        const Slab up_part = slab(p.slab.up);
         const float* const upx = W + p.red[nred - 1];
         float *const updy = S + p.dtail, *const updw = dweff(e->iUp), *const updb = dbias(e->iUp);
         CK(reduce_later(s, [=](hipStream_t rs) -> int {       // (only the weight-norm backward reads it; captured by value: it runs from a later flush)
@@ -936,25 +951,22 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         CK(conv_fwd(e, bwd_data_geom(gu), S + p.dtail, nullptr, weffT(e->iUp), fragT(e->iUp), nullptr, nullptr, cur, amx(nullptr, e->iUp, acur), s));
     }
     for (int k = nred - 1; k >= 0; --k) {
-        const probav_engine::RedSpec& rs = e->redSpec[k];
-        const int refl = rs.refl;
-        const int hi = k ? p.redH[k - 1] : Hin, ti = k ? p.redT[k - 1] : T;
+        const ConvGeom& gr = n.red[k];
         const float* xin = k ? W + p.red[k - 1] : W + p.act[R];
-        const ConvGeom gr = red_geom(e, B, (size_t)k, hi, ti, F);
         // the backward-filter only feeds the weight-norm backward at the very end: side stream; every tensor it reads stays untouched
         // (each stage of the chain writes a buffer of its own)
         { Amax m; if (h3) { m.x = k ? A.red(k - 1) : A.act(R); m.w = acur; }
-          CK(conv_wgrad(e, gr, xin, cur, W + p.red[k], dweff(e->iRed[k]), dbias(e->iRed[k]), next_part(), m, e->side_mode >= 2 ? reduce_fork(s) : s)); }
+          CK(conv_wgrad(e, gr, xin, cur, W + p.red[k], dweff(e->iRed[k]), dbias(e->iRed[k]), slab(p.slab.red[k]), m, e->side_mode >= 2 ? reduce_fork(s) : s)); }
         float* outA = S + p.gred[2 * k];
         float* outB = S + p.gred[2 * k + 1];
-        unsigned* aoth = new_slot();
+        unsigned* aoth; CK(new_slot(aoth));
         CK(conv_fwd(e, bwd_data_geom(gr), cur, W + p.red[k], weffT(e->iRed[k]), fragT(e->iRed[k]), nullptr, nullptr, outA, amx(acur, e->iRed[k], aoth), s));
-        if (refl) {
-            acur = new_slot();                      // the folded gradient is a new tensor
-            if (rs.p == 1 && !rs.refl_t) CK(reflect_fold(outA, outB, B, hi, hi, ti * F, acur, s));
+        if (gr.reflect_hw) {
+            CK(new_slot(acur));                     // the folded gradient is a new tensor
+            if (gr.ph == 1 && !gr.reflect_t) CK(reflect_fold(outA, outB, B, gr.Hi, gr.Wi, gr.Ti * gr.Cin, acur, s));
             else {
-                CK(reflect_fold3(outA, outB, B, hi, hi, ti, F, rs.p, rs.p, rs.refl_t ? rs.pt : 0, s));
-                if (h3) CK(amax_tensor(outB, (size_t)hi * hi * ti * F, B, acur, s));
+                CK(reflect_fold3(outA, outB, B, gr.Hi, gr.Wi, gr.Ti, gr.Cin, gr.ph, gr.pw, gr.reflect_t ? gr.pt : 0, s));
+                if (h3) CK(amax_tensor(outB, in_floats(gr) / B, B, acur, s));
             }
             cur = outB;
         } else {
@@ -963,9 +975,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         }
     }
     // residual blocks (models/modelsTF.py:177-189), last first.  cur = d loss / d act[i+1]
-    const ConvGeom ge = make_geom(B, Hin, T, F, Hin, T, E, 1, 1, 1, 0, 0, 0, 1);
-    const ConvGeom gd = make_geom(B, Hin, T, E, Hin, T, D, 1, 1, 1, 0, 0, 0, 0);
-    const ConvGeom gn = make_geom(B, Hin, T, D, Hin, T, F, 3, 3, 3, 1, 1, 0, 0);
+    const ConvGeom &ge = n.exp, &gd = n.dec, &gn = n.norm;
     CK(reduce_flush(s));                                   // the residual path, the upscale layer's backward-filter, the reducers' slab sums: one fork
     for (int i = R - 1; i >= 0; --i) {
         float* gDec = S + p.gDec;
@@ -976,18 +986,18 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         const bool fusedp = e->fam.pw_fused;
         { Amax m; if (h3) { m.x = A.dec(i); m.w = acur; }
           // (from the second block on, the last thing enqueued on s was the previous block's pointwise backward, whose slab sums forked right behind it)
-          CK(conv_wgrad(e, gn, W + p.dec[i], cur, nullptr, dweff(ln), dbias(ln), next_part(), m,
+          CK(conv_wgrad(e, gn, W + p.dec[i], cur, nullptr, dweff(ln), dbias(ln), slab(p.slab.norm[i]), m,
                         (fusedp && e->side_mode >= 2) ? (i < R - 1 ? reduce_fork_adjacent(s) : reduce_fork(s)) : s)); }
         if (fusedp) oth = S + p.gblk[i];                   // this block's dX goes to its own buffer: `cur` stays intact for the late backward-filter
-        unsigned* agdec = new_slot();
+        unsigned* agdec; CK(new_slot(agdec));
         CK(conv_fwd(e, bwd_data_geom(gn), cur, nullptr, weffT(ln), fragT(ln), nullptr, nullptr, gDec, amx(acur, ln, agdec), s));
         if (fusedp) {
             // fused: H recompute, dH, ReLU gate, dX (+ skip), dW1, dW2, db1, db2 -- nothing 256-wide touches HBM
-            const long nvox = (long)B * Hin * Hin * T;
-            unsigned* anew = new_slot();                     // amax slot of dX
+            const long nvox = in_voxels(ge);
+            unsigned* anew; CK(new_slot(anew));              // amax slot of dX
             {   // (the class's bracket ends HERE: the flush below launches the batched slab sums on this stream, and they are no part of this class)
-            ProfScope ps(e, e->fam.x6 ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, (double)nvox * (2.0 * F * E + 2.0 * E * D), s);   // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work
-            CK(pw_backward_launch(e, i, Wpack, A, params, grads, S + p.dweff2, W + p.act[i], gDec, cur, oth, next_part(), nvox, agdec, anew, s));
+            ProfScope ps(e, e->fam.x6 ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, 2.0 * (geom_macs(ge) + geom_macs(gd)), s);   // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work
+            CK(pw_backward_launch(e, i, dv.wpack, A, params, grads, S + p.dweff2, W + p.act[i], gDec, cur, oth, slab(p.slab.pair[i]), nvox, agdec, anew, s));
             }
             float* tmp2 = cur; cur = oth; oth = tmp2;
             acur = anew;
@@ -997,13 +1007,13 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
             continue;
         }
         // recompute H = relu(expConv_i(act[i])): the 256-channel tensor is never kept (1 KB/voxel/block)
-        CK(conv_fwd(e, ge, W + p.act[i], nullptr, Wweff + e->layers[le].wn.w_off, Frags(), params + e->layers[le].wn.b_off, nullptr, Hbuf, Amax(), s));
+        CK(conv_fwd(e, ge, W + p.act[i], nullptr, weff(le), Frags(), params + e->layers[le].wn.b_off, nullptr, Hbuf, Amax(), s));
         // decConv_i
-        CK(conv_wgrad(e, gd, Hbuf, gDec, nullptr, dweff(ld), dbias(ld), next_part(), Amax(), s));
+        CK(conv_wgrad(e, gd, Hbuf, gDec, nullptr, dweff(ld), dbias(ld), slab(p.slab.dec[i]), Amax(), s));
         CK(conv_fwd(e, bwd_data_geom(gd), gDec, nullptr, weffT(ld), fragT(ld), nullptr, nullptr, dH, Amax(), s));
         // expConv_i: ReLU gate (H > 0) applied where dH is consumed; skip path adds d loss/d act[i+1]
-        CK(conv_wgrad(e, ge, W + p.act[i], dH, Hbuf, dweff(le), dbias(le), next_part(), Amax(), s));
-        unsigned* aoth = new_slot();
+        CK(conv_wgrad(e, ge, W + p.act[i], dH, Hbuf, dweff(le), dbias(le), slab(p.slab.exp[i]), Amax(), s));
+        unsigned* aoth; CK(new_slot(aoth));
         CK(conv_fwd(e, bwd_data_geom(ge), dH, Hbuf, weffT(le), fragT(le), nullptr, cur, oth, amx(nullptr, le, aoth), s));
         float* tmp = cur; cur = oth; oth = tmp;
         acur = aoth;
@@ -1014,14 +1024,12 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     {
         ReduceSide* const ctx = side_guard.c;
         reduce_side_activate(nullptr);
-        const int rc = conv_wgrad(e, make_geom(B, Hin, T, c.in_channels, Hin, T, F, 3, 3, 3, 1, 1, 0, 1), W + p.xn, cur, W + p.act[0],
-                                  dweff(e->iMain), dbias(e->iMain), next_part(), Amax(), s);
+        const int rc = conv_wgrad(e, n.main, W + p.xn, cur, W + p.act[0], dweff(e->iMain), dbias(e->iMain), slab(p.slab.main), Amax(), s);
         reduce_side_activate(ctx);
         if (rc) return rc;
     }
-    if (npart != p.parts.size()) { set_error("probav_backward: the pass used fewer slab regions than make_plan laid out", hipSuccess); return PROBAV_EINVAL; }
     CK(reduce_join(s));                                                       // every slab sum has landed in dweff / the bias gradients
-    { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_backward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, params, S + p.dweff2, Winvn, grads, s)); }
+    { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_backward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, params, S + p.dweff2, dv.invn, grads, s)); }
     return PROBAV_OK;
 }
 
@@ -1053,63 +1061,56 @@ int probav_backward_wc(probav_engine* e, const float* params, const float* dy, f
 
 size_t probav_weight_cache_bytes(const probav_engine* e) { return e ? make_wc_plan(e).total * sizeof(float) : 0; }
 
-int probav_optimizer_step_fused(probav_engine* e, float* params, const float* grads, float* m, float* v, float lr, float beta1, float beta2,
-                                float eps, float c_g, float c_m, float c_v, void* wcache, size_t wcache_bytes, void* stream)
+// The one writer of a weight cache: checks, layout, device tables, amax reset, the launch `fill(wc, C, wam, s)` that writes the effective weights, inverse
+// norms and amax slots into the cache C, and the operand packing behind it.  `who`: the entry point's name, for its error messages
+static int write_weight_cache(probav_engine* e, const char* who, bool args_ok, void* wcache, size_t wcache_bytes, void* stream,
+                              const std::function<int(const WcPlan&, float*, unsigned*, hipStream_t)>& fill)
 {
-    if (!e || !params || !grads || !m || !v || !wcache) { set_error("probav_optimizer_step_fused: null argument", hipSuccess); return PROBAV_EINVAL; }
+    const std::string name(who);
+    if (!args_ok) { set_error((name + ": null argument").c_str(), hipSuccess); return PROBAV_EINVAL; }
     const WcPlan wc = make_wc_plan(e);
-    if (wcache_bytes < wc.total * sizeof(float)) { set_error("probav_optimizer_step_fused: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
+    if (wcache_bytes < wc.total * sizeof(float)) { set_error((name + ": weight cache too small").c_str(), hipSuccess); return PROBAV_ENOSPACE; }
     CK(device_tables(e));
     hipStream_t s = (hipStream_t)stream;
     float* C = (float*)wcache;
     unsigned* wam = reinterpret_cast<unsigned*>(C + wc.amax);
-    if (hipMemsetAsync(wam, 0, (size_t)wc.n_wamax * sizeof(unsigned), s) != hipSuccess) { set_error("probav_optimizer_step_fused: amax reset", hipGetLastError()); return PROBAV_EHIP; }
-    // one launch: the update of all 132 tensors + the weight normalisation of the updated parameters (+ the per-row maxima and the operand
-    // packing of the next pass behind it): the next probav_forward_wc starts at the head kernel
-    { ProfScope ps(e, CLS_WN, 0.0, s);
-      CK(optimizer_wn_step(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, grads, m, v, lr, beta1, beta2, eps, c_g, c_m, c_v,
-                           C + wc.weff, C + wc.weffT, C + wc.invn, wam, s)); }
+    if (hipMemsetAsync(wam, 0, (size_t)wc.n_wamax * sizeof(unsigned), s) != hipSuccess) { set_error((name + ": amax reset").c_str(), hipGetLastError()); return PROBAV_EHIP; }
+    { ProfScope ps(e, CLS_WN, 0.0, s); CK(fill(wc, C, wam, s)); }
     if (!e->jobs.empty()) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), C + wc.weff, C + wc.weffT, C + wc.wpack, wam, s)); }
     return PROBAV_OK;
+}
+
+int probav_optimizer_step_fused(probav_engine* e, float* params, const float* grads, float* m, float* v, float lr, float beta1, float beta2,
+                                float eps, float c_g, float c_m, float c_v, void* wcache, size_t wcache_bytes, void* stream)
+{
+    // one launch: the update of all 132 tensors + the weight normalisation of the updated parameters (+ the per-row maxima and the operand
+    // packing of the next pass behind it): the next probav_forward_wc starts at the head kernel
+    return write_weight_cache(e, "probav_optimizer_step_fused", e && params && grads && m && v && wcache, wcache, wcache_bytes, stream,
+        [&](const WcPlan& wc, float* C, unsigned* wam, hipStream_t s) {
+            return optimizer_wn_step(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, grads, m, v, lr, beta1, beta2, eps, c_g, c_m, c_v,
+                                     C + wc.weff, C + wc.weffT, C + wc.invn, wam, s); });
 }
 
 int probav_optimizer_step_fused_guarded(probav_engine* e, float* params, const float* grads, float* m, float* v, float lr, float beta1, float beta2,
                                         float eps, float c_g, float c_m, float c_v, void* wcache, size_t wcache_bytes, float* ema, float ema_momentum,
                                         const probav_guard_ctl* ctl, void* stream)
 {
-    if (!e || !params || !grads || !m || !v || !wcache) { set_error("probav_optimizer_step_fused_guarded: null argument", hipSuccess); return PROBAV_EINVAL; }
-    if (ema && !(ema_momentum >= 0.f && ema_momentum <= 1.f)) { set_error("probav_optimizer_step_fused_guarded: ema_momentum outside [0, 1]", hipSuccess); return PROBAV_EINVAL; }
-    const WcPlan wc = make_wc_plan(e);
-    if (wcache_bytes < wc.total * sizeof(float)) { set_error("probav_optimizer_step_fused_guarded: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
-    CK(device_tables(e));
-    hipStream_t s = (hipStream_t)stream;
-    float* C = (float*)wcache;
-    unsigned* wam = reinterpret_cast<unsigned*>(C + wc.amax);
-    if (hipMemsetAsync(wam, 0, (size_t)wc.n_wamax * sizeof(unsigned), s) != hipSuccess) { set_error("probav_optimizer_step_fused_guarded: amax reset", hipGetLastError()); return PROBAV_EHIP; }
+    const bool args_ok = e && params && grads && m && v && wcache;
+    if (args_ok && ema && !(ema_momentum >= 0.f && ema_momentum <= 1.f)) { set_error("probav_optimizer_step_fused_guarded: ema_momentum outside [0, 1]", hipSuccess); return PROBAV_EINVAL; }
     // probav_optimizer_step_fused with the control block and the EMA buffer handed to the update half; on a skipped step the same launches rebuild the
     // cache of the unchanged parameters
-    { ProfScope ps(e, CLS_WN, 0.0, s);
-      CK(optimizer_wn_step_guarded(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, grads, m, v, lr, beta1, beta2, eps, c_g, c_m, c_v,
-                                   C + wc.weff, C + wc.weffT, C + wc.invn, wam, ema, ema_momentum, ctl, s)); }
-    if (!e->jobs.empty()) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), C + wc.weff, C + wc.weffT, C + wc.wpack, wam, s)); }
-    return PROBAV_OK;
+    return write_weight_cache(e, "probav_optimizer_step_fused_guarded", args_ok, wcache, wcache_bytes, stream,
+        [&](const WcPlan& wc, float* C, unsigned* wam, hipStream_t s) {
+            return optimizer_wn_step_guarded(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, grads, m, v, lr, beta1, beta2, eps, c_g, c_m, c_v,
+                                             C + wc.weff, C + wc.weffT, C + wc.invn, wam, ema, ema_momentum, ctl, s); });
 }
 
 int probav_weight_cache_build(probav_engine* e, const float* params, void* wcache, size_t wcache_bytes, void* stream)
 {
-    if (!e || !params || !wcache) { set_error("probav_weight_cache_build: null argument", hipSuccess); return PROBAV_EINVAL; }
-    const WcPlan wc = make_wc_plan(e);
-    if (wcache_bytes < wc.total * sizeof(float)) { set_error("probav_weight_cache_build: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
-    CK(device_tables(e));
-    hipStream_t s = (hipStream_t)stream;
-    float* C = (float*)wcache;
-    unsigned* wam = reinterpret_cast<unsigned*>(C + wc.amax);
-    if (hipMemsetAsync(wam, 0, (size_t)wc.n_wamax * sizeof(unsigned), s) != hipSuccess) { set_error("probav_weight_cache_build: amax reset", hipGetLastError()); return PROBAV_EHIP; }
     // exactly what a forward pass without a cache does first: weight normalisation (+ per-column / per-row maxima) and operand packing
-    { ProfScope ps(e, CLS_WN, 0.0, s);
-      CK(wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, C + wc.weff, C + wc.weffT, C + wc.invn, wam, s)); }
-    if (!e->jobs.empty()) { ProfScope ps(e, CLS_WN, 0.0, s); CK(mfma_pack(e->d_jobs, (int)e->jobs.size(), C + wc.weff, C + wc.weffT, C + wc.wpack, wam, s)); }
-    return PROBAV_OK;
+    return write_weight_cache(e, "probav_weight_cache_build", e && params && wcache, wcache, wcache_bytes, stream,
+        [&](const WcPlan& wc, float* C, unsigned* wam, hipStream_t s) {
+            return wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, C + wc.weff, C + wc.weffT, C + wc.invn, wam, s); });
 }
 
 // ---- introspection (parity tests) -----------------------------------------------------------------
@@ -1117,15 +1118,13 @@ int probav_workspace_view(const probav_engine* e, int batch, int training, int k
 {
     if (!e || batch < 1 || !offset_floats || !count) { set_error("probav_workspace_view: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
     const Plan p = make_plan(e, batch, training);
-    const probav_net_cfg& c = e->cfg;
-    const int64_t V = (int64_t)batch * e->Hin * e->Hin * c.num_img_lr;
-    const int R = c.num_res_blocks, nred = (int)e->iRed.size(), s2 = c.scale * c.scale;
+    const Net& n = p.net;
+    const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
     switch (kind) {
-    case PROBAV_VIEW_ACT: if (index < 0 || index > R) break; *offset_floats = (int64_t)p.act[index]; *count = V * c.num_filters; return PROBAV_OK;
-    case PROBAV_VIEW_DEC: if (index < 0 || index >= R) break; *offset_floats = (int64_t)p.dec[index]; *count = V * c.dec_channels; return PROBAV_OK;
-    case PROBAV_VIEW_RED: if (index < 0 || index >= nred) break;
-        *offset_floats = (int64_t)p.red[index]; *count = (int64_t)batch * p.redH[index] * p.redH[index] * p.redT[index] * c.num_filters; return PROBAV_OK;
-    case PROBAV_VIEW_RESID1: if (index != 0) break; *offset_floats = (int64_t)p.r1; *count = (int64_t)batch * (e->Hin - 2) * (e->Hin - 2) * s2; return PROBAV_OK;
+    case PROBAV_VIEW_ACT: if (index < 0 || index > R) break; *offset_floats = (int64_t)p.act[index]; *count = (int64_t)out_floats(n.main); return PROBAV_OK;
+    case PROBAV_VIEW_DEC: if (index < 0 || index >= R) break; *offset_floats = (int64_t)p.dec[index]; *count = (int64_t)out_floats(n.dec); return PROBAV_OK;
+    case PROBAV_VIEW_RED: if (index < 0 || index >= nred) break; *offset_floats = (int64_t)p.red[index]; *count = (int64_t)out_floats(n.red[index]); return PROBAV_OK;
+    case PROBAV_VIEW_RESID1: if (index != 0) break; *offset_floats = (int64_t)p.r1; *count = (int64_t)out_floats(n.resid1); return PROBAV_OK;
     default: break;
     }
     set_error("probav_workspace_view: no such tensor", hipSuccess);
@@ -1139,16 +1138,11 @@ int probav_debug_hidden(probav_engine* e, const float* params, const void* ws, s
     const Plan p = make_plan(e, B, 1);
     if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_debug_hidden: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
     const float* W = (const float*)ws;
-    const probav_net_cfg& c = e->cfg;
-    const int R = c.num_res_blocks;
-    const long nvox = (long)B * e->Hin * e->Hin * c.num_img_lr;
-    const WcPlan wc = make_wc_plan(e);
-    const float* WC = (const float*)wcache;                           // the forward pass ran from the weight cache: its fragments and weight slots live there
-    const float* Wpack = WC ? WC + wc.wpack : W + p.wpack;
-    const AmaxSlots A(e, p, W, R, WC ? reinterpret_cast<unsigned*>(const_cast<float*>(WC + wc.amax)) : nullptr);
+    const Derived dv = derived(e, p, W, (const float*)wcache);        // (the forward pass ran from the weight cache: its fragments and weight slots live there)
+    const AmaxSlots A(e, p, W, dv.wslots);
     // the forward launch of block i again, into the caller's scratch output (the saved state is only read), with the hidden tile written out;
     // no amax report (the slots of the saved tensors stay as the forward pass left them)
-    return pw_forward_launch(e, block, Wpack, A, params, W + p.act[block], dec_scratch, nvox, nullptr, (hipStream_t)stream, hidden);
+    return pw_forward_launch(e, block, dv.wpack, A, params, W + p.act[block], dec_scratch, in_voxels(p.net.exp), nullptr, (hipStream_t)stream, hidden);
 }
 
 int probav_debug_hidden_from_forward_kernel(int on) { x6_pw_dump_from_forward_kernel(on); return PROBAV_OK; }
