@@ -315,6 +315,21 @@ int probav_prep_xcorr_surface(const uint16_t* pair, float* spec_scratch, float* 
  *                                         replaces the pad + generatePatches of utils/dataGenerator.py:107-171, 553-596 */
 int probav_prep_patches(const float* frames, const uint8_t* masks, int S, int T, int H, int W, int pad, int win, int stride, float* patches,
                         uint8_t* patch_masks, int32_t* counts, void* stream);
+/* Cloud-aware registration (csrc/kernels_prep_masked.hip): every 128 x 128 uint16 frame against its set's reference frame by a masked
+ * normalised correlation over the window [-window, window]^2 of integer shifts, 1 <= window <= 32 (otherwise PROBAV_EINVAL, nothing
+ * launched).  For a shift s, over the pixels p that are clear in the reference and whose source p - s lies inside the frame and is clear
+ * in the frame (nothing wraps): the exact integer moments n, Sa, Sb, Saa, Sbb, Sab of a = ref[p], b = frame[p - s], num = n Sab - Sa Sb,
+ * da = n Saa - Sa^2, db = n Sbb - Sb^2 (int64, all below 2^61) and v = double(num) / sqrt(double(da) * double(db)) in four correctly
+ * rounded fp64 operations.  A shift is a candidate when 10 n >= 3 max_s n, da > 0 and db > 0; the largest v wins, ties to the first shift
+ * with dy outer, both ascending.  shifts [n_frames][2] = (dy, dx); registered [n_frames] = 1, or 0 where no shift is a candidate (then the
+ * shift is (0, 0)).  out_frames[p] = frame[reflect(p - s)] (scipy.ndimage 'reflect': d c b a | a b c d), out_masks[p] = (mask[p - s] != 0)
+ * inside the frame and 0 outside, out_counts = its count of ones.  A set's reference frame is copied through (shift 0, registered 1).
+ * Preconditions and their PROBAV_PREP_BAD_SHIFT marking as probav_prep_register; no scratch.  The statement the kernel equals bit for bit:
+ * probav_amd.prep.register_masked_numpy.
+ *                                         the counterpart of registerFrame(tech='time')                utils/dataGenerator.py:663-666 */
+int probav_prep_register_masked(const uint16_t* frames, const uint8_t* masks, const int64_t* set_offsets, int n_sets, int64_t n_frames,
+                                const int32_t* ref_frame, int window, int32_t* shifts, uint8_t* registered, uint16_t* out_frames,
+                                uint8_t* out_masks, int32_t* out_counts, void* stream);
 
 /* ---- scoring (evaluate.py; proba-v_amd/scoring.py), additions of ABI 7 ------------------------------------------------------------- */
 /* The ESA PROBA-V shift-compensated clear PSNR of whole images; it replaces the reference's unfinished evaluate.py:76-87, which calls

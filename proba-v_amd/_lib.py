@@ -93,6 +93,9 @@ SIGNATURES = {
     "probav_prep_register": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "probav_prep_xcorr_surface": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "probav_prep_patches": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_void_p]),
+    # cloud-aware registration (csrc/kernels_prep_masked.hip): added under ABI 7
+    "probav_prep_register_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
     # scoring (csrc/kernels_score.hip)
     "probav_score_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "probav_score_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

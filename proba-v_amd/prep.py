@@ -13,7 +13,11 @@ Deliberate differences ('From the ESA download to train.py'):
   - masks are booleans: a nonzero QM / SM pixel is clear;
   - randomness is drawn from the `rng` that main() threads through (a numpy.random.RandomState; None = numpy's global state, as the
     reference), in the reference's call order;
-  - splitPatches restates sklearn's train_test_split(test_size=split, random_state=17) without sklearn.
+  - splitPatches restates sklearn's train_test_split(test_size=split, random_state=17) without sklearn;
+  - registerFrame(tech='time'), the reference's cloud-aware registration (utils/dataGenerator.py:663-666), is a masked normalised
+    correlation over a bounded window of integer shifts with a shift that does not wrap: `register_masked_numpy` is its statement,
+    csrc/kernels_prep_masked.hip the kernel that equals it bit for bit.  Selected by registerImages(tech='time') /
+    main(register='masked'); the default ('freq') is the plain path above, unchanged.
 """
 import glob
 import logging
@@ -26,6 +30,9 @@ from . import pngio
 
 LR_SIZE = 128          # registration geometry (PROBA-V LR frames)
 PREP_BAD_SHIFT = -2 ** 31   # PROBAV_PREP_BAD_SHIFT
+MASKED_MAX_WINDOW = 32      # largest window of the masked registration (csrc/kernels_prep_masked.hip)
+REGISTER_TECHS = ('freq', 'time')                        # registerFrame's `tech`, the reference's names
+REGISTER_MODES = {'freq': 'freq', 'masked': 'time'}      # main()'s `register` / the CLI's --register -> tech
 
 
 # ---- device helpers ----------------------------------------------------------------------------------------------------------------
@@ -92,6 +99,123 @@ def device_register(frames, masks, set_offsets, ref_frame):
         raise ValueError("probav_prep_register: set_offsets / ref_frame break the preconditions of include/probav_hip.h (empty set or a "
                          "reference outside its set)")
     return sh, rf.cpu().numpy(), rm.cpu().numpy().astype(bool), rc.cpu().numpy()
+
+
+def _check_window(window):
+    if isinstance(window, bool) or int(window) != window or not 1 <= int(window) <= MASKED_MAX_WINDOW:
+        raise ValueError("masked registration takes a window of 1..%d shifts, got %r" % (MASKED_MAX_WINDOW, window))
+    return int(window)
+
+
+def _check_tech(tech):
+    if tech not in REGISTER_TECHS:
+        raise ValueError("tech must be one of %r, got %r" % (REGISTER_TECHS, tech))
+    return tech
+
+
+def shift_masked_numpy(img, img_clear, shift):
+    """The masked registration's way of applying an integer shift s: out[p] = img[reflect(p - s)] with scipy.ndimage's 'reflect'
+    (d c b a | a b c d), exact uint16; clear_out[p] = img_clear[p - s] inside the frame, False outside.  The reference's
+    shift(img, s, mode='reflect') / shift(msk, s, mode='constant', cval=0) for integer s, without the spline's ringing on the mask."""
+    img, clear = np.asarray(img), np.asarray(img_clear) != 0
+    H, W = img.shape
+    dy, dx = int(shift[0]), int(shift[1])
+    if max(abs(dy), abs(dx)) >= min(H, W):
+        raise ValueError("shift %r does not fit a %d x %d frame" % ((dy, dx), H, W))
+    yy, xx = np.arange(H) - dy, np.arange(W) - dx
+    fold = lambda i, n: np.where(i < 0, -i - 1, np.where(i >= n, 2 * n - 1 - i, i))
+    out = img[fold(yy, H)[:, None], fold(xx, W)[None, :]]
+    inside = ((yy >= 0) & (yy < H))[:, None] & ((xx >= 0) & (xx < W))[None, :]
+    return out, clear[fold(yy, H)[:, None], fold(xx, W)[None, :]] & inside
+
+
+def register_masked_numpy(ref, img, ref_clear, img_clear, window):
+    """THE statement of the masked registration (csrc/kernels_prep_masked.hip equals it bit for bit).  ref, img uint16 [128,128], their
+    clear masks, window R in 1..32 -> ((dy, dx), registered, shifted frame uint16, shifted clear mask bool).
+
+    For every shift s = (dy, dx) in [-R, R]^2, dy outer, both ascending: over m = ref_clear & clear_s (clear_s[p] = img_clear[p - s]
+    inside the frame, False outside: nothing wraps), with a = ref and b[p] = img[p - s], the exact integer moments n, Sa, Sb, Saa, Sbb, Sab
+    (int64: a, b < 2^16 and n <= 2^14 keep every moment, product and difference below 2^61);
+        num = n Sab - Sa Sb,  da = n Saa - Sa^2,  db = n Sbb - Sb^2,    v = float64(num) / sqrt(float64(da) * float64(db)).
+    A shift is a candidate when 10 n >= 3 max n (skimage's overlap_ratio = 3/10, over the window) and da > 0 and db > 0.  The largest v
+    wins, ties to the first shift visited; without a candidate the shift is (0, 0) and registered is 0.  The frame is then shifted by
+    `shift_masked_numpy`."""
+    R = _check_window(window)
+    ref, img = np.asarray(ref), np.asarray(img)
+    if ref.shape != (LR_SIZE, LR_SIZE) or img.shape != ref.shape or np.shape(ref_clear) != ref.shape or np.shape(img_clear) != ref.shape:
+        raise ValueError("masked registration takes %d x %d frames and masks" % (LR_SIZE, LR_SIZE))
+    rc, ic = np.asarray(ref_clear) != 0, np.asarray(img_clear) != 0
+    a, b = ref.astype(np.int64) * rc, img.astype(np.int64) * ic          # zero where their own mask is: Sab needs no mask
+    aa, bb = a * a, b * b
+    rc8, ic8 = rc.astype(np.int64), ic.astype(np.int64)
+    N, Wd = LR_SIZE, 2 * R + 1
+    mom = np.zeros((6, Wd * Wd), np.int64)
+    for i in range(Wd * Wd):
+        dy, dx = i // Wd - R, i % Wd - R
+        P = (slice(max(0, dy), min(N, N + dy)), slice(max(0, dx), min(N, N + dx)))          # p with p - s inside the frame
+        Q = (slice(max(0, -dy), min(N, N - dy)), slice(max(0, -dx), min(N, N - dx)))        # p - s
+        mr, ms = rc8[P], ic8[Q]
+        mom[:, i] = ((mr * ms).sum(), (a[P] * ms).sum(), (b[Q] * mr).sum(), (aa[P] * ms).sum(), (bb[Q] * mr).sum(), (a[P] * b[Q]).sum())
+    n, Sa, Sb, Saa, Sbb, Sab = mom
+    num, da, db = n * Sab - Sa * Sb, n * Saa - Sa * Sa, n * Sbb - Sb * Sb
+    cand = (10 * n >= 3 * n.max()) & (da > 0) & (db > 0)
+    if cand.any():
+        v = np.full(Wd * Wd, -np.inf)
+        v[cand] = num[cand].astype(np.float64) / np.sqrt(da[cand].astype(np.float64) * db[cand].astype(np.float64))
+        i = int(np.argmax(v))                              # the first of the largest
+        shift, registered = (i // Wd - R, i % Wd - R), 1
+    else:
+        shift, registered = (0, 0), 0
+    out, clear = shift_masked_numpy(img, ic, shift)
+    return shift, registered, out, clear
+
+
+def register_masked_sets_numpy(frames, masks, set_offsets, ref_frame, window):
+    """`register_masked_numpy` over sets, what `device_register_masked` returns: every frame against ref_frame[its set]; the reference
+    frames themselves are copied through with shift (0, 0) and registered = 1."""
+    frames, clear = np.asarray(frames), np.asarray(masks) != 0
+    F = len(frames)
+    shifts, reg = np.zeros((F, 2), np.int32), np.ones(F, np.uint8)
+    of, om = frames.astype(np.uint16), clear.copy()
+    for s in range(len(set_offsets) - 1):
+        r = int(ref_frame[s])
+        for f in range(int(set_offsets[s]), int(set_offsets[s + 1])):
+            if f != r:
+                shifts[f], reg[f], of[f], om[f] = register_masked_numpy(frames[r], frames[f], clear[r], clear[f], window)
+    return shifts, reg, of, om, om.reshape(F, -1).sum(1).astype(np.int32)
+
+
+def device_register_masked(frames, masks, set_offsets, ref_frame, window):
+    """The masked registration on the device (csrc/kernels_prep_masked.hip): frames [F,128,128] uint16, masks [F,128,128] (nonzero = clear),
+    set_offsets [S+1], ref_frame [S] frame indices, window 1..32 -> (shifts [F,2] int32 (dy, dx), registered [F] uint8, shifted frames
+    uint16, shifted masks bool, their clear counts int32).  Equal to `register_masked_sets_numpy` bit for bit."""
+    R = _check_window(window)
+    frames, masks = np.asarray(frames), np.asarray(masks)
+    F = frames.shape[0]
+    S = len(set_offsets) - 1
+    o, r = np.asarray(set_offsets, np.int64), np.asarray(ref_frame, np.int64)
+    if S < 1 or o[0] != 0 or o[-1] != F or (np.diff(o) < 1).any() or len(r) != S or (r < o[:-1]).any() or (r >= o[1:]).any():
+        raise ValueError("registration needs set_offsets[0] = 0, set_offsets[-1] = n_frames, no empty set, one reference inside each set")
+    if frames.shape[1:] != (LR_SIZE, LR_SIZE) or masks.shape != frames.shape:
+        raise ValueError("registration takes %d x %d frames, got %r / %r" % (LR_SIZE, LR_SIZE, frames.shape, masks.shape))
+    import torch
+    from . import _lib
+    dev = _dev()
+    fr = _to_dev(frames.astype(np.uint16, copy=False), dev)
+    mk = _to_dev((masks != 0).view(np.uint8), dev)
+    off, ref = _to_dev(o, dev), _to_dev(r.astype(np.int32), dev)
+    shifts = torch.empty(F, 2, dtype=torch.int32, device=dev)
+    reg = torch.empty(F, dtype=torch.uint8, device=dev)
+    rf, rm = torch.empty_like(fr), torch.empty_like(mk)
+    rc = torch.empty(F, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().probav_prep_register_masked(_lib.ptr(fr), _lib.ptr(mk), _lib.ptr(off), S, F, _lib.ptr(ref), R, _lib.ptr(shifts),
+                                                      _lib.ptr(reg), _lib.ptr(rf), _lib.ptr(rm), _lib.ptr(rc), _lib.current_stream()),
+               "probav_prep_register_masked")
+    sh = shifts.cpu().numpy()
+    if (sh == PREP_BAD_SHIFT).any():
+        raise ValueError("probav_prep_register_masked: set_offsets / ref_frame break the preconditions of include/probav_hip.h (empty set or "
+                         "a reference outside its set)")
+    return sh, reg.cpu().numpy(), rf.cpu().numpy(), rm.cpu().numpy().astype(bool), rc.cpu().numpy()
 
 
 def device_xcorr_surface(ref, img):
@@ -170,9 +294,27 @@ def loadData(arrayDir, band):
 
 
 # ---- checkpoint 2 (utils/dataGenerator.py:599-841) --------------------------------------------------------------------------------
-def registerImages(allImgLR, allMskLR):
+def registerFrame(img, msk, referenceImg, referenceMsk, tech='freq', window=8):
+    """The reference's registerFrame (utils/dataGenerator.py:649-678) for one pair of [1, 128, 128] (or [128, 128]) frames and masks, on
+    the device: tech='freq' is the plain circular registration (csrc/kernels_prep.hip), tech='time' the masked one over `window`
+    (csrc/kernels_prep_masked.hip).  Returns (regImg float64, regMsk bool) in the shape of `img`."""
+    _check_tech(tech)
+    R = _check_window(window)
+    shape = np.shape(img)
+    pair = np.stack([np.asarray(referenceImg).reshape(LR_SIZE, LR_SIZE), np.asarray(img).reshape(LR_SIZE, LR_SIZE)]).astype(np.uint16)
+    clear = np.stack([np.asarray(referenceMsk).reshape(LR_SIZE, LR_SIZE), np.asarray(msk).reshape(LR_SIZE, LR_SIZE)]) != 0
+    if tech == 'time':
+        _, _, rf, rm, _ = device_register_masked(pair, clear, [0, 2], [0], R)
+    else:
+        _, rf, rm, _ = device_register(pair, clear, [0, 2], [0])
+    return rf[1].astype(np.float64).reshape(shape), rm[1].reshape(shape)
+
+
+def registerImages(allImgLR, allMskLR, tech='freq', window=8):
     """Per set: frames reordered by np.argsort(-clear count), the first is the reference, every other one registered against it
-    (device).  Returns an object array of float64 masked arrays [T, 1, 128, 128] (mask = ~clear)."""
+    (device; tech / window as registerFrame).  Returns an object array of float64 masked arrays [T, 1, 128, 128] (mask = ~clear)."""
+    _check_tech(tech)
+    window = _check_window(window)
     sets_img = [np.asarray(allImgLR[i]) for i in range(len(allImgLR))]
     sets_msk = [np.asarray(allMskLR[i]) for i in range(len(allMskLR))]
     for a, m in zip(sets_img, sets_msk):
@@ -184,7 +326,12 @@ def registerImages(allImgLR, allMskLR):
     masks = np.concatenate([(m != 0).reshape(-1, *m.shape[-2:]) for m in sets_msk])
     counts = device_count_nonzero(masks, hw[0] * hw[1]).astype(np.int64)
     order = np.concatenate([offsets[i] + np.argsort(-counts[offsets[i]:offsets[i + 1]]) for i in range(len(sizes))])
-    _, rf, rm, _ = device_register(frames[order], masks[order], offsets, offsets[:-1])
+    if tech == 'time':
+        _, reg, rf, rm, _ = device_register_masked(frames[order], masks[order], offsets, offsets[:-1], window)
+        logging.getLogger("dataGenerator").info('[ INFO ] Masked registration (window %d): %d of %d frames had no candidate shift and '
+                                                'stay where they are', window, int((reg == 0).sum()), len(reg))
+    else:
+        _, rf, rm, _ = device_register(frames[order], masks[order], offsets, offsets[:-1])
     out = []
     for i in range(len(sizes)):
         sl = slice(offsets[i], offsets[i + 1])
@@ -359,13 +506,18 @@ def augmentByRotating(patches):
 
 
 # ---- driver (utils/dataGenerator.py:33-273) ---------------------------------------------------------------------------------------
-def main(config, band, rng=None, online_aug=False):
-    """online_aug: stage 5 draws the frame permutations as ever (same rng, same order) but SAVES them beside the un-augmented training
+def main(config, band, rng=None, online_aug=False, register='freq', register_window=8):
+    """register: 'freq' (the default: the plain circular registration, as the reference's registerFrame default) or 'masked' (the
+    cloud-aware one over [-register_window, register_window]^2, the reference's tech='time'); stage 2 only.
+    online_aug: stage 5 draws the frame permutations as ever (same rng, same order) but SAVES them beside the un-augmented training
     arrays instead of applying them -- TRAINbasepatches{LR,HR}_<band>.npy and TRAINaugperms_<band>.npy, what `train.py --online-aug` reads
     (probav_amd.augment).  The TRAINVAL dumps do not depend on it."""
     log = logging.getLogger("dataGenerator")
     if band not in ('NIR', 'RED'):
         raise ValueError("band must be NIR or RED, got %r" % band)
+    if register not in REGISTER_MODES:
+        raise ValueError("register must be one of %r, got %r" % (tuple(REGISTER_MODES), register))
+    tech, register_window = REGISTER_MODES[register], _check_window(register_window)
     rawDataDir, cleanDataDir = config['raw_data'], config['preprocessing_out']
     d = {k: os.path.join(cleanDataDir, k) for k in ('arrayDir', 'trimmedArrayDir', 'patchesDir', 'trimmedPatchesDir', 'resolverDir',
                                                      'augmentedPatchesDir')}
@@ -384,7 +536,7 @@ def main(config, band, rng=None, online_aug=False):
     if 2 in ckpt:
         TRAIN, TEST = loadData(d['arrayDir'], band)
         allImgLR, allMskLR, allImgHR, allMskHR = TRAIN
-        allImgMskLR = registerImages(allImgLR, allMskLR)
+        allImgMskLR = registerImages(allImgLR, allMskLR, tech, register_window)
         allImgMskHR = convertToMaskedArray(allImgHR, allMskHR)
         allImgMskHR.dump(path('resolverDir', 'TRAINimgHR'))
         trmImgMskLR, trmImgMskHR, imgSetRemoved = removeCorruptedTrainImageSets(allImgMskLR, allImgMskHR, config['low_res_threshold'])
@@ -394,7 +546,7 @@ def main(config, band, rng=None, online_aug=False):
             print(f'[ WARNING ] Imgsets {imgSetRemoved} were removed')
         trmImgMskLR = pickClearLRImgsPerImgSet(trmImgMskLR, config['num_low_res_imgs_pre'], config['low_res_threshold'], rng)
         allImgLRTest, allMskLRTest = TEST
-        allImgMskLRTest = registerImages(allImgLRTest, allMskLRTest)
+        allImgMskLRTest = registerImages(allImgLRTest, allMskLRTest, tech, register_window)
         trmImgMskLRTest = removeCorruptedTestImageSets(allImgMskLRTest, config['low_res_threshold'])
         trmImgMskLRTest = pickClearLRImgsPerImgSet(trmImgMskLRTest, config['num_low_res_imgs_pre'], config['low_res_threshold'], rng)
         trmImgMskLR.dump(path('trimmedArrayDir', 'TRAINimgLR'))

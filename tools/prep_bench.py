@@ -6,6 +6,9 @@ small shifts plus noise): one JSON line with
   png_decode_ms_per_frame           pngio.imread of 16-bit 128 x 128 frames (reported separately: disk + zlib, not the GPU)
   numpy_register_est_s              the numpy fp64-FFT restatement of the reference's registration, timed on 50 sets and EXTRAPOLATED
     python tools/prep_bench.py [--sets-train 1160 --sets-test 290]
+--register masked [--register-window 8] [--rounds 5]: instead, the masked registration (probav_prep_register_masked) against the plain one
+(probav_prep_register) on the same device-resident frames in the same process, in alternated timed windows (plain, masked, plain, ...),
+each between device events after a warm-up of both: one JSON line with every window's time, the medians and masked_over_plain.
 """
 import argparse
 import json
@@ -35,10 +38,52 @@ def corpus(n_sets, rng):
     return np.stack(frames), np.stack(masks), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
 
 
+def masked_ab(opt, L, _lib, torch, n_frames, n_sets, fr, mk, od, rf, spec, sh, of_, om, oc):
+    """Plain and masked registration of the SAME resident frames, alternated; both already warm (plain by main(), masked here)."""
+    dev = fr.device
+    reg = torch.empty(n_frames, dtype=torch.uint8, device=dev)
+    st = _lib.current_stream()
+
+    def plain():
+        _lib.check(L.probav_prep_register(_lib.ptr(fr), _lib.ptr(mk), _lib.ptr(od), n_sets, n_frames, _lib.ptr(rf), _lib.ptr(spec), _lib.ptr(sh),
+                                          _lib.ptr(of_), _lib.ptr(om), _lib.ptr(oc), st), "probav_prep_register")
+
+    def masked():
+        _lib.check(L.probav_prep_register_masked(_lib.ptr(fr), _lib.ptr(mk), _lib.ptr(od), n_sets, n_frames, _lib.ptr(rf), opt.register_window,
+                                                 _lib.ptr(sh), _lib.ptr(reg), _lib.ptr(of_), _lib.ptr(om), _lib.ptr(oc), st),
+                   "probav_prep_register_masked")
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    timed(masked)                                          # warm-up: code object, the kernel's LDS attribute
+    unregistered = int((reg == 0).sum())
+    t_plain, t_masked = [], []
+    for _ in range(opt.rounds):
+        t_plain.append(timed(plain))
+        t_masked.append(timed(masked))
+    mp, mm = float(np.median(t_plain)), float(np.median(t_masked))
+    shifts = (2 * opt.register_window + 1) ** 2
+    print(json.dumps({"frames": int(n_frames), "sets": int(n_sets), "window": opt.register_window, "rounds": opt.rounds,
+                      "plain_ms": [round(t, 2) for t in t_plain], "masked_ms": [round(t, 2) for t in t_masked],
+                      "plain_median_ms": round(mp, 2), "masked_median_ms": round(mm, 2), "masked_over_plain": round(mm / mp, 2),
+                      "masked_us_per_frame": round(mm * 1e3 / n_frames, 3),
+                      "masked_pixel_pairs_per_s": round((n_frames - n_sets) * shifts * 128 * 128 / (mm * 1e-3), 0),
+                      "frames_without_candidate": unregistered}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets-train", type=int, default=1160)
     ap.add_argument("--sets-test", type=int, default=290)
+    ap.add_argument("--register", default="freq", choices=["freq", "masked"])
+    ap.add_argument("--register-window", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=5)
     opt = ap.parse_args()
     import torch
     from probav_amd import pngio, prep
@@ -75,6 +120,9 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     dev_ms = e0.elapsed_time(e1)
+    if opt.register == "masked":
+        masked_ab(opt, L, _lib, torch, n_frames, len(off) - 1, fr, mk, od, rf, spec, sh, of_, om, oc)
+        return
     del fr, mk, spec, of_, om
     # stages 3-4 on the train part: 9 frames per set
     S = opt.sets_train

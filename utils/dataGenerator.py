@@ -3,10 +3,14 @@ train.py and test.py read.  Runs on the GPU (probav_amd.prep); the same cfg keys
 reference.  --seed N seeds the frame picking and LR shuffling (equal to the reference after np.random.seed(N)); without it the run is
 unseeded, as the reference's is.
 
-    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0] [--online-aug]
+    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0] [--online-aug] [--register masked [--register-window 8]]
 
 --online-aug: stage 5 writes the un-augmented training patches and the frame permutations it drew (TRAINbasepatches{LR,HR}_<band>.npy,
 TRAINaugperms_<band>.npy) instead of the augmented set; `train.py --online-aug` augments every batch on the GPU from them.
+
+--register masked: stage 2 registers every LR frame by the cloud-aware masked correlation over a window of +-R integer shifts
+(--register-window R, 1..32) and shifts it without wrap-around (the reference's registerFrame(tech='time')); the default, freq, is the
+plain circular registration.
 """
 import argparse
 import logging
@@ -29,6 +33,11 @@ def parser(argv=None):
     p.add_argument('--online-aug', dest='online_aug', action='store_true',
                    help='stage 5 saves the un-augmented training patches and the frame permutations instead of the augmented set '
                         '(for train.py --online-aug)')
+    p.add_argument('--register', default='freq', choices=['freq', 'masked'],
+                   help="stage 2's registration: freq = plain circular cross-correlation (default); masked = cloud-aware masked "
+                        "normalised correlation over a bounded window, shifted without wrap-around")
+    p.add_argument('--register-window', dest='register_window', default=8, type=int,
+                   help='largest integer shift, per axis, that --register masked tries (1..32)')
     return p.parse_args(argv)
 
 
@@ -37,4 +46,5 @@ if __name__ == '__main__':
     opt = parser()
     logging.info(f'[ CFG - INFO ] Using {opt.cfg} as config file...')
     rng = None if opt.seed is None else np.random.RandomState(opt.seed)
-    prep.main(parseConfig(opt.cfg), opt.band, rng, online_aug=opt.online_aug)
+    prep.main(parseConfig(opt.cfg), opt.band, rng, online_aug=opt.online_aug, register=opt.register,
+              register_window=opt.register_window)
