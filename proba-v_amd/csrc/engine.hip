@@ -378,31 +378,51 @@ struct AmaxSlots {
 // The kernel that serves a convolution launch of the engine (forward, or backward-data when bias == nullptr): with the launch's profiling class,
 // whether the kernel writes am.y itself, and for the MFMA / x6 kernels the filter fragments they read (x6: in arithmetic 1 X6 or 2 H3)
 enum class ConvKernel { direct, up, up_bwd_data, cin1, x6_strip, x6_rowtile, mfma_strip, mfma_rowtile };
-struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; const float* wfrag; };
-static ConvRoute conv_route(const Family& f, const ConvGeom& g, const float* gate, const float* bias, const float* skip, const Frags& wf, const Amax& am)
+struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; const float* wfrag; StripSel strip; };     // strip: the strip kernels' selection (strip_select), made here once
+// `dedicated`: the engine's policy in front of the matrix kernels (small dedicated kernels, exotic geometries on the direct one); the single-operator entry point,
+// whose tests hold the matrix kernels to the oracle on those geometries too, routes without it
+static ConvRoute conv_route(const Family& f, const ConvGeom& g, const float* gate, const float* bias, const float* skip, const Frags& wf, const Amax& am, bool dedicated = true)
 {
     const bool pw = g.kh * g.kw * g.kt == 1;
     const bool bwd = (bias == nullptr);              // only backward-data launches run without a bias
-    // the experimental 19-frame reducer: 5x5x5 kernels, pads of 2, mirrored depth pads (and their backward-data forms): generic kernels
-    const bool exotic = g.reflect_t || g.ph > 2 || g.pw > 2 || g.pt > 2 || (!pw && g.kh != 3) || (g.reflect_hw && g.ph > 1);
-    // upscaleConv1 and its backward-data (0.2 % of the work): dedicated small VALU kernels instead of 32x32 matrix tiles around a 32x9 product
-    if (f.mfma && !gate && !skip && bwd && conv3d_up_bwd_data_supported(g)) return {ConvKernel::up_bwd_data, CLS_CONV3_BWD_DATA, true, 0, nullptr};
-    if (exotic) return {ConvKernel::direct, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, false, 0, nullptr};
-    if (f.mfma && !gate && !skip && bias && !am.y && conv3d_up_forward_supported(g)) return {ConvKernel::up, CLS_CONV3_FWD, false, 0, nullptr};
-    if (f.mfma && !gate && !skip && bias && conv3d_cin1_forward_supported(g)) return {ConvKernel::cin1, CLS_CONV3_FWD, true, 0, nullptr};
+    if (dedicated) {
+        // the experimental 19-frame reducer: 5x5x5 kernels, pads of 2, mirrored depth pads (and their backward-data forms): generic kernels
+        const bool exotic = g.reflect_t || g.ph > 2 || g.pw > 2 || g.pt > 2 || (!pw && g.kh != 3) || (g.reflect_hw && g.ph > 1);
+        // upscaleConv1 and its backward-data (0.2 % of the work): dedicated small VALU kernels instead of 32x32 matrix tiles around a 32x9 product
+        if (f.mfma && !gate && !skip && bwd && conv3d_up_bwd_data_supported(g)) return {ConvKernel::up_bwd_data, CLS_CONV3_BWD_DATA, true, 0, nullptr, {}};
+        if (exotic) return {ConvKernel::direct, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, false, 0, nullptr, {}};
+        if (f.mfma && !gate && !skip && bias && !am.y && conv3d_up_forward_supported(g)) return {ConvKernel::up, CLS_CONV3_FWD, false, 0, nullptr, {}};
+        if (f.mfma && !gate && !skip && bias && conv3d_cin1_forward_supported(g)) return {ConvKernel::cin1, CLS_CONV3_FWD, true, 0, nullptr, {}};
+    }
     const bool h3 = f.arith == 2 && wf.h3 && am.x && am.w;
     const float* wsplit = h3 ? wf.h3 : wf.x6;
     const int arith = h3 ? 2 : 1;
-    const bool pring = h3 && x6_strip_wants_tap_fragments(g, 2);                  // the H3 piece-ring strip kernel serves this geometry
-    const bool x6s = f.x6 && wsplit && (mfma_conv_strip_supported(g) || pring);
-    const bool x6r = f.x6 && wsplit && !x6s && x6_conv_rowtile_supported(g);
+    const bool split = f.x6 && wsplit;
+    const StripSel sel = split ? strip_select(g, gate, arith) : StripSel();
+    const bool x6s = sel.k != StripKernel::none;
+    const bool x6r = split && !x6s && x6_conv_rowtile_supported(g);
     const bool x6 = x6s || x6r;
     const int cls = pw ? (bwd ? CLS_PW_BWD_DATA : CLS_PW_FWD) : (bwd ? (x6 ? CLS_CONV3_BWD_DATA_X6 : CLS_CONV3_BWD_DATA) : (x6 ? CLS_CONV3_FWD_X6 : CLS_CONV3_FWD));
-    if (x6s) return {ConvKernel::x6_strip, cls, true, arith, (pring && g.Cin == 25 && wf.h3t) ? wf.h3t : wsplit};
-    if (x6r) return {ConvKernel::x6_rowtile, cls, true, arith, wsplit};
-    if (f.strip && wf.f32 && mfma_conv_strip_supported(g)) return {ConvKernel::mfma_strip, cls, true, 0, wf.f32};
-    if (f.mfma && wf.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, wf.f32};
-    return {ConvKernel::direct, cls, false, 0, nullptr};
+    if (x6s) return {ConvKernel::x6_strip, cls, true, arith, (sel.taps && g.Cin == 25 && wf.h3t) ? wf.h3t : wsplit, sel};
+    if (x6r) return {ConvKernel::x6_rowtile, cls, true, arith, wsplit, {}};
+    const StripSel s32 = (f.strip && wf.f32 && !split) ? strip_select(g, gate, 0) : StripSel();      // (split: no strip kernel took g above, so the fp32 one does not either)
+    if (s32.k != StripKernel::none) return {ConvKernel::mfma_strip, cls, true, 0, wf.f32, s32};
+    if (f.mfma && wf.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, wf.f32, {}};
+    return {ConvKernel::direct, cls, false, 0, nullptr, {}};
+}
+// the routed launch (w: the filter as the direct kernels read it)
+static int conv_launch(const ConvRoute& r, const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias,
+                       const float* skip, float* y, const Amax& am, hipStream_t s)
+{
+    switch (r.k) {
+    case ConvKernel::up_bwd_data: return conv3d_up_bwd_data(g, x, w, nullptr, y, am.y, s);
+    case ConvKernel::up: return conv3d_up_forward(g, x, w, bias, y, s);
+    case ConvKernel::cin1: return conv3d_cin1_forward(g, x, w, bias, y, am.y, s);
+    case ConvKernel::x6_strip: case ConvKernel::mfma_strip: return conv_strip_forward(r.strip, x, gate, r.wfrag, bias, skip, y, am, s);
+    case ConvKernel::x6_rowtile: return x6_conv_rowtile_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s);
+    case ConvKernel::mfma_rowtile: return mfma_conv_forward(g, x, gate, r.wfrag, bias, skip, y, am, s);
+    default: return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
+    }
 }
 // am.x / am.w: amax slots of x (one per sample) and of the layer's filter columns (H3 kernels); am.y: per-sample slots that must hold the output's amax afterwards
 static int conv_fwd(const probav_engine* e, const ConvGeom& g, const float* x, const float* gate, const float* w,
@@ -410,19 +430,7 @@ static int conv_fwd(const probav_engine* e, const ConvGeom& g, const float* x, c
 {
     const ConvRoute r = conv_route(e->fam, g, gate, bias, skip, wf, am);
     int rc;
-    {
-        ProfScope ps(e, r.cls, geom_macs(g), s);
-        switch (r.k) {
-        case ConvKernel::up_bwd_data: rc = conv3d_up_bwd_data(g, x, w, nullptr, y, am.y, s); break;
-        case ConvKernel::up: rc = conv3d_up_forward(g, x, w, bias, y, s); break;
-        case ConvKernel::cin1: rc = conv3d_cin1_forward(g, x, w, bias, y, am.y, s); break;
-        case ConvKernel::x6_strip: rc = x6_conv_strip_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s); break;
-        case ConvKernel::x6_rowtile: rc = x6_conv_rowtile_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s); break;
-        case ConvKernel::mfma_strip: rc = mfma_conv_strip_forward(g, x, gate, r.wfrag, bias, skip, y, am, s); break;
-        case ConvKernel::mfma_rowtile: rc = mfma_conv_forward(g, x, gate, r.wfrag, bias, skip, y, am, s); break;
-        default: rc = conv3d_direct_forward(g, x, gate, w, bias, skip, y, s); break;
-        }
-    }
+    { ProfScope ps(e, r.cls, geom_macs(g), s); rc = conv_launch(r, g, x, gate, w, bias, skip, y, am, s); }
     if (rc == PROBAV_OK && am.y && !r.reports) rc = amax_tensor(y, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, am.y, s);
     return rc;
 }
@@ -1231,25 +1239,23 @@ int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* g
     if (impl >= 1 && !gate && !skip && bias && conv3d_up_forward_supported(g)) return conv3d_up_forward(g, x, w, bias, y, s);
     if (impl >= 1 && !gate && !skip && !g.relu && conv3d_up_bwd_data_supported(g)) return conv3d_up_bwd_data(g, x, w, bias, y, nullptr, s);
     if (impl == 0) return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
-    // impl 1 the MFMA row-tile kernel, 2 the strip kernel, 3 / 4 the x6 strip kernel (X6 / H3; the piece-ring form where it applies) or, where
-    // the strip kernels do not apply, its row-tile form; a geometry the chosen kernel does not cover is refused
-    const int arith = impl >= 3 ? impl - 2 : 0;
-    const bool pstrip = impl == 4 && x6_strip_wants_tap_fragments(g, 2);
-    const bool x6row = impl >= 3 && !mfma_conv_strip_supported(g) && !pstrip && x6_conv_rowtile_supported(g);
-    const bool okk = x6row || pstrip || (impl >= 2 ? mfma_conv_strip_supported(g) : mfma_conv_supported(g));
-    if (!okk) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
-    CK(op_scratch());
+    // impl 1 the MFMA row-tile kernel, 2 the strip kernel, 3 / 4 the x6 strip kernel (X6 / H3; the piece-ring form where it applies) or, where the strip kernels do not apply, its row-tile
+    // form: what conv_route gives family `impl` behind the engine's dedicated kernels, anything else is refused.  The route only asks WHICH operands exist (any address will do): they are packed below
+    static const float some = 0.f;
     Amax am;
+    if (impl == 4) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
+    ConvRoute r = conv_route(make_family(impl, false), g, gate, bias, skip, Frags{&some, &some, &some, &some}, am, false);
+    const bool documented = impl == 1 ? r.k == ConvKernel::mfma_rowtile : (impl == 2 ? r.k == ConvKernel::mfma_strip : r.k == ConvKernel::x6_strip || r.k == ConvKernel::x6_rowtile);
+    if (!documented) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
+    CK(op_scratch());
     if (impl == 4) {
         if (g.Cout > 256) { set_error("probav_conv3d_forward: Cout > 256", hipSuccess); return PROBAV_EINVAL; }
         CK(op_amax_conv(g, x, w, nullptr, s));
         am.x = g_op.amax; am.w = g_op.amax + 2 * g.N; am.y = g_op.amax + g.N;
     }
-    CK(op_pack(g, w, s, arith, pstrip));
-    if (x6row) return x6_conv_rowtile_forward(g, x, gate, g_op.frag, bias, skip, y, arith, am, s);
-    if (arith) return x6_conv_strip_forward(g, x, gate, g_op.frag, bias, skip, y, arith, am, s);
-    if (impl == 2) return mfma_conv_strip_forward(g, x, gate, g_op.frag, bias, skip, y, am, s);
-    return mfma_conv_forward(g, x, gate, g_op.frag, bias, skip, y, am, s);
+    CK(op_pack(g, w, s, r.arith, r.strip.taps));
+    r.wfrag = g_op.frag;
+    return conv_launch(r, g, x, gate, w, bias, skip, y, am, s);
 }
 
 size_t probav_conv3d_wgrad_scratch_bytes(const int32_t geom[17], int impl)
@@ -1267,6 +1273,7 @@ int probav_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy,
     if (!geom || !x || !dy || !dw || !scratch) { set_error("probav_conv3d_wgrad: null argument", hipSuccess); return PROBAV_EINVAL; }
     const ConvGeom g = geom_from(geom);
     if (!geom_ok(g)) { set_error("probav_conv3d_wgrad: bad geometry", hipSuccess); return PROBAV_EINVAL; }
+    // (impl names a kernel here, not an engine family: 2 is the direct kernel, so the call does not go through wgrad_route)
     if (impl == 3 || impl == 4) {
         if (!x6_wgrad_supported(g)) { set_error("probav_conv3d_wgrad: geometry not supported by the x6 kernel", hipSuccess); return PROBAV_EINVAL; }
         if (scratch_bytes < x6_wgrad_partial_floats(g) * sizeof(float)) { set_error("probav_conv3d_wgrad: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }

@@ -1,6 +1,7 @@
 // Host-visible interface of kernels_mfma.hip (fp32-MFMA kernels + weight fragment packing).
 #pragma once
 #include "probav_common.h"
+#include "w4_switch.h"
 
 namespace probav {
 
@@ -38,21 +39,30 @@ void mfma_conv_pack_job(PackJob& J, int Cin, int Cout);    // fills type/Cin/Cou
 int mfma_conv_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag, const float* bias,
                       const float* skip, float* y, const Amax& am, hipStream_t s);
 
-// strip form (ring of input rows, flattened tiles, K split over wave pairs); same fragment layout as mfma_conv_forward
-bool mfma_conv_strip_supported(const ConvGeom& g);
-int mfma_conv_strip_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag, const float* bias,
-                            const float* skip, float* y, const Amax& am, hipStream_t s);
+// strip form (ring of input rows, flattened tiles, K split over wave pairs); same fragment layout as mfma_conv_forward.  What the kernels are handed:
+struct StripArgs {
+    ConvGeom g;
+    int Wp, Tp;                 // staged width / depth (Wo + 2, To + 2; piece-ring kernel: Wt + 2)
+    int SR, nstrips;            // output rows per strip, strips per patch
+    unsigned mTo, mNvr, mTi, mSrcCol;
+    int nsplit, Wt;             // piece-ring kernel: output rows cut into nsplit column ranges of Wt columns when four full rows do not fit the LDS
+    int nslot;                  // alternating-halves kernel: ring depth
+    unsigned mNslot;
+};
+struct StripPlan { bool ok; int CC, KS; size_t lds_bytes; int grid; StripArgs a; };
+// The kernel that serves a strip launch of g in arithmetic `arith` (0 fp32, 1 X6, 2 H3), chosen ONCE per launch: the engine's route asks, reads the fragment form off the
+// answer and hands it to conv_strip_forward.  H3 where a piece-ring plan exists (per-tap filters even for 25 channels: PACK_H3_CONV / _CONVP): conv3_w4_kernel (cw4) while
+// W4::conv is on and it takes the layer, else conv3_pp_kernel (rvp staging items per thread), else conv3_pstrip_kernel.  Everything else: conv3_strip_kernel (25 channels: PACK_*_CONVK)
+enum class StripKernel { none, cw4, pp, pstrip, strip };
+struct StripSel { StripKernel k = StripKernel::none; int arith = 0, rvp = 2; bool taps = false; StripPlan plan = {}; };     // plan: of pp / pstrip / strip (cw4: the piece-ring plan; plan.a.g = g)
+StripSel strip_select(const ConvGeom& g, const float* gate, int arith);
+int conv_strip_forward(const StripSel& sel, const float* x, const float* gate, const float* wfrag, const float* bias,
+                       const float* skip, float* y, const Amax& am, hipStream_t s);
 // row-tile kernel with a split-operand tap loop (32-channel inputs: reducers, upscale; any pads / reflect).  arith 1: X6,
 // wfrag6 = PACK_X6_CONV / _CONVK fragments; arith 2: H3, PACK_H3_* fragments and am.x / am.w set (x6_device.h)
 bool x6_conv_rowtile_supported(const ConvGeom& g);
 int x6_conv_rowtile_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag6, const float* bias,
                             const float* skip, float* y, int arith, const Amax& am, hipStream_t s);
-// the strip kernel with a split-operand tap loop (same fragments; when x6_strip_wants_tap_fragments(g, arith) the filters of a
-// 25-channel layer must be the per-tap PACK_H3_CONV form, not PACK_H3_CONVK: the H3 piece-ring kernel serves the call)
-bool x6_strip_wants_tap_fragments(const ConvGeom& g, int arith);
-int x6_conv_strip_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag6, const float* bias,
-                          const float* skip, float* y, int arith, const Amax& am, hipStream_t s);
-
 bool mfma_wgrad_supported(const ConvGeom& g);
 size_t mfma_wgrad_partial_floats(const ConvGeom& g);
 int mfma_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db,
@@ -75,12 +85,9 @@ int mfma_pw_backward_reduce(const float* slabs, int D, float* dW1, float* dW2, f
 int mfma_pw_backward_grid();
 
 // 3x3x3 'same' convolution of the residual blocks (25 -> 32 channels, and its backward-data 32 -> 25 / 32) as ONE-WAVE-PER-SIMD kernel (kernels_cw4.hip; H3
-// arithmetic only): the filter's first pieces stay in registers for the whole launch.  x6_conv_strip_forward dispatches to it when cw4_conv_supported();
-// cw4_set_enabled(0) (or PROBAV_GEN1=1 in the environment, which also selects the general pointwise backward) keeps conv3_pp_kernel.
+// arithmetic only): the filter's first pieces stay in registers for the whole launch.  strip_select takes it when cw4_conv_supported(); with W4::conv off conv3_pp_kernel stays.
 // wfrag: PACK_H3_CONVP (25 input channels) / PACK_H3_CONV (32) fragments, as conv3_pp_kernel reads them
 bool cw4_conv_supported(const ConvGeom& g, const float* gate);
-bool cw4_enabled();
-void cw4_set_enabled(int on);
 int cw4_conv_forward(const ConvGeom& g, const float* x, const float* wfrag, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s);
 
 }  // namespace probav

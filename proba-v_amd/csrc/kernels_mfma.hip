@@ -744,17 +744,6 @@ int x6_conv_rowtile_forward(const ConvGeom& g, const float* x, const float* gate
 // Inputs with more channels than CC run nchunk passes over the strip; pass p > 0 adds to the partial output of pass p-1
 // (re-read from L2), the last pass applies bias / ReLU / skip.
 // ---------------------------------------------------------------------------------------------------
-struct StripArgs {
-    ConvGeom g;
-    int Wp, Tp;                 // staged width / depth (Wo + 2, To + 2; piece-ring kernel: Wt + 2)
-    int SR, nstrips;            // output rows per strip, strips per patch
-    unsigned mTo, mNvr, mTi, mSrcCol;
-    int nsplit, Wt;             // piece-ring kernel: output rows cut into nsplit column ranges of Wt columns when four full rows do not fit the LDS
-    int nslot;                  // alternating-halves kernel: ring depth
-    unsigned mNslot;
-};
-
-
 template <int CC, int KS, typename Mid>
 __device__ __forceinline__ void strip_taps(const StripArgs& a, const float* lds, int base0, int base1, int base2, int tap0, int ntap,
                                            const float4* __restrict__ wf, f32x16& acc, int ks, Mid mid)
@@ -1265,8 +1254,6 @@ __global__ __launch_bounds__(512, 2) void conv3_strip_kernel(StripArgs a, const 
     if (am.y) amax_commit(omax, am.y + n);
     XS_OUT;
 }
-
-struct StripPlan { bool ok; int CC, KS; size_t lds_bytes; int grid; StripArgs a; };
 
 // ---------------------------------------------------------------------------------------------------
 // Strip convolution with a ring of fp16 PIECE records (H3 arithmetic only).  Same decomposition as conv3_strip_kernel (strip of
@@ -2465,64 +2452,53 @@ static StripPlan strip_plan(const ConvGeom& g)
     return p;
 }
 
-bool mfma_conv_strip_supported(const ConvGeom& g) { return strip_plan(g).ok; }
-// does x6_conv_strip_forward(g, ..., arith) read per-tap fragments (PACK_*_CONV) even for 25 input channels?  (the H3 piece-ring kernel does;
-// the other 25-channel split kernels read the K-concatenated PACK_*_CONVK form)
-bool x6_strip_wants_tap_fragments(const ConvGeom& g, int arith)
+// today's precedence, each plan computed at most once (kernels_mfma.h)
+StripSel strip_select(const ConvGeom& g, const float* gate, int arith)
 {
-    StripPlan pp;
-    int rvp;
-    return arith == 2 && (pstrip_plan(g, pp) || pp_plan(g, pp, rvp));   // (the alternating-halves form also takes rows shorter than 128 voxels: the later reducers)
+    StripSel r; r.arith = arith;
+    if (arith == 2) {
+        const bool pp = pp_plan(g, r.plan, r.rvp);
+        r.taps = pp || pstrip_plan(g, r.plan);
+        if (r.taps) r.k = w4_enabled(W4::conv) && cw4_conv_supported(g, gate) ? StripKernel::cw4 : (pp ? StripKernel::pp : StripKernel::pstrip);
+    }
+    if (!r.taps) { r.plan = strip_plan(g); if (r.plan.ok) r.k = StripKernel::strip; }
+    return r;
 }
 
-
-static int strip_launch(const ConvGeom& g, const float* x, const float* gate, const float* wfrag, const float* bias,
-                        const float* skip, float* y, int arith, const Amax& am, hipStream_t s)
+int conv_strip_forward(const StripSel& sel, const float* x, const float* gate, const float* wfrag, const float* bias,
+                       const float* skip, float* y, const Amax& am, hipStream_t s)
 {
-    if (arith == 2 && (!am.x || !am.w)) { set_error("x6_conv_strip_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
-    if (arith == 2 && x6_strip_wants_tap_fragments(g, arith)) {               // H3: the piece-ring kernel (filters: PACK_H3_CONV)
-        if (cw4_enabled() && cw4_conv_supported(g, gate)) return cw4_conv_forward(g, x, wfrag, bias, skip, y, am, s);      // one wave per SIMD, the filter in registers (kernels_cw4.hip)
-        StripPlan pp;
-        int rvp = 2;
-        if (pp_plan(g, pp, rvp)) {
-            // the instances that ship: 25 input channels (the forward pass of the residual blocks) in the pair-split form; 32 input channels (backward-data, reducers) in
-            // the 16x16x32 MFMA form -- except the gated layer with three staging items per thread (reducers at T = 13), whose new-form instance would spill 42
-            // registers: it keeps the one-wave-per-tile 32x32x16 form.  (Rounds 3 / 4 carried the superseded forms behind PROBAV_PP_K16 / PROBAV_PP_OLD25 for A/B runs.)
-            if (g.Cin == 25 && gate) { set_error("x6_conv_strip_forward: a gated 25-channel layer has no piece-ring instance (none occurs in the reference's networks)", hipSuccess); return PROBAV_EINVAL; }
-#define PROBAV_PPK(...) return launch_lds<conv3_pp_kernel<__VA_ARGS__>>("conv3_pp", dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
-            if (g.Cin == 25) { if (rvp == 2) PROBAV_PPK(25, false, 2, true); else PROBAV_PPK(25, false, 3, true); }
-            else if (gate) { if (rvp == 2) PROBAV_PPK(32, true, 2, true); else PROBAV_PPK(32, true, 3); }
-            else { if (rvp == 2) PROBAV_PPK(32, false, 2, true); else PROBAV_PPK(32, false, 3, true); }
+    const StripPlan& p = sel.plan;
+    const ConvGeom& g = p.a.g;
+    if (sel.arith == 2 && (!am.x || !am.w)) { set_error("x6_conv_strip_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
+    switch (sel.k) {
+    case StripKernel::cw4: return cw4_conv_forward(g, x, wfrag, bias, skip, y, am, s);      // one wave per SIMD, the filter in registers (kernels_cw4.hip)
+    case StripKernel::pp:
+        // the instances: 25 input channels (the residual blocks' forward) in the pair-split form; 32 (backward-data, reducers) in the 16x16x32 MFMA form -- except the gated layer with
+        // three staging items per thread (reducers at T = 13), whose instance of that form would spill 42 registers: it keeps the one-wave-per-tile 32x32x16 form
+        if (g.Cin == 25 && gate) { set_error("x6_conv_strip_forward: a gated 25-channel layer has no piece-ring instance (none occurs in the reference's networks)", hipSuccess); return PROBAV_EINVAL; }
+#define PROBAV_PPK(...) return launch_lds<conv3_pp_kernel<__VA_ARGS__>>("conv3_pp", dim3(p.grid), dim3(512), p.lds_bytes, s, p.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
+        if (g.Cin == 25) { if (sel.rvp == 2) PROBAV_PPK(25, false, 2, true); else PROBAV_PPK(25, false, 3, true); }
+        else if (gate) { if (sel.rvp == 2) PROBAV_PPK(32, true, 2, true); else PROBAV_PPK(32, true, 3); }
+        else { if (sel.rvp == 2) PROBAV_PPK(32, false, 2, true); else PROBAV_PPK(32, false, 3, true); }
 #undef PROBAV_PPK
-        }
-        if (!pstrip_plan(g, pp)) { set_error("x6_conv_strip_forward: no piece-ring plan for this geometry", hipSuccess); return PROBAV_EINVAL; }
-#define PROBAV_PSTRIP(C, G) return launch_lds<conv3_pstrip_kernel<C, G>>("conv3_pstrip", dim3(pp.grid), dim3(512), pp.lds_bytes, s, pp.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
+    case StripKernel::pstrip:
+#define PROBAV_PSTRIP(C, G) return launch_lds<conv3_pstrip_kernel<C, G>>("conv3_pstrip", dim3(p.grid), dim3(512), p.lds_bytes, s, p.a, x, gate, (const uint4*)wfrag, bias, skip, y, am)
         if (g.Cin == 25) { if (gate) PROBAV_PSTRIP(25, true); else PROBAV_PSTRIP(25, false); }
         else             { if (gate) PROBAV_PSTRIP(32, true); else PROBAV_PSTRIP(32, false); }
 #undef PROBAV_PSTRIP
-    }
-    const StripPlan p = strip_plan(g);
-    if (!p.ok) { set_error("mfma_conv_strip_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
+    case StripKernel::strip:
 #define PROBAV_STRIP(C, K, G, S, X) return launch_lds<conv3_strip_kernel<C, K, G, S, X>>("conv3_strip", dim3(p.grid), dim3(512), p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am)
 #define PROBAV_STRIP_A(X) do { \
         if (p.CC == 25) { if (gate) PROBAV_STRIP(25, 13, true, 5, X); else PROBAV_STRIP(25, 13, false, 5, X); } \
         else            { if (gate) PROBAV_STRIP(32, 16, true, 4, X); else PROBAV_STRIP(32, 16, false, 4, X); } } while (0)
-    if (arith == 2) PROBAV_STRIP_A(2);
-    else if (arith == 1) PROBAV_STRIP_A(1);
-    else PROBAV_STRIP_A(0);
+        if (sel.arith == 2) PROBAV_STRIP_A(2);
+        else if (sel.arith == 1) PROBAV_STRIP_A(1);
+        else PROBAV_STRIP_A(0);
 #undef PROBAV_STRIP_A
 #undef PROBAV_STRIP
-}
-
-int mfma_conv_strip_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag, const float* bias,
-                            const float* skip, float* y, const Amax& am, hipStream_t s)
-{
-    return strip_launch(g, x, gate, wfrag, bias, skip, y, 0, am, s);
-}
-int x6_conv_strip_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag6, const float* bias,
-                          const float* skip, float* y, int arith, const Amax& am, hipStream_t s)
-{
-    return strip_launch(g, x, gate, wfrag6, bias, skip, y, arith, am, s);
+    default: set_error("mfma_conv_strip_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------

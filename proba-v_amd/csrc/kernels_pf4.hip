@@ -341,16 +341,6 @@ __global__ __launch_bounds__(256, 1) void pw_fwd_w4_kernel(const float* __restri
 }
 
 // ---- host side ----
-#ifndef PF4_DIAG
-static int g_pf4_enabled = -1;
-bool pf4_enabled()
-{
-    if (g_pf4_enabled < 0) { const char* e = getenv("PROBAV_GEN1"); g_pf4_enabled = !(e && (e[0] == '1' || (e[0] == 'p' && e[1] == 'w' && e[2] != 'b'))); }      // PROBAV_GEN1 = 1 | pw | pwf | pwb | conv
-    return g_pf4_enabled != 0;
-}
-void pf4_set_enabled(int on) { g_pf4_enabled = on ? 1 : 0; }
-#endif
-
 bool pf4_forward_supported(long nvox, long vps, int D)
 {
     return D >= 1 && D <= 32 && vps >= 1 && nvox % vps == 0 && nvox * (long)D * 4 < 0x40000000L && nvox * 128L < 0xffffffffL;      // (32-bit buffer offsets)

@@ -714,14 +714,6 @@ __global__ __launch_bounds__(256, 1) void pw_bwd_w4_kernel(
 #endif
 }
 
-static int g_pw4_enabled = -1;
-bool pw4_enabled()
-{
-    if (g_pw4_enabled < 0) { const char* e = getenv("PROBAV_GEN1"); g_pw4_enabled = !(e && (e[0] == '1' || (e[0] == 'p' && e[1] == 'w' && e[2] != 'f'))); }      // PROBAV_GEN1 = 1 (every general form) | pw (both pointwise kernels) | pwf | pwb (forward / backward only) | conv
-    return g_pw4_enabled != 0;
-}
-void pw4_set_enabled(int on) { g_pw4_enabled = on ? 1 : 0; }
-
 bool pw4_backward_supported(long nvox, long vps, int D)
 {
     if (vps <= 0 || nvox % vps || D != 25) return false;        // (the dT staging knows where channel D - 1 sits in a lane's slices; every network of the reference has D = int(32 * 0.8) = 25)

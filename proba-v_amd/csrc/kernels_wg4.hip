@@ -600,16 +600,6 @@ static bool wg4_plan(const ConvGeom& g, const float* gate, Wg4Args& p, int& grid
     return true;
 }
 
-#ifndef WG4_DIAG
-static int g_wg4_enabled = -1;
-bool wg4_enabled()
-{
-    if (g_wg4_enabled < 0) { const char* e = getenv("PROBAV_GEN1"); g_wg4_enabled = !(e && (e[0] == '1' || e[0] == 'w')); }      // PROBAV_GEN1 = 1 (every general form) | conv | wg | pw | pwf | pwb
-    return g_wg4_enabled != 0;
-}
-void wg4_set_enabled(int on) { g_wg4_enabled = on ? 1 : 0; }
-#endif
-
 bool wg4_wgrad_supported(const ConvGeom& g, const float* gate)
 {
     Wg4Args p;

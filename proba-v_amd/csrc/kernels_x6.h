@@ -27,21 +27,17 @@ int x6_pw_backward(const float* x, const float* dT, const float* dOut, const flo
                    int arith, const PwAmax& am, hipStream_t s);
 
 // the same reverse pass as ONE-WAVE-PER-SIMD kernel (kernels_pw4.hip; H3 arithmetic only): four independent waves per workgroup, each with a run of
-// tiles of one sample and all eight hidden chunks, dW1 / dW2 of the run in 256 accumulator registers.  x6_pw_backward dispatches to it when
-// pw4_backward_supported(); pw4_set_enabled(0) (or PROBAV_GEN1=1 in the environment) keeps the general eight-wave form pw_bwd_x6_kernel<H3>
+// tiles of one sample and all eight hidden chunks, dW1 / dW2 of the run in 256 accumulator registers.  x6_pw_backward_select takes it when
+// pw4_backward_supported(); with W4::pw_bwd off the general eight-wave form pw_bwd_x6_kernel<H3> stays
 bool pw4_backward_supported(long nvox, long vps, int D);
-bool pw4_enabled();
-void pw4_set_enabled(int on);
 int pw4_backward(const float* x, const float* dT, const float* dOut, const float* w1f, const float* w2kf, const float* w1cf,
                  const float* b1, float* dX, float* dW1, float* dW2, float* db1, float* db2, float* slabs, long nvox, long vps, int D,
                  const PwAmax& am, hipStream_t s);
 
 // the fused pointwise forward as ONE-WAVE-PER-SIMD kernel (kernels_pf4.hip; H3 arithmetic only): the arithmetic of pw_fwd_x6_kernel<H3> -- the order in which the reverse
-// pass recomputes the hidden tile --, the weight fragments in registers, no LDS traffic in the tile loop.  x6_pw_forward dispatches to it when pf4_forward_supported();
-// pf4_set_enabled(0) (or PROBAV_GEN1=1 / pw in the environment) keeps pw_fwd_h3k_kernel
+// pass recomputes the hidden tile --, the weight fragments in registers, no LDS traffic in the tile loop.  x6_pw_forward_select takes it when pf4_forward_supported();
+// with W4::pw_fwd off pw_fwd_h3k_kernel stays
 bool pf4_forward_supported(long nvox, long vps, int D);
-bool pf4_enabled();
-void pf4_set_enabled(int on);
 int pf4_forward(const float* x, const float* w1frag, const float* w2frag, const float* b1, const float* b2, float* dec, long nvox, long vps, int D,
                 const PwAmax& am, hipStream_t s, float* hdump = nullptr);
 
@@ -56,11 +52,9 @@ int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const floa
 // the backward-filter of the residual blocks (25 -> 32 channels, 'same' padding, depth 9 or 7) and of the reducers (32 -> 32, tf.pad(REFLECT) rows / columns, no depth pads,
 // output depth 7 / 5 / 3, dY masked by `gate` = the layer's output) on rows of 22 columns and at most 256 samples as ONE-WAVE-PER-SIMD kernel
 // (kernels_wg4.hip; H3 arithmetic only): a conflict-free piece image of the input ring, dY straight from memory, one instruction stream per output row.
-// x6_conv_wgrad dispatches to it when wg4_wgrad_supported(); wg4_set_enabled(0) (or PROBAV_GEN1=1 / wg in the environment) keeps conv3_wgrad_x6_kernel.
+// x6_wgrad_select takes it when wg4_wgrad_supported(); with W4::wgrad off conv3_wgrad_x6_kernel stays.
 // partial: x6_wgrad_partial_floats(g) floats, as for the general form
 bool wg4_wgrad_supported(const ConvGeom& g, const float* gate);
-bool wg4_enabled();
-void wg4_set_enabled(int on);
 int wg4_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, const Amax& am, hipStream_t s);
 
 }  // namespace probav

@@ -414,31 +414,42 @@ __global__ __launch_bounds__(512, 2) void pw_fwd_h3k_kernel(const float* __restr
     XS_OUT;
 }
 
+static int g_w4_disabled = -1;         // the generation switch (w4_switch.h): the mask of disabled kernels, -1 = PROBAV_GEN1 not read yet
+static unsigned w4_disabled() { if (g_w4_disabled < 0) g_w4_disabled = (int)w4_parse_disabled(getenv("PROBAV_GEN1")); return (unsigned)g_w4_disabled; }
+bool w4_enabled(W4 k) { return w4_mask_enabled(w4_disabled(), k); }
+void w4_set_enabled(W4 k, int on) { g_w4_disabled = (int)(on ? w4_disabled() & ~w4_bit(k) : w4_disabled() | w4_bit(k)); }
 static int g_pw_dump_h3k = 0;
 void x6_pw_dump_from_forward_kernel(int on) { g_pw_dump_h3k = on ? 1 : 0; }
+
+// The kernel that serves a forward launch.  hdump (tests) comes from the 32x32x16 arrangement -- the order the reverse pass recomputes the tile in (pw_bwd_w4_kernel) -- or,
+// after x6_pw_dump_from_forward_kernel(1), from the forward kernel itself: the one-wave-per-SIMD kernel's (kernels_pf4.hip) dump IS "from the forward kernel"
+enum class PwFwdKernel { w4, h3k, h3k_dump, x6_h3_dump, x6, x6_dump };     // pw_fwd_w4_kernel | pw_fwd_h3k_kernel<dump> | pw_fwd_x6_kernel<H3 | X6, dump>
+static PwFwdKernel x6_pw_forward_select(long nvox, long vps, int D, int arith, bool hdump)
+{
+    if (arith != 2) return hdump ? PwFwdKernel::x6_dump : PwFwdKernel::x6;
+    const bool own_dump = hdump && g_pw_dump_h3k;
+    if (w4_enabled(W4::pw_fwd) && pf4_forward_supported(nvox, vps, D) && (!hdump || own_dump)) return PwFwdKernel::w4;
+    return own_dump ? PwFwdKernel::h3k_dump : (hdump ? PwFwdKernel::x6_h3_dump : PwFwdKernel::h3k);
+}
 
 int x6_pw_forward(const float* x, const float* w1frag, const float* w2frag, const float* b1, const float* b2, float* dec,
                   long nvox, long vps, int D, int arith, const PwAmax& am, hipStream_t s, float* hdump)
 {
     if (vps <= 0 || vps > nvox) vps = nvox;                          // one "sample"
     if (nvox % vps || vps > 0x7fffffffL) { set_error("x6_pw_forward: nvox must be a multiple of the voxels per sample", hipSuccess); return PROBAV_EINVAL; }
-    if (arith == 2) {
-        if (!am.x || !am.w1 || !am.w2c || !am.b1) { set_error("x6_pw_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
-        const size_t lds = (size_t)2 * 8 * 2 * H3::NP * 64 * 16 + (256 + 32 + 32 + 8 * 256) * sizeof(float);      // (+ pw_fwd_h3k_kernel's per-wave bias tables; two workgroups per CU still fit)
-        // hdump (tests): from the 32x32x16 arrangement -- the order the reverse pass recomputes the tile in (pw_bwd_w4_kernel) -- or, after
-        // x6_pw_dump_from_forward_kernel(1), from the forward kernel itself
-        if (pf4_enabled() && pf4_forward_supported(nvox, vps, D) && (!hdump || g_pw_dump_h3k))          // one wave per SIMD (kernels_pf4.hip); its dump IS "from the forward kernel"
-            return pf4_forward(x, w1frag, w2frag, b1, b2, dec, nvox, vps, D, am, s, hdump);
-        if (hdump && g_pw_dump_h3k) return launch_lds<pw_fwd_h3k_kernel<true>>("pw_fwd_x6", dim3(256 * 2), dim3(512), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, hdump);
-        if (hdump) return launch_lds<pw_fwd_x6_kernel<H3, true>>("pw_fwd_x6", dim3(256 * PwfShape<H3>::WGS), dim3(64 * PwfShape<H3>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
-                                                                 b1, b2, dec, nvox, (int)vps, D, am, hdump);
-        return launch_lds<pw_fwd_h3k_kernel<false>>("pw_fwd_x6", dim3(256 * 2), dim3(512), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
+    if (arith == 2 && (!am.x || !am.w1 || !am.w2c || !am.b1)) { set_error("x6_pw_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
+    const uint4 *w1 = (const uint4*)w1frag, *w2 = (const uint4*)w2frag;
+    const size_t lds3 = (size_t)2 * 8 * 2 * H3::NP * 64 * 16 + (256 + 32 + 32 + 8 * 256) * sizeof(float);      // (+ pw_fwd_h3k_kernel's per-wave bias tables; two workgroups per CU still fit)
+    const size_t lds6 = (size_t)2 * 8 * 2 * X6::NP * 64 * 16 + (256 + 32 + 32) * sizeof(float);
+    const dim3 g3(256 * PwfShape<H3>::WGS), t3(64 * PwfShape<H3>::WAVES), g6(256 * PwfShape<X6>::WGS), t6(64 * PwfShape<X6>::WAVES);
+    switch (x6_pw_forward_select(nvox, vps, D, arith, hdump != nullptr)) {
+    case PwFwdKernel::w4: return pf4_forward(x, w1frag, w2frag, b1, b2, dec, nvox, vps, D, am, s, hdump);
+    case PwFwdKernel::h3k_dump: return launch_lds<pw_fwd_h3k_kernel<true>>("pw_fwd_x6", dim3(256 * 2), dim3(512), lds3, s, x, w1, w2, b1, b2, dec, nvox, (int)vps, D, am, hdump);
+    case PwFwdKernel::x6_h3_dump: return launch_lds<pw_fwd_x6_kernel<H3, true>>("pw_fwd_x6", g3, t3, lds3, s, x, w1, w2, b1, b2, dec, nvox, (int)vps, D, am, hdump);
+    case PwFwdKernel::h3k: return launch_lds<pw_fwd_h3k_kernel<false>>("pw_fwd_x6", dim3(256 * 2), dim3(512), lds3, s, x, w1, w2, b1, b2, dec, nvox, (int)vps, D, am, nullptr);
+    case PwFwdKernel::x6_dump: return launch_lds<pw_fwd_x6_kernel<X6, true>>("pw_fwd_x6", g6, t6, lds6, s, x, w1, w2, b1, b2, dec, nvox, (int)vps, D, am, hdump);
+    default: return launch_lds<pw_fwd_x6_kernel<X6, false>>("pw_fwd_x6", g6, t6, lds6, s, x, w1, w2, b1, b2, dec, nvox, (int)vps, D, am, hdump);
     }
-    const size_t lds = (size_t)2 * 8 * 2 * X6::NP * 64 * 16 + (256 + 32 + 32) * sizeof(float);
-    if (hdump) return launch_lds<pw_fwd_x6_kernel<X6, true>>("pw_fwd_x6", dim3(256 * PwfShape<X6>::WGS), dim3(64 * PwfShape<X6>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
-                                                             b1, b2, dec, nvox, (int)vps, D, am, hdump);
-    return launch_lds<pw_fwd_x6_kernel<X6, false>>("pw_fwd_x6", dim3(256 * PwfShape<X6>::WGS), dim3(64 * PwfShape<X6>::WAVES), lds, s, x, (const uint4*)w1frag, (const uint4*)w2frag,
-                                                   b1, b2, dec, nvox, (int)vps, D, am, hdump);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -875,26 +886,30 @@ __global__ __launch_bounds__(512, 2) void pw_bwd_x6_kernel(
 }
 
 
+// H3: one wave per SIMD, 512 registers, no barrier in the tile loop (kernels_pw4.hip) where it applies; pw_bwd_x6_kernel<H3> is the general form (any batch, any D <= 32)
+enum class PwBwdKernel { w4, x6_h3, x6 };
+static PwBwdKernel x6_pw_backward_select(long nvox, long vps, int D, int arith)
+{
+    if (arith != 2) return PwBwdKernel::x6;
+    return w4_enabled(W4::pw_bwd) && pw4_backward_supported(nvox, vps, D) ? PwBwdKernel::w4 : PwBwdKernel::x6_h3;
+}
+
 int x6_pw_backward(const float* x, const float* dT, const float* dOut, const float* w1f, const float* w2kf, const float* w1cf,
                    const float* b1, float* dX, float* dW1, float* dW2, float* db1, float* db2, float* slabs, long nvox, long vps, int D,
                    int arith, const PwAmax& am, hipStream_t s)
 {
     if (vps <= 0 || vps > nvox) vps = nvox;
     if (nvox % vps || vps > 0x7fffffffL) { set_error("x6_pw_backward: nvox must be a multiple of the voxels per sample", hipSuccess); return PROBAV_EINVAL; }
+    if (arith == 2 && (!am.x || !am.w1 || !am.w2 || !am.b1 || !am.dt || !am.w1r)) { set_error("x6_pw_backward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
+    const uint4 *w1 = (const uint4*)w1f, *w2k = (const uint4*)w2kf, *w1c = (const uint4*)w1cf;
+    const dim3 grid(mfma_pw_backward_grid());
+    const size_t lds3 = (size_t)4 * H3::NP * PB_IMG + ((size_t)16 * PB_TB + 256) * sizeof(float) + (size_t)8 * 2 * H3::NP * PT_IMG;   // (two transpose images per wave)
+    const size_t lds6 = (size_t)4 * X6::NP * PB_IMG + ((size_t)16 * PB_TB + 256) * sizeof(float) + (size_t)8 * X6::NP * PT_IMG;
     int rc;
-    if (arith == 2) {
-        if (!am.x || !am.w1 || !am.w2 || !am.b1 || !am.dt || !am.w1r) { set_error("x6_pw_backward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
-        // round 5: one wave per SIMD, 512 registers, no barrier in the tile loop (kernels_pw4.hip).  pw_bwd_x6_kernel<H3> below is the general form: any
-        // batch, any D <= 32 (and PROBAV_GEN1=1 / pw4_set_enabled(0) for A/B runs); rounds 3 and 4's schedules of it (pw_bwd_h3s / h3t) left with round 5
-        if (pw4_enabled() && pw4_backward_supported(nvox, vps, D))
-            return pw4_backward(x, dT, dOut, w1f, w2kf, w1cf, b1, dX, dW1, dW2, db1, db2, slabs, nvox, vps, D, am, s);
-        const size_t lds = (size_t)4 * H3::NP * PB_IMG + ((size_t)16 * PB_TB + 256) * sizeof(float) + (size_t)8 * 2 * H3::NP * PT_IMG;   // (two transpose images per wave)
-        rc = launch_lds<pw_bwd_x6_kernel<H3>>("pw_bwd_x6", dim3(mfma_pw_backward_grid()), dim3(512), lds, s, x, dT, dOut, (const uint4*)w1f,
-                                              (const uint4*)w2kf, (const uint4*)w1cf, b1, dX, slabs, nvox, (int)vps, D, am);
-    } else {
-        const size_t lds = (size_t)4 * X6::NP * PB_IMG + ((size_t)16 * PB_TB + 256) * sizeof(float) + (size_t)8 * X6::NP * PT_IMG;
-        rc = launch_lds<pw_bwd_x6_kernel<X6>>("pw_bwd_x6", dim3(mfma_pw_backward_grid()), dim3(512), lds, s, x, dT, dOut, (const uint4*)w1f,
-                                              (const uint4*)w2kf, (const uint4*)w1cf, b1, dX, slabs, nvox, (int)vps, D, am);
+    switch (x6_pw_backward_select(nvox, vps, D, arith)) {
+    case PwBwdKernel::w4: return pw4_backward(x, dT, dOut, w1f, w2kf, w1cf, b1, dX, dW1, dW2, db1, db2, slabs, nvox, vps, D, am, s);
+    case PwBwdKernel::x6_h3: rc = launch_lds<pw_bwd_x6_kernel<H3>>("pw_bwd_x6", grid, dim3(512), lds3, s, x, dT, dOut, w1, w2k, w1c, b1, dX, slabs, nvox, (int)vps, D, am); break;
+    default: rc = launch_lds<pw_bwd_x6_kernel<X6>>("pw_bwd_x6", grid, dim3(512), lds6, s, x, dT, dOut, w1, w2k, w1c, b1, dX, slabs, nvox, (int)vps, D, am); break;
     }
     if (rc) return rc;
     return mfma_pw_backward_reduce(slabs, D, dW1, dW2, db1, db2, s);
@@ -1402,21 +1417,26 @@ size_t x6_wgrad_partial_floats(const ConvGeom& g)
     return (size_t)(g1 > g2 ? g1 : g2) * ((size_t)27 * g.Cin * g.Cout + g.Cout);
 }
 
+// The residual blocks' and the reducers' layers run as one-wave-per-SIMD kernel (kernels_wg4.hip); conv3_wgrad_x6_kernel is the general form (any extent, pads, reflect, gate, 32 channels).
+// H3 on the general form has PLAIN second pieces (one scale per operand tensor: a channel 2^-24 below its mates is resolved to 7e-5), so a layer without an instance of
+// the new kernel runs the unscaled x6 arithmetic on it; its H3 instance stays for A/B runs (W4::wgrad off: H3 wherever the dY image also fits, as before that kernel)
+enum class WgradX6Kernel { none, w4, x6_h3, x6 };
+static WgradX6Kernel x6_wgrad_select(const ConvGeom& g, const float* gate, int arith)
+{
+    if (!x6_wgrad_supported(g)) return WgradX6Kernel::none;
+    if (arith != 2) return WgradX6Kernel::x6;
+    if (w4_enabled(W4::wgrad)) return wg4_wgrad_supported(g, gate) ? WgradX6Kernel::w4 : WgradX6Kernel::x6;
+    return x6_wgrad_split(g, 2) ? WgradX6Kernel::x6_h3 : WgradX6Kernel::x6;
+}
+
 int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial,
                   int arith, const Amax& am, hipStream_t s)
 {
-    if (!x6_wgrad_supported(g)) { set_error("x6_conv_wgrad: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
+    const WgradX6Kernel k = x6_wgrad_select(g, gate, arith);
+    if (k == WgradX6Kernel::none) { set_error("x6_conv_wgrad: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (arith == 2 && (!am.x || !am.w)) { set_error("x6_conv_wgrad: H3 arithmetic needs the per-sample amax slots of x (am.x) and dY (am.w)", hipSuccess); return PROBAV_EINVAL; }
-    // round 5: the residual blocks' and the reducers' layers as one-wave-per-SIMD kernel (kernels_wg4.hip); this kernel is the general form (any extent, pads, reflect, gate, 32 channels).
-    // H3 on the general form would be H3 with PLAIN second pieces: one scale per operand tensor and a channel 2^-24 below its mates resolved to 7e-5 (the lifted pieces of
-    // conv3_wgrad_w4_kernel need a second accumulator set, and this kernel's 112 accumulator registers live in a budget of 128).  A layer without an instance of that kernel
-    // (depth 19, other extents, more than 256 samples) therefore runs the x6 arithmetic here -- bf16 pieces carry fp32's exponent, no operand is scaled, every slice is resolved;
-    // the H3 instance stays reachable for A/B runs (PROBAV_GEN1 = wg | 1: every layer on this kernel, H3 as in rounds 2 - 4).
-    if (arith == 2 && wg4_enabled()) {
-        if (wg4_wgrad_supported(g, gate)) return wg4_conv_wgrad(g, x, dy, gate, dw, db, partial, am, s);
-        arith = 1;
-    }
-    if (arith == 2 && x6_wgrad_split(g, 2) == 0) arith = 1;                  // (the H3 form also needs room for the dY image; the scale-free form serves the rest)
+    if (k == WgradX6Kernel::w4) return wg4_conv_wgrad(g, x, dy, gate, dw, db, partial, am, s);
+    arith = k == WgradX6Kernel::x6_h3 ? 2 : 1;
     WgArgs a;
     a.nsplit = x6_wgrad_split(g, arith); a.Wt = (g.Wo + a.nsplit - 1) / a.nsplit;
     a.N = g.N; a.H = g.Ho; a.W = g.Wo; a.T = g.To; a.Cout = g.Cout; a.Hi = g.Hi; a.Wi = g.Wi; a.Ti = g.Ti;

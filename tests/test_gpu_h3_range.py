@@ -77,7 +77,7 @@ def _oracle_conv(x, w, bias, skip, pad):
     return y
 
 
-# normConv forward (pstrip<25>), its backward-data (pstrip<32>), a reducer (row-tile kernel)
+# normConv forward (conv3_w4_kernel<25, 32>), its backward-data (conv3_w4_kernel<32, 25>), a reducer (row-tile kernel)
 CASES = [("normConv same 25->32 + skip", 4, (22, 22, 9), 25, 32, (1, 1, 1), True),
          ("bwd-data of normConv: same 32->25", 4, (22, 22, 9), 32, 25, (1, 1, 1), False),
          ("convReducer valid 32->32", 4, (22, 22, 7), 32, 32, (0, 0, 0), False)]

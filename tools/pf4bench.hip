@@ -46,7 +46,7 @@ int main(int argc, char** argv)
         std::vector<float> ya((size_t)nv * D), yb((size_t)nv * D), ha, hb_;
         std::vector<unsigned> sa(B), sb(B);
         for (int k = 0; k < 2; ++k) {
-            pf4_set_enabled(k);
+            w4_set_enabled(W4::pw_fwd, k);
             x6_pw_dump_from_forward_kernel(k);                          // k = 0: the dump of pw_fwd_x6_kernel<H3>; k = 1: of the new kernel
             hipMemset(dec, 0xff, nvmax * 32 * 4);
             if (dump) hipMemset(hd, 0xff, (size_t)nv * 256 * 4);
@@ -72,7 +72,7 @@ int main(int argc, char** argv)
     const double gflop = (double)nvmax * 2e-9 * 14592;
     for (int pass = 0; pass < 4; ++pass)
         for (int k = 0; k < 2; ++k) {
-            pf4_set_enabled(k);
+            w4_set_enabled(W4::pw_fwd, k);
             auto run = [&] { x6_pw_forward(x, w, w + fw, b1, b2, dec, nvmax, V, 25, 2, pam, 0, nullptr); };
             for (int i = 0; i < 3; ++i) run();
             hipDeviceSynchronize();

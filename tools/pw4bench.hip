@@ -55,7 +55,7 @@ int main(int argc, char** argv)
     PwAmax pam; pam.x = am_; pam.w1 = am_ + 2048; pam.w2 = am_ + 2049; pam.b1 = am_ + 2050; pam.dt = am_ + 1024; pam.y = am_ + 4096;
     pam.w2c = am_ + 2100; pam.w1r = am_ + 2200;
     auto run = [&](int newk, int B, long vps) {
-        pw4_set_enabled(newk);
+        w4_set_enabled(W4::pw_bwd, newk);
         return x6_pw_backward(x, dT, dOut, w, w + fw, w + 2 * fw, b1, dX, dW1, dW2, db1, db2, slabs, (long)B * vps, vps, D, 2, pam, 0);
     };
     auto fetch = [&](int B, long vps) {

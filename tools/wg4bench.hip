@@ -44,7 +44,7 @@ int main(int argc, char** argv)
         if (!wg4_wgrad_supported(g, gate)) { printf("B %3d %dx22x%d%s: not taken by the new kernel\n", c.B, c.H, c.T, c.red ? " reducer" : ""); continue; }
         std::vector<float> wa(nw), wb(nw), ba(32), bb(32);
         for (int k = 0; k < 2; ++k) {
-            wg4_set_enabled(k);
+            w4_set_enabled(W4::wgrad, k);
             hipMemset(dw, 0xff, nw * 4); hipMemset(db, 0xff, 32 * 4);
             if (x6_conv_wgrad(g, x, d, gate, dw, db, part, 2, am, 0)) { printf("launch failed: %s\n", last_error()); return 1; }
             hipDeviceSynchronize();
@@ -74,7 +74,7 @@ int main(int argc, char** argv)
         const double gflop = (double)BMAX * 22 * 22 * To * 2e-9 * 27 * g.Cin * 32;
         for (int pass = 0; pass < 3; ++pass)
             for (int k = 0; k < 2; ++k) {
-                wg4_set_enabled(k);
+                w4_set_enabled(W4::wgrad, k);
                 auto run = [&] { x6_conv_wgrad(g, x, d, gate, dw, db, part, 2, am, 0); };
                 for (int i = 0; i < 3; ++i) run();
                 hipDeviceSynchronize();

@@ -31,7 +31,7 @@ int main(int argc, char** argv)
     auto run = [&] { return diag::wg4_conv_wgrad(g, x, d, nullptr, dw, db, part, am, 0); };
     {   // agreement with the general form (the library's kernel) on this input
         std::vector<float> wa(nw), wb(nw);
-        wg4_set_enabled(0);
+        w4_set_enabled(W4::wgrad, 0);
         x6_conv_wgrad(g, x, d, nullptr, dw, db, part, 2, am, 0); hipDeviceSynchronize();
         hipMemcpy(wa.data(), dw, nw * 4, hipMemcpyDeviceToHost);
         hipMemset(dw, 0xff, nw * 4);
