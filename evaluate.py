@@ -6,6 +6,9 @@
     python evaluate.py --cfg C --band NIR --model --ensemble d8 [--ensemble-permute P --ensemble-seed s]     # ... its test-time self-ensemble
     python evaluate.py --cfg C --band NIR --model --tile-stride 8 [--tile-window hat|box]                    # ... its overlapped, blended tiles
     python evaluate.py --cfg C --band NIR --model --weights ema                                              # ... its EMA weights (train.py --ema-momentum)
+    python evaluate.py --cfg C --band NIR --baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered]   # the bicubic-mean baseline, no checkpoint
+    python evaluate.py --cfg C --band NIR --model --benchmark-baseline                                       # the checkpoint against that baseline
+    python evaluate.py --cfg C --band NIR --model --norm computed                                            # N_i from the esa / raw baseline (a stand-in for norm.csv)
 
 --toCompare scores the imgsetNNNN.png of a folder (test.py's output) against resolverDir/TRAINimgHR_<band>.npy, matching by id: train ids
 below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted, skipped).  --model resolves resolverDir/TRAINpatchesLR_<band>.npy
@@ -14,7 +17,10 @@ scores the images on the device; with --ensemble d8 the images are the self-ense
 probav_amd/ensemble.py), so a checkpoint is scored with and without it in one place; with --tile-stride s the images are the blended overlapping
 tiles `test.py --tile-stride s` writes (read from trimmedArrayDir/TRAINimgLR_<band>.npy, same set order and ids; probav_amd/tiles.py).  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
 Losses.shiftCompensatedcPSNR instead (HR unmasked, what the reference's script computes).  The score is mean(N_i / cPSNR_i) with N_i from
-norm.csv (default <raw_data>/norm.csv when present; lower is better).
+norm.csv (default <raw_data>/norm.csv when present; lower is better).  --baseline scores the competition's bicubic-mean baseline of the band's
+TRAIN sets (probav_amd/baseline.py; no checkpoint, no PNGs), --benchmark-baseline compares --model against it instead of a --benchmark folder, and
+--norm computed takes N_i from the esa / raw baseline's own cPSNR: a stand-in, since ESA's norm.csv was made with another interpolator
+(INTEGRATION.md).  The JSON line says where the norm came from: "norm_source": "file", "computed" or null.
 
 Prints one JSON line; writes <out>/scores.csv and, when matplotlib imports and there is a --benchmark, <out>/comparison.png.
 """
@@ -40,7 +46,8 @@ def parser(argv=None):
     p.add_argument("--toCompare", type=str, default=None, help="folder of imgsetNNNN.png to score")
     p.add_argument("--benchmark", type=str, default=None, help="folder of imgsetNNNN.png to compare against")
     p.add_argument("--band", type=str, default="both", help="NIR, RED or both")
-    p.add_argument("--norm", type=str, default=None, help="norm.csv (default: <raw_data>/norm.csv if present)")
+    p.add_argument("--norm", type=str, default=None, help="norm.csv (default: <raw_data>/norm.csv if present), or `computed`: N_i = the cPSNR of "
+                   "this repository's own esa / raw bicubic-mean baseline (a stand-in: ESA's file was made with another interpolator)")
     p.add_argument("--formula", type=str, default="esa", choices=("esa", "reference"))
     p.add_argument("--model", action="store_true", help="score the cfg's latest checkpoint on resolverDir/TRAINpatchesLR_<band>.npy")
     p.add_argument("--out", type=str, default=".", help="folder for scores.csv and comparison.png")
@@ -53,13 +60,24 @@ def parser(argv=None):
     p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
     p.add_argument("--weights", type=str, default="raw", choices=("raw", "ema"), help="with --model: score the checkpoint's raw weights (default) or "
                    "the moving average saved by train.py --ema-momentum; ema on a checkpoint without one is an error")
+    p.add_argument("--baseline", action="store_true", help="score the bicubic-mean baseline of the band's TRAIN sets (probav_amd/baseline.py); "
+                   "no checkpoint, no PNGs written")
+    p.add_argument("--benchmark-baseline", action="store_true", help="with --model: compare against the bicubic-mean baseline instead of a "
+                   "--benchmark folder")
+    from probav_amd.baseline import add_cli_args, cli_spec
+    add_cli_args(p)
     p.add_argument("--border", type=int, default=3, help=argparse.SUPPRESS)
     opt = p.parse_args(argv)
     opt.band = opt.band.upper()
     if opt.band not in ("NIR", "RED", "BOTH"):
         p.error("--band must be NIR, RED or both, got %r" % opt.band)
-    if opt.model == (opt.toCompare is not None):
-        p.error("give exactly one of --toCompare DIR and --model")
+    if int(opt.model) + int(opt.toCompare is not None) + int(opt.baseline) != 1:
+        p.error("give exactly one of --toCompare DIR, --model and --baseline")
+    if opt.benchmark_baseline and not opt.model:
+        p.error("--benchmark-baseline applies to --model")
+    if opt.benchmark_baseline and opt.benchmark is not None:
+        p.error("give at most one of --benchmark DIR and --benchmark-baseline")
+    opt.baseline_spec = cli_spec(p, opt, opt.baseline or opt.benchmark_baseline, "--baseline or --benchmark-baseline")
     if opt.ensemble != "none" and not opt.model:
         p.error("--ensemble applies to --model (a folder of PNGs is scored as it is)")
     if opt.ensemble == "none" and opt.ensemble_permute:
@@ -72,7 +90,7 @@ def parser(argv=None):
         d = getattr(opt, name)
         if d is not None and not os.path.isdir(d):
             p.error("--%s: no such folder %r" % (name, d))
-    if opt.norm is not None and not os.path.isfile(opt.norm):
+    if opt.norm is not None and opt.norm != "computed" and not os.path.isfile(opt.norm):
         p.error("--norm: no such file %r" % opt.norm)
     if not os.path.isfile(opt.cfg):
         p.error("--cfg: no such file %r" % opt.cfg)
@@ -131,6 +149,16 @@ def model_images(config, cfg_path, band, ensemble=None, tiles=None, weights="raw
     return out
 
 
+def baseline_train_images(config, bands, spec):
+    """{id: uint16 image} of the bicubic-mean baseline on the TRAIN sets of `bands` (probav_amd/baseline.py)."""
+    from probav_amd import baseline
+    out = {}
+    for b in bands:
+        imgs, ids = baseline.baseline_images(config, b, "TRAIN", spec)
+        out.update(zip(ids, imgs))
+    return out
+
+
 def main(opt):
     from probav_amd.parseConfig import parseConfig
     config = parseConfig(opt.cfg)
@@ -139,10 +167,25 @@ def main(opt):
     if norm_path is None:
         cand = os.path.join(config.get("raw_data", ""), "norm.csv")
         norm_path = cand if config.get("raw_data") and os.path.isfile(cand) else None
-    norm = scoring.read_norm(norm_path) if norm_path else None
     hr = {b: scoring.load_hr(config, b) for b in bands}
     removed = {b: scoring.read_removed(b) for b in bands}
-    if opt.model:
+    baseline_rows = {}                                      # BaselineSpec -> scored rows: one baseline serves --baseline, the benchmark and the norm
+
+    def baseline_scored(spec):
+        if spec not in baseline_rows:
+            baseline_rows[spec] = scoring.score_images(baseline_train_images(config, bands, spec), hr, border=opt.border, formula=opt.formula,
+                                                       removed=removed)
+        return baseline_rows[spec]
+
+    if norm_path == "computed":
+        from probav_amd.baseline import BaselineSpec
+        norm = {r["id"]: r["cpsnr"] for r in baseline_scored(BaselineSpec("esa", "raw"))[0]}
+    else:
+        norm = scoring.read_norm(norm_path) if norm_path else None
+    norm_source = None if norm is None else ("computed" if norm_path == "computed" else "file")
+    if opt.baseline:
+        rows, counts = baseline_scored(opt.baseline_spec)
+    elif opt.model:
         spec = None
         if opt.ensemble != "none":
             from probav_amd.ensemble import EnsembleSpec
@@ -156,9 +199,12 @@ def main(opt):
             images.update(model_images(config, opt.cfg, b, ensemble=spec, tiles=tiles, weights=opt.weights))
     else:
         images = scoring.load_sr_dir(opt.toCompare)
-    rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
+    if not opt.baseline:
+        rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
     bench_rows = None
-    if opt.benchmark is not None:
+    if opt.benchmark_baseline:
+        bench_rows = baseline_scored(opt.baseline_spec)[0]
+    elif opt.benchmark is not None:
         bench_rows, _ = scoring.score_images(scoring.load_sr_dir(opt.benchmark), hr, border=opt.border, formula=opt.formula, removed=removed)
     summary = scoring.summarize(rows, counts, norm=norm, bench_rows=bench_rows)
     summary["formula"] = opt.formula
@@ -168,7 +214,10 @@ def main(opt):
         summary["weights"] = opt.weights
     if opt.tile_stride:
         summary["tiles"] = {"stride": opt.tile_stride, "window": opt.tile_window}
+    if opt.baseline_spec is not None:
+        summary["baseline"] = {"mode": opt.baseline_spec.mode, "frames": opt.baseline_spec.frames}
     summary["norm"] = norm_path
+    summary["norm_source"] = norm_source
     os.makedirs(opt.out, exist_ok=True)
     scoring.write_csv(os.path.join(opt.out, "scores.csv"), rows, norm=norm, bench_rows=bench_rows)
     if bench_rows is not None:

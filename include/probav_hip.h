@@ -399,6 +399,32 @@ int probav_ensemble_reduce(const float* sr, const int32_t* recipe, int64_t n_bas
  *                                         replaces reconstruct_from_patches for overlapping tiles         test.py:149-160 */
 int probav_tile_blend(const float* sr, const int32_t* w, int64_t n_images, int n, int S, int hr_stride, float lo, float hi, float* out, void* stream);
 
+/* ---- bicubic-mean baseline (proba-v_amd/baseline.py), an addition of ABI 7 --------------------------------------------------------------- */
+/* The competition's baseline ('Bicubic-mean baseline'): every LR frame of an image set upscaled 3 x by the Keys cubic
+ * (a = -1/2, half-pixel centres, clamped indices) and the chosen frames averaged, in exact integer arithmetic.  frames uint16 and clear
+ * uint8 (nonzero = clear pixel) are [n_frames][H][W]; set_offsets [n_sets + 1] as above.  HR index Y reads the LR rows
+ * clamp(i0 - 1 .. i0 + 2, 0, H - 1), i0 = floor((Y - 1) / 3), with the weights over 27 of the phase (Y - 1) mod 3:
+ *     0: (0, 27, 0, 0)      1: (-2, 21, 9, -1)      2: (-1, 9, 21, -2)
+ * columns likewise; U_f[Y][X] = sum_ij wy_i wx_j frame_f[row_i][col_j], an integer over 729.
+ * mode PROBAV_BASELINE_ESA: the frames of a set whose clear count equals the set's largest, all ties included (K per set);
+ * mode PROBAV_BASELINE_CLEAR: at HR pixel (Y, X) the frames with clear[f][Y / 3][X / 3] set, or every frame of the set where none is (K per pixel).
+ *     N = sum_f U_f,  D = 729 K,  out = clip(N / D rounded half to even, 0, 65535)     (floor division, 2 (N mod D) against D, ties to even)
+ * out [n_sets][3 H][3 W] fp32 holding integers; k_used [n_sets] = K (esa) or the set's frame count (clear).  counts_scratch: int32
+ * [n_frames], the caller's; it receives every frame's clear count in esa mode and is not touched in clear mode.  Nothing is floating point
+ * and nothing is atomic, so the image does not depend on the launch.  H, W >= 1; 3 H, 3 W <= 2^20; sets of 1 .. 4096 frames
+ * (N stays below 4096 * 65535 * 1089 < 2^39).  Preconditions on the device array as probav_prep_register: set_offsets[0] = 0,
+ * set_offsets[n_sets] = n_frames, every set of 1 .. 4096 frames; a set that breaks them is not read or written and gets
+ * k_used = PROBAV_BASELINE_BAD_SET (probav_amd.baseline raises on it).  PROBAV_EINVAL, nothing launched: a null pointer, scale != 3,
+ * an unknown mode, a size outside the ranges above.  Kernel: csrc/kernels_baseline.hip; the statement it equals bit for bit:
+ * probav_amd.baseline.baseline_numpy.
+ *                                         replaces the unfinished bicubicMean / padding and the baseline upscaling it was meant to call
+ *                                                                                                     evaluate.py:142-197, utils/utils.py:534-586 */
+#define PROBAV_BASELINE_ESA 0
+#define PROBAV_BASELINE_CLEAR 1
+#define PROBAV_BASELINE_BAD_SET (-1)
+int probav_baseline_upscale_mean(const uint16_t* frames, const uint8_t* clear, const int64_t* set_offsets, int n_sets, int64_t n_frames, int H, int W,
+                                 int scale, int mode, int32_t* counts_scratch, float* out, int32_t* k_used, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,9 @@ SIGNATURES = {
     "probav_ensemble_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
     # overlapped-tile inference (csrc/kernels_tile.hip)
     "probav_tile_blend": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    # bicubic-mean baseline (csrc/kernels_baseline.hip): added under ABI 7
+    "probav_baseline_upscale_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
 }
 
 _lib = None

@@ -30,6 +30,9 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::tile_blend(sr, w, n_images, n, hr_stride, lo, hi) -> images [n_images, G, G]
                                                                             overlapping tile predictions blended by an integer window, exact
                                                                             64-bit arithmetic, rounded half to even   test.py:149-160 (tiles.py)
+  probav::baseline_upscale_mean(frames, clear, set_offsets, mode) -> (out [S, 3H, 3W], k_used [S])
+                                                                            the competition's bicubic-mean baseline of ragged image sets, exact
+                                                                            integer arithmetic   evaluate.py:142-197 (baseline.py)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -612,6 +615,52 @@ def tile_blend(sr: Tensor, w: Tensor, n_images: int, n: int, hr_stride: int, lo:
 def _(sr, w, n_images, n, hr_stride, lo, hi):
     S, G = _tile_blend_args(sr, w, n_images, n, hr_stride, lo, hi)
     return sr.new_empty((n_images, G, G), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# bicubic-mean baseline (csrc/kernels_baseline.hip; the definition and the numpy statement are in baseline.py).  No autograd: a yardstick.
+# frames [F, H, W] uint16 (int16 is taken as the same bits), clear [F, H, W] bool or uint8 (nonzero = clear), set_offsets [S + 1] int64.
+# ---------------------------------------------------------------------------------------------------------------------------------
+BASELINE_MODES = ("esa", "clear")          # index = PROBAV_BASELINE_ESA / PROBAV_BASELINE_CLEAR
+
+
+def _baseline_args(frames, clear, set_offsets, mode):
+    """-> (S, H, W) after the checks the real and the fake kernel share."""
+    if frames.dim() != 3 or clear.shape != frames.shape or set_offsets.dim() != 1 or set_offsets.shape[0] < 2:
+        raise ValueError("baseline_upscale_mean: frames, clear [F, H, W], set_offsets [S + 1]; got %s %s %s"
+                         % (tuple(frames.shape), tuple(clear.shape), tuple(set_offsets.shape)))
+    if frames.dtype not in (torch.uint16, torch.int16) or clear.dtype not in (torch.bool, torch.uint8) or set_offsets.dtype != torch.int64:
+        raise ValueError("baseline_upscale_mean: frames must be uint16 (or int16 bits), clear bool or uint8, set_offsets int64; got %s %s %s"
+                         % (frames.dtype, clear.dtype, set_offsets.dtype))
+    if mode not in BASELINE_MODES:
+        raise ValueError("baseline_upscale_mean: mode must be one of %r, got %r" % (BASELINE_MODES, mode))
+    if frames.shape[0] < 1 or frames.shape[1] < 1 or frames.shape[2] < 1:
+        raise ValueError("baseline_upscale_mean: no frames, or frames without pixels: %s" % (tuple(frames.shape),))
+    return set_offsets.shape[0] - 1, frames.shape[1], frames.shape[2]
+
+
+@torch.library.custom_op("probav::baseline_upscale_mean", mutates_args=(), device_types="cuda")
+def baseline_upscale_mean(frames: Tensor, clear: Tensor, set_offsets: Tensor, mode: str) -> tuple[Tensor, Tensor]:
+    """(out [S, 3H, 3W] fp32 holding integers, k_used [S] int32): every frame upscaled 3 x by the Keys cubic in integers over 729, the frames
+    `mode` chooses summed in int64, divided by 729 K with one rounding half to even, clipped to [0, 65535] -- baseline.baseline_numpy, bit for bit.
+    The sets must satisfy the preconditions of include/probav_hip.h (baseline.baseline_device checks them on the host before the upload); a set
+    that breaks them gets k_used = -1 and its image is left unwritten."""
+    S, H, W = _baseline_args(frames, clear, set_offsets, mode)
+    _dev(frames, "frames"), _dev(clear, "clear"), _dev(set_offsets, "set_offsets")
+    frames, clear, set_offsets = frames.contiguous(), clear.contiguous(), set_offsets.contiguous()
+    out = torch.empty((S, 3 * H, 3 * W), dtype=torch.float32, device=frames.device)
+    k_used = torch.empty((S,), dtype=torch.int32, device=frames.device)
+    counts = torch.empty((frames.shape[0],), dtype=torch.int32, device=frames.device)
+    _lib.check(_lib.lib().probav_baseline_upscale_mean(_lib.ptr(frames), _lib.ptr(clear), _lib.ptr(set_offsets), S, frames.shape[0], H, W, 3,
+                                                       BASELINE_MODES.index(mode), _lib.ptr(counts), _lib.ptr(out), _lib.ptr(k_used),
+                                                       _lib.current_stream()), "probav_baseline_upscale_mean")
+    return out, k_used
+
+
+@baseline_upscale_mean.register_fake
+def _(frames, clear, set_offsets, mode):
+    S, H, W = _baseline_args(frames, clear, set_offsets, mode)
+    return frames.new_empty((S, 3 * H, 3 * W), dtype=torch.float32), frames.new_empty((S,), dtype=torch.int32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,11 @@ hence the PNG names and the omitted ids, is the same.  ((128 - P) / s + 1)^2 / 6
 
 --weights ema predicts with the moving average of the weights that `train.py --ema-momentum M` keeps and saves beside the raw weights (the
 checkpoint's "ema" entry); --weights raw (default) is the path above.  A checkpoint without an "ema" entry is refused, not silently read raw.
+
+--method baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered] writes the competition's bicubic-mean baseline instead
+(probav_amd/baseline.py): every LR frame upscaled by the Keys cubic and the frames of maximum clearance averaged, in exact
+integer arithmetic on the device.  It reads <preprocessing_out>/arrayDir (raw: every set, unregistered) or trimmedArrayDir (registered) and
+needs no checkpoint; it does not combine with --ensemble, --tile-stride or --weights ema.  --method network (default) is the path above.
 """
 import argparse
 import logging
@@ -59,7 +64,16 @@ def parser(argv=None):
     p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
     p.add_argument("--weights", type=str, default="raw", choices=("raw", "ema"), help="which weights of the checkpoint to predict with: raw (default) or "
                    "the moving average a run with train.py --ema-momentum saved; ema on a checkpoint without one is an error")
+    p.add_argument("--method", type=str, default="network", choices=("network", "baseline"), help="network (default): the cfg's latest checkpoint; "
+                   "baseline: the competition's bicubic-mean baseline of the LR frames, which needs no checkpoint")
+    from probav_amd.baseline import add_cli_args, cli_spec
+    add_cli_args(p)
     opt = p.parse_args(argv)
+    if opt.method == "baseline":
+        for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.tile_stride != 0, "--tile-stride"), (opt.weights == "ema", "--weights ema")):
+            if given:
+                p.error("%s predicts with the network: it cannot be combined with --method baseline" % flag)
+    opt.baseline = cli_spec(p, opt, opt.method == "baseline", "--method baseline")
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
     if opt.ensemble != "none" and opt.reference_loop:
@@ -86,7 +100,21 @@ def ensemble_spec(opt):
     return EnsembleSpec(opt.ensemble, permute=opt.ensemble_permute, seed=opt.ensemble_seed)
 
 
+def main_baseline(config, opt):
+    """--method baseline: the bicubic-mean baseline of every image set (probav_amd/baseline.py), named as the network's PNGs are."""
+    from probav_amd.baseline import baseline_images
+    logger.info("[ INFO ] Bicubic-mean baseline (%s frames, %s mode)..." % (opt.baseline.frames, opt.baseline.mode))
+    imgs, ids = baseline_images(config, opt.band.upper(), "TEST" if opt.totest == "TEST" else "TRAIN", opt.baseline)
+    outDir = (config["test_out"] if opt.totest == "TEST" else config["train_out"]) + "_" + os.path.basename(opt.cfg).split(".")[0]
+    os.makedirs(outDir, exist_ok=True)
+    logger.info("[ SAVE ] Saving baseline images to %s..." % outDir)
+    for i, img in zip(ids, imgs):
+        imsave_uint16(os.path.join(outDir, "imgset%04d.png" % i), img)
+
+
 def main(config, opt):
+    if getattr(opt, "baseline", None) is not None:
+        return main_baseline(config, opt)
     logger.info("[ INFO ] Loading data...")
     tiles = tile_spec(opt)
     if tiles is not None:
