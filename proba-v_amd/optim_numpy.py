@@ -52,7 +52,7 @@ def coefficients(name, t, momentum_cache=1.0, beta_1=0.9, beta_2=0.999, epsilon=
         return beta_1, beta_2, epsilon, (1.0 - mu_t) / (1.0 - pi_t), mu_t1 / (1.0 - pi_t * mu_t1), 1.0 / (1.0 - beta_2 ** t), pi_t
     if name == "adam":
         return beta_1, beta_2, epsilon, 0.0, (1.0 - beta_2 ** t) ** 0.5 / (1.0 - beta_1 ** t), 1.0, momentum_cache
-    return 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, momentum_cache
+    return 0.0, 1.0, 1.0, 1.0, 0.0, 0.0, momentum_cache          # (beta_2 = 1: v stays 0 -- with 0 the fp32 kernel would form g * g, inf for |g| > 1.85e19)
 
 
 def update(theta, g, m, v, lr, b1, b2, eps, c_g, c_m, c_v):

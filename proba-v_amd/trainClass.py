@@ -297,6 +297,13 @@ def load_nadam_state(optimizer, step, momentum_cache, m, v):
         raise TypeError("the reference checkpoint carries Nadam slots; optimizer is %s" % type(optimizer).__name__)
 
 
+def _as_fp32(x):
+    """The value the kernels receive for a hyperparameter passed as `float` (and the value Keras holds: its hyperparameters are fp32 variables).
+    The bias corrections 1 - beta^t computed on the host must be those of the beta the kernel applies: 1 - fl32(0.999) is 1.3e-5 off 0.001, and a
+    c_v = 1 / (1 - 0.999^t) taken from the double would be off by that much against the v the kernel accumulates at small t."""
+    return float(np.float32(x))
+
+
 def _fused_update(model, p, g, st, lr, b1, b2, eps, c_g, c_m, c_v):
     """One optimizer update of the flat parameter `p`: with a WDSRModel behind it (make_optimizer passes it) the update is fused with the
     weight normalisation and operand packing of the NEXT forward pass (torch.ops.probav.optimizer_wn_step, SURVEY.md section 8f-2);
@@ -418,7 +425,7 @@ class HipNadam(_GuardedOptions, torch.optim.Optimizer):
     def step(self, closure=None):
         from . import _lib, ops                          # noqa: F401  (ops registers torch.ops.probav.nadam_step)
         for group in self.param_groups:
-            b1, b2 = group["beta_1"], group["beta_2"]
+            b1, b2 = _as_fp32(group["beta_1"]), _as_fp32(group["beta_2"])
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -457,7 +464,7 @@ class HipAdam(_GuardedOptions, torch.optim.Optimizer):
     def step(self, closure=None):
         from . import _lib, ops                          # noqa: F401  (ops registers torch.ops.probav.nadam_step)
         for group in self.param_groups:
-            b1, b2 = group["beta_1"], group["beta_2"]
+            b1, b2 = _as_fp32(group["beta_1"]), _as_fp32(group["beta_2"])
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -476,7 +483,9 @@ class HipAdam(_GuardedOptions, torch.optim.Optimizer):
 
 
 class HipSGD(_GuardedOptions, torch.optim.Optimizer):
-    """Keras ``SGD`` without momentum through the same fused launch (c_g = 1, c_m = 0, c_v = 0, eps = 1: theta -= lr g)."""
+    """Keras ``SGD`` without momentum through the same fused launch (c_g = 1, c_m = 0, c_v = 0, eps = 1: theta -= lr g).  beta_2 = 1: the slot v
+    stays what it is (0) and the denominator is sqrt(v * 0) + 1 = 1 whatever the gradient.  With beta_2 = 0 the kernel formed v = g * g, which is
+    inf in fp32 for a finite |g| > 1.85e19, and inf * c_v = NaN took the parameter with it where Keras gives theta - lr g."""
 
     def __init__(self, params, lr=1e-2, model=None, global_clipnorm=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99):
         super().__init__(params, dict(lr=lr))
@@ -494,9 +503,9 @@ class HipSGD(_GuardedOptions, torch.optim.Optimizer):
                 if not st:
                     st["m"], st["v"] = torch.zeros_like(p), torch.zeros_like(p)
                 if self.guard is None:
-                    _fused_update(self.model, p, p.grad.contiguous(), st, group["lr"], 0.0, 0.0, 1.0, 1.0, 0.0, 0.0)
+                    _fused_update(self.model, p, p.grad.contiguous(), st, group["lr"], 0.0, 1.0, 1.0, 1.0, 0.0, 0.0)
                 else:
-                    self._guarded_update(p, p.grad.contiguous(), st, group["lr"], 0.0, 0.0, 1.0, 1.0, 0.0, 0.0)
+                    self._guarded_update(p, p.grad.contiguous(), st, group["lr"], 0.0, 1.0, 1.0, 1.0, 0.0, 0.0)
 
 
 def make_optimizer(name, model, learning_rate, global_clipnorm=None, skip_nonfinite=False, use_ema=False, ema_momentum=0.99):

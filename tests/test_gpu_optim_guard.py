@@ -181,13 +181,14 @@ def test_clip_against_the_numpy_statement(dev, name, factor):
 
 # ---- 4. skip -----------------------------------------------------------------------------------------------------------------------------------
 def _advance_schedule(opt, steps):
-    """What the host does to a HipNadam's schedule in `steps` steps, without a launch."""
+    """What the host does to a HipNadam's schedule in `steps` steps, without a launch (beta_1 at its fp32 value, as HipNadam.step takes it)."""
+    from probav_amd.trainClass import _as_fp32
     for group in opt.param_groups:
         for p in group["params"]:
             st = opt.state[p]
             for _ in range(steps):
                 st["step"] += 1
-                st["momentum_cache"] *= group["beta_1"] * (1.0 - 0.5 * 0.96 ** (st["step"] * group["schedule_decay"]))
+                st["momentum_cache"] *= _as_fp32(group["beta_1"]) * (1.0 - 0.5 * 0.96 ** (st["step"] * group["schedule_decay"]))
 
 
 def test_nonfinite_gradient_costs_one_step_not_the_run(dev):
