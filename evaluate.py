@@ -5,6 +5,7 @@
     python evaluate.py --cfg C --band NIR --model          # the cfg's latest checkpoint on the TRAIN sets, no PNGs written
     python evaluate.py --cfg C --band NIR --model --ensemble d8 [--ensemble-permute P --ensemble-seed s]     # ... its test-time self-ensemble
     python evaluate.py --cfg C --band NIR --model --tile-stride 8 [--tile-window hat|box]                    # ... its overlapped, blended tiles
+    python evaluate.py --cfg C --band NIR --model --frame-windows 3 [--frame-window-step s --frame-window-weights clear|uniform]   # ... its frame-window ensemble
     python evaluate.py --cfg C --band NIR --model --weights ema                                              # ... its EMA weights (train.py --ema-momentum)
     python evaluate.py --cfg C --band NIR --baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered]   # the bicubic-mean baseline, no checkpoint
     python evaluate.py --cfg C --band NIR --model --benchmark-baseline                                       # the checkpoint against that baseline
@@ -15,7 +16,8 @@ below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted,
 with the latest checkpoint exactly as `test.py --totest TRAIN` does (same ids, removedTrainSets<BAND>.txt skipped, the same uint16 cast) and
 scores the images on the device; with --ensemble d8 the images are the self-ensemble `test.py --ensemble d8` writes (same three flags,
 probav_amd/ensemble.py), so a checkpoint is scored with and without it in one place; with --tile-stride s the images are the blended overlapping
-tiles `test.py --tile-stride s` writes (read from trimmedArrayDir/TRAINimgLR_<band>.npy, same set order and ids; probav_amd/tiles.py).  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
+tiles `test.py --tile-stride s` writes (read from trimmedArrayDir/TRAINimgLR_<band>.npy, same set order and ids; probav_amd/tiles.py); with --frame-windows W
+they are the frame-window ensemble `test.py --frame-windows W` writes (the same file and flags; probav_amd/frame_windows.py).  The metric (proba-v_amd/scoring.py) is the ESA shift-compensated clear PSNR; --formula reference gives
 Losses.shiftCompensatedcPSNR instead (HR unmasked, what the reference's script computes).  The score is mean(N_i / cPSNR_i) with N_i from
 norm.csv (default <raw_data>/norm.csv when present; lower is better).  --baseline scores the competition's bicubic-mean baseline of the band's
 TRAIN sets (probav_amd/baseline.py; no checkpoint, no PNGs), --benchmark-baseline compares --model against it instead of a --benchmark folder, and
@@ -58,6 +60,8 @@ def parser(argv=None):
     p.add_argument("--tile-stride", type=int, default=0, help="with --model: score the blend of overlapping tiles at this LR stride, as "
                    "test.py --tile-stride writes it; 0 = disjoint patches")
     p.add_argument("--tile-window", type=str, default=None, choices=("hat", "box"), help="with --tile-stride: the blend window (default hat)")
+    from probav_amd.frame_windows import add_cli_args as add_window_args, cli_window_args
+    add_window_args(p, "with --model: ")
     p.add_argument("--weights", type=str, default="raw", choices=("raw", "ema"), help="with --model: score the checkpoint's raw weights (default) or "
                    "the moving average saved by train.py --ema-momentum; ema on a checkpoint without one is an error")
     p.add_argument("--baseline", action="store_true", help="score the bicubic-mean baseline of the band's TRAIN sets (probav_amd/baseline.py); "
@@ -96,21 +100,25 @@ def parser(argv=None):
         p.error("--cfg: no such file %r" % opt.cfg)
     from probav_amd.tiles import cli_tile_args
     cli_tile_args(p, opt)
+    if opt.frame_windows and not opt.model:
+        p.error("--frame-windows applies to --model (a folder of PNGs is scored as it is)")
+    opt.windows = cli_window_args(p, opt)
     if not 0 <= opt.border <= 3:
         p.error("--border must be in 0..3")
     return opt
 
 
-def model_images(config, cfg_path, band, ensemble=None, tiles=None, weights="raw"):
+def model_images(config, cfg_path, band, ensemble=None, tiles=None, weights="raw", windows=None):
     """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN, without the PNGs.
     ensemble: an EnsembleSpec for the self-ensemble images test.py --ensemble writes (None: the plain prediction).
     tiles: a TileSpec for the blended overlapping tiles test.py --tile-stride writes (None: disjoint patches).
-    weights: "raw" or "ema" -- the checkpoint entry test.py --weights predicts with."""
+    weights: "raw" or "ema" -- the checkpoint entry test.py --weights predicts with.
+    windows: a FrameWindowSpec for the frame-window ensemble test.py --frame-windows writes (None: one prediction per tile)."""
     import torch
     from probav_amd.modelsTF import WDSRConv3D
-    from probav_amd.testClass import evaluate_device, evaluate_tiled_frames
+    from probav_amd.testClass import evaluate_device, evaluate_tiled_frames, evaluate_windowed_frames
     from probav_amd.trainClass import ModelTrainer
-    if tiles is not None:
+    if tiles is not None or windows is not None:
         framesLR = np.load(os.path.join(config["preprocessing_out"], "trimmedArrayDir", "TRAINimgLR_%s.npy" % band), allow_pickle=True)
     else:
         dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
@@ -133,7 +141,9 @@ def model_images(config, cfg_path, band, ensemble=None, tiles=None, weights="raw
             raise SystemExit("evaluate.py --model --weights ema: %s" % exc)
     if trainer.latest_checkpoint is None and trainer._tf_latest() is None:
         raise SystemExit("evaluate.py --model: no checkpoint under %s" % ckptDir)
-    if tiles is not None:
+    if windows is not None:
+        y_preds = evaluate_windowed_frames(model, framesLR, windows, config, tiles=tiles, ensemble=ensemble)
+    elif tiles is not None:
         y_preds = evaluate_tiled_frames(model, framesLR, tiles, config, ensemble=ensemble)
     else:
         y_preds = evaluate_device(model, patchLR) if ensemble is None else evaluate_device(model, patchLR, ensemble=ensemble, final="round")
@@ -196,7 +206,7 @@ def main(opt):
             tiles = TileSpec(opt.tile_stride, opt.tile_window)
         images = {}
         for b in bands:
-            images.update(model_images(config, opt.cfg, b, ensemble=spec, tiles=tiles, weights=opt.weights))
+            images.update(model_images(config, opt.cfg, b, ensemble=spec, tiles=tiles, weights=opt.weights, windows=getattr(opt, "windows", None)))
     else:
         images = scoring.load_sr_dir(opt.toCompare)
     if not opt.baseline:
@@ -214,6 +224,8 @@ def main(opt):
         summary["weights"] = opt.weights
     if opt.tile_stride:
         summary["tiles"] = {"stride": opt.tile_stride, "window": opt.tile_window}
+    if getattr(opt, "windows", None) is not None:
+        summary["frame_windows"] = {"windows": opt.windows.windows, "step": opt.windows.step, "weights": opt.windows.weights}
     if opt.baseline_spec is not None:
         summary["baseline"] = {"mode": opt.baseline_spec.mode, "frames": opt.baseline_spec.frames}
     summary["norm"] = norm_path

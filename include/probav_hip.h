@@ -425,6 +425,39 @@ int probav_tile_blend(const float* sr, const int32_t* w, int64_t n_images, int n
 int probav_baseline_upscale_mean(const uint16_t* frames, const uint8_t* clear, const int64_t* set_offsets, int n_sets, int64_t n_frames, int H, int W,
                                  int scale, int mode, int32_t* counts_scratch, float* out, int32_t* k_used, void* stream);
 
+/* ---- frame-window ensemble (proba-v_amd/frame_windows.py), an addition of ABI 7 ---------------------------------------------------------- */
+/* W predictions of every tile, each from another window of k frames slid over the tile's frames sorted from clearest to dirtiest, and their
+ * weighted mean ('Frame windows').
+ * Gather.  patches [N][T_pre][win][win] fp32 and counts [N][T_pre] int32 (masked pixels of every frame of the tile, 0 .. pixels = win^2):
+ * the outputs of probav_prep_patches.  Per tile: frame t is eligible iff counts[t] < L (L = frame_windows.max_masked(pixels, threshold):
+ * the builder's fp64 test turned into an integer one on the host); when none is, all T_pre are.  The E eligible frames ordered by (count
+ * ascending, frame index ascending) are r[0 .. E); m = ceil(k / E); Q[i] = r[i / m] for i < E m, the dataset builder's tiled, sorted list;
+ * window j < W takes Q[(j step + i) % (E m)], i < k.
+ *     x      [N][W][win][win][k] fp32: x[n][j][y][x][i] = patches[n][sel[n][j][i]][y][x], copied bit for bit (test.py's transpose);
+ *     sel    [N][W][k] int32: the frame indices;
+ *     weight [N][W] int32: mode PROBAV_WINDOWS_CLEAR the sum over the window's k frames of (pixels - count), mode PROBAV_WINDOWS_UNIFORM 1;
+ *            a tile whose weights are all 0 gets all 1.
+ * (W - 1) step + k <= T_pre, so a tile whose frames are all eligible never wraps; W = 1 is exempt (one window is the builder's own choice, which
+ * tiles a pool shorter than k).  One workgroup per tile stages the tile in LDS once:
+ * T_pre planes of win^2 floats, each padded by up to 3, which must fit 160 KiB beside 1 KiB of tables (T_pre win^2 <= 40 960 floats at the most: win = 44 admits
+ * T_pre <= 21).  PROBAV_EINVAL, nothing launched: a null pointer, N < 1, T_pre, W or k outside 1..64, step < 1, (W - 1) step + k > T_pre with W > 1,
+ * L outside 0 .. win^2 + 1, an unknown mode, a tile that does not fit LDS.
+ * Reduce.  sr [N W][S][S] fp32 (raw network output, or members that are already rounded), weight [N][W] int32, non-negative with a positive
+ * sum per tile (what the gather writes); p = rint(clip(sr, lo, hi)) as probav_clip_round;
+ *     out[n][y][x] = (sum_j weight[n][j] p[n W + j][y][x]) / (sum_j weight[n][j])   rounded half to even
+ * in exact 64-bit integer arithmetic (floor division, 2 (N mod D) against D, ties to the even quotient): out [N][S][S] fp32 holding integers.
+ * Range: weight < 2^31, p <= 2^24, W <= 64: sums below 2^61 (the gather's weights are at most k pixels: below 2^46 at the shipped sizes).
+ * A tile whose weights sum to 0 or less breaks the precondition and gets 0.  PROBAV_EINVAL, nothing launched: a null pointer, N or S below 1,
+ * W outside 1..64, lo > hi or a NaN bound, clip bounds beyond +-2^24.  Kernels: csrc/kernels_windows.hip; the statements they equal bit for
+ * bit: probav_amd.frame_windows.frame_windows_select_numpy / _gather_numpy / _reduce_numpy.
+ *                                         the "sliding window over the LR frames sorted from clearest to dirtiest" of the reference's
+ *                                         ideas to try; the frame choice is removeAndReplaceDirtyFrames'     utils/dataGenerator.py:326-551 */
+#define PROBAV_WINDOWS_CLEAR 0
+#define PROBAV_WINDOWS_UNIFORM 1
+int probav_frame_windows_gather(const float* patches, const int32_t* counts, int64_t N, int T_pre, int win, int k, int L, int W, int step, int mode,
+                                float* x, int32_t* weight, int32_t* sel, void* stream);
+int probav_frame_windows_reduce(const float* sr, const int32_t* weight, int64_t N, int W, int S, float lo, float hi, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,9 @@ SIGNATURES = {
     # bicubic-mean baseline (csrc/kernels_baseline.hip): added under ABI 7
     "probav_baseline_upscale_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
+    # frame-window ensemble (csrc/kernels_windows.hip): added under ABI 7
+    "probav_frame_windows_gather": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "probav_frame_windows_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

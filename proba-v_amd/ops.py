@@ -30,6 +30,11 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::tile_blend(sr, w, n_images, n, hr_stride, lo, hi) -> images [n_images, G, G]
                                                                             overlapping tile predictions blended by an integer window, exact
                                                                             64-bit arithmetic, rounded half to even   test.py:149-160 (tiles.py)
+  probav::frame_windows_gather(patches, counts, k, limit, windows, step, mode) -> (x [N, W, win, win, k, 1], weight [N, W], sel [N, W, k])
+                                                                            the frames of every tile chosen and ordered on the device, the inputs
+                                                                            of W sliding windows over them written from one read of the tile
+  probav::frame_windows_reduce(sr, weight, lo, hi) -> [N, S, S]             the weighted mean of the W clipped, rounded predictions of every tile,
+                                                                            exact 64-bit arithmetic, rounded half to even   (frame_windows.py)
   probav::baseline_upscale_mean(frames, clear, set_offsets, mode) -> (out [S, 3H, 3W], k_used [S])
                                                                             the competition's bicubic-mean baseline of ragged image sets, exact
                                                                             integer arithmetic   evaluate.py:142-197 (baseline.py)
@@ -615,6 +620,104 @@ def tile_blend(sr: Tensor, w: Tensor, n_images: int, n: int, hr_stride: int, lo:
 def _(sr, w, n_images, n, hr_stride, lo, hi):
     S, G = _tile_blend_args(sr, w, n_images, n, hr_stride, lo, hi)
     return sr.new_empty((n_images, G, G), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# frame-window ensemble (csrc/kernels_windows.hip; the definition and the numpy statements are in frame_windows.py).  No autograd: inference.
+# patches [N, T_pre, win, win] fp32 and counts [N, T_pre] int32: the builder's unfold of N tiles; sr [N W, S, S] or [..., S, S, 1] fp32.
+# ---------------------------------------------------------------------------------------------------------------------------------
+WINDOW_MODES = ("clear", "uniform")        # index = PROBAV_WINDOWS_CLEAR / PROBAV_WINDOWS_UNIFORM
+WINDOWS_MAX = 64                           # W, and T_pre (one lane of the ranking wave per frame)
+WINDOWS_LDS_BYTES = 160 * 1024 - 1040      # the staged tile: T_pre planes of _windows_plane_stride(win^2) floats beside the kernel's tables
+
+
+def _windows_plane_stride(px):
+    """The LDS plane stride of the gather kernel (csrc/kernels_windows.hip, fw_plane_stride)."""
+    while px % 32 in (0, 1, 8, 11, 16, 21, 24, 31):
+        px += 1
+    return px
+
+
+def _windows_gather_args(patches, counts, k, limit, windows, step, mode):
+    """-> (N, T_pre, win) after the checks the real and the fake kernel share."""
+    if patches.dim() != 4 or counts.dim() != 2 or patches.shape[2] != patches.shape[3] or tuple(counts.shape) != tuple(patches.shape[:2]):
+        raise ValueError("frame_windows_gather: patches [N, T_pre, win, win], counts [N, T_pre]; got %s %s" % (tuple(patches.shape), tuple(counts.shape)))
+    if patches.dtype != torch.float32 or counts.dtype != torch.int32:
+        raise ValueError("frame_windows_gather: patches must be float32, counts int32; got %s %s" % (patches.dtype, counts.dtype))
+    if mode not in WINDOW_MODES:
+        raise ValueError("frame_windows_gather: mode must be one of %r, got %r" % (WINDOW_MODES, mode))
+    N, T_pre, win = patches.shape[0], patches.shape[1], patches.shape[2]
+    if N < 1 or win < 1 or not 1 <= T_pre <= WINDOWS_MAX or not 1 <= windows <= WINDOWS_MAX or not 1 <= k <= WINDOWS_MAX or step < 1:
+        raise ValueError("frame_windows_gather: N = %d tiles of %d frames, k = %d, %d windows at step %d; N, step >= 1, 1 <= T_pre, k, windows <= %d"
+                         % (N, T_pre, k, windows, step, WINDOWS_MAX))
+    if windows > 1 and (windows - 1) * step + k > T_pre:
+        raise ValueError("frame_windows_gather: (windows - 1) * step + k = %d frames, the pool has T_pre = %d" % ((windows - 1) * step + k, T_pre))
+    if not 0 <= limit <= win * win + 1:
+        raise ValueError("frame_windows_gather: limit = %d outside 0 .. win^2 + 1 = %d" % (limit, win * win + 1))
+    if T_pre * win * win > 40960 or 4 * T_pre * _windows_plane_stride(win * win) > WINDOWS_LDS_BYTES:
+        raise ValueError("frame_windows_gather: a tile of %d frames of %d x %d does not fit the 160 KiB of LDS it is staged in (at most 40960 floats, "
+                         "each frame padded by up to 3)" % (T_pre, win, win))
+    return N, T_pre, win
+
+
+@torch.library.custom_op("probav::frame_windows_gather", mutates_args=(), device_types="cuda")
+def frame_windows_gather(patches: Tensor, counts: Tensor, k: int, limit: int, windows: int, step: int, mode: str) -> tuple[Tensor, Tensor, Tensor]:
+    """(x [N, W, win, win, k, 1] fp32, weight [N, W] int32, sel [N, W, k] int32): per tile the frames with counts < limit (all when none)
+    ordered by (count, index), tiled to at least k as the dataset builder tiles them, window j taking k of them from position j step on;
+    x holds the chosen frames bit for bit with the frame index innermost, weight the clear pixels of every window's frames ("clear") or 1
+    ("uniform"), all 1 where all are 0 -- frame_windows.frame_windows_select_numpy + _gather_numpy."""
+    N, T_pre, win = _windows_gather_args(patches, counts, k, limit, windows, step, mode)
+    _dev(patches, "patches"), _dev(counts, "counts")
+    patches, counts = patches.contiguous(), counts.contiguous()
+    x = torch.empty((N, windows, win, win, k, 1), dtype=torch.float32, device=patches.device)
+    weight = torch.empty((N, windows), dtype=torch.int32, device=patches.device)
+    sel = torch.empty((N, windows, k), dtype=torch.int32, device=patches.device)
+    _lib.check(_lib.lib().probav_frame_windows_gather(_lib.ptr(patches), _lib.ptr(counts), N, T_pre, win, k, limit, windows, step, WINDOW_MODES.index(mode),
+                                                      _lib.ptr(x), _lib.ptr(weight), _lib.ptr(sel), _lib.current_stream()), "probav_frame_windows_gather")
+    return x, weight, sel
+
+
+@frame_windows_gather.register_fake
+def _(patches, counts, k, limit, windows, step, mode):
+    N, T_pre, win = _windows_gather_args(patches, counts, k, limit, windows, step, mode)
+    return (patches.new_empty((N, windows, win, win, k, 1), dtype=torch.float32), patches.new_empty((N, windows), dtype=torch.int32),
+            patches.new_empty((N, windows, k), dtype=torch.int32))
+
+
+def _windows_reduce_args(sr, weight, lo, hi):
+    """-> (N, W, S) after the checks the real and the fake kernel share."""
+    if sr.dim() == 4 and sr.shape[3] == 1:
+        sr = sr[..., 0]
+    if sr.dim() != 3 or sr.shape[1] != sr.shape[2] or weight.dim() != 2:
+        raise ValueError("frame_windows_reduce: sr [N W, S, S] (or [..., S, S, 1]), weight [N, W]; got %s %s" % (tuple(sr.shape), tuple(weight.shape)))
+    if sr.dtype != torch.float32 or weight.dtype != torch.int32:
+        raise ValueError("frame_windows_reduce: sr must be float32, weight int32; got %s %s" % (sr.dtype, weight.dtype))
+    N, W, S = weight.shape[0], weight.shape[1], sr.shape[1]
+    if N < 1 or S < 1 or not 1 <= W <= WINDOWS_MAX or sr.shape[0] != N * W:
+        raise ValueError("frame_windows_reduce: %d predictions of side %d do not make %d tiles of %d windows (1 <= W <= %d)" % (sr.shape[0], S, N, W, WINDOWS_MAX))
+    if not lo <= hi:
+        raise ValueError("frame_windows_reduce: lo = %r > hi = %r" % (lo, hi))
+    return N, W, S
+
+
+@torch.library.custom_op("probav::frame_windows_reduce", mutates_args=(), device_types="cuda")
+def frame_windows_reduce(sr: Tensor, weight: Tensor, lo: float, hi: float) -> Tensor:
+    """out[n] = (sum_j weight[n, j] p[n W + j]) / (sum_j weight[n, j]) rounded half to even in exact 64-bit integer arithmetic,
+    p = rint(clip(sr, lo, hi)) -> [N, S, S] fp32 holding integers -- frame_windows.frame_windows_reduce_numpy.  The weights must be
+    non-negative with a positive sum per tile (what frame_windows_gather writes)."""
+    N, W, S = _windows_reduce_args(sr, weight, lo, hi)
+    _dev(sr, "sr"), _dev(weight, "weight")
+    sr, weight = sr.contiguous(), weight.contiguous()
+    out = torch.empty((N, S, S), dtype=torch.float32, device=sr.device)
+    _lib.check(_lib.lib().probav_frame_windows_reduce(_lib.ptr(sr), _lib.ptr(weight), N, W, S, lo, hi, _lib.ptr(out), _lib.current_stream()),
+               "probav_frame_windows_reduce")
+    return out
+
+
+@frame_windows_reduce.register_fake
+def _(sr, weight, lo, hi):
+    N, W, S = _windows_reduce_args(sr, weight, lo, hi)
+    return sr.new_empty((N, S, S), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

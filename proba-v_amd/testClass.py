@@ -13,6 +13,7 @@ from . import _lib, ops            # noqa: F401  (ops registers torch.ops.probav
 from .ensemble import EnsembleSpec, ensemble_reduce_numpy, validate_ensemble_recipe      # noqa: F401  (re-exported)
 from . import tiles as _tiles
 from .tiles import TileSpec, tile_blend_numpy      # noqa: F401  (re-exported)
+from .frame_windows import FrameWindowSpec         # noqa: F401  (re-exported)
 
 
 def _device_of(model):
@@ -256,6 +257,81 @@ def evaluate_tiled_frames(model, imgsLR_masked, spec, config, ensemble=None, lau
     return [im[:, :, None] for im in imgs]
 
 
+def resolve_windowed(model, patches, counts, wspec, tspec=None, ensemble=None, launch_batch=None):
+    """The frame-window ensemble of one chunk of images (frame_windows.py states it).  patches [images, n n, T_pre, win, win] fp32 and counts
+    [images, n n, T_pre] int32 are the builder's unfold at the tile stride (device tensors); `wspec` a FrameWindowSpec.  One gather kernel
+    chooses the frames of every tile and writes the inputs of its W windows, the forward passes run over the flat [images n n W, win, win,
+    k, 1] inputs in launch sets (with an `ensemble` through `resolve_ensemble`'s kernels, every window member rounded), one reduce kernel
+    takes the weighted integer mean of the W members of every tile and `tile_blend` places the tiles: `tspec` (a TileSpec), or stride P with
+    the box window, the plain stitch -> [images, G, G].  Integer arithmetic after each member's rint: the images do not depend on the
+    launch sets."""
+    dev = _device_of(model)
+    if dev.type != "cuda":
+        raise RuntimeError("the model lives on %s: the frame windows run as HIP kernels on a gfx950 device (no CPU fallback)" % dev)
+    if patches.dim() != 5 or counts.dim() != 3:
+        raise ValueError("patches [images, n n, T_pre, win, win] and counts [images, n n, T_pre] expected, got %s %s" % (tuple(patches.shape), tuple(counts.shape)))
+    images, nn_, T_pre, win = patches.shape[:4]
+    n = int(round(nn_ ** 0.5))
+    P, r, k = model.patchSizeLR, model.scale, model.numImgLR
+    if n * n != nn_:
+        raise ValueError("%d tiles per image do not make a square grid" % nn_)
+    wspec.validate(T_pre, k)
+    tspec = TileSpec(P, "box") if tspec is None else tspec
+    if not 1 <= tspec.stride <= P:
+        raise ValueError("tile stride %d outside 1..%d" % (tspec.stride, P))
+    S = r * P
+    w = torch.from_numpy(tspec.weights(S)).to(dev)
+    x, weight, _ = torch.ops.probav.frame_windows_gather(patches.reshape(images * nn_, T_pre, win, win), counts.reshape(images * nn_, T_pre), k,
+                                                         wspec.limit(win * win), wspec.windows, wspec.step, wspec.weights)
+    flat = x.reshape((-1,) + tuple(x.shape[2:]))
+    sr = torch.empty((flat.shape[0], S, S), dtype=torch.float32, device=dev)
+    if ensemble is not None:
+        i = 0
+        for out in _ensemble_launch_sets(model, flat, ensemble, "round", launch_batch):
+            sr[i:i + out.shape[0]] = out
+            i += out.shape[0]
+    else:
+        per = max(1, LAUNCH_BATCH if launch_batch is None else launch_batch)
+        with torch.no_grad():
+            for i in range(0, flat.shape[0], per):
+                sr[i:i + per] = model(flat[i:i + per], training=False)[..., 0]
+    del x, flat
+    tiles_sr = torch.ops.probav.frame_windows_reduce(sr, weight, 0.0, float(2 ** 16))
+    return torch.ops.probav.tile_blend(tiles_sr, w, images, n, r * tspec.stride, 0.0, float(2 ** 16))
+
+
+def resolve_windowed_frames(model, imgsLR_masked, wspec, config, tiles=None, ensemble=None, launch_batch=None, budget=None):
+    """The registered LR frames of whole image sets (trimmedArrayDir/<TEST|TRAIN>imgLR_<band>.npy, masked [images, T_pre, 1, H, H]) -> the
+    frame-window images [images, G, G] on the device: the builder's unfold at the tile stride (`tiles`, a TileSpec; None: stride P, the
+    plain stitch) + `resolve_windowed`, in chunks of whole images sized so that the unfolded tiles, the W-fold network inputs and the
+    predictions of a chunk each stay under `budget` bytes (default tiles.CHUNK_BYTES).  No counts come to the host."""
+    from . import frame_windows as _fw, prep
+    S_, T_pre, C, H, W_ = imgsLR_masked.shape
+    if C != 1 or H != W_:
+        raise ValueError("square greyscale frames [images, T, 1, H, H] expected, got %s" % (imgsLR_masked.shape,))
+    P, b, win, _, k, _ = _tiles.geometry(config)
+    tspec = TileSpec(P, "box") if tiles is None else tiles
+    tspec.validate(P, H)
+    wspec = wspec.bind(config).validate(T_pre, k, config)
+    per = _fw.images_per_chunk(wspec, tspec, config, H, T_pre, budget)
+    outs = []
+    for i in range(0, S_, per):
+        chunk = imgsLR_masked[i:i + per]
+        data = np.ma.getdata(chunk).reshape(-1, T_pre, H, H)
+        mask = np.ma.getmaskarray(chunk).reshape(-1, T_pre, H, H)
+        pt, _, pc = prep._device_patches(data, mask, b, win, tspec.stride)
+        outs.append(resolve_windowed(model, pt, pc, wspec, tspec, ensemble=ensemble, launch_batch=launch_batch))
+        del pt, pc
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+def evaluate_windowed_frames(model, imgsLR_masked, wspec, config, tiles=None, ensemble=None, launch_batch=None, budget=None):
+    """`resolve_windowed_frames` in the form `evaluate_device` returns: a list of [G, G, 1] float64 arrays, one copy back."""
+    imgs = resolve_windowed_frames(model, imgsLR_masked, wspec, config, tiles=tiles, ensemble=ensemble, launch_batch=launch_batch, budget=budget)
+    imgs = imgs.cpu().numpy().astype(np.float64)
+    return [im[:, :, None] for im in imgs]
+
+
 def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round", tiles=None):
     """All image sets at once: patches [sets, n*n, P+s, P+s, T, 1] -> uint16-range images [sets, 3nP, 3nP] (device tensor).
     Samples are independent in every kernel family (models/modelsTF.py:15-43 has no cross-sample term; the H3 kernels scale their
@@ -293,12 +369,19 @@ def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble
     return stitch_device(torch.cat(outs) if len(outs) > 1 else outs[0], sets)
 
 
-def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round", tiles=None):
+def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round", tiles=None, windows=None, config=None):
     """test.py:103-111 through the device pipeline: every image set in micro-batches of `micro_batch` patches (16 = the reference's
     resolveByBatch; coalesced into launch sets unless `launch_batch` says otherwise), clip / round and the 8 x 8 stitch on the device, ONE
     copy back.  Returns a list of [384, 384, 1] float64 arrays, element for element what the reference's `evaluate` returns.
     `ensemble`, `final`: the self-ensemble of `resolve_images` instead of the plain prediction (None: today's path and bytes).
-    `tiles`: a TileSpec when X_test_patches are overlapping tiles to be blended (`resolve_images`; None: today's path and bytes)."""
+    `tiles`: a TileSpec when X_test_patches are overlapping tiles to be blended (`resolve_images`; None: today's path and bytes).
+    `windows`: a FrameWindowSpec when X_test_patches are the registered frames of whole image sets (masked [images, T_pre, 1, H, H]) and the
+    images are their frame-window ensemble, `evaluate_windowed_frames` with the parsed cfg `config` (`tiles` is then the tile grid of the
+    frames; None: today's path and bytes)."""
+    if windows is not None:
+        if final != "round" or config is None:
+            raise ValueError("frame windows give integers (final must be 'round', got %r) and take the parsed cfg as config=" % (final,))
+        return evaluate_windowed_frames(model, X_test_patches, windows, config, tiles=tiles, ensemble=ensemble, launch_batch=launch_batch)
     if tiles is not None:
         imgs = resolve_images(model, X_test_patches, launch_batch=launch_batch, ensemble=ensemble, final=final, tiles=tiles)
     elif ensemble is None:

@@ -16,13 +16,19 @@ builder chooses them, every tile predicted, and the predictions blended by an in
 hence the PNG names and the omitted ids, is the same.  ((128 - P) / s + 1)^2 / 64 times the forward passes (3.5 x at s = 8); combines with
 --ensemble.  --tile-stride 0 (default) is the path above, byte for byte.
 
+--frame-windows W [--frame-window-step s --frame-window-weights clear|uniform] writes the frame-window ensemble instead (probav_amd/frame_windows.py,
+INTEGRATION.md): per tile, W windows of num_low_res_imgs frames slid over the frames of trimmedArrayDir/<TEST|TRAIN>imgLR_<band>.npy sorted from
+clearest to dirtiest, one prediction per window, their mean weighted by clear pixels in exact integer arithmetic on the device.  W times the forward
+passes; it needs num_low_res_imgs_pre >= (W - 1) s + num_low_res_imgs; combines with --tile-stride, --ensemble and --weights ema.
+--frame-windows 0 (default) is the path above, byte for byte.
+
 --weights ema predicts with the moving average of the weights that `train.py --ema-momentum M` keeps and saves beside the raw weights (the
 checkpoint's "ema" entry); --weights raw (default) is the path above.  A checkpoint without an "ema" entry is refused, not silently read raw.
 
 --method baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered] writes the competition's bicubic-mean baseline instead
 (probav_amd/baseline.py): every LR frame upscaled by the Keys cubic and the frames of maximum clearance averaged, in exact
 integer arithmetic on the device.  It reads <preprocessing_out>/arrayDir (raw: every set, unregistered) or trimmedArrayDir (registered) and
-needs no checkpoint; it does not combine with --ensemble, --tile-stride or --weights ema.  --method network (default) is the path above.
+needs no checkpoint; it does not combine with --ensemble, --tile-stride, --frame-windows or --weights ema.  --method network (default) is the path above.
 """
 import argparse
 import logging
@@ -34,7 +40,8 @@ import torch
 from probav_amd.modelsTF import WDSRConv3D
 from probav_amd.parseConfig import parseConfig
 from probav_amd.pngio import imsave_uint16
-from probav_amd.testClass import evaluate, evaluate_device, evaluate_tiled_frames
+from probav_amd.frame_windows import add_cli_args as add_window_args, cli_window_args
+from probav_amd.testClass import evaluate, evaluate_device, evaluate_tiled_frames, evaluate_windowed_frames
 from probav_amd.tiles import cli_tile_args
 from probav_amd.trainClass import ModelTrainer
 
@@ -66,11 +73,13 @@ def parser(argv=None):
                    "the moving average a run with train.py --ema-momentum saved; ema on a checkpoint without one is an error")
     p.add_argument("--method", type=str, default="network", choices=("network", "baseline"), help="network (default): the cfg's latest checkpoint; "
                    "baseline: the competition's bicubic-mean baseline of the LR frames, which needs no checkpoint")
+    add_window_args(p)
     from probav_amd.baseline import add_cli_args, cli_spec
     add_cli_args(p)
     opt = p.parse_args(argv)
     if opt.method == "baseline":
-        for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.tile_stride != 0, "--tile-stride"), (opt.weights == "ema", "--weights ema")):
+        for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.tile_stride != 0, "--tile-stride"), (opt.weights == "ema", "--weights ema"),
+                            (opt.frame_windows != 0, "--frame-windows")):
             if given:
                 p.error("%s predicts with the network: it cannot be combined with --method baseline" % flag)
     opt.baseline = cli_spec(p, opt, opt.method == "baseline", "--method baseline")
@@ -81,6 +90,9 @@ def parser(argv=None):
     if opt.tile_stride and opt.reference_loop:
         p.error("--reference-loop is the reference's plain loop: it cannot be combined with --tile-stride")
     cli_tile_args(p, opt)
+    if opt.frame_windows and opt.reference_loop:
+        p.error("--reference-loop is the reference's plain loop: it cannot be combined with --frame-windows")
+    opt.windows = cli_window_args(p, opt)
     return opt
 
 
@@ -117,7 +129,8 @@ def main(config, opt):
         return main_baseline(config, opt)
     logger.info("[ INFO ] Loading data...")
     tiles = tile_spec(opt)
-    if tiles is not None:
+    windows = getattr(opt, "windows", None)
+    if tiles is not None or windows is not None:
         framesLR = np.load(os.path.join(config["preprocessing_out"], "trimmedArrayDir", "%simgLR_%s.npy" % (opt.totest, opt.band)), allow_pickle=True)
     else:
         dataDir = os.path.join(config["preprocessing_out"], "resolverDir")
@@ -139,7 +152,12 @@ def main(config, opt):
         raise SystemExit("test.py --weights ema: %s" % exc)
     logger.info("[ INFO ] Generating predictions...")
     spec = ensemble_spec(opt)
-    if tiles is not None:
+    if windows is not None:
+        logger.info("[ INFO ] %d frame windows at step %d, %s weights%s%s" % (windows.windows, windows.step, windows.weights,
+                                                                           "" if tiles is None else ", overlapping tiles at stride %d (%s window)" % (tiles.stride, tiles.window),
+                                                                           "" if spec is None else ", self-ensemble of %d members per window" % spec.V))
+        y_preds = evaluate_windowed_frames(model, framesLR, windows, config, tiles=tiles, ensemble=spec)
+    elif tiles is not None:
         logger.info("[ INFO ] Overlapping tiles at stride %d, %s window%s" % (tiles.stride, tiles.window, "" if spec is None else ", self-ensemble of %d members per tile" % spec.V))
         y_preds = evaluate_tiled_frames(model, framesLR, tiles, config, ensemble=spec)
     elif spec is not None:
