@@ -23,6 +23,9 @@
  *     PROBAV_EHIP (-3) a HIP call failed; probav_last_error() gives the text (thread-local).
  *   - thread-safety: an engine handle and its workspace may be used by one thread at a time;
  *     distinct handles are independent (one process per GPU under data parallelism).
+ *   - NaN and inf in any buffer are ordinary data.  What each entry point does with them, and the four contracts the library keeps (a
+ *     non-finite training step shows in the loss or in probav_grad_guard; clean samples are untouched by poisoned batch mates; non-finite
+ *     parameters are refused by the Python loaders; a non-finite prediction stays non-finite) is INTEGRATION.md, "Non-finite values".
  */
 #ifndef PROBAV_HIP_H
 #define PROBAV_HIP_H

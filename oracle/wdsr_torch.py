@@ -5,7 +5,9 @@ TEST INFRASTRUCTURE ONLY (see oracle/__init__.py) -- PARITY UNPINNED.
 Second, independent formulation of oracle/wdsr_numpy.py: convolutions go through
 ``torch.nn.functional.conv3d/conv2d`` on permuted tensors and gradients come from autograd
 (the stand-in for ``tf.GradientTape`` at models/trainClass.py:126-131).  It runs in fp64 as the
-gradient oracle and in fp32 on all host cores as the timed CPU baseline of bench.py.
+gradient oracle, in fp32 on all host cores as the timed CPU baseline of bench.py, and in fp32 as the reference of the
+non-finite contracts (tests/nonfinite_cases.py: fp64 does not overflow where fp32 does) -- the network and the L1 / L2 / cPSNR
+terms follow the dtype of their tensors, the two table losses and candidate_grad take a `dtype` argument.
 """
 import torch
 import torch.nn.functional as F
@@ -122,11 +124,11 @@ def shift_tables(hr, mask, pred, cropBorder=3, only=None):
     return _shift_terms(hr, mask, pred, cropBorder, only)
 
 
-def candidate_grad(table_fn, pred, arg, upstream=1.0):
+def candidate_grad(table_fn, pred, arg, upstream=1.0, dtype=torch.float64):
     """Autograd through candidate `arg` alone: d(upstream * mean_B table[arg[b], b])/d(pred), or d(upstream * table[arg])/d(pred) for a
     batch-level table.  table_fn(pred, only) evaluates the listed shift ids only (nothing of any other candidate enters the graph).  This is
     what the device differentiates: the shift it selected, not tf.reduce_min's equal split among exact ties."""
-    pt = torch.as_tensor(pred).detach().to(torch.float64).clone().requires_grad_(True)
+    pt = torch.as_tensor(pred).detach().to(dtype).clone().requires_grad_(True)
     arg = [int(a) for a in (arg.reshape(-1).tolist() if hasattr(arg, "reshape") else ([arg] if isinstance(arg, int) else list(arg)))]
     ids = sorted(set(arg))
     t = table_fn(pt, ids)
@@ -182,17 +184,17 @@ def shift_l1edge_loss(hr, mask, pred, border=3, pi=0.7):
     return shift_l1edge_table(hr, mask, pred, border, pi).min(dim=0).values.mean()
 
 
-def shift_l1edge_table(hr, mask, pred, border=3, pi=0.7, only=None):
+def shift_l1edge_table(hr, mask, pred, border=3, pi=0.7, only=None, dtype=torch.float64):
     """[shifts, B] candidates of cfg loss = sobel_l1_mix (models/loss.py:86-97, 126-137, 214-219): min over the shifts of
     pi * L1 + (1 - pi) * sum |tf.image.sobel_edges(HR) - sobel_edges(corrected SR)| / n, batch mean.
     tf.image.sobel_edges = depthwise 3x3 cross-correlation of the REFLECT-padded image with
     [[-1,-2,-1],[0,0,0],[1,2,1]] (dy) and its transpose (dx)."""
     import torch.nn.functional as F
-    hr, pred = hr.to(torch.float64), pred.to(torch.float64)
-    m = mask.to(torch.float64)
+    hr, pred = hr.to(dtype), pred.to(dtype)
+    m = mask.to(dtype)
     S = pred.shape[1]
     L = S - 2 * border
-    ky = torch.tensor([[-1., -2., -1.], [0., 0., 0.], [1., 2., 1.]], dtype=torch.float64)
+    ky = torch.tensor([[-1., -2., -1.], [0., 0., 0.], [1., 2., 1.]], dtype=dtype)
     k = torch.stack([ky, ky.t()]).unsqueeze(1)                      # [2,1,3,3]
 
     def sobel(img):                                                  # [B,L,L,1] -> [B,2,L,L]
@@ -216,17 +218,17 @@ def shift_revssim_loss(hr, mask, pred, border=3, bit_depth=16, eta=0.25):
     return shift_revssim_table(hr, mask, pred, border, bit_depth, eta).min()
 
 
-def shift_revssim_table(hr, mask, pred, border=3, bit_depth=16, eta=0.25, only=None):
+def shift_revssim_table(hr, mask, pred, border=3, bit_depth=16, eta=0.25, only=None, dtype=torch.float64):
     """[shifts] candidates of cfg loss = l1msssim (models/loss.py:99-124, 189-212), with the reference's quirks: exponential (not Gaussian) windows
     exp(-x / (2 sigma^2)) over x = linspace(-L/2, L/2, L); C1 in the contrast term; variances (not standard deviations) called sigma;
     one scalar per shift for the WHOLE batch, minimum over the shifts."""
-    hr, pred = hr.to(torch.float64), pred.to(torch.float64)
-    m = mask.to(torch.float64)
+    hr, pred = hr.to(dtype), pred.to(dtype)
+    m = mask.to(dtype)
     B, S = pred.shape[0], pred.shape[1]
     L = S - 2 * border
     nb = 2.0 ** bit_depth - 1
     C1, C3 = (0.01 * nb) ** 2, (0.03 * nb) ** 2 / 2
-    x = torch.linspace(-L / 2, L / 2, L, dtype=torch.float64)
+    x = torch.linspace(-L / 2, L / 2, L, dtype=dtype)
     cp = pred[:, border:border + L, border:border + L]
     cands = []
     for i, j in _shift_ids(border, only):

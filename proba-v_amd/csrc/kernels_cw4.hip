@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256, 1) void conv3_w4_kernel(Cw4Args a, const float
                 if (K < 16 && j == 2) {
                     const int e = K, jj = e >> 2, i = e & 3;
                     float v = ldexpf(pacc[e], eun[e]);
-                    if (RELU) v = fmaxf(v, lo);
+                    if (RELU) v = relu_keep_nan(v, lo);
                     const float o = SKIP ? v + skq[jj][i] : v;
                     skq[jj][i] = o;
                     if ((e & 1) == 0) m2 = o; else asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(omax) : "v"(m2), "v"(o));
@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256, 1) void conv3_w4_kernel(Cw4Args a, const float
         for (int e = 0; e < 16; ++e) {
             const int jj = e >> 2, i = e & 3;
             float v = ldexpf(accB[e], eun[e]);                             // (the second round of a pair accumulates into accB)
-            if (RELU) v = fmaxf(v, lo);
+            if (RELU) v = relu_keep_nan(v, lo);
             const float o = SKIP ? v + skq[jj][i] : v;
             skq[jj][i] = o;
             omax = fmaxf(omax, fabsf(o));

@@ -39,18 +39,23 @@ __global__ __launch_bounds__(256) void conv_direct_fwd_kernel(
 #pragma unroll
     for (int j = 0; j < COUT_T; ++j) acc[j] = 0.f;
 
+    // A tap on the zero padding is MULTIPLIED by its zero, not skipped: 0 * w is NaN for a non-finite filter value, as it is in every kernel that
+    // materialises its pads and in the fp64 oracle ('Non-finite values').  Its loads go to voxel 0 of the axis, a valid address.
     for (int a = 0; a < g.kh; ++a) {
         int ih = h + a - g.ph;
+        bool pad_h = false;
         if (g.reflect_hw) ih = reflect_idx(ih, g.Hi);
-        else if (ih < 0 || ih >= g.Hi) continue;
+        else if (ih < 0 || ih >= g.Hi) { pad_h = true; ih = 0; }
         for (int b = 0; b < g.kw; ++b) {
             int iw = wo + b - g.pw;
+            bool pad_w = pad_h;
             if (g.reflect_hw) iw = reflect_idx(iw, g.Wi);
-            else if (iw < 0 || iw >= g.Wi) continue;
+            else if (iw < 0 || iw >= g.Wi) { pad_w = true; iw = 0; }
             for (int c = 0; c < g.kt; ++c) {
                 int it = t + c - g.pt;
+                bool pad = pad_w;
                 if (g.reflect_t) it = reflect_idx(it, g.Ti);
-                else if (it < 0 || it >= g.Ti) continue;
+                else if (it < 0 || it >= g.Ti) { pad = true; it = 0; }
                 const long vin = (((long)n * g.Hi + ih) * g.Wi + iw) * g.Ti + it;
                 const float* xp = x + vin * g.Cin;
                 const float* gp = gate ? gate + vin * g.Cin : nullptr;
@@ -71,6 +76,7 @@ __global__ __launch_bounds__(256) void conv_direct_fwd_kernel(
                     }
 #pragma unroll
                     for (int u = 0; u < VEC; ++u) {
+                        if (pad) xv[u] = 0.f;
                         const float* wr = wp + (long)(ci + u) * g.Cout;
 #pragma unroll
                         for (int j = 0; j < COUT_T; ++j) acc[j] = fmaf(xv[u], wr[j], acc[j]);
@@ -84,7 +90,7 @@ __global__ __launch_bounds__(256) void conv_direct_fwd_kernel(
 #pragma unroll
     for (int j = 0; j < COUT_T; ++j) {
         float o = acc[j] + (bias ? bias[co0 + j] : 0.f);
-        if (g.relu) o = fmaxf(o, 0.f);
+        if (g.relu) o = relu_keep_nan(o);
         if (sp) o += sp[j];
         yp[j] = o;
     }
@@ -154,7 +160,7 @@ __global__ __launch_bounds__(256) void conv3_cin1_fwd_kernel(ConvGeom g, const f
                         const float4 q = wt[(dh * 3 + dw) * 3 + dt];
                         acc.x = fmaf(xv, q.x, acc.x); acc.y = fmaf(xv, q.y, acc.y); acc.z = fmaf(xv, q.z, acc.z); acc.w = fmaf(xv, q.w, acc.w);
                     }
-            if (g.relu) { acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f); }
+            if (g.relu) { acc.x = relu_keep_nan(acc.x); acc.y = relu_keep_nan(acc.y); acc.z = relu_keep_nan(acc.z); acc.w = relu_keep_nan(acc.w); }
             *reinterpret_cast<float4*>(yrow + (long)v * 32 + 4 * cg) = acc;
             omax = fmaxf(fmaxf(omax, fmaxf(fabsf(acc.x), fabsf(acc.y))), fmaxf(fabsf(acc.z), fabsf(acc.w)));
         }
@@ -256,7 +262,7 @@ __global__ __launch_bounds__(256) void conv3_up_fwd_kernel(ConvGeom g, const flo
 #pragma unroll
         for (int j = 0; j < 9; ++j) o = kp == j ? acc[j] : o;
         o += bias ? bias[kp] : 0.f;
-        if (g.relu) o = fmaxf(o, 0.f);
+        if (g.relu) o = relu_keep_nan(o);
         y[(((long)n * g.Ho + h) * g.Wo + wo) * 9 + kp] = o;
     }
     }
@@ -706,7 +712,7 @@ __device__ __forceinline__ void rp_conv(const float* src, int Hi, int Cin, const
             }
 #pragma unroll
         for (int j = 0; j < RP_C; ++j) {
-            const float o = RELU ? fmaxf(acc[j], 0.f) : acc[j];
+            const float o = RELU ? relu_keep_nan(acc[j]) : acc[j];
             if (KEEP) keep[v * RP_C + j] = o;
             out[v * RP_C + j] = o;
         }

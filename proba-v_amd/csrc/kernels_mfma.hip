@@ -624,7 +624,7 @@ __global__ __launch_bounds__(256, 2) void conv3_mfma_kernel(TileArgs a, const fl
                 float v = tsel ? acc1[r] : acc0[r];
                 if constexpr (AM == 2) v = ldexpf(v, eun);                // back from the operands' power-of-two scales
                 v += bv;
-                if (g.relu) v = fmaxf(v, 0.f);
+                if (g.relu) v = relu_keep_nan(v);
                 ov[r] += v;
                 omax = fmaxf(omax, oo[r] >= 0 ? fabsf(ov[r]) : 0.f);
             }
@@ -1213,7 +1213,7 @@ __global__ __launch_bounds__(512, 2) void conv3_strip_kernel(StripArgs a, const 
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         float v = ov[i] + bv;
-                        if (g.relu) v = fmaxf(v, 0.f);
+                        if (g.relu) v = relu_keep_nan(v);
                         ov[i] = v + sk[i];
                     }
                 } else {
@@ -1233,7 +1233,7 @@ __global__ __launch_bounds__(512, 2) void conv3_strip_kernel(StripArgs a, const 
 #pragma unroll
                         for (int i = 0; i < 16; ++i) {
                             float v = ov[i] + bv;
-                            if (g.relu) v = fmaxf(v, 0.f);
+                            if (g.relu) v = relu_keep_nan(v);
                             ov[i] = v + s2[i];
                         }
                     }
@@ -1506,7 +1506,7 @@ __global__ __launch_bounds__(512, 2) void conv3_pstrip_kernel(StripArgs a, const
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float v = ldexpf(acc[i] + fv[i], eun) + bv;                   // final values in the accumulator layout: the filter column's exponent and the bias are per lane here
-                if (g.relu) v = fmaxf(v, 0.f);
+                if (g.relu) v = relu_keep_nan(v);
                 slot[rowmap(i, half) * 32 + col] = v;                         // [voxel][channel]
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // (a wave's LDS operations execute in order: the wait orders the compiler)
@@ -2237,7 +2237,7 @@ __global__ __launch_bounds__(512, 2) void conv3_pp_kernel(StripArgs a, const flo
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         float v = ldexpf(keep16[4 * jj + i] + xq[i], eq4[i]) + bq[i];
-                        if (g.relu) v = fmaxf(v, 0.f);
+                        if (g.relu) v = relu_keep_nan(v);
                         o[i] = v + skq[jj][i];
                     }
                     if (full) {
@@ -2266,7 +2266,7 @@ __global__ __launch_bounds__(512, 2) void conv3_pp_kernel(StripArgs a, const flo
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         float v = ldexpf(keep[jj][i] + xq[i], eun8[v_][i]) + bv8[v_][i];
-                        if (g.relu) v = fmaxf(v, 0.f);
+                        if (g.relu) v = relu_keep_nan(v);
                         o[i] = v + skq[jj][i];
                     }
                     if (full) {
@@ -2286,7 +2286,7 @@ __global__ __launch_bounds__(512, 2) void conv3_pp_kernel(StripArgs a, const flo
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     float v = ldexpf(acc[i], eun) + bv;                       // the filter column's exponent and the bias are per lane in the accumulator layout
-                    if (g.relu) v = fmaxf(v, 0.f);
+                    if (g.relu) v = relu_keep_nan(v);
                     turn[rowmap(i, half) * 32 + col] = v;
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // (a wave's LDS operations execute in order: the wait orders the compiler)

@@ -35,6 +35,9 @@ __device__ __forceinline__ float wave_sum(float v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// sign(e) of the L1 terms' derivatives: -1, 0, 1 -- and NaN for NaN.  `e > 0 ? 1 : (e < 0 ? -1 : 0)` calls a NaN zero: one NaN in a
+// prediction made every e of its sample NaN, hence every sign and the whole gradient exactly 0 beside a NaN loss ('Non-finite values')
+__device__ __forceinline__ double sign_keep_nan(double e) { return e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : (e == e ? 0.0 : e)); }
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
@@ -186,7 +189,7 @@ __device__ __forceinline__ void wn_forward_body(const WnLayer* __restrict__ laye
 #pragma unroll
         for (int j = 0; j < WN_Q; ++j) ss = fmaf(q[j], q[j], ss);              // (the same order as the loop: zeros beyond the column add nothing)
         ss = wave_sum(ss);
-        const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));            // tf.nn.l2_normalize epsilon
+        const float inv = 1.0f / sqrtf(ss < 1e-12f ? 1e-12f : ss);   // tf.nn.l2_normalize epsilon (written so that a NaN sum stays NaN: fmaxf would clamp it)
         const float scale = gain * inv;
         if (lane == 0) inv_norm[L.n_off + co] = inv;
 #pragma unroll
@@ -203,7 +206,7 @@ __device__ __forceinline__ void wn_forward_body(const WnLayer* __restrict__ laye
     } else {
         for (int k = lane; k < L.K; k += 64) { const float q = v[(long)k * L.Cout + co]; ss = fmaf(q, q, ss); }
         ss = wave_sum(ss);
-        const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+        const float inv = 1.0f / sqrtf(ss < 1e-12f ? 1e-12f : ss);
         const float scale = gain * inv;
         if (lane == 0) inv_norm[L.n_off + co] = inv;
         for (int k = lane; k < L.K; k += 64) {
@@ -1007,7 +1010,7 @@ __global__ __launch_bounds__(256) void shift_loss_bwd_kernel(
         const int r = k / L, c = k - r * L;
         const double m = M[(i + r) * S + j + c] ? 1.0 : 0.0;
         const double e = (double)H[(i + r) * S + j + c] - ((double)P[(border + r) * S + border + c] + bias) * m;
-        const double sg = which == 1 ? (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) : 2.0 * e;
+        const double sg = which == 1 ? sign_keep_nan(e) : 2.0 * e;
         ssum += sg * m;
     }
     ssum = wave_sum(ssum);
@@ -1020,7 +1023,7 @@ __global__ __launch_bounds__(256) void shift_loss_bwd_kernel(
         if (r >= 0 && r < L && c >= 0 && c < L) {
             const double m = M[(i + r) * S + j + c] ? 1.0 : 0.0;
             const double e = (double)H[(i + r) * S + j + c] - ((double)P[Y * S + X] + bias) * m;
-            const double sg = which == 1 ? (e > 0.0 ? 1.0 : (e < 0.0 ? -1.0 : 0.0)) : 2.0 * e;
+            const double sg = which == 1 ? sign_keep_nan(e) : 2.0 * e;
             gk = (float)(-(m / cnt) * (sg - ssum / cnt) * (double)scale);
         }
         G[k] = gk;
@@ -1148,8 +1151,8 @@ __global__ __launch_bounds__(256) void shift_l1edge_bwd_kernel(
         const int c0 = mirror(c - 1, L), c2 = mirror(c + 1, L);
         const double gy = ((double)sD[r2 + c0] + 2.0 * sD[r2 + c] + sD[r2 + c2]) - ((double)sD[r0 + c0] + 2.0 * sD[r0 + c] + sD[r0 + c2]);
         const double gx = ((double)sD[r0 + c2] + 2.0 * sD[r1 + c2] + sD[r2 + c2]) - ((double)sD[r0 + c0] + 2.0 * sD[r1 + c0] + sD[r2 + c0]);
-        sY[k] = gy > 0.0 ? 1.f : (gy < 0.0 ? -1.f : 0.f);
-        sX[k] = gx > 0.0 ? 1.f : (gx < 0.0 ? -1.f : 0.f);
+        sY[k] = (float)sign_keep_nan(gy);
+        sX[k] = (float)sign_keep_nan(gx);
     }
     __syncthreads();
     // adjoint of the two correlations on the PADDED crop: position (u, v) in [-1, L] x [-1, L] collects the outputs q it feeds
@@ -1182,7 +1185,7 @@ __global__ __launch_bounds__(256) void shift_l1edge_bwd_kernel(
             for (int bb = 0; bb < 3; ++bb)
                 if (us[a] != -2 && vs[bb] != -2) acc += sG[(us[a] + 1) * Lp + vs[bb] + 1];
         const float d = sD[k];
-        const float g = pi * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) + (1.f - pi) * acc;
+        const float g = pi * (float)sign_keep_nan((double)d) + (1.f - pi) * acc;
         sY[k] = g;                                                   // sY is dead: reuse for G * n
         gm += (double)g * (M[(i + r) * S + j + c] ? 1.0 : 0.0);
     }

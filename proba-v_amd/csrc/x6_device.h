@@ -85,6 +85,9 @@ __device__ __forceinline__ unsigned amax_over_samples(const unsigned* slots, int
     for (int o = 32; o; o >>= 1) { const unsigned v = (unsigned)__shfl_xor((int)m, o, 64); m = v > m ? v : m; }
     return m;
 }
+// The ReLU of an output epilogue: NaN goes through (fmaxf(NaN, 0) is 0, and a layer that turns NaN into a finite number hides a diverged
+// step from the loss and the gradient guard: INTEGRATION.md, 'Non-finite values').  lo = 0, or -inf where a run-time flag switches the ReLU off.
+__device__ __forceinline__ float relu_keep_nan(float v, float lo = 0.f) { return v < lo ? lo : v; }
 __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }      // -126 <= e <= 127
 // the largest |value| a wave has produced -> its tensor's slot (one atomic per wave)
 __device__ __forceinline__ void amax_commit(float m, unsigned* slot)

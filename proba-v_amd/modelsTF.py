@@ -81,16 +81,35 @@ class WDSRModel(torch.nn.Module):
             out += [g[L.g_off:L.v_off], g[L.v_off:L.b_off].view(L.vshape), g[L.b_off:L.b_off + L.cout]]
         return out
 
+    def _require_finite(self, flat, what):
+        """Non-finite parameters are refused where they enter ('Non-finite values', contract P): a ReLU layer maps NaN to 0,
+        so a NaN in a ReLU layer's bias would give a finite prediction, a finite loss and a gradient of exactly 0 -- nothing downstream could
+        see it.  One reduction over the flat buffer, on paths that load 535 k floats anyway; the search for the name runs only on failure."""
+        finite = torch.isfinite(flat.detach().reshape(-1))
+        if bool(finite.all()):
+            return
+        i = int((~finite).nonzero()[0])
+        for L in self.layers:
+            if i < L.b_off + L.cout:
+                key = "g" if i < L.v_off else "v" if i < L.b_off else "bias"
+                raise ValueError("%s: non-finite parameter in %s/%s (%r at element %d of the flat buffer; first of %d): refused, see INTEGRATION.md "
+                                 "'Non-finite values'" % (what, L.name, key, float(flat.detach().reshape(-1)[i]), i, int((~finite).sum())))
+        raise ValueError("%s: non-finite parameter at element %d" % (what, i))
+
     def load_variables(self, params):
-        """params: {layer: {"g","v","bias"}} numpy/torch -> flat buffer (e.g. a converted checkpoint)."""
+        """params: {layer: {"g","v","bias"}} numpy/torch -> flat buffer (e.g. a converted checkpoint).  A NaN or inf anywhere in `params` is a
+        ValueError naming the first offending layer and tensor; the model's parameters are then unchanged."""
+        staged = torch.empty(self.flat.numel(), dtype=torch.float32)
+        for L in self.layers:
+            p = params[L.name]
+            for key, lo, hi in (("g", L.g_off, L.v_off), ("v", L.v_off, L.b_off), ("bias", L.b_off, L.b_off + L.cout)):
+                t = torch.as_tensor(p[key]).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+                if t.numel() != hi - lo:
+                    raise ValueError("%s/%s: expected %d values, got %d" % (L.name, key, hi - lo, t.numel()))
+                staged[lo:hi] = t
+        self._require_finite(staged, "load_variables")
         with torch.no_grad():
-            for L in self.layers:
-                p = params[L.name]
-                for key, lo, hi in (("g", L.g_off, L.v_off), ("v", L.v_off, L.b_off), ("bias", L.b_off, L.b_off + L.cout)):
-                    t = torch.as_tensor(p[key], dtype=torch.float32).reshape(-1)
-                    if t.numel() != hi - lo:
-                        raise ValueError("%s/%s: expected %d values, got %d" % (L.name, key, hi - lo, t.numel()))
-                    self.flat[lo:hi] = t.to(self.flat.device)
+            self.flat.copy_(staged)
         self.invalidate_weight_cache()
 
     def _apply(self, fn, recurse=True):
@@ -99,8 +118,11 @@ class WDSRModel(torch.nn.Module):
         self.invalidate_weight_cache()
         return out
 
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        flat = state_dict.get("flat") if hasattr(state_dict, "get") else None
+        if torch.is_tensor(flat) and flat.numel() == self.flat.numel():      # (any other shape is torch's own error, below)
+            self._require_finite(flat, "load_state_dict")
+        out = super().load_state_dict(state_dict, *args, **kwargs)
         self.invalidate_weight_cache()
         return out
 
@@ -245,7 +267,8 @@ class WDSRModel(torch.nn.Module):
             with model.weights_from(ema):
                 y = model(x)                                # the prediction of the EMA weights
 
-        flat: float32, contiguous, `param_count` values in the model's layout, on the model's device.  On entry its weight normalisation and operand
+        flat: float32, contiguous, `param_count` finite values in the model's layout, on the model's device (a NaN or inf is a ValueError naming
+        the layer and tensor: INTEGRATION.md, 'Non-finite values').  On entry its weight normalisation and operand
         packing are built once (probav_weight_cache_build) into a cache that belongs to the scope, so every pass inside starts at its first
         convolution and is bit for bit the pass of a model loaded with those values.  The buffer must not change while the scope is open.  Forward
         only: a pass that would need gradients raises.  Scopes nest; on exit the model is back on `self.flat` and its untouched cache."""
@@ -254,6 +277,7 @@ class WDSRModel(torch.nn.Module):
             raise ValueError("weights_from: a contiguous float32 buffer of %d values on %s, got %s %s on %s"
                              % (self.flat.numel(), self.flat.device, flat.dtype, tuple(flat.shape), flat.device))
         flat = flat.reshape(-1)
+        self._require_finite(flat, "weights_from")                       # one reduction and one read-back per scope, not per pass
         n = _lib.lib().probav_weight_cache_bytes(self._handle())
         cache = self._alt_wcache if self._alt is None else None          # (a nested scope gets a buffer of its own)
         if cache is None or cache.device != flat.device:
