@@ -31,12 +31,14 @@ from fractions import Fraction
 
 import numpy as np
 
+from .inference import FIRST_ID, numbered
+from .intmath import round_half_even_div
+
 SCALE = 3
 MAX_FRAMES = 4096                 # frames per set (csrc/kernels_baseline.hip)
 MODES = ("esa", "clear")          # index = PROBAV_BASELINE_ESA / PROBAV_BASELINE_CLEAR
 FRAMES = ("raw", "registered")
 BAD_SET = -1                      # PROBAV_BASELINE_BAD_SET
-FIRST_ID = {("TEST", "NIR"): 1306, ("TEST", "RED"): 1160, ("TRAIN", "NIR"): 594, ("TRAIN", "RED"): 0}    # test.py
 SETS_PER_LAUNCH = 256             # baseline_images: image sets per call (a band's 600 sets of 128 x 128 frames need no more than ~0.5 GB at once)
 
 
@@ -80,17 +82,6 @@ def upscale_numpy(frames):
     ci, cw = _taps(p.shape[2])
     v = sum(rw[None, :, k, None] * p[:, ri[:, k], :] for k in range(4))
     return sum(cw[None, None, :, k] * v[:, :, ci[:, k]] for k in range(4))
-
-
-def round_half_even_div(N, D):
-    """N / D rounded half to even, in integers (D > 0, any sign of N): floor division, then 2 (N mod D) against D."""
-    N, D = np.asarray(N, np.int64), np.asarray(D, np.int64)
-    if (D <= 0).any():
-        raise ValueError("round_half_even_div: D must be positive")
-    q = N // D                                                         # floor
-    r = N - q * D                                                      # 0 <= r < D
-    up = (2 * r > D) | ((2 * r == D) & (q % 2 != 0))
-    return q + up
 
 
 def check_sets(set_offsets, n_frames):
@@ -212,19 +203,13 @@ def load_sets(config, band, split, frames):
         return fr, cl, [first + k for k in range(len(fr))]              # every set of the band, as ESA scores them
     if frames != "registered":
         raise ValueError("baseline frames must be one of %r, got %r" % (FRAMES, frames))
-    from . import scoring
     a = np.load(os.path.join(config["preprocessing_out"], "trimmedArrayDir", "%simgLR_%s.npy" % (split, band)), allow_pickle=True)
     data, masked = np.ma.getdata(a), np.ma.getmaskarray(a)              # [sets, T, 1, H, W], mask = obscured
     if data.ndim != 5 or data.shape[2] != 1:
         raise ValueError("trimmedArrayDir/%simgLR_%s.npy: expected [sets, T, 1, H, W], got %r" % (split, band, data.shape))
     if np.any(data != np.rint(data)) or (data.size and (data.min() < 0 or data.max() > 65535)):
         raise ValueError("trimmedArrayDir/%simgLR_%s.npy: the frames are not 16-bit integers" % (split, band))
-    ids, i, omit = [], first, set(scoring.read_removed(band))           # test.py's rule: the removed ids are skipped, whatever the split
-    for _ in range(len(data)):
-        while i in omit:
-            i += 1
-        ids.append(i)
-        i += 1
+    ids = [i for i, _ in numbered(data, split, band)]                   # test.py's rule: the removed ids are skipped, whatever the split
     return [d[:, 0].astype(np.uint16) for d in data], [~m[:, 0] for m in masked], ids
 
 

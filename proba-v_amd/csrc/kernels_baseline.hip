@@ -67,6 +67,7 @@ __device__ __forceinline__ void bsl_pass(long long p0, long long p1, long long p
 }
 
 // N / (729 K) rounded half to even, 1 <= K <= 4096, |N| <= 1089 * 65535 * K; clipped to [0, 65535]
+// (not image_math.h's round_div_half_even: a narrower algorithm, unsigned 32-bit steps with the fixed divisor 729 taken first)
 __device__ __forceinline__ float bsl_mean(long long N, unsigned K)
 {
     const unsigned D = 729u * K;                           // < 2^22

@@ -26,6 +26,7 @@
 // decision); the host validates recipes first (ensemble.py).  Neither kernel reads the recipe's base index to address the predictions.
 #include "probav_common.h"
 #include "augment_part.h"
+#include "image_math.h"
 #include "../../include/probav_hip.h"
 
 namespace probav {
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(AUG_THREADS) void ensemble_reduce_kernel(const floa
             const int src = Q0 + y * QI + x * QJ;
             AugVec<float, W> a = *reinterpret_cast<AugVec<float, W>*>(acc + e);
 #pragma unroll
-            for (int j = 0; j < W; ++j) a.v[j] += rintf(fminf(fmaxf(tile[src + j * QJ], g.lo), g.hi));      // probav_clip_round's arithmetic
+            for (int j = 0; j < W; ++j) a.v[j] += clip_rint(tile[src + j * QJ], g.lo, g.hi);
             *reinterpret_cast<AugVec<float, W>*>(acc + e) = a;
         }
         __syncthreads();

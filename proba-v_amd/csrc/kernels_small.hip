@@ -6,6 +6,7 @@
 //   clip + round-half-even                              (test.py:117-119, models/testClass.py:27-28)
 //   shift-compensated L1 / L2 / cPSNR fwd + bwd         (models/loss.py:37-84, 140-187, 226-238)
 #include "probav_common.h"
+#include "image_math.h"
 #include "../../include/probav_hip.h"
 #include <cstdlib>
 #include <vector>
@@ -798,7 +799,7 @@ int reflect_fold3(const float* dpad, float* dx, int N, int H, int W, int T, int 
 __global__ __launch_bounds__(256) void clip_round_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n, float lo, float hi)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = rintf(fminf(fmaxf(in[i], lo), hi));
+    if (i < n) out[i] = clip_rint(in[i], lo, hi);
 }
 int clip_round(const float* in, float* out, size_t n, float lo, float hi, hipStream_t s)
 {

@@ -16,6 +16,7 @@
 // pixel is read exactly once.  Wd = 4 (16-byte loads and stores) when S, hr_stride (hence G and every tile origin) are multiples of 4 and the
 // arrays are 16-byte aligned: the four pixels of a group then lie under the same tiles.  Wd = 1 otherwise.
 #include "probav_common.h"
+#include "image_math.h"
 #include "../../include/probav_hip.h"
 
 namespace probav {
@@ -28,16 +29,6 @@ struct TileGeom {
     int n, S, hs, G;                    // tiles per axis, side of a prediction, HR stride between tile origins, side of an image
     float lo, hi;
 };
-
-struct alignas(16) TileVec4 { float v[4]; };
-
-__device__ __forceinline__ float tile_round_div(long long N, long long D)
-{
-    long long q = N / D, r = N % D;     // D > 0; C++ truncates, the definition floors
-    if (r < 0) { r += D; q -= 1; }
-    if (2 * r > D || (2 * r == D && (q & 1))) q += 1;
-    return (float)q;
-}
 
 template <int Wd>
 __global__ __launch_bounds__(TILE_THREADS) void tile_blend_kernel(const float* __restrict__ sr, const int32_t* __restrict__ w, TileGeom g, size_t groups,
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_blend_kernel(const float* _
             const float* src = sr + ((img * g.n + a) * g.n + c) * px + (size_t)dy * g.S + dx;
             float m[Wd];
             if (Wd == 4) {
-                const TileVec4 in = *reinterpret_cast<const TileVec4*>(src);
+                const Vec4f in = *reinterpret_cast<const Vec4f*>(src);
 #pragma unroll
                 for (int j = 0; j < Wd; ++j) m[j] = in.v[j];
             } else {
@@ -70,18 +61,18 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_blend_kernel(const float* _
 #pragma unroll
             for (int j = 0; j < Wd; ++j) {
                 const long long w2 = wy * w[dx + j];
-                N[j] += w2 * (long long)rintf(fminf(fmaxf(m[j], g.lo), g.hi));      // probav_clip_round's arithmetic
+                N[j] += w2 * (long long)clip_rint(m[j], g.lo, g.hi);
                 D[j] += w2;
             }
         }
     }
     if (Wd == 4) {
-        TileVec4 o;
+        Vec4f o;
 #pragma unroll
-        for (int j = 0; j < Wd; ++j) o.v[j] = tile_round_div(N[j], D[j]);
-        *reinterpret_cast<TileVec4*>(out + e) = o;
+        for (int j = 0; j < Wd; ++j) o.v[j] = round_div_half_even(N[j], D[j]);     // D > 0: every pixel lies under a tile, every weight is >= 1
+        *reinterpret_cast<Vec4f*>(out + e) = o;
     } else {
-        out[e] = tile_round_div(N[0], D[0]);
+        out[e] = round_div_half_even(N[0], D[0]);
     }
 }
 
@@ -106,15 +97,9 @@ extern "C" int probav_tile_blend(const float* sr, const int32_t* w, int64_t n_im
     }
     TileGeom g;
     g.n = n; g.S = S; g.hs = hr_stride; g.G = (int)G; g.lo = lo; g.hi = hi;
-    const size_t pixels = (size_t)n_images * G * G;
-    const bool vec = S % 4 == 0 && hr_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(sr) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
-    const size_t groups = vec ? pixels / 4 : pixels;
-    const size_t blocks = (groups + TILE_THREADS - 1) / TILE_THREADS;
-    if (blocks > 0x7fffffff) {
-        set_error("probav_tile_blend: too many output pixels for one launch: blend fewer images per call", hipSuccess);
-        return PROBAV_EINVAL;
-    }
-    if (vec) hipLaunchKernelGGL(tile_blend_kernel<4>, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, (hipStream_t)stream, sr, w, g, groups, out);
-    else hipLaunchKernelGGL(tile_blend_kernel<1>, dim3((unsigned)blocks), dim3(TILE_THREADS), 0, (hipStream_t)stream, sr, w, g, groups, out);
-    return check_launch("tile_blend_kernel");
+    return launch_pixel_groups<TILE_THREADS>(S % 4 == 0 && hr_stride % 4 == 0, sr, out, (size_t)n_images * G * G,
+                                             "probav_tile_blend: too many output pixels for one launch: blend fewer images per call", "tile_blend_kernel",
+                                             [&](auto Wd, unsigned blocks, size_t groups) {
+        hipLaunchKernelGGL(tile_blend_kernel<decltype(Wd)::value>, dim3(blocks), dim3(TILE_THREADS), 0, (hipStream_t)stream, sr, w, g, groups, out);
+    });
 }

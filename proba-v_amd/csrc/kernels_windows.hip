@@ -33,6 +33,7 @@
 // (16-byte loads and stores) when S^2 is a multiple of 4 and the arrays are 16-byte aligned, per pixel otherwise.  No atomics, no float after
 // the rint.  w < 2^31, p <= 2^24 and W <= 64 keep the sums below 2^61 (what the gather writes: w <= k pixels, so below 2^46 at the shipped sizes).
 #include "probav_common.h"
+#include "image_math.h"
 #include "../../include/probav_hip.h"
 
 namespace probav {
@@ -49,8 +50,6 @@ struct FwGeom {
     int T, win, px, PS, k, L, W, step, mode;    // px = win^2, PS = the LDS plane stride in floats
     int vec;                                    // the tile bases are 16-byte aligned and a tile is a whole number of float4
 };
-
-struct alignas(16) FwVec4 { float v[4]; };
 
 // the LDS plane stride in floats (the header comment has the reasoning): the smallest PS >= px with PS mod 32 outside {0, 1, 8, 11, 16, 21, 24, 31}
 inline int64_t fw_plane_stride(int64_t px)
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(FW_THREADS) void frame_windows_gather_kernel(const 
     const int total = g.T * g.px;
     if (g.vec) {
         for (int q = tid * 4; q < total; q += FW_THREADS * 4) {
-            const FwVec4 in = *reinterpret_cast<const FwVec4*>(src + q);
+            const Vec4f in = *reinterpret_cast<const Vec4f*>(src + q);
             int f = q / g.px, p = q - f * g.px;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -147,14 +146,8 @@ __global__ __launch_bounds__(FW_THREADS) void frame_windows_gather_kernel(const 
     }
 }
 
-__device__ __forceinline__ float fw_round_div(long long N, long long D)
-{
-    if (D <= 0) return 0.f;             // a precondition broken by the caller (weights with no positive sum): no division by zero
-    long long q = N / D, r = N % D;     // C++ truncates, the definition floors
-    if (r < 0) { r += D; q -= 1; }
-    if (2 * r > D || (2 * r == D && (q & 1))) q += 1;
-    return (float)q;
-}
+// a precondition broken by the caller (weights with no positive sum) gives 0: no division by zero
+__device__ __forceinline__ float fw_mean(long long N, long long D) { return D <= 0 ? 0.f : round_div_half_even(N, D); }
 
 template <int Wd>
 __global__ __launch_bounds__(FW_THREADS) void frame_windows_reduce_kernel(const float* __restrict__ sr, const int32_t* __restrict__ weight, int W, size_t SS,
@@ -172,23 +165,23 @@ __global__ __launch_bounds__(FW_THREADS) void frame_windows_reduce_kernel(const 
         const long long wv = w[v];
         float mbr[Wd];
         if (Wd == 4) {
-            const FwVec4 in = *reinterpret_cast<const FwVec4*>(src + (size_t)v * SS);
+            const Vec4f in = *reinterpret_cast<const Vec4f*>(src + (size_t)v * SS);
 #pragma unroll
             for (int j = 0; j < Wd; ++j) mbr[j] = in.v[j];
         } else {
             mbr[0] = src[(size_t)v * SS];
         }
 #pragma unroll
-        for (int j = 0; j < Wd; ++j) N[j] += wv * (long long)rintf(fminf(fmaxf(mbr[j], lo), hi));    // probav_clip_round's arithmetic
+        for (int j = 0; j < Wd; ++j) N[j] += wv * (long long)clip_rint(mbr[j], lo, hi);
         D += wv;
     }
     if (Wd == 4) {
-        FwVec4 o;
+        Vec4f o;
 #pragma unroll
-        for (int j = 0; j < Wd; ++j) o.v[j] = fw_round_div(N[j], D);
-        *reinterpret_cast<FwVec4*>(out + e) = o;
+        for (int j = 0; j < Wd; ++j) o.v[j] = fw_mean(N[j], D);
+        *reinterpret_cast<Vec4f*>(out + e) = o;
     } else {
-        out[e] = fw_round_div(N[0], D);
+        out[e] = fw_mean(N[0], D);
     }
 }
 
@@ -243,15 +236,10 @@ extern "C" int probav_frame_windows_reduce(const float* sr, const int32_t* weigh
         set_error("probav_frame_windows_reduce: too many predictions for one launch", hipSuccess);
         return PROBAV_EINVAL;
     }
-    const size_t pixels = (size_t)N * SS;
-    const bool vec = SS % 4 == 0 && (reinterpret_cast<uintptr_t>(sr) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
-    const size_t groups = vec ? pixels / 4 : pixels;
-    const size_t blocks = (groups + FW_THREADS - 1) / FW_THREADS;
-    if (blocks > 0x7fffffff) {
-        set_error("probav_frame_windows_reduce: too many output pixels for one launch: reduce fewer tiles per call", hipSuccess);
-        return PROBAV_EINVAL;
-    }
-    if (vec) hipLaunchKernelGGL(frame_windows_reduce_kernel<4>, dim3((unsigned)blocks), dim3(FW_THREADS), 0, (hipStream_t)stream, sr, weight, W, SS, groups, lo, hi, out);
-    else hipLaunchKernelGGL(frame_windows_reduce_kernel<1>, dim3((unsigned)blocks), dim3(FW_THREADS), 0, (hipStream_t)stream, sr, weight, W, SS, groups, lo, hi, out);
-    return check_launch("frame_windows_reduce_kernel");
+    return launch_pixel_groups<FW_THREADS>(SS % 4 == 0, sr, out, (size_t)N * SS,
+                                           "probav_frame_windows_reduce: too many output pixels for one launch: reduce fewer tiles per call",
+                                           "frame_windows_reduce_kernel", [&](auto Wd, unsigned blocks, size_t groups) {
+        hipLaunchKernelGGL(frame_windows_reduce_kernel<decltype(Wd)::value>, dim3(blocks), dim3(FW_THREADS), 0, (hipStream_t)stream, sr, weight, W, SS, groups, lo,
+                           hi, out);
+    });
 }

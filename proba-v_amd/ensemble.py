@@ -25,6 +25,7 @@ v = 8 p + 4 f + k with the geometry on (V = 8 (P + 1)), v = p without (V = P + 1
 import numpy as np
 
 from .augment import FLIP_AXES, draw_perms, validate_recipe
+from .intmath import clip_rint_numpy
 
 MAX_MEMBERS = 256
 GEOMETRIES = {None: ((0, 0),), "d8": tuple((f, k) for f in (0, 1) for k in (0, 1, 2, 3))}
@@ -115,7 +116,7 @@ def ensemble_reduce_numpy(sr, recipe, V, lo=0.0, hi=float(2 ** 16), final="mean"
     for n in range(N):
         acc = np.zeros((S, S), np.float32)
         for v in range(V):
-            member = np.rint(np.clip(sr[n * V + v], np.float32(lo), np.float32(hi)))
+            member = clip_rint_numpy(sr[n * V + v], lo, hi)
             acc += inverse_geometry(member, r[n * V + v, 1], r[n * V + v, 2])
         out[n] = acc / np.float32(V)
     if final == "round":

@@ -31,6 +31,8 @@ import math
 
 import numpy as np
 
+from .intmath import clip_rint_numpy, round_half_even_div
+
 WEIGHTS = ("clear", "uniform")          # index = PROBAV_WINDOWS_CLEAR / PROBAV_WINDOWS_UNIFORM
 MAX_WINDOWS = 64
 MAX_POOL = 64                           # T_pre: one lane of a wave per frame in the ranking
@@ -150,12 +152,8 @@ def frame_windows_reduce_numpy(sr, weight, lo=0.0, hi=float(2 ** 16)):
         raise ValueError("at most %d windows; weights in [0, 2**31) with a positive sum per tile (they are multiplied by members up to 2**24 and "
                          "summed in 64-bit integers)" % MAX_WINDOWS)
     N, W = w.shape
-    p = np.rint(np.clip(m, np.float32(lo), np.float32(hi))).astype(np.int64).reshape(N, W, m.shape[1], m.shape[2])
-    Nn = (w[:, :, None, None] * p).sum(1)
-    D = w.sum(1)[:, None, None]
-    q, r = np.divmod(Nn, D)                                         # floor division; 0 <= r < D
-    q += (2 * r > D) | ((2 * r == D) & (q % 2 == 1))                # half to even
-    return q.astype(np.float32)
+    p = clip_rint_numpy(m, lo, hi).astype(np.int64).reshape(N, W, m.shape[1], m.shape[2])
+    return round_half_even_div((w[:, :, None, None] * p).sum(1), w.sum(1)[:, None, None]).astype(np.float32)
 
 
 def images_per_chunk(wspec, tspec, config, H, T_pre, budget=None):
@@ -169,39 +167,3 @@ def images_per_chunk(wspec, tspec, config, H, T_pre, budget=None):
     per_image = 4 * n * n * max(T_pre * win * win, W * k * win * win, W * (r * P) ** 2)
     return max(1, int(tiles.CHUNK_BYTES if budget is None else budget) // per_image)
 
-
-def add_cli_args(p, where=""):
-    """The three flags, shared by test.py and evaluate.py."""
-    p.add_argument("--frame-windows", type=int, default=0, help=where + "predict W images per tile, each from another window of num_low_res_imgs "
-                   "frames slid over the tile's frames sorted from clearest to dirtiest, and write their weighted mean (W forward passes per "
-                   "tile; needs num_low_res_imgs_pre > num_low_res_imgs at preprocessing time); 0 = off")
-    p.add_argument("--frame-window-step", type=int, default=None, help="with --frame-windows: positions of the sorted frame list between two windows (default 1)")
-    p.add_argument("--frame-window-weights", type=str, default=None, choices=WEIGHTS, help="with --frame-windows: weigh every window by the clear "
-                   "pixels of its frames (clear, default) or equally (uniform)")
-
-
-def cli_window_args(p, opt):
-    """The parser errors of the three flags (`p`: the ArgumentParser, `opt`: its result, with .cfg); step and weights are resolved to their
-    defaults.  Returns the FrameWindowSpec, or None without --frame-windows."""
-    if opt.frame_windows == 0:
-        if opt.frame_window_step is not None:
-            p.error("--frame-window-step needs --frame-windows")
-        if opt.frame_window_weights is not None:
-            p.error("--frame-window-weights needs --frame-windows")
-        return None
-    from .parseConfig import parseConfig
-    if opt.frame_window_step is None:
-        opt.frame_window_step = 1
-    if opt.frame_window_weights is None:
-        opt.frame_window_weights = "clear"
-    try:
-        config = parseConfig(opt.cfg)
-    except OSError as e:
-        p.error("--frame-windows: cannot read --cfg: %s" % e)
-    try:
-        spec = FrameWindowSpec(opt.frame_windows, opt.frame_window_step, opt.frame_window_weights)
-        if "num_low_res_imgs_pre" not in config:
-            raise ValueError("the cfg has no num_low_res_imgs_pre: the pool of registered frames the windows slide over")
-        return spec.validate(config["num_low_res_imgs_pre"], config["num_low_res_imgs"], config)
-    except ValueError as e:
-        p.error("--frame-windows: %s" % e)

@@ -15,7 +15,7 @@ norm.csv; lower is better.  This is the ESA / HighRes-net shift_cPSNR (HR normal
 Losses.shiftCompensatedcPSNR (models/loss.py:37-53), which the reference's evaluate.py calls, only in that HR is masked too:
 ``formula="reference"`` computes that one instead.
 
-Ids.  Image sets are named imgsetNNNN.  Train ids below 594 are RED, 594 .. 1159 NIR (test.py FIRST_ID); ids from 1160 are test sets and
+Ids.  Image sets are named imgsetNNNN.  Train ids below 594 are RED, 594 .. 1159 NIR (inference.FIRST_ID); ids from 1160 are test sets and
 have no HR.  The HR row of a train id is id - first id of its band: TRAINimgHR_<band>.npy holds every set of the band, the ones
 dataGenerator.py removed included.  Images are matched to HR by id, never by position.
 """
@@ -30,9 +30,10 @@ import numpy as np
 import torch
 
 from . import _lib, ops       # noqa: F401  (ops registers torch.ops.probav.*)
+from .inference import FIRST_ID
 
-FIRST_TRAIN_ID = {"RED": 0, "NIR": 594}
-FIRST_TEST_ID = 1160
+FIRST_TRAIN_ID = {b: FIRST_ID[("TRAIN", b)] for b in ("RED", "NIR")}
+FIRST_TEST_ID = FIRST_ID[("TEST", "RED")]
 BANDS = ("RED", "NIR")
 MAX_PER_LAUNCH = 4096                                     # images per launch (the C ABI takes up to 65535)
 

@@ -20,6 +20,19 @@ def _device_of(model):
     return next(model.parameters()).device
 
 
+def _require_hip(model, what):
+    """The model's device; RuntimeError unless it is a HIP device (`what`: "the self-ensemble runs as HIP kernels", ...)."""
+    dev = _device_of(model)
+    if dev.type != "cuda":
+        raise RuntimeError("the model lives on %s: %s on a gfx950 device (no CPU fallback)" % (dev, what))
+    return dev
+
+
+def _host_images(imgs):
+    """Device images [n, G, G] -> the list of [G, G, 1] float64 arrays the reference's `evaluate` returns: one copy back."""
+    return [im[:, :, None] for im in imgs.cpu().numpy().astype(np.float64)]
+
+
 def resolve_device(model, lr_batch):
     """test.py:114-122 without the final host copy: float32 cast -> model -> clip_by_value(0, 2**16) -> round."""
     dev = _device_of(model)
@@ -37,6 +50,11 @@ def resolve(model, lr_batch):
 
 
 LAUNCH_BATCH = 2048        # patches per launch set of the coalesced paths (5.0 GB of workspace at T = 9)
+
+
+def _whole_micro_batches(launch_batch, micro_batch):
+    """Patches per launch set: the whole micro-batches that fit `launch_batch`, at least one."""
+    return max(1, launch_batch // max(1, micro_batch)) * max(1, micro_batch)
 
 
 def _is_engine_model(model):
@@ -68,7 +86,7 @@ def resolve_coalesced(model, lr_batch, batch_size=16, launch_batch=None):
     """`resolveByBatch` on the device: the reference's micro-batches of `batch_size` grouped into launch sets of whole micro-batches
     (at most `launch_batch` patches, default LAUNCH_BATCH); returns the device tensor [n, 3P, 3P, 1]."""
     launch_batch = LAUNCH_BATCH if launch_batch is None else launch_batch
-    per = max(1, launch_batch // max(1, batch_size)) * max(1, batch_size)          # whole micro-batches per launch set
+    per = _whole_micro_batches(launch_batch, batch_size)
     n = lr_batch.shape[0]
     outs = [resolve_device(model, lr_batch[i:i + per]) for i in range(0, n, per)]
     return outs[0] if len(outs) == 1 else torch.cat(outs)
@@ -95,9 +113,7 @@ def _ensemble_launch_sets(model, flat, spec, final, launch_batch, grid=0):
     device.  grid = g: launch sets are whole images of g * g patches and every yielded tensor is [images, g S, g S]; grid = 0: [n, S, S]."""
     if final not in ("mean", "round"):
         raise ValueError("final must be 'mean' or 'round', got %r" % (final,))
-    dev = _device_of(model)
-    if dev.type != "cuda":
-        raise RuntimeError("the model lives on %s: the self-ensemble runs as HIP kernels on a gfx950 device (no CPU fallback)" % dev)
+    dev = _require_hip(model, "the self-ensemble runs as HIP kernels")
     N, T, V = flat.shape[0], flat.shape[3], spec.V
     per = max(1, (LAUNCH_BATCH if launch_batch is None else launch_batch) // V)
     if grid:
@@ -199,26 +215,12 @@ def stitch_device(sr, sets):
     return sr.reshape(sets, n, n, ps, ps).permute(0, 1, 3, 2, 4).reshape(sets, n * ps, n * ps)
 
 
-def resolve_tiled(model, tiles, spec, ensemble=None, launch_batch=None):
-    """Overlapping tiles [images, n n, P+s, P+s, T, 1] (tiles.build_tiles at spec.stride; the chunk of images the caller chose) -> the blended
-    uint16-range images [images, G, G] (device tensor), G = scale * ((n - 1) * stride + P): tiles.py states the blend.  The forward passes
-    run in launch sets of at most `launch_batch` tiles (default LAUNCH_BATCH), with an `ensemble` (EnsembleSpec) in launch sets of
-    launch_batch // V tiles through `resolve_ensemble`'s kernels, every tile rounded (final="round"); then ONE blend kernel, which clips and
-    rounds the raw predictions itself.  Integer arithmetic from there on: the images do not depend on the launch sets."""
+def _predict_flat(model, flat, ensemble, launch_batch):
+    """The predictions sr [n, S, S] (device tensor) of the flat batch `flat` [n, win, win, T, 1]: forward passes in launch sets of at most
+    `launch_batch` inputs (default LAUNCH_BATCH), raw; with an `ensemble` in launch sets of launch_batch // V inputs through
+    `resolve_ensemble`'s kernels, every prediction the rounded self-ensemble (final="round")."""
     dev = _device_of(model)
-    if dev.type != "cuda":
-        raise RuntimeError("the model lives on %s: the tile blend runs as a HIP kernel on a gfx950 device (no CPU fallback)" % dev)
-    t = torch.as_tensor(tiles)
-    images, nn_ = t.shape[0], t.shape[1]
-    n = int(round(nn_ ** 0.5))
-    if t.dim() != 6 or n * n != nn_:
-        raise ValueError("tiles must be [images, n * n, win, win, T, 1], got %s" % (tuple(t.shape),))
-    P, r = model.patchSizeLR, model.scale
-    if not 1 <= spec.stride <= P:
-        raise ValueError("tile stride %d outside 1..%d" % (spec.stride, P))
-    S = r * P
-    w = torch.from_numpy(spec.weights(S)).to(dev)                    # validated on the host: every weight in [1, 1024]
-    flat = t.reshape((-1,) + tuple(t.shape[2:]))
+    S = model.scale * model.patchSizeLR
     sr = torch.empty((flat.shape[0], S, S), dtype=torch.float32, device=dev)
     if ensemble is not None:
         i = 0
@@ -231,6 +233,27 @@ def resolve_tiled(model, tiles, spec, ensemble=None, launch_batch=None):
             for i in range(0, flat.shape[0], per):
                 x = flat[i:i + per].to(device=dev, dtype=torch.float32)
                 sr[i:i + x.shape[0]] = model(x, training=False)[..., 0]
+    return sr
+
+
+def resolve_tiled(model, tiles, spec, ensemble=None, launch_batch=None):
+    """Overlapping tiles [images, n n, P+s, P+s, T, 1] (tiles.build_tiles at spec.stride; the chunk of images the caller chose) -> the blended
+    uint16-range images [images, G, G] (device tensor), G = scale * ((n - 1) * stride + P): tiles.py states the blend.  The forward passes
+    run in launch sets of at most `launch_batch` tiles (default LAUNCH_BATCH), with an `ensemble` (EnsembleSpec) in launch sets of
+    launch_batch // V tiles through `resolve_ensemble`'s kernels, every tile rounded (final="round"); then ONE blend kernel, which clips and
+    rounds the raw predictions itself.  Integer arithmetic from there on: the images do not depend on the launch sets."""
+    dev = _require_hip(model, "the tile blend runs as a HIP kernel")
+    t = torch.as_tensor(tiles)
+    images, nn_ = t.shape[0], t.shape[1]
+    n = int(round(nn_ ** 0.5))
+    if t.dim() != 6 or n * n != nn_:
+        raise ValueError("tiles must be [images, n * n, win, win, T, 1], got %s" % (tuple(t.shape),))
+    P, r = model.patchSizeLR, model.scale
+    if not 1 <= spec.stride <= P:
+        raise ValueError("tile stride %d outside 1..%d" % (spec.stride, P))
+    S = r * P
+    w = torch.from_numpy(spec.weights(S)).to(dev)                    # validated on the host: every weight in [1, 1024]
+    sr = _predict_flat(model, t.reshape((-1,) + tuple(t.shape[2:])), ensemble, launch_batch)
     return torch.ops.probav.tile_blend(sr, w, images, n, r * spec.stride, 0.0, float(2 ** 16))
 
 
@@ -252,9 +275,7 @@ def resolve_tiled_frames(model, imgsLR_masked, spec, config, ensemble=None, laun
 
 def evaluate_tiled_frames(model, imgsLR_masked, spec, config, ensemble=None, launch_batch=None, budget=None):
     """`resolve_tiled_frames` in the form `evaluate_device` returns: a list of [G, G, 1] float64 arrays, one copy back."""
-    imgs = resolve_tiled_frames(model, imgsLR_masked, spec, config, ensemble=ensemble, launch_batch=launch_batch, budget=budget)
-    imgs = imgs.cpu().numpy().astype(np.float64)
-    return [im[:, :, None] for im in imgs]
+    return _host_images(resolve_tiled_frames(model, imgsLR_masked, spec, config, ensemble=ensemble, launch_batch=launch_batch, budget=budget))
 
 
 def resolve_windowed(model, patches, counts, wspec, tspec=None, ensemble=None, launch_batch=None):
@@ -265,9 +286,7 @@ def resolve_windowed(model, patches, counts, wspec, tspec=None, ensemble=None, l
     takes the weighted integer mean of the W members of every tile and `tile_blend` places the tiles: `tspec` (a TileSpec), or stride P with
     the box window, the plain stitch -> [images, G, G].  Integer arithmetic after each member's rint: the images do not depend on the
     launch sets."""
-    dev = _device_of(model)
-    if dev.type != "cuda":
-        raise RuntimeError("the model lives on %s: the frame windows run as HIP kernels on a gfx950 device (no CPU fallback)" % dev)
+    dev = _require_hip(model, "the frame windows run as HIP kernels")
     if patches.dim() != 5 or counts.dim() != 3:
         raise ValueError("patches [images, n n, T_pre, win, win] and counts [images, n n, T_pre] expected, got %s %s" % (tuple(patches.shape), tuple(counts.shape)))
     images, nn_, T_pre, win = patches.shape[:4]
@@ -283,19 +302,8 @@ def resolve_windowed(model, patches, counts, wspec, tspec=None, ensemble=None, l
     w = torch.from_numpy(tspec.weights(S)).to(dev)
     x, weight, _ = torch.ops.probav.frame_windows_gather(patches.reshape(images * nn_, T_pre, win, win), counts.reshape(images * nn_, T_pre), k,
                                                          wspec.limit(win * win), wspec.windows, wspec.step, wspec.weights)
-    flat = x.reshape((-1,) + tuple(x.shape[2:]))
-    sr = torch.empty((flat.shape[0], S, S), dtype=torch.float32, device=dev)
-    if ensemble is not None:
-        i = 0
-        for out in _ensemble_launch_sets(model, flat, ensemble, "round", launch_batch):
-            sr[i:i + out.shape[0]] = out
-            i += out.shape[0]
-    else:
-        per = max(1, LAUNCH_BATCH if launch_batch is None else launch_batch)
-        with torch.no_grad():
-            for i in range(0, flat.shape[0], per):
-                sr[i:i + per] = model(flat[i:i + per], training=False)[..., 0]
-    del x, flat
+    sr = _predict_flat(model, x.reshape((-1,) + tuple(x.shape[2:])), ensemble, launch_batch)
+    del x
     tiles_sr = torch.ops.probav.frame_windows_reduce(sr, weight, 0.0, float(2 ** 16))
     return torch.ops.probav.tile_blend(tiles_sr, w, images, n, r * tspec.stride, 0.0, float(2 ** 16))
 
@@ -327,9 +335,8 @@ def resolve_windowed_frames(model, imgsLR_masked, wspec, config, tiles=None, ens
 
 def evaluate_windowed_frames(model, imgsLR_masked, wspec, config, tiles=None, ensemble=None, launch_batch=None, budget=None):
     """`resolve_windowed_frames` in the form `evaluate_device` returns: a list of [G, G, 1] float64 arrays, one copy back."""
-    imgs = resolve_windowed_frames(model, imgsLR_masked, wspec, config, tiles=tiles, ensemble=ensemble, launch_batch=launch_batch, budget=budget)
-    imgs = imgs.cpu().numpy().astype(np.float64)
-    return [im[:, :, None] for im in imgs]
+    return _host_images(resolve_windowed_frames(model, imgsLR_masked, wspec, config, tiles=tiles, ensemble=ensemble, launch_batch=launch_batch,
+                                                budget=budget))
 
 
 def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble=None, final="round", tiles=None):
@@ -362,7 +369,7 @@ def resolve_images(model, patches, micro_batch=2048, launch_batch=None, ensemble
         return out if whole else stitch_device(out.unsqueeze(-1), sets)
     if launch_batch is None:
         launch_batch = max(micro_batch, LAUNCH_BATCH)
-    per = max(1, launch_batch // max(1, micro_batch)) * max(1, micro_batch)
+    per = _whole_micro_batches(launch_batch, micro_batch)
     outs = []
     for i in range(0, flat.shape[0], per):
         outs.append(resolve_device(model, flat[i:i + per].to(dev)))
@@ -382,11 +389,5 @@ def evaluate_device(model, X_test_patches, micro_batch=2048, launch_batch=None, 
         if final != "round" or config is None:
             raise ValueError("frame windows give integers (final must be 'round', got %r) and take the parsed cfg as config=" % (final,))
         return evaluate_windowed_frames(model, X_test_patches, windows, config, tiles=tiles, ensemble=ensemble, launch_batch=launch_batch)
-    if tiles is not None:
-        imgs = resolve_images(model, X_test_patches, launch_batch=launch_batch, ensemble=ensemble, final=final, tiles=tiles)
-    elif ensemble is None:
-        imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch)
-    else:
-        imgs = resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch, ensemble=ensemble, final=final)
-    imgs = imgs.cpu().numpy().astype(np.float64)
-    return [im[:, :, None] for im in imgs]
+    return _host_images(resolve_images(model, X_test_patches, micro_batch=micro_batch, launch_batch=launch_batch, ensemble=ensemble, final=final,
+                                       tiles=tiles))

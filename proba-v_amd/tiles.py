@@ -24,6 +24,8 @@ N < 2**13 * 2**20 * 2**16 = 2**49.
 """
 import numpy as np
 
+from .intmath import clip_rint_numpy, round_half_even_div
+
 WINDOWS = ("hat", "box")
 MAX_WEIGHT = 1024
 LR_SIZE = 128                  # PROBA-V LR frames
@@ -97,16 +99,14 @@ def tile_blend_numpy(members, w, n, hr_stride, lo=0.0, hi=float(2 ** 16)):
         raise ValueError("hr_stride = %d; 1 <= hr_stride <= S = %d (a gap between tiles would leave pixels without a weight)" % (hs, S))
     w = validate_window(w, S).astype(np.int64)
     W2 = w[:, None] * w[None, :]
-    p = np.rint(np.clip(m, np.float32(lo), np.float32(hi))).astype(np.int64).reshape(images, n, n, S, S)
+    p = clip_rint_numpy(m, lo, hi).astype(np.int64).reshape(images, n, n, S, S)
     G = (n - 1) * hs + S
     N, D = np.zeros((images, G, G), np.int64), np.zeros((G, G), np.int64)
     for a in range(n):
         for c in range(n):
             N[:, a * hs:a * hs + S, c * hs:c * hs + S] += W2 * p[:, a, c]
             D[a * hs:a * hs + S, c * hs:c * hs + S] += W2
-    q, r = np.divmod(N, D)                                          # floor division; 0 <= r < D
-    q += (2 * r > D) | ((2 * r == D) & (q % 2 == 1))                # half to even
-    return q.astype(np.float32)
+    return round_half_even_div(N, D).astype(np.float32)
 
 
 # ---- the tile builder ---------------------------------------------------------------------------------------------------------------
@@ -175,22 +175,3 @@ def images_per_chunk(spec, config, H, T_pre, budget=CHUNK_BYTES):
     per_image = 4 * n * n * max(T_pre * win * win, (r * P) ** 2)
     return max(1, int(budget) // per_image)
 
-
-def cli_tile_args(p, opt):
-    """The parser errors of --tile-stride / --tile-window, shared by test.py and evaluate.py (`p`: the ArgumentParser, `opt`: its result, with
-    .cfg); --tile-window is resolved to its default."""
-    if opt.tile_stride == 0:
-        if opt.tile_window is not None:
-            p.error("--tile-window needs --tile-stride")
-        return
-    from .parseConfig import parseConfig
-    if opt.tile_window is None:
-        opt.tile_window = "hat"
-    try:
-        config = parseConfig(opt.cfg)
-    except OSError as e:
-        p.error("--tile-stride: cannot read --cfg: %s" % e)
-    try:
-        TileSpec(opt.tile_stride, opt.tile_window).validate(config["patch_size"], LR_SIZE)
-    except ValueError as e:
-        p.error("--tile-stride: %s" % e)

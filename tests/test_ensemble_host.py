@@ -238,9 +238,9 @@ def test_cli_flags_default_to_the_plain_path(tmp_path):
     test_py, evaluate_py = _load("test"), _load("evaluate")
     opt = test_py.parser(["--cfg", "x.cfg", "--band", "NIR"])
     assert (opt.ensemble, opt.ensemble_permute, opt.ensemble_seed) == ("none", 0, 0)
-    assert test_py.ensemble_spec(opt) is None
+    assert opt.inference.ensemble is None
     opt = test_py.parser(["--ensemble", "d8", "--ensemble-permute", "1", "--ensemble-seed", "3"])
-    spec = test_py.ensemble_spec(opt)
+    spec = opt.inference.ensemble
     assert (spec.geometry, spec.permute, spec.seed, spec.V) == ("d8", 1, 3, 16)
     for bad in (["--ensemble", "d4"], ["--ensemble-permute", "2"], ["--ensemble", "d8", "--reference-loop"]):
         with pytest.raises(SystemExit):

@@ -324,7 +324,7 @@ def test_cli_frame_window_flags(tmp_path, capsys):
     opt = test_py.parser(["--cfg", cfg, "--frame-windows", "3", "--frame-window-step", "5", "--frame-window-weights", "uniform", "--tile-stride", "8",
                           "--ensemble", "d8", "--weights", "ema"])
     assert (opt.windows.windows, opt.windows.step, opt.windows.weights) == (3, 5, "uniform")
-    assert test_py.tile_spec(opt).stride == 8 and test_py.ensemble_spec(opt).V == 8
+    assert opt.inference.tiles.stride == 8 and opt.inference.ensemble.V == 8
     assert test_py.parser(["--cfg", cfg, "--frame-windows", "11"]).windows.windows == 11       # 10 + 9 == 19
     for bad in (["--cfg", cfg, "--frame-window-step", "2"], ["--cfg", cfg, "--frame-window-weights", "clear"], ["--cfg", cfg, "--frame-windows", "65"],
                 ["--cfg", cfg, "--frame-windows", "-1"], ["--cfg", cfg, "--frame-windows", "12"], ["--cfg", cfg, "--frame-windows", "3", "--frame-window-step", "6"],

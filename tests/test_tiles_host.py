@@ -263,13 +263,13 @@ def test_cli_tile_flags(tmp_path):
     with open(cfg32, "w") as fh:
         fh.write(CFG.format(P=32))
     opt = test_py.parser(["--cfg", "x.cfg", "--band", "NIR"])       # the default reads nothing: today's path
-    assert opt.tile_stride == 0 and opt.tile_window is None and test_py.tile_spec(opt) is None
+    assert opt.tile_stride == 0 and opt.tile_window is None and opt.inference.tiles is None
     opt = test_py.parser(["--cfg", cfg, "--tile-stride", "8"])
-    spec = test_py.tile_spec(opt)
+    spec = opt.inference.tiles
     assert (spec.stride, spec.window) == (8, "hat") and opt.tile_window == "hat"
     opt = test_py.parser(["--cfg", cfg, "--tile-stride", "4", "--tile-window", "box", "--ensemble", "d8"])
-    assert (test_py.tile_spec(opt).stride, test_py.tile_spec(opt).window, test_py.ensemble_spec(opt).V) == (4, "box", 8)
-    assert test_py.tile_spec(test_py.parser(["--cfg", cfg32, "--tile-stride", "32"])).stride == 32      # valid for THAT cfg: (128 - 32) % 32 == 0
+    assert (opt.inference.tiles.stride, opt.inference.tiles.window, opt.inference.ensemble.V) == (4, "box", 8)
+    assert test_py.parser(["--cfg", cfg32, "--tile-stride", "32"]).inference.tiles.stride == 32      # valid for THAT cfg: (128 - 32) % 32 == 0
     for bad in (["--cfg", cfg, "--tile-window", "hat"], ["--cfg", cfg, "--tile-stride", "8", "--reference-loop"], ["--cfg", cfg, "--tile-stride", "3"],
                 ["--cfg", cfg, "--tile-stride", "32"], ["--cfg", cfg, "--tile-stride", "-8"], ["--cfg", cfg, "--tile-stride", "8", "--tile-window", "gauss"],
                 ["--cfg", cfg32, "--tile-stride", "7"], ["--cfg", str(tmp_path / "none.cfg"), "--tile-stride", "8"]):

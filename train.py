@@ -14,6 +14,7 @@ import os
 import numpy as np
 import torch
 
+from probav_amd.inference import BAND_STATS
 from probav_amd.loss import Losses
 from probav_amd.modelsTF import WDSRConv3D
 from probav_amd.parseConfig import parseConfig
@@ -21,8 +22,6 @@ from probav_amd.trainClass import ModelTrainer, make_optimizer
 
 logging.basicConfig(format="%(asctime)s - %(message)s", level=logging.INFO)
 logger = logging.getLogger("probav_amd")
-
-BAND_STATS = {"NIR": (8075.2045, 3160.7272), "RED": (5266.2245, 3431.8614)}      # train.py:47-52
 
 
 def parser(argv=None):
