@@ -241,6 +241,10 @@ int probav_pw_forward(const float* x, const float* w1, const float* b1, const fl
  * column of such a channel is resolved to <= 1e-4 of its own maximum at k = 24 (measured 4.8e-5 / 9.0e-5) -- still far inside
  * north_star's 1e-3, and invisible in a whole-tensor norm.  The cure of the 3x3x3 backward-filter kernel (second pieces lifted by 2^11,
  * the cross products in an accumulator set of their own) needs 256 more accumulator registers than a wave has.  impl 2 / 3: no such floor. */
+/* db1 AT LARGE BATCHES (measured; tests/test_gpu_plans.py::test_pointwise_plan_backward_matches_oracle).  The outputs of the bf16 / fp16 MFMA pipe carry a one-sided
+ * error of about -1.4e-8 of their magnitude (the fp32 MFMA of impl 2: none).  db1 is the one plain sum of such outputs over every voxel of the call, so the term grows with
+ * the voxel count while db1 grows with its square root.  impl 4 up to 1 024 samples (pw_bwd_w4_kernel) alternates the sign of that product tile by tile and cancels it:
+ * 2.9e-7 of max |db1| at 128 x 4 356 voxels.  The general forms (impl 3; impl 4 above 1 024 samples) sum it as it comes: 5e-7 at 4 356 voxels, 5.2e-6 at 128 x 4 356. */
 size_t probav_pw_backward_scratch_bytes(int D);
 int probav_pw_backward(const float* x, const float* d_dec, const float* d_skip, const float* w1, const float* b1,
                        const float* w2, float* dx, float* dw1, float* db1, float* dw2, float* db2, void* scratch,
@@ -289,6 +293,39 @@ int probav_debug_hidden(probav_engine* e, const float* params, const void* ws /*
  * reverse pass recomputes the tile -- and decides its ReLU gates -- in; 1 the forward kernel's own (16x16x32).  The two sum the same piece products in different
  * orders; a pre-activation that is zero to rounding can be open in one and closed in the other (tests/test_gpu_parity.py bounds how many, and how large).  Process-wide. */
 int probav_debug_hidden_from_forward_kernel(int on);
+
+/* ---- plan report (parity tests), an addition made under ABI 7 ------------------------------------------------------------------------- */
+/* Which kernel a single-operator call would launch, and the integers of its launch plan, from the very functions the launch paths call.  Host only: nothing
+ * is launched and no device is needed.  tests/plan_cases.py names, per plan class, the geometry that reaches it; tests/test_gpu_plans.py holds each to the oracle.
+ * probav_plan_conv: geom as probav_conv3d_forward; gated / has_skip: whether the call passes a gate (forward, backward-data: the input's; backward-filter: dY's)
+ * / a skip tensor; op FORWARD = probav_conv3d_forward with a bias, BWD_DATA = the same without one (the engine's backward-data launches), WGRAD =
+ * probav_conv3d_wgrad.  report[0] = the kernel (PROBAV_PLAN_NONE: the call is refused with PROBAV_EINVAL), [1] nsplit column ranges per row, [2] nstrips per
+ * patch (row-tile kernels: tiles), [3] SR rows per strip (tile), [4] nslot ring depth (cw4, pp), [5] grid, [6] rvp staging items per thread (pp), [7] 0; a
+ * field the kernel's plan does not have is 0.  DIRECT: a VALU kernel (the generic one, or the dedicated upscale pair).
+ * probav_plan_pw: the fused pointwise pair, arguments as probav_pw_forward / probav_pw_backward; report[0] = the kernel, [7] = wps, the waves per sample of
+ * pw_bwd_w4_kernel (PW4), the rest 0. */
+#define PROBAV_PLAN_NONE 0
+#define PROBAV_PLAN_CW4 1            /* conv3_w4_kernel */
+#define PROBAV_PLAN_PP 2             /* conv3_pp_kernel */
+#define PROBAV_PLAN_PSTRIP 3         /* conv3_pstrip_kernel */
+#define PROBAV_PLAN_STRIP 4          /* conv3_strip_kernel */
+#define PROBAV_PLAN_ROWTILE 5        /* conv3_mfma_kernel, any arithmetic */
+#define PROBAV_PLAN_DIRECT 6
+#define PROBAV_PLAN_WG4 7            /* conv3_wgrad_w4_kernel */
+#define PROBAV_PLAN_WGRAD_X6 8       /* conv3_wgrad_x6_kernel, X6 arithmetic */
+#define PROBAV_PLAN_WGRAD_X6_H3 9    /* conv3_wgrad_x6_kernel, H3 arithmetic */
+#define PROBAV_PLAN_WGRAD_MFMA 10    /* conv3_wgrad_mfma_kernel */
+#define PROBAV_PLAN_PW4 20           /* pw_bwd_w4_kernel */
+#define PROBAV_PLAN_PW_X6_H3 21      /* pw_bwd_x6_kernel, H3 arithmetic */
+#define PROBAV_PLAN_PW_X6 22         /* pw_fwd_x6_kernel / pw_bwd_x6_kernel, X6 arithmetic */
+#define PROBAV_PLAN_PF4 23           /* pw_fwd_w4_kernel */
+#define PROBAV_PLAN_PW_H3K 24        /* pw_fwd_h3k_kernel */
+#define PROBAV_PLAN_PW_MFMA 25       /* pw_fwd_mfma_kernel / its backward */
+#define PROBAV_PLAN_OP_FORWARD 0
+#define PROBAV_PLAN_OP_BWD_DATA 1
+#define PROBAV_PLAN_OP_WGRAD 2
+int probav_plan_conv(const int32_t geom[17], int impl, int gated, int has_skip, int op, int32_t report[8]);
+int probav_plan_pw(int64_t nvox, int64_t vox_per_sample, int D, int impl, int backward, int32_t report[8]);
 
 /* ---- dataset builder (utils/dataGenerator.py; proba-v_amd/prep.py), additions of ABI 7 ------------------------------------------------ */
 /* Frames are one flat [n_frames][H][W] array; a ragged list of image sets is that array plus set_offsets[n_sets+1] (int64, ascending,

@@ -81,6 +81,9 @@ SIGNATURES = {
     "probav_mfma_probe_shape": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "probav_debug_hidden": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "probav_debug_hidden_from_forward_kernel": (c_int, [c_int]),
+    # plan report (csrc/engine.hip): added under ABI 7, host only
+    "probav_plan_conv": (c_int, [POINTER(c_int32 * 17), c_int, c_int, c_int, c_int, POINTER(c_int32 * 8)]),
+    "probav_plan_pw": (c_int, [c_int64, c_int64, c_int, c_int, c_int, POINTER(c_int32 * 8)]),
     "probav_workspace_split": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "probav_backward_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
     "probav_weight_cache_bytes": (c_size_t, [c_void_p]),

@@ -1227,6 +1227,26 @@ static int op_pack(const ConvGeom& g, const float* w, hipStream_t s, int arith, 
     return op_pack_jobs(&J, 1, w, w, s, "probav_conv3d_forward: job upload");
 }
 
+// The kernel that serves a single-operator convolution call: the one decision probav_conv3d_forward (launch) and probav_plan_conv (report) read.  Only WHICH of gate / bias /
+// skip exist matters.  impl 0 the direct kernel; impl 1 the MFMA row-tile kernel, 2 the strip kernel, 3 / 4 the x6 strip kernel (X6 / H3; the piece-ring form where it applies) or,
+// where the strip kernels do not apply, its row-tile form: what conv_route gives family `impl` behind the engine's dedicated kernels, anything else is refused
+enum class OpConvKernel { up, up_bwd_data, direct, routed, refused };
+struct OpConvRoute { OpConvKernel k; ConvRoute r; };
+static OpConvRoute op_conv_route(const ConvGeom& g, bool gate, bool bias, bool skip, int impl)
+{
+    // (what the engine does for these two geometries in every kernel family but 0)
+    if (impl >= 1 && !gate && !skip && bias && conv3d_up_forward_supported(g)) return {OpConvKernel::up, {}};
+    if (impl >= 1 && !gate && !skip && !g.relu && conv3d_up_bwd_data_supported(g)) return {OpConvKernel::up_bwd_data, {}};
+    if (impl == 0) return {OpConvKernel::direct, {}};
+    // The route only asks WHICH operands exist (any address will do): the caller packs them
+    static const float some = 0.f;
+    Amax am;
+    if (impl == 4) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
+    const ConvRoute r = conv_route(make_family(impl, false), g, gate ? &some : nullptr, bias ? &some : nullptr, skip ? &some : nullptr, Frags{&some, &some, &some, &some}, am, false);
+    const bool documented = impl == 1 ? r.k == ConvKernel::mfma_rowtile : (impl == 2 ? r.k == ConvKernel::mfma_strip : r.k == ConvKernel::x6_strip || r.k == ConvKernel::x6_rowtile);
+    return {documented ? OpConvKernel::routed : OpConvKernel::refused, r};
+}
+
 int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* gate, const float* w, const float* bias,
                           const float* skip, float* y, int impl, void* stream)
 {
@@ -1235,18 +1255,13 @@ int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* g
     if (!geom_ok(g)) { set_error("probav_conv3d_forward: bad geometry", hipSuccess); return PROBAV_EINVAL; }
     if (impl < 0 || impl > 4) { set_error("probav_conv3d_forward: impl must be 0..4", hipSuccess); return PROBAV_EINVAL; }
     const hipStream_t s = (hipStream_t)stream;
-    // (what the engine does for these two geometries in every kernel family but 0)
-    if (impl >= 1 && !gate && !skip && bias && conv3d_up_forward_supported(g)) return conv3d_up_forward(g, x, w, bias, y, s);
-    if (impl >= 1 && !gate && !skip && !g.relu && conv3d_up_bwd_data_supported(g)) return conv3d_up_bwd_data(g, x, w, bias, y, nullptr, s);
-    if (impl == 0) return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
-    // impl 1 the MFMA row-tile kernel, 2 the strip kernel, 3 / 4 the x6 strip kernel (X6 / H3; the piece-ring form where it applies) or, where the strip kernels do not apply, its row-tile
-    // form: what conv_route gives family `impl` behind the engine's dedicated kernels, anything else is refused.  The route only asks WHICH operands exist (any address will do): they are packed below
-    static const float some = 0.f;
+    const OpConvRoute o = op_conv_route(g, gate != nullptr, bias != nullptr, skip != nullptr, impl);
+    if (o.k == OpConvKernel::up) return conv3d_up_forward(g, x, w, bias, y, s);
+    if (o.k == OpConvKernel::up_bwd_data) return conv3d_up_bwd_data(g, x, w, bias, y, nullptr, s);
+    if (o.k == OpConvKernel::direct) return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
+    if (o.k == OpConvKernel::refused) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
+    ConvRoute r = o.r;
     Amax am;
-    if (impl == 4) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
-    ConvRoute r = conv_route(make_family(impl, false), g, gate, bias, skip, Frags{&some, &some, &some, &some}, am, false);
-    const bool documented = impl == 1 ? r.k == ConvKernel::mfma_rowtile : (impl == 2 ? r.k == ConvKernel::mfma_strip : r.k == ConvKernel::x6_strip || r.k == ConvKernel::x6_rowtile);
-    if (!documented) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
     CK(op_scratch());
     if (impl == 4) {
         if (g.Cout > 256) { set_error("probav_conv3d_forward: Cout > 256", hipSuccess); return PROBAV_EINVAL; }
@@ -1258,13 +1273,26 @@ int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* g
     return conv_launch(r, g, x, gate, w, bias, skip, y, am, s);
 }
 
+// The kernel family that serves a single-operator backward-filter call (impl names a kernel here, not an engine family: 2 is the direct kernel, so the call does not go
+// through wgrad_route): read by probav_conv3d_wgrad_scratch_bytes, probav_conv3d_wgrad and probav_plan_conv
+enum class OpWgradKernel { x6, mfma, direct, refused };
+static OpWgradKernel op_wgrad_kernel(const ConvGeom& g, int impl)
+{
+    if (impl == 3 || impl == 4) return x6_wgrad_supported(g) ? OpWgradKernel::x6 : OpWgradKernel::refused;
+    if (impl == 1) return mfma_wgrad_supported(g) ? OpWgradKernel::mfma : OpWgradKernel::refused;
+    return OpWgradKernel::direct;
+}
+
 size_t probav_conv3d_wgrad_scratch_bytes(const int32_t geom[17], int impl)
 {
     if (!geom) return 0;
     const ConvGeom g = geom_from(geom);
-    if (impl == 3 || impl == 4) return x6_wgrad_supported(g) ? x6_wgrad_partial_floats(g) * sizeof(float) : 0;
-    if (impl == 1) return mfma_wgrad_supported(g) ? mfma_wgrad_partial_floats(g) * sizeof(float) : 0;
-    return wgrad_partial_floats(g) * sizeof(float);
+    switch (op_wgrad_kernel(g, impl)) {
+    case OpWgradKernel::x6: return x6_wgrad_partial_floats(g) * sizeof(float);
+    case OpWgradKernel::mfma: return mfma_wgrad_partial_floats(g) * sizeof(float);
+    case OpWgradKernel::direct: return wgrad_partial_floats(g) * sizeof(float);
+    default: return 0;
+    }
 }
 
 int probav_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy, const float* gate, float* dw, float* db,
@@ -1273,9 +1301,9 @@ int probav_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy,
     if (!geom || !x || !dy || !dw || !scratch) { set_error("probav_conv3d_wgrad: null argument", hipSuccess); return PROBAV_EINVAL; }
     const ConvGeom g = geom_from(geom);
     if (!geom_ok(g)) { set_error("probav_conv3d_wgrad: bad geometry", hipSuccess); return PROBAV_EINVAL; }
-    // (impl names a kernel here, not an engine family: 2 is the direct kernel, so the call does not go through wgrad_route)
+    const OpWgradKernel k = op_wgrad_kernel(g, impl);
     if (impl == 3 || impl == 4) {
-        if (!x6_wgrad_supported(g)) { set_error("probav_conv3d_wgrad: geometry not supported by the x6 kernel", hipSuccess); return PROBAV_EINVAL; }
+        if (k != OpWgradKernel::x6) { set_error("probav_conv3d_wgrad: geometry not supported by the x6 kernel", hipSuccess); return PROBAV_EINVAL; }
         if (scratch_bytes < x6_wgrad_partial_floats(g) * sizeof(float)) { set_error("probav_conv3d_wgrad: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
         Amax am;
         if (impl == 4) {
@@ -1286,7 +1314,7 @@ int probav_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy,
         return x6_conv_wgrad(g, x, dy, gate, dw, db, (float*)scratch, impl == 4 ? 2 : 1, am, (hipStream_t)stream);
     }
     if (impl == 1) {
-        if (!mfma_wgrad_supported(g)) { set_error("probav_conv3d_wgrad: geometry not supported by the MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
+        if (k != OpWgradKernel::mfma) { set_error("probav_conv3d_wgrad: geometry not supported by the MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
         if (scratch_bytes < mfma_wgrad_partial_floats(g) * sizeof(float)) { set_error("probav_conv3d_wgrad: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
         return mfma_conv_wgrad(g, x, dy, gate, dw, db, (float*)scratch, (hipStream_t)stream);
     }
@@ -1370,6 +1398,67 @@ int probav_pw_backward(const float* x, const float* d_dec, const float* d_skip, 
     PwOps f;
     CK(op_pack_pw(w1, w2, D, impl - 2, 3 * (int)(nvox / vps), s, f));
     return pw_backward(impl - 2, f, x, d_dec, d_skip, b1, dx, dw1, dw2, db1, db2, (float*)scratch, (long)nvox, vps, D, am, s);
+}
+
+// ---- plan report (host only: nothing is launched, no device is touched) ----
+int probav_plan_conv(const int32_t geom[17], int impl, int gated, int has_skip, int op, int32_t report[8])
+{
+    if (!geom || !report || impl < 0 || impl > 4 || op < PROBAV_PLAN_OP_FORWARD || op > PROBAV_PLAN_OP_WGRAD) { set_error("probav_plan_conv: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    const ConvGeom g = geom_from(geom);
+    if (!geom_ok(g)) { set_error("probav_plan_conv: bad geometry", hipSuccess); return PROBAV_EINVAL; }
+    for (int i = 0; i < 8; ++i) report[i] = 0;
+    int32_t &kernel = report[0], &nsplit = report[1], &nstrips = report[2], &SR = report[3], &nslot = report[4], &grid = report[5], &rvp = report[6];
+    static const float some = 0.f;
+    const float* gate = gated ? &some : nullptr;
+    if (op == PROBAV_PLAN_OP_WGRAD) {
+        int v[4] = {0, 0, 0, 0};
+        switch (op_wgrad_kernel(g, impl)) {
+        case OpWgradKernel::x6: {
+            static const int32_t names[4] = {PROBAV_PLAN_NONE, PROBAV_PLAN_WG4, PROBAV_PLAN_WGRAD_X6_H3, PROBAV_PLAN_WGRAD_X6};
+            kernel = names[x6_wgrad_plan_ints(g, gate, impl == 4 ? 2 : 1, v)];
+            nsplit = v[0]; nstrips = v[1]; SR = v[2]; grid = v[3];
+            break;
+        }
+        case OpWgradKernel::mfma: if (mfma_conv_plan_ints(g, true, v)) { kernel = PROBAV_PLAN_WGRAD_MFMA; SR = v[0]; nstrips = v[1]; grid = v[2]; nsplit = 1; } break;
+        case OpWgradKernel::direct: kernel = PROBAV_PLAN_DIRECT; break;
+        default: break;
+        }
+        return PROBAV_OK;
+    }
+    const OpConvRoute o = op_conv_route(g, gated != 0, op == PROBAV_PLAN_OP_FORWARD, has_skip != 0, impl);
+    if (o.k == OpConvKernel::refused) return PROBAV_OK;
+    if (o.k != OpConvKernel::routed) { kernel = PROBAV_PLAN_DIRECT; return PROBAV_OK; }      // the VALU kernels: generic, or the two dedicated upscale ones
+    if (o.r.k == ConvKernel::x6_rowtile || o.r.k == ConvKernel::mfma_rowtile) {
+        int v[3];
+        if (mfma_conv_plan_ints(g, false, v)) { kernel = PROBAV_PLAN_ROWTILE; SR = v[0]; nstrips = v[1]; grid = v[2]; nsplit = 1; }
+        return PROBAV_OK;
+    }
+    const StripSel& sel = o.r.strip;
+    if (sel.k == StripKernel::cw4) {
+        int v[5];
+        if (cw4_conv_plan_ints(g, gate, v)) { kernel = PROBAV_PLAN_CW4; nsplit = v[0]; nstrips = v[1]; SR = v[2]; nslot = v[3]; grid = v[4]; }
+        return PROBAV_OK;
+    }
+    kernel = sel.k == StripKernel::pp ? PROBAV_PLAN_PP : (sel.k == StripKernel::pstrip ? PROBAV_PLAN_PSTRIP : PROBAV_PLAN_STRIP);
+    nsplit = sel.plan.a.nsplit; nstrips = sel.plan.a.nstrips; SR = sel.plan.a.SR; grid = sel.plan.grid;
+    if (sel.k == StripKernel::pp) { nslot = sel.plan.a.nslot; rvp = sel.rvp; }
+    return PROBAV_OK;
+}
+
+int probav_plan_pw(int64_t nvox, int64_t vox_per_sample, int D, int impl, int backward, int32_t report[8])
+{
+    if (!report || nvox < 1 || impl < 2 || impl > 4) { set_error("probav_plan_pw: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    for (int i = 0; i < 8; ++i) report[i] = 0;
+    const long vps = vox_per_sample > 0 ? (long)vox_per_sample : (long)nvox;      // as probav_pw_forward / probav_pw_backward
+    if (!mfma_pw_supported(32, 256, D) || nvox % vps) return PROBAV_OK;            // what those two refuse: no kernel
+    if (impl == 2) { report[0] = PROBAV_PLAN_PW_MFMA; return PROBAV_OK; }
+    static const int32_t fwd[4] = {PROBAV_PLAN_NONE, PROBAV_PLAN_PF4, PROBAV_PLAN_PW_H3K, PROBAV_PLAN_PW_X6};
+    static const int32_t bwd[4] = {PROBAV_PLAN_NONE, PROBAV_PLAN_PW4, PROBAV_PLAN_PW_X6_H3, PROBAV_PLAN_PW_X6};
+    int wps = 0;
+    const int k = x6_pw_plan_kernel((long)nvox, vps, D, impl - 2, backward != 0, &wps);
+    report[0] = backward ? bwd[k] : fwd[k];
+    report[7] = wps;
+    return PROBAV_OK;
 }
 
 int probav_wn_forward(probav_engine* e, const float* params, float* weff, float* weffT, float* inv_norm, void* stream)

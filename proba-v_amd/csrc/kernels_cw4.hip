@@ -666,6 +666,16 @@ bool cw4_conv_supported(const ConvGeom& g, const float* gate)
     return gate == nullptr && cw4_plan(g, p, lds_bytes, grid);
 }
 
+bool cw4_conv_plan_ints(const ConvGeom& g, const float* gate, int out[5])
+{
+    Cw4Args p;
+    size_t lds_bytes;
+    int grid;
+    if (gate != nullptr || !cw4_plan(g, p, lds_bytes, grid)) return false;
+    out[0] = p.nsplit; out[1] = p.nstrips; out[2] = p.SR; out[3] = p.nslot; out[4] = grid;
+    return true;
+}
+
 int cw4_conv_forward(const ConvGeom& g, const float* x, const float* wfrag, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s)
 {
     Cw4Args p;

@@ -63,6 +63,9 @@ int conv_strip_forward(const StripSel& sel, const float* x, const float* gate, c
 bool x6_conv_rowtile_supported(const ConvGeom& g);
 int x6_conv_rowtile_forward(const ConvGeom& g, const float* x, const float* gate, const float* wfrag6, const float* bias,
                             const float* skip, float* y, int arith, const Amax& am, hipStream_t s);
+// introspection (probav_plan_conv): the row-tile plan of g as the forward / backward-data kernels (wgrad false: conv3_mfma_kernel in any arithmetic) or the backward-filter
+// kernel (wgrad true: conv3_wgrad_mfma_kernel) launch it.  out = {rows per tile, tiles per patch, grid}; false = no plan
+bool mfma_conv_plan_ints(const ConvGeom& g, bool wgrad, int out[3]);
 bool mfma_wgrad_supported(const ConvGeom& g);
 size_t mfma_wgrad_partial_floats(const ConvGeom& g);
 int mfma_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db,
@@ -88,6 +91,8 @@ int mfma_pw_backward_grid();
 // arithmetic only): the filter's first pieces stay in registers for the whole launch.  strip_select takes it when cw4_conv_supported(); with W4::conv off conv3_pp_kernel stays.
 // wfrag: PACK_H3_CONVP (25 input channels) / PACK_H3_CONV (32) fragments, as conv3_pp_kernel reads them
 bool cw4_conv_supported(const ConvGeom& g, const float* gate);
+// introspection (probav_plan_conv): the plan cw4_conv_forward launches.  out = {nsplit, nstrips, SR, nslot, grid}; false = the kernel does not take g
+bool cw4_conv_plan_ints(const ConvGeom& g, const float* gate, int out[5]);
 int cw4_conv_forward(const ConvGeom& g, const float* x, const float* wfrag, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s);
 
 }  // namespace probav

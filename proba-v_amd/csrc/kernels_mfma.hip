@@ -681,6 +681,7 @@ static ConvPlan conv_plan(const ConvGeom& g, bool all_channels)
 }
 
 bool mfma_conv_supported(const ConvGeom& g) { return conv_plan(g, false).ok; }
+static int rowtile_grid(const ConvPlan& p, const ConvGeom& g) { return g.N * p.a.ntile_rows; }      // one workgroup per (patch, tile of R rows)
 
 size_t mfma_conv_wfrag_floats(int Cin, int Cout)
 {
@@ -703,7 +704,7 @@ int mfma_conv_forward(const ConvGeom& g, const float* x, const float* gate, cons
 {
     const ConvPlan p = conv_plan(g, false);
     if (!p.ok) { set_error("mfma_conv_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
-    const dim3 grid((unsigned)(g.N * p.a.ntile_rows)), block(256);
+    const dim3 grid((unsigned)rowtile_grid(p, g)), block(256);
     if (p.CC == 1) return launch_lds<conv3_mfma_kernel<1, 1, 0>>("conv3_mfma", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
     if (p.CC == 25) return launch_lds<conv3_mfma_kernel<25, 13, 0>>("conv3_mfma", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
     return launch_lds<conv3_mfma_kernel<16, 8, 0>>("conv3_mfma", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag, bias, skip, y, am);
@@ -721,7 +722,7 @@ int x6_conv_rowtile_forward(const ConvGeom& g, const float* x, const float* gate
     const ConvPlan p = conv_plan(g, false);
     if (!x6_conv_rowtile_supported(g)) { set_error("x6_conv_rowtile_forward: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (arith == 2 && (!am.x || !am.w)) { set_error("x6_conv_rowtile_forward: H3 arithmetic needs the operands' amax slots", hipSuccess); return PROBAV_EINVAL; }
-    const dim3 grid((unsigned)(g.N * p.a.ntile_rows)), block(256);
+    const dim3 grid((unsigned)rowtile_grid(p, g)), block(256);
 #define PROBAV_RT(C, K, A) return launch_lds<conv3_mfma_kernel<C, K, A>>("conv3_mfma_x6", grid, block, p.lds_bytes, s, p.a, x, gate, (const float4*)wfrag6, bias, skip, y, am)
     if (arith == 2) { if (p.CC == 25) PROBAV_RT(25, 13, 2); else PROBAV_RT(16, 8, 2); }
     else            { if (p.CC == 25) PROBAV_RT(25, 13, 1); else PROBAV_RT(16, 8, 1); }
@@ -2639,6 +2640,14 @@ bool mfma_wgrad_supported(const ConvGeom& g)
 {
     if (g.Cout > 32) return false;
     return conv_plan(g, true).ok;
+}
+
+bool mfma_conv_plan_ints(const ConvGeom& g, bool wgrad, int out[3])
+{
+    if (wgrad ? !mfma_wgrad_supported(g) : !mfma_conv_supported(g)) return false;
+    const ConvPlan p = conv_plan(g, wgrad);
+    out[0] = p.R; out[1] = p.a.ntile_rows; out[2] = wgrad ? wgrad_grid(p, g) : rowtile_grid(p, g);
+    return true;
 }
 
 size_t mfma_wgrad_partial_floats(const ConvGeom& g)

@@ -607,6 +607,15 @@ bool wg4_wgrad_supported(const ConvGeom& g, const float* gate)
     return wg4_plan(g, gate, p, grid);
 }
 
+bool wg4_wgrad_plan_ints(const ConvGeom& g, const float* gate, int out[4])
+{
+    Wg4Args p;
+    int grid;
+    if (!wg4_plan(g, gate, p, grid)) return false;
+    out[0] = p.nsplit; out[1] = p.nstrips; out[2] = p.SR; out[3] = grid;
+    return true;
+}
+
 int wg4_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, const Amax& am, hipStream_t s)
 {
     Wg4Args p;

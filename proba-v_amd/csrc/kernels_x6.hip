@@ -1429,6 +1429,30 @@ static WgradX6Kernel x6_wgrad_select(const ConvGeom& g, const float* gate, int a
     return x6_wgrad_split(g, 2) ? WgradX6Kernel::x6_h3 : WgradX6Kernel::x6;
 }
 
+int x6_wgrad_plan_ints(const ConvGeom& g, const float* gate, int arith, int out[4])
+{
+    const WgradX6Kernel k = x6_wgrad_select(g, gate, arith);
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (k == WgradX6Kernel::none) return 0;
+    if (k == WgradX6Kernel::w4) return wg4_wgrad_plan_ints(g, gate, out) ? 1 : 0;
+    const int a = k == WgradX6Kernel::x6_h3 ? 2 : 1;
+    out[0] = x6_wgrad_split(g, a); out[3] = x6_wgrad_grid(g, a);
+    return a == 2 ? 2 : 3;
+}
+
+int x6_pw_plan_kernel(long nvox, long vps, int D, int arith, bool backward, int* wps)
+{
+    if (vps <= 0 || vps > nvox) vps = nvox;                          // as x6_pw_forward / x6_pw_backward
+    *wps = 0;
+    if (backward) {
+        const PwBwdKernel k = x6_pw_backward_select(nvox, vps, D, arith);
+        if (k == PwBwdKernel::w4) { *wps = pw4_backward_wps(nvox, vps); return 1; }
+        return k == PwBwdKernel::x6_h3 ? 2 : 3;
+    }
+    const PwFwdKernel k = x6_pw_forward_select(nvox, vps, D, arith, false);
+    return k == PwFwdKernel::w4 ? 1 : (k == PwFwdKernel::h3k ? 2 : 3);
+}
+
 int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial,
                   int arith, const Amax& am, hipStream_t s)
 {

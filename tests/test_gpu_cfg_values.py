@@ -36,12 +36,12 @@ def _keep_workspaces(monkeypatch):
     monkeypatch.setenv("PROBAV_KEEP_WS", "1")
 
 
-def _build(dev, row, T, gray, seed):
+def _build(dev, row, T, gray, seed, P=16):
     from probav_amd.modelsTF import WDSRConv3D
     F, R, E, decay, D = row
     arch = arch_of(row, T, gray)
     params = synth.synth_params(seed=seed, perturb=True, **arch)
-    m = WDSRConv3D("t", "NIR", synth.NIR_MEAN, synth.NIR_STD, 6).build(3, F, (3, 3, 3), R, E, decay, T, 16, gray, seed=0)
+    m = WDSRConv3D("t", "NIR", synth.NIR_MEAN, synth.NIR_STD, 6).build(3, F, (3, 3, 3), R, E, decay, T, P, gray, seed=0)
     assert int(m.numFilters * m.decayRate) == D
     m.load_variables(params)
     return m.to(dev), params
@@ -50,20 +50,22 @@ def _build(dev, row, T, gray, seed):
 _oracle_cache = {}
 
 
-def _oracle(row, T, gray, B):
-    """Inputs, weights and the un-gated fp64 results of one configuration (numpy forward; torch forward, loss and gradients), shared by its five families."""
-    key = case_id(row, T, gray, B)
+def _oracle(row, T, gray, B, P=16):
+    """Inputs, weights and the un-gated fp64 results of one configuration (numpy forward; torch forward, loss and gradients), shared by its five families.
+    P: patchSizeLR (inputs of P + 6, predictions of 3 P pixels a side)."""
+    key = case_id(row, T, gray, B) + ("" if P == 16 else "-p%d" % P)
     if key not in _oracle_cache:
         _oracle_cache.clear()                                   # cases run configuration by configuration: keep one
         F, R, E, decay, D = row
         C = 1 if gray else 3
-        seed = 7000 + 131 * F + 17 * R + 3 * E + D + T + C + B
+        seed = 7000 + 131 * F + 17 * R + 3 * E + D + T + C + B + (0 if P == 16 else 1000 * P)
         arch = arch_of(row, T, gray)
-        x, hr, mask = synth.synth_batch(B, seed=seed + 1, numImgLR=T, inChannels=C)
+        x, hr, mask = synth.synth_batch(B, seed=seed + 1, numImgLR=T, inChannels=C, patchSizeLR=P)
         params = synth.synth_params(seed=seed, perturb=True, **arch)
         ref = on.wdsr_forward(x, params, synth.NIR_MEAN, synth.NIR_STD, numResBlocks=R, numImgLR=T)
         pred_o, loss_o, grads_o = ot.train_step_grads(torch.tensor(x, dtype=torch.float64), torch.tensor(hr), torch.tensor(mask), ot.to_torch_params(params),
                                                       synth.NIR_MEAN, synth.NIR_STD, numResBlocks=R, numImgLR=T)
+        assert pred_o.shape == ref.shape == (B, 3 * P, 3 * P, 1)
         assert np.abs(pred_o.numpy() - ref).max() < 1e-9 * np.abs(ref).max()          # the two formulations of the oracle agree at these shapes
         _oracle_cache[key] = dict(seed=seed, x=x, hr=hr, mask=mask, params=params, ref=ref, loss=float(loss_o), grads=grads_o)
     return _oracle_cache[key]
@@ -99,14 +101,18 @@ def test_cfg_value_matches_the_oracle(dev, case, impl):
     """Forward against the fp64 numpy oracle, loss against the fp64 torch oracle, every gradient tensor against its autograd, and the properties the README
     claims for every family: training and inference predictions equal bit for bit, a repeated step equal bit for bit, a sample's result independent of its
     batch mates bit for bit."""
+    row, T, gray, B = case
+    _check_against_the_oracle(dev, row, T, gray, B, impl, 16, case_id(*case))
+
+
+def _check_against_the_oracle(dev, row, T, gray, B, impl, P, label):
     from probav_amd.introspect import device_gates
     from probav_amd.loss import Losses
-    row, T, gray, B = case
     F, R, E, decay, D = row
-    o = _oracle(row, T, gray, B)
-    m, params = _build(dev, row, T, gray, o["seed"])
+    o = _oracle(row, T, gray, B, P)
+    m, params = _build(dev, row, T, gray, o["seed"], P)
     m.set_impl(impl)
-    lo = Losses(targetShape=(48, 48, 1))
+    lo = Losses(targetShape=(3 * P, 3 * P, 1))
     x, hr, mask = (torch.as_tensor(o[k]).to(dev) for k in ("x", "hr", "mask"))
 
     def step():
@@ -117,7 +123,7 @@ def test_cfg_value_matches_the_oracle(dev, case, impl):
         return p.detach().clone(), float(l), m.flat.grad.detach().clone()
 
     pred, loss, grad = step()
-    assert tuple(pred.shape) == (B, 48, 48, 1) and torch.isfinite(pred).all() and torch.isfinite(grad).all()
+    assert tuple(pred.shape) == (B, 3 * P, 3 * P, 1) and torch.isfinite(pred).all() and torch.isfinite(grad).all()
     fused = impl >= 1 and pw_fused(F, E, D)
     gated = (not fused) or impl >= 3
     gates = device_gates(m, m.flat.detach(), B, T) if gated else None            # (before the next pass replaces the workspace)
@@ -132,8 +138,8 @@ def test_cfg_value_matches_the_oracle(dev, case, impl):
         assert torch.equal(m(x[:1].contiguous(), training=False), pred[:1]), "sample 0 depends on its batch mates"
     (pred3, _, grad3), routes = _route_record(m, step)
     assert torch.equal(pred, pred3) and torch.equal(grad, grad3), "the side-stream mode changes the result"
-    print("cfg %s impl %d: %s pointwise pair; launches per kernel class: %s" % (case_id(*case), impl, "fused" if fused else "un-fused", routes))
-    print("cfg %s impl %d: output err / max |ref| = %.3g, loss rel err = %.3g" % (case_id(*case), impl, e_pred, e_loss))
+    print("cfg %s impl %d: %s pointwise pair; launches per kernel class: %s" % (label, impl, "fused" if fused else "un-fused", routes))
+    print("cfg %s impl %d: output err / max |ref| = %.3g, loss rel err = %.3g" % (label, impl, e_pred, e_loss))
     assert e_pred < 2e-5, "output rel err %.3e (bar 1e-3)" % e_pred
     assert e_loss < 1e-5, "loss rel err %.3e" % e_loss
     gdev = grad.cpu().double().numpy()
@@ -146,14 +152,14 @@ def test_cfg_value_matches_the_oracle(dev, case, impl):
         nflip = sum(r[0][0] for r in report.values())
         worst_margin = max((r[0][1] / max(r[0][2], 1e-30)) for r in report.values())
         print("cfg %s impl %d: %d of %d ReLU gates differ between the device and the fp64 evaluation; largest |pre-activation| among them = %.3g of the layer's rms"
-              % (case_id(*case), impl, nflip, sum(int(np.prod(g.shape)) for g in gates.values()), worst_margin))
+              % (label, impl, nflip, sum(int(np.prod(g.shape)) for g in gates.values()), worst_margin))
         assert worst_margin < 1e-4, "a gate that differs is NOT a ~0 pre-activation: the forward itself is off"
         for name, key, a, b in _tensors(m):
             r = grads_o[name][key].numpy().reshape(-1)
             e = np.abs(gdev[a:b] - r).max() / (np.abs(r).max() + 1e-30)
             if e > worst[0]:
                 worst = (e, name + "/" + key)
-        print("cfg %s impl %d: worst per-tensor max-norm gradient error with the device's gates: %.3g (%s)" % (case_id(*case), impl, worst[0], worst[1]))
+        print("cfg %s impl %d: worst per-tensor max-norm gradient error with the device's gates: %.3g (%s)" % (label, impl, worst[0], worst[1]))
         assert worst[0] < 1e-3, worst
     else:
         for name, key, a, b in _tensors(m):
@@ -161,8 +167,22 @@ def test_cfg_value_matches_the_oracle(dev, case, impl):
             e = np.sqrt(((gdev[a:b] - r) ** 2).sum()) / (np.sqrt((r ** 2).sum()) + 1e-30)
             if e > worst[0]:
                 worst = (e, name + "/" + key)
-        print("cfg %s impl %d: worst un-gated relative-L2 gradient error per tensor: %.3g (%s)" % (case_id(*case), impl, worst[0], worst[1]))
+        print("cfg %s impl %d: worst un-gated relative-L2 gradient error per tensor: %.3g (%s)" % (label, impl, worst[0], worst[1]))
         assert worst[0] < GRAD_L2_TOL, worst
+
+
+SHIPPED = (32, 12, 8, 0.8, 25)
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+@pytest.mark.parametrize("P", [24, 17, 4], ids=["p24", "p17", "p4"])
+def test_patch_size_matches_the_oracle(dev, P, impl):
+    """patchSizeLR is a cfg value too (`[Patches]`): the shipped network at patch sizes other than 16, whole network, against the oracle on every kernel family, with the bars
+    and the bit-for-bit properties of test_cfg_value_matches_the_oracle (test_gpu_parity.py::test_other_patch_sizes_agree_across_engines compares impl 4 with impl 0 only, in
+    relative L2 of the whole flat gradient).  24: 30-wide rows -- three column ranges in conv3_w4_kernel, the general backward-filter kernel; 17: odd 23-wide rows, which
+    conv3_w4_kernel declines (tests/plan_cases.py holds both kernel by kernel); 4: 10 x 10 inputs and a 12-pixel prediction, whose loss crop of 6 x 6 = 36 pixels is the
+    smallest of tests/loss_cases.py.  The oracle's two formulations are asserted to agree at each of these extents (_oracle)."""
+    _check_against_the_oracle(dev, SHIPPED, 9, True, 2, impl, P, "%s-p%d" % (case_id(SHIPPED), P))
 
 
 @pytest.mark.parametrize("row", [(32, 3, 8, 0.82, 26), (48, 2, 6, 0.9, 43)], ids=["fused-f32-r3-e8-d26", "unfused-f48-r2-e6-d43"])
