@@ -164,7 +164,7 @@ int probav_shift_l1edge_backward(const float* hr, const uint8_t* mask, const flo
 /* cfg loss = l1msssim: Losses.shiftCompensatedRevSSIM                             models/loss.py:99-124,189-212
  * ONE scalar for the batch: min over the shifts of  eta * (1 - sum_{scale,sample} luminance * prod_scale(contrast * structure) / B)
  * + (1 - eta) * weighted L1 / (B * (2^bit_depth - 1)), with the reference's five exponential windows (its quirks restated in
- * kernels_small.hip).  scratch: probav_revssim_scratch_bytes() bytes, written by the forward and read by the backward; loss and arg
+ * kernels_loss.hip).  scratch: probav_revssim_scratch_bytes() bytes, written by the forward and read by the backward; loss and arg
  * are one element each (the batch shares the shift).                                                                               */
 size_t probav_revssim_scratch_bytes(int batch, int border);
 int probav_revssim_forward(const float* hr, const uint8_t* mask, const float* pred, int batch, int size, int border, int bit_depth,

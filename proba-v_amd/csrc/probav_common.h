@@ -141,7 +141,7 @@ bool conv3d_up_bwd_data_supported(const ConvGeom& g);
 int conv3d_up_bwd_data(const ConvGeom& g, const float* dy, const float* wT, const float* bias, float* dx, unsigned* amax, hipStream_t s);
 bool conv3d_direct_wgrad_is_tuned(const ConvGeom& g);
 
-// ---- kernels_small.hip ---------------------------------------------------------------------------
+// ---- kernels_small.hip : weight normalisation, head / tail, pad folds, clip + round, optimizer (and set_error / check_launch above) ----
 struct WnLayer {            // one weight-normalised layer inside the flat parameter buffer
     int g_off, v_off, b_off;    // offsets into params / grads (floats)
     int w_off;                  // offset into weff / weffT / dweff (floats) == running sum of K*Cout
@@ -170,6 +170,19 @@ int reflect_fold(const float* dpad, float* dx, int N, int H, int W, int TC, unsi
 // general form: gradient of tf.pad(x, [ph, pw, pt] 'reflect') folded back onto x [N,H,W,T,C]; pads <= 2
 int reflect_fold3(const float* dpad, float* dx, int N, int H, int W, int T, int C, int ph, int pw, int pt, hipStream_t s);
 int clip_round(const float* in, float* out, size_t n, float lo, float hi, hipStream_t s);
+int nadam_step(float* theta, const float* grad, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+               float c_g, float c_m, float c_v, hipStream_t s);
+// optimizer options on the device (include/probav_hip.h): the gradient's global norm -> control block (two launches; partial: grad_guard_scratch_bytes()),
+// and the two update launches reading it (ctl / ema may be null)
+size_t grad_guard_scratch_bytes();
+int grad_guard(const float* grad, long n, float clipnorm, int skip_nonfinite, double* partial, probav_guard_ctl* ctl, hipStream_t s);
+int nadam_step_guarded(float* theta, const float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
+                       float c_g, float c_m, float c_v, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s);
+int optimizer_wn_step_guarded(const WnLayer* d_layers, int nlayers, int cout_total, int cin_total, float* params, const float* grad, float* m, float* v,
+                              float lr, float b1, float b2, float eps, float c_g, float c_m, float c_v,
+                              float* weff, float* weffT, float* inv_norm, unsigned* amax, float* ema, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s);
+
+// ---- kernels_loss.hip : the shift-compensated losses (their device helpers shared with kernels_small.hip: reduce_device.h) ----------
 int shift_loss_forward(const float* hr, const uint8_t* mask, const float* pred, int B, int S, int border,
                        float* l1_per_sample, float* l2_per_sample, float* cpsnr_per_sample,
                        int* arg_l1, int* arg_l2, float* mean_l1, float* mean_l2, float max_val, hipStream_t s);
@@ -187,17 +200,5 @@ int revssim_forward(const float* hr, const uint8_t* mask, const float* pred, int
                     double* scratch, float* loss, int* arg, hipStream_t s);
 int revssim_backward(const float* hr, const uint8_t* mask, const float* pred, const int* arg, const double* scratch, int B, int S,
                      int border, float max_val, float eta, const float* upstream, float* dpred, hipStream_t s);
-
-int nadam_step(float* theta, const float* grad, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-               float c_g, float c_m, float c_v, hipStream_t s);
-// optimizer options on the device (include/probav_hip.h): the gradient's global norm -> control block (two launches; partial: grad_guard_scratch_bytes()),
-// and the two update launches reading it (ctl / ema may be null)
-size_t grad_guard_scratch_bytes();
-int grad_guard(const float* grad, long n, float clipnorm, int skip_nonfinite, double* partial, probav_guard_ctl* ctl, hipStream_t s);
-int nadam_step_guarded(float* theta, const float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
-                       float c_g, float c_m, float c_v, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s);
-int optimizer_wn_step_guarded(const WnLayer* d_layers, int nlayers, int cout_total, int cin_total, float* params, const float* grad, float* m, float* v,
-                              float lr, float b1, float b2, float eps, float c_g, float c_m, float c_v,
-                              float* weff, float* weffT, float* inv_norm, unsigned* amax, float* ema, float ema_mom, const probav_guard_ctl* ctl, hipStream_t s);
 
 }  // namespace probav

@@ -10,6 +10,11 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
                                                                             Losses.shiftCompensatedL1Loss / L2Loss   models/loss.py:55-84
   probav::shift_loss_backward(hr, mask, pred, arg, upstream, border, which) -> dpred
   probav::shift_metrics(hr, mask, pred, border, bit_depth) -> (f[3,B], arg[2,B], means[2])     one launch: L1, L2, cPSNR of every sample
+  probav::shift_l1edge_loss(pred, hr, mask, border, pi) -> (loss, arg [B], per_sample [B])   Losses.shiftCompensatedL1EdgeLoss (cfg sobel_l1_mix)   models/loss.py:86-97
+  probav::shift_l1edge_loss_backward(hr, mask, pred, arg, upstream, border, pi) -> dpred
+  probav::revssim_loss(pred, hr, mask, border, bit_depth, eta) -> (loss, arg [1], moments f64 [shifts, B, 5, 7])
+                                                                            Losses.shiftCompensatedRevSSIM (cfg l1msssim)   models/loss.py:99-124
+  probav::revssim_loss_backward(hr, mask, pred, arg, moments, upstream, border, bit_depth, eta) -> dpred
   probav::nadam_step(theta, grad, m, v, lr, b1, b2, eps, c_g, c_m, c_v) -> ()                 optimizer.apply_gradients   trainClass.py:132
   probav::optimizer_wn_step(theta, grad, m, v, wcache, engine, lr, ...) -> ()                 the same update fused with the weight normalisation
                                                                             and operand packing of the NEXT step (wdsr_forward's optional `wcache`)
@@ -189,7 +194,7 @@ wdsr_forward.register_autograd(_wdsr_bwd, setup_context=_wdsr_setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# shift-compensated loss / metric
+# shift-compensated losses / metric (csrc/kernels_loss.hip)
 # ---------------------------------------------------------------------------------------------------------------------------------
 @torch.library.custom_op("probav::shift_metrics", mutates_args=(), device_types="cuda")
 def shift_metrics(hr: Tensor, mask: Tensor, pred: Tensor, border: int, bit_depth: int) -> tuple[Tensor, Tensor, Tensor]:
@@ -272,6 +277,160 @@ def _shift_bwd(ctx, g_loss, g_arg, g_per):
 
 
 shift_loss.register_autograd(_shift_bwd, setup_context=_shift_setup)
+
+
+def _crop_loss_args(name, pred, hr, mask, border, min_crop):
+    """-> (B, S) after the checks the real and the fake kernel of a crop-in-LDS loss share."""
+    if pred.dim() != 4 or pred.shape[3] != 1 or pred.shape[1] != pred.shape[2] or hr.shape != pred.shape or mask.shape != pred.shape:
+        raise ValueError("%s: pred, hr, mask must all be [B, S, S, 1]; got %s %s %s" % (name, tuple(pred.shape), tuple(hr.shape), tuple(mask.shape)))
+    if pred.dtype != torch.float32 or hr.dtype != torch.float32 or mask.dtype != torch.uint8:
+        raise ValueError("%s: pred / hr must be float32, mask uint8 (nonzero = clear); got %s %s %s" % (name, pred.dtype, hr.dtype, mask.dtype))
+    B, S = pred.shape[0], pred.shape[1]
+    if B < 1 or border < 0 or S - 2 * border < min_crop:
+        raise ValueError("%s: bad shape (crop = size - 2 * border must be at least %d)" % (name, min_crop))
+    return B, S
+
+
+def _crop_loss_backward_args(name, pred, hr, mask, arg, n_arg, upstream, border, min_crop):
+    B, S = _crop_loss_args(name, pred, hr, mask, border, min_crop)
+    if arg.dtype != torch.int32 or arg.numel() != (B if n_arg is None else n_arg) or upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("%s: arg int32 [%d], upstream float32 [1]; got %s %s, %s %s"
+                         % (name, B if n_arg is None else n_arg, arg.dtype, tuple(arg.shape), upstream.dtype, tuple(upstream.shape)))
+    return B, S
+
+
+@torch.library.custom_op("probav::shift_l1edge_loss", mutates_args=(), device_types="cuda")
+def shift_l1edge_loss(pred: Tensor, hr: Tensor, mask: Tensor, border: int, pi: float) -> tuple[Tensor, Tensor, Tensor]:
+    """cfg loss = sobel_l1_mix (models/loss.py:86-97): pi * L1 + (1 - pi) * Sobel-edge L1 of the bias-corrected residual, minimum over the shifts
+    -> (batch-mean loss [scalar], arg-min shift per sample [B], per-sample minima [B]).  Two launches: all shifts of every sample, the batch mean."""
+    B, S = _crop_loss_args("shift_l1edge_loss", pred, hr, mask, border, 3)
+    _dev(pred, "predPatchHR")
+    pred, hr, mask = pred.contiguous(), hr.contiguous(), mask.contiguous()
+    per = torch.empty((B,), dtype=torch.float32, device=pred.device)
+    arg = torch.empty((B,), dtype=torch.int32, device=pred.device)
+    mean = torch.empty((2,), dtype=torch.float32, device=pred.device)       # the C entry point's mean[2]: the loss and a scratch word
+    _lib.check(_lib.lib().probav_shift_l1edge_forward(_lib.ptr(hr), _lib.ptr(mask), _lib.ptr(pred), B, S, border, pi, _lib.ptr(per), _lib.ptr(arg),
+                                                      _lib.ptr(mean), _lib.current_stream()), "probav_shift_l1edge_forward")
+    return mean[0], arg, per                   # (a 0-dim view of this call's own allocation: no copy launch)
+
+
+@shift_l1edge_loss.register_fake
+def _(pred, hr, mask, border, pi):
+    B, _ = _crop_loss_args("shift_l1edge_loss", pred, hr, mask, border, 3)
+    return (pred.new_empty((), dtype=torch.float32), pred.new_empty((B,), dtype=torch.int32), pred.new_empty((B,), dtype=torch.float32))
+
+
+@torch.library.custom_op("probav::shift_l1edge_loss_backward", mutates_args=(), device_types="cuda")
+def shift_l1edge_loss_backward(hr: Tensor, mask: Tensor, pred: Tensor, arg: Tensor, upstream: Tensor, border: int, pi: float) -> Tensor:
+    B, S = _crop_loss_backward_args("shift_l1edge_loss_backward", pred, hr, mask, arg, None, upstream, border, 3)
+    _dev(pred, "predPatchHR")
+    pred, hr, mask, arg = pred.contiguous(), hr.contiguous(), mask.contiguous(), arg.contiguous()
+    dpred = torch.empty_like(pred)
+    _lib.check(_lib.lib().probav_shift_l1edge_backward(_lib.ptr(hr), _lib.ptr(mask), _lib.ptr(pred), _lib.ptr(arg), B, S, border, pi, _lib.ptr(upstream),
+                                                       _lib.ptr(dpred), _lib.current_stream()), "probav_shift_l1edge_backward")
+    return dpred
+
+
+@shift_l1edge_loss_backward.register_fake
+def _(hr, mask, pred, arg, upstream, border, pi):
+    _crop_loss_backward_args("shift_l1edge_loss_backward", pred, hr, mask, arg, None, upstream, border, 3)
+    return torch.empty_like(pred, memory_format=torch.contiguous_format)
+
+
+def _l1edge_setup(ctx, inputs, output):
+    pred, hr, mask, border, pi = inputs
+    ctx.save_for_backward(pred, hr, mask, output[1])
+    ctx.border, ctx.pi = border, pi
+    ctx.set_materialize_grads(False)
+
+
+def _l1edge_bwd(ctx, g_loss, g_arg, g_per):
+    if g_loss is None:                         # (only the batch-mean loss is differentiable)
+        return None, None, None, None, None
+    pred, hr, mask, arg = ctx.saved_tensors
+    dpred = torch.ops.probav.shift_l1edge_loss_backward(hr, mask, pred, arg, g_loss.contiguous().float().reshape(1), ctx.border, ctx.pi)
+    return dpred, None, None, None, None
+
+
+shift_l1edge_loss.register_autograd(_l1edge_bwd, setup_context=_l1edge_setup)
+
+REVSSIM_SCALES, REVSSIM_SUMS = 5, 7            # csrc/kernels_loss.hip: the weighted sums one (shift, sample, scale) leaves for the reverse pass
+
+
+def _revssim_moments_shape(B, border):
+    ns = 2 * border + 1
+    return (ns * ns, B, REVSSIM_SCALES, REVSSIM_SUMS)
+
+
+@torch.library.custom_op("probav::revssim_loss", mutates_args=(), device_types="cuda")
+def revssim_loss(pred: Tensor, hr: Tensor, mask: Tensor, border: int, bit_depth: int, eta: float) -> tuple[Tensor, Tensor, Tensor]:
+    """cfg loss = l1msssim (models/loss.py:99-124, 189-212): the batch-level multi-scale SSIM / weighted-L1 mixture, minimum over the shifts
+    -> (loss [scalar], the batch's arg-min shift [1], moments float64 [shifts, B, 5, 7]).  `moments` is the saved state of the pass: an OUTPUT
+    here (like wdsr_forward's workspace), an input of revssim_loss_backward; every element is written."""
+    B, S = _crop_loss_args("revssim_loss", pred, hr, mask, border, 2)
+    _dev(pred, "predPatchHR")
+    pred, hr, mask = pred.contiguous(), hr.contiguous(), mask.contiguous()
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    arg = torch.empty((1,), dtype=torch.int32, device=pred.device)
+    moments = torch.empty(_revssim_moments_shape(B, border), dtype=torch.float64, device=pred.device)
+    nbytes = _lib.lib().probav_revssim_scratch_bytes(B, border)
+    if moments.numel() * 8 != nbytes:
+        raise RuntimeError("revssim_loss: moments of %d bytes, probav_revssim_scratch_bytes(%d, %d) = %d" % (moments.numel() * 8, B, border, nbytes))
+    _lib.check(_lib.lib().probav_revssim_forward(_lib.ptr(hr), _lib.ptr(mask), _lib.ptr(pred), B, S, border, bit_depth, eta, _lib.ptr(moments),
+                                                 nbytes, _lib.ptr(loss), _lib.ptr(arg), _lib.current_stream()), "probav_revssim_forward")
+    return loss, arg, moments
+
+
+@revssim_loss.register_fake
+def _(pred, hr, mask, border, bit_depth, eta):
+    B, _ = _crop_loss_args("revssim_loss", pred, hr, mask, border, 2)
+    return (pred.new_empty((), dtype=torch.float32), pred.new_empty((1,), dtype=torch.int32),
+            pred.new_empty(_revssim_moments_shape(B, border), dtype=torch.float64))
+
+
+def _revssim_backward_args(hr, mask, pred, arg, moments, upstream, border):
+    B, S = _crop_loss_backward_args("revssim_loss_backward", pred, hr, mask, arg, 1, upstream, border, 2)
+    if moments.dtype != torch.float64 or tuple(moments.shape) != _revssim_moments_shape(B, border) or not moments.is_contiguous():
+        raise ValueError("revssim_loss_backward: moments must be the contiguous float64 %s that revssim_loss returned; got %s %s"
+                         % (_revssim_moments_shape(B, border), moments.dtype, tuple(moments.shape)))
+    return B, S
+
+
+@torch.library.custom_op("probav::revssim_loss_backward", mutates_args=(), device_types="cuda")
+def revssim_loss_backward(hr: Tensor, mask: Tensor, pred: Tensor, arg: Tensor, moments: Tensor, upstream: Tensor, border: int, bit_depth: int,
+                          eta: float) -> Tensor:
+    B, S = _revssim_backward_args(hr, mask, pred, arg, moments, upstream, border)
+    _dev(pred, "predPatchHR")
+    pred, hr, mask = pred.contiguous(), hr.contiguous(), mask.contiguous()
+    dpred = torch.empty_like(pred)
+    _lib.check(_lib.lib().probav_revssim_backward(_lib.ptr(hr), _lib.ptr(mask), _lib.ptr(pred), _lib.ptr(arg), _lib.ptr(moments), B, S, border, bit_depth,
+                                                  eta, _lib.ptr(upstream), _lib.ptr(dpred), _lib.current_stream()), "probav_revssim_backward")
+    return dpred
+
+
+@revssim_loss_backward.register_fake
+def _(hr, mask, pred, arg, moments, upstream, border, bit_depth, eta):
+    _revssim_backward_args(hr, mask, pred, arg, moments, upstream, border)
+    return torch.empty_like(pred, memory_format=torch.contiguous_format)
+
+
+def _revssim_setup(ctx, inputs, output):
+    pred, hr, mask, border, bit_depth, eta = inputs
+    ctx.save_for_backward(pred, hr, mask, output[1], output[2])      # (moments is an output of this node: through save_for_backward, see _wdsr_setup)
+    ctx.border, ctx.bit_depth, ctx.eta = border, bit_depth, eta
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.set_materialize_grads(False)
+
+
+def _revssim_bwd(ctx, g_loss, g_arg, g_moments):
+    if g_loss is None:
+        return None, None, None, None, None, None
+    pred, hr, mask, arg, moments = ctx.saved_tensors
+    dpred = torch.ops.probav.revssim_loss_backward(hr, mask, pred, arg, moments, g_loss.contiguous().float().reshape(1), ctx.border, ctx.bit_depth, ctx.eta)
+    return dpred, None, None, None, None, None
+
+
+revssim_loss.register_autograd(_revssim_bwd, setup_context=_revssim_setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The shift-compensated losses (csrc/kernels_small.hip: L1 / L2 / cPSNR, sobel_l1_mix, l1msssim) on the device against the fp64 oracle, at
+"""The shift-compensated losses (csrc/kernels_loss.hip: L1 / L2 / cPSNR, sobel_l1_mix, l1msssim) on the device against the fp64 oracle, at
 the shapes where the kernels take another path: every case of tests/loss_cases.py, whose conditions tests/test_loss_cases_host.py proves
 on the host -- so nothing is skipped here and no pixel or sample is left out.
 

@@ -23,7 +23,12 @@ def test_ops_are_registered_with_schemas():
     import probav_amd.ops  # noqa: F401
     want = {"wdsr_forward": "(Tensor flat, Tensor x, SymInt engine, SymInt out_size, bool training, Tensor? wcache=None) -> (Tensor, Tensor)",
             "wdsr_backward": "(Tensor flat, Tensor dy, Tensor ws, SymInt engine, Tensor? wcache=None) -> Tensor",      # functional: the saved state is only read
-            "nadam_step": None, "optimizer_wn_step": None, "shift_loss": None, "shift_loss_backward": None, "shift_metrics": None, "clip_round": None}
+            "nadam_step": None, "optimizer_wn_step": None, "shift_loss": None, "shift_loss_backward": None, "shift_metrics": None, "clip_round": None,
+            "shift_l1edge_loss": "(Tensor pred, Tensor hr, Tensor mask, SymInt border, float pi) -> (Tensor, Tensor, Tensor)",
+            "shift_l1edge_loss_backward": "(Tensor hr, Tensor mask, Tensor pred, Tensor arg, Tensor upstream, SymInt border, float pi) -> Tensor",
+            "revssim_loss": "(Tensor pred, Tensor hr, Tensor mask, SymInt border, SymInt bit_depth, float eta) -> (Tensor, Tensor, Tensor)",
+            "revssim_loss_backward": "(Tensor hr, Tensor mask, Tensor pred, Tensor arg, Tensor moments, Tensor upstream, SymInt border, SymInt bit_depth, "
+                                     "float eta) -> Tensor"}
     for name, schema in want.items():
         op = getattr(torch.ops.probav, name).default
         if schema is not None:
@@ -74,9 +79,86 @@ def test_opcheck_loss_optimizer_and_epilogue_ops(dev):
     assert torch.ops.probav.clip_round(xx, 0.0, 65536.0).tolist() == [0.0, 0.0, 2.0, 2.0, 65536.0, 65536.0]
 
 
-def test_ops_trace_under_torch_compile_fullgraph(dev):
+def _loss_case_inputs(case, dev):
+    from tests import loss_cases as lc
+    hr, mask, pred = lc.inputs(case)
+    return torch.as_tensor(hr).to(dev), torch.as_tensor(mask).to(dev).view(torch.uint8), torch.as_tensor(pred).to(dev)
+
+
+def _bits(t):
+    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
+
+
+def test_opcheck_edge_and_l1msssim_loss_ops(dev):
+    """opcheck with its default tests (schema, autograd registration, fake tensor, AOT dispatch) on both forward ops with a prediction that
+    requires a gradient, and on both reverse ops.  Every output element is written (the moments are sized exactly), so outputs compare."""
+    from tests import loss_cases as lc
+    up = torch.full((1,), 1.3, device=dev)
+    case = lc.by_id("edge-S19-b1-B3-random-random")                                      # crop 17: 289 pixels, one past a 256-thread round
+    hd, md, pd = _loss_case_inputs(case, dev)
+    p = pd.clone().requires_grad_(True)
+    torch.library.opcheck(torch.ops.probav.shift_l1edge_loss.default, (p, hd, md, 1, 0.7))
+    _, arg, _ = torch.ops.probav.shift_l1edge_loss(pd, hd, md, 1, 0.7)
+    torch.library.opcheck(torch.ops.probav.shift_l1edge_loss_backward.default, (hd, md, pd, arg, up, 1, 0.7))
+    case = lc._case(lc.REVSSIM, 9, 1, 3, 703, kind="faint")
+    hd, md, pd = _loss_case_inputs(case, dev)
+    p = pd.clone().requires_grad_(True)
+    torch.library.opcheck(torch.ops.probav.revssim_loss.default, (p, hd, md, 1, 16, 0.25))
+    _, arg, mom = torch.ops.probav.revssim_loss(pd, hd, md, 1, 16, 0.25)
+    assert mom.shape == (9, 3, 5, 7) and mom.numel() * 8 == _lib().lib().probav_revssim_scratch_bytes(3, 1)
+    torch.library.opcheck(torch.ops.probav.revssim_loss_backward.default, (hd, md, pd, arg, mom, up, 1, 16, 0.25))
+
+
+def _lib():
+    from probav_amd import _lib as L
+    return L
+
+
+# crop 3 at border 1 (both mirror folds land on row 1), crop 17 (one past a 256-thread round), a sample with no candidate, an exact tie;
+# crop 2 (the smallest accepted), B = 33, a sample with no candidate, an exact tie
+LOSS_OP_CASES = ["edge-S5-b1-B3-random-random", "edge-S19-b1-B3-random-random", "edge-S12-b2-B3-random-none1", "edge-S14-b3-B2-tie_lr-full",
+                 "revssim-S4-b1-B3-faint-random", "revssim-S9-b1-B33-faint-random", "revssim-S12-b2-B3-random-none1", "revssim-S20-b4-B3-tie_cols-full"]
+
+
+@pytest.mark.parametrize("cid", LOSS_OP_CASES)
+def test_losses_wrapper_ops_and_c_abi_agree_bit_for_bit(dev, cid):
+    """Losses.shiftCompensatedL1EdgeLoss / RevSSIM == the ops called directly == the C ABI called as tests/test_gpu_losses.py calls it:
+    value and gradient of the prediction, compared as bit patterns (a NaN must be the same NaN)."""
+    from tests import loss_cases as lc
+    from tests import test_gpu_losses as tl
+    case = lc.by_id(cid)
+    hd, md, pd = _loss_case_inputs(case, dev)
+    b, up = case["border"], case["upstream"]
+    lo = tl._losses(case)
+    pw, po = pd.clone().requires_grad_(True), pd.clone().requires_grad_(True)
+    if case["loss"] == lc.EDGE:
+        vw = lo.shiftCompensatedL1EdgeLoss(hd, md, pw)
+        vo, arg, per = torch.ops.probav.shift_l1edge_loss(po, hd, md, b, float(lo.pi))
+        rc, c_per, c_arg, c_mean = tl._c_edge_forward(dev, hd, md, pd, case)
+        assert rc == 0
+        rc, c_dp = tl._c_edge_backward(dev, hd, md, pd, c_arg, case, up)
+        assert rc == 0
+        assert torch.equal(arg, c_arg) and torch.equal(_bits(per), _bits(c_per))
+        c_val = c_mean[0]
+    else:
+        vw = lo.shiftCompensatedRevSSIM(hd, md, pw)
+        vo, arg, mom = torch.ops.probav.revssim_loss(po, hd, md, b, case["bit_depth"], float(lo.eta))
+        rc, c_loss, c_arg, c_dp, c_scratch = tl._c_revssim(dev, hd, md, pd, case, up)
+        assert rc == 0
+        assert torch.equal(arg, c_arg) and torch.equal(_bits(mom.reshape(-1)), _bits(c_scratch[:mom.numel()]))
+        c_val = c_loss[0]
+    (up * vw).backward()
+    (up * vo).backward()
+    assert vw.shape == () and vo.shape == ()
+    assert torch.equal(_bits(vw.detach()), _bits(vo.detach())) and torch.equal(_bits(vo.detach()), _bits(c_val))
+    assert torch.equal(_bits(pw.grad), _bits(po.grad)) and torch.equal(_bits(po.grad), _bits(c_dp))
+
+
+@pytest.mark.parametrize("loss_op,loss_args", [("shift_loss", (3, 16, 1)), ("shift_l1edge_loss", (3, 0.7)), ("revssim_loss", (3, 16, 0.25))],
+                         ids=["shift_loss", "shift_l1edge_loss", "revssim_loss"])
+def test_ops_trace_under_torch_compile_fullgraph(dev, loss_op, loss_args):
     """The ops are opaque, well-typed graph nodes: a step function using them traces with fullgraph=True (aot_eager backend: no codegen
-    toolchain needed) and gives the eager numbers."""
+    toolchain needed) and gives the eager numbers, with each of the three loss ops."""
     m = _model(dev)
     x, hr, mask = (torch.as_tensor(a).to(dev) for a in synth.synth_batch(2, seed=64))
     mk = mask.view(torch.uint8)
@@ -84,7 +166,7 @@ def test_ops_trace_under_torch_compile_fullgraph(dev):
 
     def step(flat, x, hr, mk):
         y, _ = torch.ops.probav.wdsr_forward(flat, x, eng, 48, True)
-        return torch.ops.probav.shift_loss(y, hr, mk, 3, 16, 1)[0]
+        return getattr(torch.ops.probav, loss_op)(y, hr, mk, *loss_args)[0]
     flat = m.flat.detach().clone().requires_grad_(True)
     want = step(flat, x, hr, mk)
     want.backward()
@@ -92,13 +174,14 @@ def test_ops_trace_under_torch_compile_fullgraph(dev):
     flat.grad = None
     try:                                                       # ONLY a torch build without dynamo may skip; "aot_eager" needs no codegen toolchain
         import importlib
-        importlib.import_module("torch._dynamo")               # (a plain `import torch._dynamo` here would make `torch` a local of this function)
+        dynamo = importlib.import_module("torch._dynamo")      # (a plain `import torch._dynamo` here would make `torch` a local of this function)
+        dynamo.reset()                                         # every case traces afresh: after another case's trace the integers that differ would turn symbolic
         cstep = torch.compile(step, backend="aot_eager", fullgraph=True)
     except (ImportError, ModuleNotFoundError) as exc:
         pytest.skip("torch.compile (dynamo) is not part of this torch build: %r" % (exc,))
     got = cstep(flat, x, hr, mk)                               # a failure of the trace, of the call or of its backward FAILS the test
     got.backward(retain_graph=True)
-    assert float(got) == float(want) and torch.equal(flat.grad, gw)
+    assert torch.equal(got.detach().view(torch.int32), want.detach().view(torch.int32)) and torch.equal(flat.grad.view(torch.int32), gw.view(torch.int32))
     flat.grad = None
     got.backward()                                             # the saved state is only read: a second reverse pass over the same graph gives the same bits
     assert torch.equal(flat.grad, gw)

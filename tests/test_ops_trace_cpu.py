@@ -10,7 +10,14 @@ class _Stop(Exception):
     pass
 
 
-def test_train_step_traces_with_its_backward_on_fake_tensors(built_lib, monkeypatch):
+# the step's loss: (the op, its arguments after (pred, hr, mask), the reverse op the joint graph must hold)
+LOSS_OPS = [("shift_loss", (3, 16, 1), "probav.shift_loss_backward"),
+            ("shift_l1edge_loss", (3, 0.7), "probav.shift_l1edge_loss_backward"),
+            ("revssim_loss", (3, 16, 0.25), "probav.revssim_loss_backward")]
+
+
+@pytest.mark.parametrize("loss_op,loss_args,reverse_op", LOSS_OPS, ids=[c[0] for c in LOSS_OPS])
+def test_train_step_traces_with_its_backward_on_fake_tensors(built_lib, monkeypatch, loss_op, loss_args, reverse_op):
     pytest.importorskip("torch._dynamo")
     from functorch.compile import min_cut_rematerialization_partition
     from torch._functorch.aot_autograd import aot_module_simplified
@@ -35,7 +42,7 @@ def test_train_step_traces_with_its_backward_on_fake_tensors(built_lib, monkeypa
 
     def step(flat, x, hr, mk):
         y, _ = torch.ops.probav.wdsr_forward(flat, x, 1234, 48, True)
-        return torch.ops.probav.shift_loss(y, hr, mk, 3, 16, 1)[0]
+        return getattr(torch.ops.probav, loss_op)(y, hr, mk, *loss_args)[0]
 
     flat = torch.zeros(535267, requires_grad=True)
     x, hr = torch.zeros(2, 22, 22, 9, 1), torch.zeros(2, 48, 48, 1)
@@ -46,7 +53,7 @@ def test_train_step_traces_with_its_backward_on_fake_tensors(built_lib, monkeypa
     torch._dynamo.reset()
     assert "probav.wdsr_forward" in seen["fw"]
     # the joint graph holds the reverse pass as two opaque, FUNCTIONAL nodes (no copy_ back into the saved workspace)
-    assert "probav.wdsr_backward" in seen["joint"] and "probav.shift_loss_backward" in seen["joint"]
+    assert "probav.wdsr_backward" in seen["joint"] and reverse_op in seen["joint"]
     assert "copy_" not in seen["joint"]
 
 
