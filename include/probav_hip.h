@@ -498,6 +498,36 @@ int probav_frame_windows_gather(const float* patches, const int32_t* counts, int
                                 float* x, int32_t* weight, int32_t* sel, void* stream);
 int probav_frame_windows_reduce(const float* sr, const int32_t* weight, int64_t N, int W, int S, float lo, float hi, float* out, void* stream);
 
+/* ---- random crops (proba-v_amd/crops.py), additions of ABI 7 ----------------------------------------------------------------------------- */
+/* Training samples cut at arbitrary origins out of registered scenes that stay on the device ('Random crops'), instead of
+ * the fixed grid of patches that stages 3 to 5 of the dataset builder dump.  Kernels: csrc/kernels_crops.hip; the statements they equal bit
+ * for bit: probav_amd.crops.window_counts_numpy / crop_batch_numpy.
+ *
+ * Window counts.  masks uint8 [M][H][W] (nonzero = masked) -> counts int32 [M][ny][nx]: counts[m][a][c] = the masked pixels of rows
+ * a stride .. a stride + win - 1 and columns c stride .. c stride + win - 1 of mask m padded by `pad` on every side as np.pad(..., 'reflect')
+ * pads it; ny = (H + 2 pad - win) / stride + 1, nx likewise.  Exact integers, no atomics.  The validity table of every crop origin is
+ * the HR masks with pad 0, win = scale P, stride = scale.  PROBAV_EINVAL, nothing launched: a null pointer, M < 1, H or W outside 1..32767,
+ * pad outside 0 .. min(H, W) - 1, win outside 1 .. min(1024, H + 2 pad, W + 2 pad), stride outside 1..1024, 64 (W + 2 pad) bytes of column sums
+ * over the 160 KiB of LDS. */
+int probav_window_counts(const uint8_t* masks, int64_t M, int H, int W, int pad, int win, int stride, int32_t* counts, void* stream);
+/* Crop batch.  Scenes: lr fp32 and lr_mask uint8 (nonzero = masked) [n_scenes][T_pre][H][H]; hr fp32 and hr_clear (one byte per pixel,
+ * 1 = clear) [n_scenes][scale H][scale H].  positions int32 [n_positions][3] = {scene, y, x}, 0 <= y, x <= H - P; recipe int32
+ * [batch][3 + k] = {j, f, q, perm[0..k)}: position j, then flip code f and q quarter turns in the convention of probav_augment_batch.
+ * Per row, with the LR window = rows y .. y + win - 1, columns x .. x + win - 1 of the scene reflect-padded by `pad` (data and mask alike):
+ *     counts[t] = masked pixels of frame t of the window; Q = window 0 of probav_frame_windows_gather's list for (counts, k, L);
+ *     sel  [batch][k] int32:              sel[b][i] = Q[i]
+ *     lr_b [batch][win][win][k] fp32:     rot90(flip(W, FL[f]), q) of W[y][x][i] = frame Q[perm[i]] of the LR window
+ *     hr_b [batch][S][S] fp32, S = scale P: the same flip and turns of rows scale y .. scale y + S - 1, columns scale x .. of hr
+ *     mask_b [batch][S][S]:               likewise of hr_clear
+ * copied bit for bit.  A row with j outside [0, n_positions), f or q outside 0..3, a perm entry outside [0, k), or whose position lies
+ * outside the scenes is skipped (its outputs are left as they were); callers validate recipes on the host.  Every output byte has one
+ * writer.  PROBAV_EINVAL, nothing launched: a null pointer, a count below 1, T_pre or k outside 1..64, P outside 1..H, pad outside 0 .. H - 1,
+ * win outside P .. min(P + 2 pad, 1024), scale outside 1..64 or scale P over 1024, L outside 0 .. win^2 + 1, or a sample (k LR windows, or the HR
+ * window, beside a row table) that does not fit the 160 KiB of LDS. */
+int probav_crop_batch(const float* lr, const uint8_t* lr_mask, const float* hr, const uint8_t* hr_clear, int64_t n_scenes, int T_pre, int H,
+                      int P, int pad, int win, int scale, int k, int L, const int32_t* positions, int64_t n_positions, const int32_t* recipe,
+                      int64_t batch, float* lr_b, float* hr_b, uint8_t* mask_b, int32_t* sel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

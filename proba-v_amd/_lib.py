@@ -116,6 +116,10 @@ SIGNATURES = {
     # frame-window ensemble (csrc/kernels_windows.hip): added under ABI 7
     "probav_frame_windows_gather": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_void_p]),
     "probav_frame_windows_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    # random crops (csrc/kernels_crops.hip): added under ABI 7
+    "probav_window_counts": (c_int, [c_void_p, c_int64] + [c_int] * 5 + [c_void_p, c_void_p]),
+    "probav_crop_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 8 + [c_void_p, c_int64, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -142,6 +142,32 @@ def virtual_index_batches(V, rank, world, epochs, batchSize, bufferSize, rng):
     return per, (rank + world * idx for idx in shuffle_repeat_batch(per, epochs, batchSize, bufferSize, rng))
 
 
+class RecipeUploader:
+    """Host recipes -> device, through pinned slots, asynchronously on the current stream: no pageable copy, no host synchronisation (a
+    slot is reused only after its upload has left the host; its event is `slots` batches old when the slot comes round again)."""
+
+    def __init__(self, device, slots=4):
+        self.device, self.slots = device, int(slots)
+        self._pinned = [None] * self.slots
+        self._events = [None] * self.slots
+        self._k = 0
+
+    def __call__(self, recipe):
+        import torch
+        k, B = self._k, len(recipe)
+        self._k = (k + 1) % self.slots
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        if self._pinned[k] is None or self._pinned[k].shape[0] < B or self._pinned[k].shape[1] != recipe.shape[1]:
+            self._pinned[k] = torch.empty((B, recipe.shape[1]), dtype=torch.int32, pin_memory=True)
+        pin = self._pinned[k][:B]
+        pin.numpy()[...] = recipe
+        dev = pin.to(self.device, non_blocking=True)
+        self._events[k] = torch.cuda.Event()
+        self._events[k].record(torch.cuda.current_stream(self.device))
+        return dev
+
+
 class DeviceDataset:
     """The base arrays on the device, uploaded once (cast like trainClass.BatchPrefetcher casts its batches: LR and HR to fp32, the mask in
     its own dtype), and batches of the virtual augmented set made from them by one kernel launch each.  There is no host path: a device
@@ -163,9 +189,7 @@ class DeviceDataset:
             raise MemoryError("the un-augmented training set does not fit on %s: %d bytes were asked for (%d samples; LR %d, HR %d, mask %d bytes). "
                               "There is no host-memory fallback: train from the materialised arrays, or on fewer samples."
                               % (self.device, self.nbytes, self.N, host[0].nbytes, host[1].nbytes, host[2].nbytes)) from exc
-        self._pinned = [None] * self.SLOTS                # recipe staging: pinned slots, each reused only after its upload has left the host
-        self._events = [None] * self.SLOTS
-        self._k = 0
+        self._upload = RecipeUploader(self.device, self.SLOTS)
 
     @staticmethod
     def _host_arrays(X, yHR, yMask):
@@ -180,23 +204,6 @@ class DeviceDataset:
 
     def __len__(self):
         return self.N
-
-    def _upload(self, recipe):
-        """Host recipe -> device, through a pinned slot, asynchronously on the current stream: no pageable copy, no host synchronisation
-        (a slot's event is four batches old when the slot comes round again)."""
-        import torch
-        k, B = self._k, len(recipe)
-        self._k = (k + 1) % self.SLOTS
-        if self._events[k] is not None:
-            self._events[k].synchronize()
-        if self._pinned[k] is None or self._pinned[k].shape[0] < B:
-            self._pinned[k] = torch.empty((B, recipe.shape[1]), dtype=torch.int32, pin_memory=True)
-        pin = self._pinned[k][:B]
-        pin.numpy()[...] = recipe
-        dev = pin.to(self.device, non_blocking=True)
-        self._events[k] = torch.cuda.Event()
-        self._events[k].record(torch.cuda.current_stream(self.device))
-        return dev
 
     def batch_from_recipe(self, recipe):
         """(lr_b, hr_b, mask_b) device tensors of a host recipe [B, 3 + T]; validated here, before anything is launched."""

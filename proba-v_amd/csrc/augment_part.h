@@ -35,23 +35,25 @@ __device__ __forceinline__ int aug_src_pixel(int y, int x, int side, int f, int 
 template <typename E, int V>
 struct alignas(sizeof(E) * V) AugVec { E v[V]; };
 
-// one sample of one tensor: src [side][side][TC] -> dst, TC = frames x channels (1 for HR / mask), perm = the recipe's frame
-// permutation in global memory (null: identity)
+// the staged sample and its row table inside one workgroup's LDS (aug_part_lds bytes)
+template <typename E>
+__device__ __forceinline__ E* aug_tile(unsigned char* smem) { return reinterpret_cast<E*>(smem); }
+template <typename E>
+__device__ __forceinline__ int* aug_table(unsigned char* smem, int elems)
+{
+    return reinterpret_cast<int*>(smem + (((size_t)elems * sizeof(E) + 15) & ~(size_t)15));
+}
+
+// the second half of augment_part, for a sample that is ALREADY staged in LDS as tile [side][side][TC] (by the caller, by any loads: a
+// barrier is taken here before the tile is read): build the row table, then write dst in order through the affine source map.
+// csrc/kernels_crops.hip stages windows cut out of whole scenes and writes them with this.
 template <typename E, int V>
-__device__ __forceinline__ void augment_part(const E* __restrict__ src, E* __restrict__ dst, int side, int TC, int C,
-                                             const int32_t* __restrict__ perm, int f, int k, unsigned char* smem)
+__device__ __forceinline__ void augment_emit(E* __restrict__ dst, int side, int TC, int C, const int32_t* __restrict__ perm, int f, int k,
+                                             unsigned char* smem)
 {
     const int row = side * TC, elems = side * row;
-    E* tile = reinterpret_cast<E*>(smem);
-    int* tab = reinterpret_cast<int*>(smem + (((size_t)elems * sizeof(E) + 15) & ~(size_t)15));
-    if (V > 1) {
-        const uint4* s16 = reinterpret_cast<const uint4*>(src);
-        uint4* t16 = reinterpret_cast<uint4*>(smem);
-        const int n16 = (int)((size_t)elems * sizeof(E) / 16);
-        for (int q = threadIdx.x; q < n16; q += AUG_THREADS) t16[q] = s16[q];
-    } else {
-        for (int q = threadIdx.x; q < elems; q += AUG_THREADS) tile[q] = src[q];
-    }
+    E* tile = aug_tile<E>(smem);
+    int* tab = aug_table<E>(smem, elems);
     const int P0 = aug_src_pixel(0, 0, side, f, k);
     const int PI = aug_src_pixel(1, 0, side, f, k) - P0, PJ = aug_src_pixel(0, 1, side, f, k) - P0;
     for (int j = threadIdx.x; j < row; j += AUG_THREADS) {
@@ -73,6 +75,25 @@ __device__ __forceinline__ void augment_part(const E* __restrict__ src, E* __res
         }
         *reinterpret_cast<AugVec<E, V>*>(dst + o) = out;
     }
+}
+
+// one sample of one tensor: src [side][side][TC] -> dst, TC = frames x channels (1 for HR / mask), perm = the recipe's frame
+// permutation in global memory (null: identity)
+template <typename E, int V>
+__device__ __forceinline__ void augment_part(const E* __restrict__ src, E* __restrict__ dst, int side, int TC, int C,
+                                             const int32_t* __restrict__ perm, int f, int k, unsigned char* smem)
+{
+    const int elems = side * (side * TC);
+    E* tile = aug_tile<E>(smem);
+    if (V > 1) {
+        const uint4* s16 = reinterpret_cast<const uint4*>(src);
+        uint4* t16 = reinterpret_cast<uint4*>(smem);
+        const int n16 = (int)((size_t)elems * sizeof(E) / 16);
+        for (int q = threadIdx.x; q < n16; q += AUG_THREADS) t16[q] = s16[q];
+    } else {
+        for (int q = threadIdx.x; q < elems; q += AUG_THREADS) tile[q] = src[q];
+    }
+    augment_emit<E, V>(dst, side, TC, C, perm, f, k, smem);
 }
 
 inline bool aug_aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }

@@ -43,6 +43,12 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::baseline_upscale_mean(frames, clear, set_offsets, mode) -> (out [S, 3H, 3W], k_used [S])
                                                                             the competition's bicubic-mean baseline of ragged image sets, exact
                                                                             integer arithmetic   evaluate.py:142-197 (baseline.py)
+  probav::window_counts(masks, pad, win, stride) -> counts int32 [M, ny, nx]  the masked pixels of every window of reflect-padded masks, exact:
+                                                                            the validity table of every crop origin   (crops.py)
+  probav::crop_batch(lr, lr_mask, hr, hr_clear, positions, recipe, P, pad, win, scale, limit) -> (lr_b, hr_b, mask_b, sel [B, k])
+                                                                            a training batch cut at arbitrary origins out of resident scenes: the
+                                                                            window's frames chosen as the builder chooses them, then frame order,
+                                                                            flip, quarter turns   utils/dataGenerator.py:99-174, 326-551 (crops.py)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -923,6 +929,104 @@ def baseline_upscale_mean(frames: Tensor, clear: Tensor, set_offsets: Tensor, mo
 def _(frames, clear, set_offsets, mode):
     S, H, W = _baseline_args(frames, clear, set_offsets, mode)
     return frames.new_empty((S, 3 * H, 3 * W), dtype=torch.float32), frames.new_empty((S,), dtype=torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# random crops (csrc/kernels_crops.hip; the definition, the numpy statements and the recipes are in crops.py).  No autograd: they move
+# and count input bits.
+# ---------------------------------------------------------------------------------------------------------------------------------
+CROPS_LDS_BYTES = 160 * 1024
+CROPS_STATIC_LDS = 768             # the crop kernel's counts and frame list
+
+
+def _window_counts_args(masks, pad, win, stride):
+    """-> (M, H, W, ny, nx) after the checks the real and the fake kernel share."""
+    if masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("window_counts: masks [M, H, W] uint8 or bool; got %s %s" % (tuple(masks.shape), masks.dtype))
+    M, H, W = masks.shape
+    if M < 1 or not 1 <= H <= 32767 or not 1 <= W <= 32767 or not 0 <= pad < min(H, W) or not 1 <= win <= min(1024, H + 2 * pad, W + 2 * pad) \
+            or not 1 <= stride <= 1024:
+        raise ValueError("window_counts: %d masks of %d x %d, pad %d, win %d, stride %d; M >= 1, 1 <= H, W <= 32767, 0 <= pad < min(H, W), "
+                         "1 <= win <= min(1024, H + 2 pad, W + 2 pad), 1 <= stride <= 1024" % (M, H, W, pad, win, stride))
+    if 64 * (W + 2 * pad) > CROPS_LDS_BYTES:
+        raise ValueError("window_counts: 16 rows of column sums of %d padded columns do not fit the 160 KiB of LDS" % (W + 2 * pad))
+    return M, H, W, (H + 2 * pad - win) // stride + 1, (W + 2 * pad - win) // stride + 1
+
+
+@torch.library.custom_op("probav::window_counts", mutates_args=(), device_types="cuda")
+def window_counts(masks: Tensor, pad: int, win: int, stride: int) -> Tensor:
+    """int32 [M, ny, nx]: the nonzero pixels of every win x win window at `stride` of masks [M, H, W] reflect-padded by `pad`
+    (crops.window_counts_numpy), exact."""
+    M, H, W, ny, nx = _window_counts_args(masks, pad, win, stride)
+    _dev(masks, "masks")
+    masks = masks.contiguous()
+    out = torch.empty((M, ny, nx), dtype=torch.int32, device=masks.device)
+    _lib.check(_lib.lib().probav_window_counts(_lib.ptr(masks), M, H, W, pad, win, stride, _lib.ptr(out), _lib.current_stream()), "probav_window_counts")
+    return out
+
+
+@window_counts.register_fake
+def _(masks, pad, win, stride):
+    M, _, _, ny, nx = _window_counts_args(masks, pad, win, stride)
+    return masks.new_empty((M, ny, nx), dtype=torch.int32)
+
+
+def _crop_batch_args(lr, lr_mask, hr, hr_clear, positions, recipe, P, pad, win, scale, limit):
+    """-> (S, T_pre, H, k, B, side) after the checks the real and the fake kernel share (side = scale P, the HR window's)."""
+    if lr.dim() != 4 or lr.shape[2] != lr.shape[3] or tuple(lr_mask.shape) != tuple(lr.shape) or hr.dim() != 3 or tuple(hr_clear.shape) != tuple(hr.shape) \
+            or positions.dim() != 2 or positions.shape[1] != 3 or recipe.dim() != 2:
+        raise ValueError("crop_batch: lr / lr_mask [S, T_pre, H, H], hr / hr_clear [S, r H, r H], positions [V, 3], recipe [B, 3 + k]; got %s %s %s %s %s %s"
+                         % tuple(tuple(t.shape) for t in (lr, lr_mask, hr, hr_clear, positions, recipe)))
+    if lr.dtype != torch.float32 or hr.dtype != torch.float32 or lr_mask.dtype not in (torch.uint8, torch.bool) \
+            or hr_clear.dtype not in (torch.uint8, torch.bool) or positions.dtype != torch.int32 or recipe.dtype != torch.int32:
+        raise ValueError("crop_batch: lr / hr must be float32, lr_mask / hr_clear uint8 or bool, positions / recipe int32; got %s %s %s %s %s %s"
+                         % (lr.dtype, lr_mask.dtype, hr.dtype, hr_clear.dtype, positions.dtype, recipe.dtype))
+    S, T_pre, H = lr.shape[0], lr.shape[1], lr.shape[2]
+    k, B = recipe.shape[1] - 3, recipe.shape[0]
+    if S < 1 or positions.shape[0] < 1 or not 1 <= T_pre <= WINDOWS_MAX or not 1 <= k <= WINDOWS_MAX:
+        raise ValueError("crop_batch: %d scenes of %d frames, %d positions, k = %d; S, V >= 1, 1 <= T_pre, k <= %d" % (S, T_pre, positions.shape[0], k, WINDOWS_MAX))
+    if not 1 <= P <= H <= 32767 or not 0 <= pad < H or not P <= win <= min(P + 2 * pad, 1024) or not 1 <= scale <= 64 or scale * P > 1024:
+        raise ValueError("crop_batch: H = %d, P = %d, pad = %d, win = %d, scale = %d; 1 <= P <= H, 0 <= pad < H, P <= win <= min(P + 2 pad, 1024), "
+                         "1 <= scale <= 64, scale P <= 1024" % (H, P, pad, win, scale))
+    if hr.shape[0] != S or hr.shape[1] != scale * H or hr.shape[2] != scale * H:
+        raise ValueError("crop_batch: hr must be [%d, %d, %d] for scale %d; got %s" % (S, scale * H, scale * H, scale, tuple(hr.shape)))
+    if not 0 <= limit <= win * win + 1:
+        raise ValueError("crop_batch: limit = %d outside 0 .. win^2 + 1 = %d" % (limit, win * win + 1))
+    side = scale * P
+    rnd = lambda b: (b + 15) & ~15
+    if max(rnd(4 * win * win * k) + 4 * win * k, rnd(4 * side * side) + 4 * side) + CROPS_STATIC_LDS > CROPS_LDS_BYTES:
+        raise ValueError("crop_batch: one sample (k = %d LR windows of %d x %d, or an HR window of %d x %d floats) does not fit the 160 KiB of LDS it is "
+                         "staged in" % (k, win, win, side, side))
+    return S, T_pre, H, k, B, side
+
+
+@torch.library.custom_op("probav::crop_batch", mutates_args=(), device_types="cuda")
+def crop_batch(lr: Tensor, lr_mask: Tensor, hr: Tensor, hr_clear: Tensor, positions: Tensor, recipe: Tensor, P: int, pad: int, win: int, scale: int,
+               limit: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(lr_b [B, win, win, k, 1] fp32, hr_b [B, rP, rP, 1] fp32, mask_b [B, rP, rP, 1] in hr_clear's dtype, sel [B, k] int32): the training samples
+    of recipe rows {j, f, q, perm}, cut at positions[j] = {scene, y, x} out of the resident scenes, their k frames chosen per window as the
+    dataset builder chooses them (counts < limit, (count, index) order, tiled) -- crops.crop_batch_numpy.  One launch.  The kernel skips a row
+    it could not apply without reading outside the arrays; callers validate recipes on the host (crops.CropDataset does)."""
+    S, T_pre, H, k, B, side = _crop_batch_args(lr, lr_mask, hr, hr_clear, positions, recipe, P, pad, win, scale, limit)
+    for t, name in ((lr, "lr"), (lr_mask, "lr_mask"), (hr, "hr"), (hr_clear, "hr_clear"), (positions, "positions"), (recipe, "recipe")):
+        _dev(t, name)
+    lr, lr_mask, hr, hr_clear, positions, recipe = (t.contiguous() for t in (lr, lr_mask, hr, hr_clear, positions, recipe))
+    lr_b = torch.empty((B, win, win, k, 1), dtype=torch.float32, device=lr.device)
+    hr_b = torch.empty((B, side, side, 1), dtype=torch.float32, device=lr.device)
+    mask_b = torch.empty((B, side, side, 1), dtype=hr_clear.dtype, device=lr.device)
+    sel = torch.empty((B, k), dtype=torch.int32, device=lr.device)
+    if B:
+        _lib.check(_lib.lib().probav_crop_batch(_lib.ptr(lr), _lib.ptr(lr_mask), _lib.ptr(hr), _lib.ptr(hr_clear), S, T_pre, H, P, pad, win, scale, k, limit,
+                                                _lib.ptr(positions), positions.shape[0], _lib.ptr(recipe), B, _lib.ptr(lr_b), _lib.ptr(hr_b),
+                                                _lib.ptr(mask_b), _lib.ptr(sel), _lib.current_stream()), "probav_crop_batch")
+    return lr_b, hr_b, mask_b, sel
+
+
+@crop_batch.register_fake
+def _(lr, lr_mask, hr, hr_clear, positions, recipe, P, pad, win, scale, limit):
+    _, _, _, k, B, side = _crop_batch_args(lr, lr_mask, hr, hr_clear, positions, recipe, P, pad, win, scale, limit)
+    return (lr.new_empty((B, win, win, k, 1)), hr.new_empty((B, side, side, 1)), hr_clear.new_empty((B, side, side, 1)),
+            recipe.new_empty((B, k), dtype=torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

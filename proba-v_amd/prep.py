@@ -505,13 +505,32 @@ def augmentByRotating(patches):
                               np.rot90(patches, k=3, axes=(1, 2))))
 
 
+def gridPatches(imgLR, imgHR, config):
+    """Stages 3 and 4 for the training arrays of whole scenes (trimmedArrayDir's TRAINimgLR [S, T_pre, 1, H, H], TRAINimgHR [S, 1, 1, rH, rH]) in
+    one go, through the functions those stages call: unfold on the patch grid, frame choice per threshold, the HR clarity filter, the
+    transposes -> (LR [N, win, win, k, 1], HR [N, rP, rP, 1]) as trimmedPatchesDir holds them."""
+    pad = config['max_shift'] // 2 if config['max_shift'] > 0 else 0
+    lr = _patches(imgLR, config['patch_size'] + config['max_shift'], config['patch_stride'], pad)[0]
+    khr = config['patch_size'] * (imgHR.shape[3] // imgLR.shape[3])
+    hr = _patches(imgHR, khr, khr, 0)[0]
+    for thr in config['low_res_patch_thresholds']:
+        lr = pickClearPatchesLR(lr, k=config['num_low_res_imgs'], clarityThreshold=thr)
+    lr, hr = removeCorruptedTrainPatchSets(lr, hr, config['high_res_threshold'])
+    lr, hr = pickClearPatches(lr, hr, config['high_res_threshold'])
+    return lr.transpose((0, 3, 4, 1, 2)), hr.transpose((0, 3, 4, 1, 2)).squeeze(4)
+
+
 # ---- driver (utils/dataGenerator.py:33-273) ---------------------------------------------------------------------------------------
-def main(config, band, rng=None, online_aug=False, register='freq', register_window=8):
+def main(config, band, rng=None, online_aug=False, register='freq', register_window=8, scene_split=False):
     """register: 'freq' (the default: the plain circular registration, as the reference's registerFrame default) or 'masked' (the
     cloud-aware one over [-register_window, register_window]^2, the reference's tech='time'); stage 2 only.
     online_aug: stage 5 draws the frame permutations as ever (same rng, same order) but SAVES them beside the un-augmented training
     arrays instead of applying them -- TRAINbasepatches{LR,HR}_<band>.npy and TRAINaugperms_<band>.npy, what `train.py --online-aug` reads
-    (probav_amd.augment).  The TRAINVAL dumps do not depend on it."""
+    (probav_amd.augment).  The TRAINVAL dumps do not depend on it.
+    scene_split: stage 5 holds out whole SCENES of trimmedArrayDir instead of patches (crops.scene_split: RandomState(17).permutation(S), the
+    first ceil(split S) scenes) -- random crops of the training scenes would overlap validation patches of the same scenes.  It writes
+    the TRAINVAL dumps from the held-out scenes' grid patches (gridPatches) and TRAINscenes_<band>.npy, the training scenes' indices into
+    trimmedArrayDir: what `train.py --random-crops` reads (probav_amd.crops).  Nothing else of stage 5 runs."""
     log = logging.getLogger("dataGenerator")
     if band not in ('NIR', 'RED'):
         raise ValueError("band must be NIR or RED, got %r" % band)
@@ -581,6 +600,17 @@ def main(config, band, rng=None, online_aug=False, register='freq', register_win
         test.dump(path('trimmedPatchesDir', 'TESTpatchesLR'), protocol=4)
         train.dump(path('trimmedPatchesDir', 'TRAINpatchesLR'), protocol=4)
         hr.dump(path('trimmedPatchesDir', 'TRAINpatchesHR'), protocol=4)
+
+    if 5 in ckpt and scene_split:
+        from .crops import scene_split as split_scenes
+        imgLR, imgHR = load('trimmedArrayDir', 'TRAINimgLR'), load('trimmedArrayDir', 'TRAINimgHR')
+        val, train = split_scenes(len(imgLR), config['split'])
+        lrVal, hrVal = gridPatches(imgLR[val], imgHR[val], config)
+        lrVal.dump(path('augmentedPatchesDir', 'TRAINVALpatchesLR'), protocol=4)
+        hrVal.dump(path('augmentedPatchesDir', 'TRAINVALpatchesHR'), protocol=4)
+        np.save(path('augmentedPatchesDir', 'TRAINscenes'), np.sort(train).astype(np.int64))
+        log.info('[ INFO ] Scene split: %d validation scenes (%d grid patches), %d training scenes', len(val), len(lrVal), len(train))
+        return
 
     if 5 in ckpt:
         lr, hr = load('trimmedPatchesDir', 'TRAINpatchesLR'), load('trimmedPatchesDir', 'TRAINpatchesHR')

@@ -65,3 +65,17 @@ def synth_batch(batch, seed=1234, numImgLR=9, patchSizeLR=16, maxShift=6, scale=
         while mask[b].mean() < 0.85:
             mask[b] |= rng.random(size=mask[b].shape) < 0.5
     return x, hr, mask
+
+
+def synth_scenes(scenes, seed=1234, numImgPre=9, sizeLR=128, scale=3, mean=NIR_MEAN, std=NIR_STD, cloud=0.04):
+    """Registered, trimmed scenes in the form of trimmedArrayDir (what `train.py --random-crops` and `dataGenerator.py --scene-split` read):
+    (TRAINimgLR masked float64 [S, T_pre, 1, H, H], TRAINimgHR masked float64 [S, 1, 1, rH, rH]), mask True = obscured.  Frame t of a scene is
+    obscured with density cloud * (t + 1) (the frames are sorted clearest-first, as pickClearImg leaves them), the HR image with `cloud`."""
+    rng = np.random.default_rng(seed)
+    G = scale * sizeLR
+    lr = np.rint(np.clip(rng.normal(mean, std, size=(scenes, numImgPre, 1, sizeLR, sizeLR)), 0, 16383))
+    hr = np.rint(np.clip(rng.normal(mean, std, size=(scenes, 1, 1, G, G)), 0, 16383))
+    dens = cloud * (1 + np.arange(numImgPre))
+    lr_mask = rng.random(lr.shape) < dens[None, :, None, None, None]
+    hr_mask = rng.random(hr.shape) < cloud
+    return np.ma.masked_array(lr, mask=lr_mask), np.ma.masked_array(hr, mask=hr_mask)

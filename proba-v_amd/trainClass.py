@@ -770,12 +770,17 @@ class ModelTrainer:
 
     # -- training loop (models/trainClass.py:61-122) ---------------------------------------------------
     def fitTrainData(self, X, y, globalBatchSize, epochs, valData, bufferSize=256, valSteps=64,
-                     saveBestOnly=True, initEpoch=0, seed=0, augment=None):
+                     saveBestOnly=True, initEpoch=0, seed=0, augment=None, crops=None, crops_per_epoch=None):
         """augment: an augment.AugmentSpec -- X, y are then the UN-augmented arrays; they are uploaded once and every batch is built on the device
-        from the virtual augmented set the spec describes (augment.py), over the index stream the materialised set would be walked by."""
+        from the virtual augmented set the spec describes (augment.py), over the index stream the materialised set would be walked by.
+        crops: (crops.CropDataset, crops.CropSpec), with `augment` the cfg's AugmentSpec -- X and y are None; every batch is cut out of the
+        dataset's resident scenes (crops.py).  An epoch is len(grid positions) x multiplicity // batch steps in both of the spec's modes, or
+        crops_per_epoch // batch ("all" only)."""
         logger.info("[ INFO ] Loading data set to buffer cache...")
-        yHR, yMask = y[0], y[1]
         rank, world = self._rank(), self._world()
+        if crops is not None:
+            return self._fit_crops(crops, augment, crops_per_epoch, globalBatchSize, epochs, valData, bufferSize, valSteps, saveBestOnly, initEpoch, seed)
+        yHR, yMask = y[0], y[1]
         if world > 1 and self.multiGPU and augment is None:        # (augment: the shard is taken on the VIRTUAL indices below)
             # per-replica batch = cfg batch (debug/trainClassMultiGPU0.py:67-73).  Every rank gets EXACTLY len(X) // world samples
             # (the tail of an indivisible data set is dropped): equal shard lengths give every rank the same number of batches, so the
@@ -807,6 +812,34 @@ class ModelTrainer:
             batches = BatchPrefetcher((X, yHR, yMask), (torch.float32, torch.float32, mask_dtype),
                                       shuffle_repeat_batch(dataSetLength, epochs, globalBatchSize, bufferSize, rng), self._device())
 
+        self._run_batches(batches, totalSteps, step, epoch, epochs, globalStep, valData, globalBatchSize, bufferSize, vrng, valSteps, saveBestOnly)
+
+    def _fit_crops(self, crops, augment, crops_per_epoch, globalBatchSize, epochs, valData, bufferSize, valSteps, saveBestOnly, initEpoch, seed):
+        from . import crops as cr
+        dataset, spec = crops
+        if augment is None:
+            raise ValueError("crops=(dataset, spec) needs augment=AugmentSpec (the cfg's: which codes and frame orders a sample may take)")
+        if crops_per_epoch is not None and spec.positions != "all":
+            raise ValueError("crops_per_epoch applies to CropSpec('all'): the grid is walked once per epoch")
+        rank, world = self._rank(), self._world()
+        if not (world > 1 and self.multiGPU):
+            rank, world = 0, 1
+        rng = np.random.default_rng(seed + self._rank())
+        vrng = np.random.default_rng(seed + 7919)
+        totalSteps = cr.steps_per_epoch(dataset.n_grid, augment, globalBatchSize, world, crops_per_epoch)
+        if totalSteps < 1:
+            raise ValueError("an epoch of %d grid positions x %d (or crops_per_epoch) is smaller than one batch (%d)"
+                             % (dataset.n_grid, augment.multiplicity, globalBatchSize))
+        globalStep = self.step
+        logger.info("[ INFO ] Begin training...")
+        logger.info("[ INFO ] %d scenes on the device (%d bytes): %d valid crop positions, %d of them on the patch grid; positions '%s', %d steps per epoch",
+                    dataset.S, dataset.nbytes, dataset.V, dataset.n_grid, spec.positions, totalSteps)
+        batches = dataset.batches(spec, augment, globalBatchSize, steps=None if spec.positions == "grid" else totalSteps * epochs, rank=rank, world=world,
+                                  epochs=epochs, bufferSize=bufferSize, rng=rng)
+        self._run_batches(batches, totalSteps, globalStep % totalSteps, initEpoch, epochs, globalStep, valData, globalBatchSize, bufferSize, vrng, valSteps,
+                          saveBestOnly)
+
+    def _run_batches(self, batches, totalSteps, step, epoch, epochs, globalStep, valData, globalBatchSize, bufferSize, vrng, valSteps, saveBestOnly):
         def emit(vals, meta):
             ep, st, gs = meta
             if len(vals) > 2:                               # clipping or the guard is on: the step's norm and the running count ride along

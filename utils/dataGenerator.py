@@ -3,10 +3,14 @@ train.py and test.py read.  Runs on the GPU (probav_amd.prep); the same cfg keys
 reference.  --seed N seeds the frame picking and LR shuffling (equal to the reference after np.random.seed(N)); without it the run is
 unseeded, as the reference's is.
 
-    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0] [--online-aug] [--register masked [--register-window 8]]
+    python utils/dataGenerator.py --cfg cfg/p16t9c85r12.cfg --band NIR [--seed 0] [--online-aug | --scene-split] [--register masked [--register-window 8]]
 
 --online-aug: stage 5 writes the un-augmented training patches and the frame permutations it drew (TRAINbasepatches{LR,HR}_<band>.npy,
 TRAINaugperms_<band>.npy) instead of the augmented set; `train.py --online-aug` augments every batch on the GPU from them.
+
+--scene-split: stage 5 holds out whole scenes instead of patches and writes the TRAINVAL dumps from their grid patches and the training
+scenes' indices (TRAINscenes_<band>.npy); `train.py --random-crops` cuts its samples out of those scenes of trimmedArrayDir on the GPU.
+Validation scores under a scene split are not comparable with the patch split's.
 
 --register masked: stage 2 registers every LR frame by the cloud-aware masked correlation over a window of +-R integer shifts
 (--register-window R, 1..32) and shifts it without wrap-around (the reference's registerFrame(tech='time')); the default, freq, is the
@@ -33,12 +37,18 @@ def parser(argv=None):
     p.add_argument('--online-aug', dest='online_aug', action='store_true',
                    help='stage 5 saves the un-augmented training patches and the frame permutations instead of the augmented set '
                         '(for train.py --online-aug)')
+    p.add_argument('--scene-split', dest='scene_split', action='store_true',
+                   help='stage 5 holds out whole scenes instead of patches: TRAINVAL dumps from their grid patches, TRAINscenes_<band>.npy for the '
+                        'rest (for train.py --random-crops)')
     p.add_argument('--register', default='freq', choices=['freq', 'masked'],
                    help="stage 2's registration: freq = plain circular cross-correlation (default); masked = cloud-aware masked "
                         "normalised correlation over a bounded window, shifted without wrap-around")
     p.add_argument('--register-window', dest='register_window', default=8, type=int,
                    help='largest integer shift, per axis, that --register masked tries (1..32)')
-    return p.parse_args(argv)
+    opt = p.parse_args(argv)
+    if opt.scene_split and opt.online_aug:
+        p.error('--scene-split and --online-aug are mutually exclusive: a scene split writes no training patches to augment')
+    return opt
 
 
 if __name__ == '__main__':
@@ -47,4 +57,4 @@ if __name__ == '__main__':
     logging.info(f'[ CFG - INFO ] Using {opt.cfg} as config file...')
     rng = None if opt.seed is None else np.random.RandomState(opt.seed)
     prep.main(parseConfig(opt.cfg), opt.band, rng, online_aug=opt.online_aug, register=opt.register,
-              register_window=opt.register_window)
+              register_window=opt.register_window, scene_split=opt.scene_split)
