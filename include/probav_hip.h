@@ -110,6 +110,14 @@ int probav_backward(probav_engine* e, const float* params, const float* dy, floa
 int probav_workspace_split(const probav_engine* e, int batch, size_t* saved_bytes, size_t* scratch_bytes);
 int probav_backward_split(probav_engine* e, const float* params, const float* dy, float* grads, const void* saved, size_t saved_bytes,
                           void* scratch, size_t scratch_bytes, int batch, const void* wcache, size_t wcache_bytes, void* stream);
+/* replaces  tape.gradient(loss, [x] + model.trainable_variables): the reverse of models/modelsTF.py:23-27 (normalisation, temporal mean),
+ * :45-53 (the low-frequency residual path) and :58 (mainConv1) carried one layer further, down to the LR frames.
+ * probav_backward_split with one more output: `grads` is filled exactly as probav_backward_split fills it (the same launches in the same
+ * order, the same bits), and dx [B, P+maxShift, P+maxShift, T, C] receives d loss / d x -- one more launch at the end of the pass
+ * (probav_input_grad below), fed by d loss / d relu(mainConv1) and by the residual path's gradient at residConv1, which the pass
+ * forms anyway.  With frozen parameters the filter gradients are still computed; the caller drops them.                               */
+int probav_backward_input(probav_engine* e, const float* params, const float* dy, float* grads, const void* saved, size_t saved_bytes,
+                          void* scratch, size_t scratch_bytes, int batch, const void* wcache, size_t wcache_bytes, float* dx, void* stream);
 
 /* ---- optimizer update fused with the weight normalisation of the next step ---------------------------------
  * replaces  optimizer.apply_gradients(...)  +  the WeightNormalization kernel recomputation of the NEXT model call
@@ -249,6 +257,16 @@ size_t probav_pw_backward_scratch_bytes(int D);
 int probav_pw_backward(const float* x, const float* d_dec, const float* d_skip, const float* w1, const float* b1,
                        const float* w2, float* dx, float* dw1, float* db1, float* dw2, float* db2, void* scratch,
                        size_t scratch_bytes, int64_t nvox, int64_t vox_per_sample, int D, int impl, void* stream);
+/* the network's input gradient as ONE launch: the reverse of models/modelsTF.py:23-27 (xn = (x - mean) / std, mn = the temporal mean of xn),
+ * :45-47 (residConv1, 3x3 'valid' on mn) and :58 (mainConv1, 3x3x3 'same' on xn, ReLU)
+ *   dx[n,h,w,t,c] = 1/std * (  sum_{a,b,d,co} G[n,h+1-a,w+1-b,t+1-d,co] * wmain[a,b,d,c,co]
+ *                            + 1/T * sum_{a,b,co} D1[n,h-a,w-b,co] * w1[a,b,c,co] )          (indices outside a tensor contribute 0)
+ * G = g where act0 > 0, else 0; D1 = d1 where gate1 > 0 (gate1 == NULL: d1 as it is).
+ * g, act0 [B,H,H,T,32]: d loss / d relu(mainConv1) and relu(mainConv1); wmain [3,3,3,C,32] (all three 16-byte aligned);
+ * d1, gate1 [B,H-2,H-2,9]: the gradient at residConv1's output and that output; w1 [3,3,1,C,9]; C = 1 or 3; dx [B,H,H,T,C].
+ * fp32 VALU, no atomics, one fixed summation order: the same inputs give the same bits, and a sample never reads another sample.      */
+int probav_input_grad(int batch, int H, int T, int C, const float* g, const float* act0, const float* wmain, const float* d1,
+                      const float* gate1 /* or NULL */, const float* w1, float stdv, float* dx, void* stream);
 /* weight normalisation of every layer of the engine: params -> weff, weffT, inv_norm (ws-internal
  * layouts, exported for tests): sizes probav_weff_count() floats and probav_cout_total() floats      */
 int64_t probav_weff_count(const probav_engine* e);
@@ -282,6 +300,7 @@ int probav_mfma_probe_shape(const void* seed, float* sink, int iters, int launch
 #define PROBAV_VIEW_DEC 1
 #define PROBAV_VIEW_RED 2
 #define PROBAV_VIEW_RESID1 3
+#define PROBAV_VIEW_INPUT 4         /* the normalised input xn [B, P+maxShift, P+maxShift, T, C] (models/modelsTF.py:23-24): its count is the size of d loss / d x */
 int probav_workspace_view(const probav_engine* e, int batch, int training, int kind, int index, int64_t* offset_floats, int64_t* count);
 /* the post-ReLU hidden tile relu(expConv_block(x)) [B*(P+s)^2*T][256] (models/modelsTF.py:179-180) exactly as the fused forward kernel
  * of the current kernel family (3 or 4) evaluates it -- that tensor never reaches memory otherwise.  Call after probav_forward(training=1)

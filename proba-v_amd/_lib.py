@@ -86,6 +86,10 @@ SIGNATURES = {
     "probav_plan_pw": (c_int, [c_int64, c_int64, c_int, c_int, c_int, POINTER(c_int32 * 8)]),
     "probav_workspace_split": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "probav_backward_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
+    # input gradients (csrc/kernels_input_grad.hip): added under ABI 7
+    "probav_backward_input": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p,
+                                      c_void_p]),
+    "probav_input_grad": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "probav_weight_cache_bytes": (c_size_t, [c_void_p]),
     "probav_optimizer_step_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
                                             c_void_p, c_size_t, c_void_p]),

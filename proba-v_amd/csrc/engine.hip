@@ -875,14 +875,19 @@ int probav_forward_wc(probav_engine* e, const float* params, const float* x, flo
 
 // ws: the saved state of the matching forward pass (READ ONLY here); scratch: what the reverse pass writes on its way (gradient buffers, slabs, its amax
 // slots; contents meaningless before and after).  scratch == nullptr: the one-piece form, the scratch is the tail of `ws`.
+// dx (optional): d loss / d x, one more launch at the end of the pass (kernels_input_grad.hip); null: the pass issues the launches and writes the bits it always did
 static int backward_impl(probav_engine* e, const float* params, const float* dy, float* grads, const void* ws, size_t ws_bytes,
-                         void* scratch, size_t scratch_bytes, int B, const float* WC, void* stream)
+                         void* scratch, size_t scratch_bytes, int B, const float* WC, void* stream, float* dx = nullptr)
 {
     if (!e || !params || !dy || !grads || !ws || B < 1) { set_error("probav_backward: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     const Plan p = make_plan(e, B, 1);
     if (ws_bytes < (scratch ? p.fwd_total : p.total) * sizeof(float)) { set_error("probav_backward: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
     if (scratch && scratch_bytes < p.bwd_total * sizeof(float)) { set_error("probav_backward: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
+    if (dx && (e->cfg.num_filters != 32 || !input_grad_supported(e->Hin, e->cfg.num_img_lr, e->cfg.in_channels))) {
+        set_error("probav_backward_input: the input-gradient kernel needs num_filters == 32 and a tile of all frames inside its LDS budget", hipSuccess);
+        return PROBAV_EINVAL;
+    }
     CK(device_tables(e));
     const float* W = (const float*)ws;
     float* S = scratch ? (float*)scratch : const_cast<float*>(W) + p.fwd_total;
@@ -932,8 +937,9 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         const float *w2r = weff(e->iResid2), *w3r = weff(e->iResid3);
         if (resid_path_fused(e)) {
             CK(slab_fits(rp3, resid_path_slab_floats(B, g1.Cin)));
+            float* const dr1_out = dx ? dr1 : nullptr;         // the gated gradient at residConv1, which the kernel otherwise keeps in LDS: only the input gradient reads it
             CK(reduce_later(s, [=](hipStream_t rs) -> int {    // one launch + one slab sum (residConv3's region holds the patches' slabs: make_plan sized it)
-                return resid_path_backward(B, g1.Hi, g1.Cin, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp3.p, rs); }));
+                return resid_path_backward(B, g1.Hi, g1.Cin, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp3.p, rs, dr1_out); }));
         } else
         CK(reduce_later(s, [=](hipStream_t rs) -> int {
             CK(conv_wgrad(e, g3, r2, dtail, nullptr, dw3, db3, rp3, Amax(), rs));
@@ -1037,6 +1043,13 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         if (rc) return rc;
     }
     CK(reduce_join(s));                                                       // every slab sum has landed in dweff / the bias gradients
+    if (dx) {
+        // d loss / d x (models/modelsTF.py:23-27, 45-47, 58 in reverse): mainConv1's backward-data on the gated `cur`, and residConv1's on the residual path's
+        // d r1 -- which has arrived with the join -- spread over the frames.  Fused residual path: dr1 holds the gated gradient; un-fused: the plain
+        // backward-data output, gated here by r1 as its backward-filter gates it
+        CK(input_grad(B, e->Hin, e->cfg.num_img_lr, e->cfg.in_channels, cur, W + p.act[0], weff(e->iMain), S + p.dr1,
+                      resid_path_fused(e) ? nullptr : W + p.r1, weff(e->iResid1), e->cfg.std, dx, s));
+    }
     { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_backward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, params, S + p.dweff2, dv.invn, grads, s)); }
     return PROBAV_OK;
 }
@@ -1051,6 +1064,18 @@ int probav_backward_split(probav_engine* e, const float* params, const float* dy
     if (!scratch) { set_error("probav_backward_split: null scratch", hipSuccess); return PROBAV_EINVAL; }
     if (wcache && (!e || wcache_bytes < make_wc_plan(e).total * sizeof(float))) { set_error("probav_backward_split: weight cache too small", hipSuccess); return PROBAV_EINVAL; }
     return backward_impl(e, params, dy, grads, saved, saved_bytes, scratch, scratch_bytes, B, (const float*)wcache, stream);
+}
+int probav_backward_input(probav_engine* e, const float* params, const float* dy, float* grads, const void* saved, size_t saved_bytes,
+                          void* scratch, size_t scratch_bytes, int B, const void* wcache, size_t wcache_bytes, float* dx, void* stream)
+{
+    if (!scratch || !dx) { set_error("probav_backward_input: null scratch / dx", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache && (!e || wcache_bytes < make_wc_plan(e).total * sizeof(float))) { set_error("probav_backward_input: weight cache too small", hipSuccess); return PROBAV_EINVAL; }
+    return backward_impl(e, params, dy, grads, saved, saved_bytes, scratch, scratch_bytes, B, (const float*)wcache, stream, dx);
+}
+int probav_input_grad(int batch, int H, int T, int C, const float* g, const float* act0, const float* wmain, const float* d1,
+                      const float* gate1, const float* w1, float stdv, float* dx, void* stream)
+{
+    return input_grad(batch, H, T, C, g, act0, wmain, d1, gate1, w1, stdv, dx, (hipStream_t)stream);
 }
 int probav_workspace_split(const probav_engine* e, int batch, size_t* saved_bytes, size_t* scratch_bytes)
 {
@@ -1133,6 +1158,7 @@ int probav_workspace_view(const probav_engine* e, int batch, int training, int k
     case PROBAV_VIEW_DEC: if (index < 0 || index >= R) break; *offset_floats = (int64_t)p.dec[index]; *count = (int64_t)out_floats(n.dec); return PROBAV_OK;
     case PROBAV_VIEW_RED: if (index < 0 || index >= nred) break; *offset_floats = (int64_t)p.red[index]; *count = (int64_t)out_floats(n.red[index]); return PROBAV_OK;
     case PROBAV_VIEW_RESID1: if (index != 0) break; *offset_floats = (int64_t)p.r1; *count = (int64_t)out_floats(n.resid1); return PROBAV_OK;
+    case PROBAV_VIEW_INPUT: if (index != 0) break; *offset_floats = (int64_t)p.xn; *count = (int64_t)in_floats(n.main); return PROBAV_OK;
     default: break;
     }
     set_error("probav_workspace_view: no such tensor", hipSuccess);

@@ -765,7 +765,7 @@ __device__ __forceinline__ void rp_bwd_data(const float* dd, int Ho, const float
 
 __global__ __launch_bounds__(1024) void resid_path_bwd_kernel(int Hin, int Cx, const float* __restrict__ mn, const float* __restrict__ r1, const float* __restrict__ r2,
                                                               const float* __restrict__ dtail, const float* __restrict__ w2, const float* __restrict__ w3,
-                                                              float* __restrict__ slabs)
+                                                              float* __restrict__ slabs, float* __restrict__ d1_out)
 {
     extern __shared__ float rp_lds[];
     const int n = blockIdx.x, tid = threadIdx.x;
@@ -788,6 +788,8 @@ __global__ __launch_bounds__(1024) void resid_path_bwd_kernel(int Hin, int Cx, c
     __syncthreads();
     rp_bwd_data<true>(d2, H2, W2, a1, d1, tid, 1024);
     __syncthreads();
+    if (d1_out)                                // the input gradient's residual share starts here (kernels_input_grad.hip); nobody else asks for it
+        for (int i = tid; i < H1 * H1 * RP_C; i += 1024) d1_out[(long)n * H1 * H1 * RP_C + i] = d1[i];
     // the patch's slab: [dw3 9*9*9 | db3 9 | dw2 9*9*9 | db2 9 | dw1 9*Cx*9 | db1 9]
     const int nw = 9 * RP_C * RP_C, nw1 = 9 * Cx * RP_C, total = 2 * (nw + RP_C) + nw1 + RP_C;
     float* sl = slabs + (long)n * total;
@@ -821,10 +823,10 @@ int resid_path_forward(int N, int Hin, int Cx, const float* mn, const float* w1,
 }
 
 int resid_path_backward(int N, int Hin, int Cx, const float* mn, const float* r1, const float* r2, const float* dtail, const float* w2, const float* w3,
-                        float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* slabs, hipStream_t s)
+                        float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* slabs, hipStream_t s, float* d1_out)
 {
     if (!resid_path_supported(Hin, Cx, RP_C) || N < 1) { set_error("resid_path_backward: unsupported shape", hipSuccess); return PROBAV_EINVAL; }
-    const int rc = launch_lds<resid_path_bwd_kernel>("resid_path_bwd", dim3((unsigned)N), dim3(1024), rp_bwd_lds(Hin, Cx), s, Hin, Cx, mn, r1, r2, dtail, w2, w3, slabs);
+    const int rc = launch_lds<resid_path_bwd_kernel>("resid_path_bwd", dim3((unsigned)N), dim3(1024), rp_bwd_lds(Hin, Cx), s, Hin, Cx, mn, r1, r2, dtail, w2, w3, slabs, d1_out);
     if (rc) return rc;
     const long nw = 9L * RP_C * RP_C, nw1 = 9L * Cx * RP_C, total = rp_slab_floats(Cx);
     const SlabSumJob jobs[6] = {{slabs, dw3, total, (int)nw, N}, {slabs + nw, db3, total, RP_C, N},

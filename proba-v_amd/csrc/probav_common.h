@@ -131,8 +131,14 @@ bool resid_path_supported(int Hin, int Cx, int C);
 size_t resid_path_slab_floats(int N, int Cx);
 int resid_path_forward(int N, int Hin, int Cx, const float* mn, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
                        float* r1, float* r2, float* r3, hipStream_t s);
+// d1_out (optional): receives the gated gradient at residConv1's output [N][Hin-2]^2[9] that the kernel forms in LDS (what input_grad reads); null: not written
 int resid_path_backward(int N, int Hin, int Cx, const float* mn, const float* r1, const float* r2, const float* dtail, const float* w2, const float* w3,
-                        float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* slabs, hipStream_t s);
+                        float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* slabs, hipStream_t s, float* d1_out = nullptr);
+// ---- kernels_input_grad.hip : d loss / d x (include/probav_hip.h: probav_input_grad) as one launch.  g, act0 [N][H][H][T][32], wmain [27][C][32] (all three 16-byte aligned),
+// d1 / gate1 (optional) [N][H-2][H-2][9], w1 [9][C][9], dx [N][H][H][T][C]; C = 1 or 3
+bool input_grad_supported(int H, int T, int C);
+int input_grad(int N, int H, int T, int C, const float* g, const float* act0, const float* wmain, const float* d1, const float* gate1, const float* w1,
+               float stdv, float* dx, hipStream_t s);
 // geometries for which conv3d_direct_wgrad runs a dedicated kernel that beats the matrix kernels (one input channel: mainConv1)
 // upscaleConv1 (32 -> 9, valid, depth 3 -> 1) and its backward-data (9 -> 32, full, depth 1 -> 3; w = the flipped, channel-swapped filter): small VALU kernels
 bool conv3d_up_forward_supported(const ConvGeom& g);

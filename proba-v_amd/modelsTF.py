@@ -141,7 +141,8 @@ class WDSRModel(torch.nn.Module):
             flat, wc = self._alt
             y, ws = torch.ops.probav.wdsr_forward(flat, x, int(self._handle().value), self.scale * self.patchSizeLR, False, wc)
             return y
-        need_grad = bool(training) and torch.is_grad_enabled() and self.flat.requires_grad
+        # (x.requires_grad: the input gradient -- probav::wdsr_backward_input -- needs the saved activations as the parameter gradients do)
+        need_grad = bool(training) and torch.is_grad_enabled() and (self.flat.requires_grad or x.requires_grad)
         wc = self.weight_cache()
         if wc is None and not need_grad:
             # inference on weights nothing is updating (test.py:117 calls the model once per micro-batch of 16): normalise and pack them once

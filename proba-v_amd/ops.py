@@ -6,6 +6,8 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
 
   probav::wdsr_forward(flat, x, engine, out_size, training) -> (y, ws)      model(x, training=...)      models/trainClass.py:127,139
   probav::wdsr_backward(flat, dy, ws, engine) -> dflat                      tape.gradient(loss, vars)   models/trainClass.py:131
+  probav::wdsr_backward_input(flat, dy, ws, engine) -> (dflat, dx)          tape.gradient(loss, [x] + vars): called instead of wdsr_backward
+                                                                            when the model input requires grad (modelsTF.py:23-27, 45-53, 58 in reverse)
   probav::shift_loss(pred, hr, mask, border, bit_depth, which) -> (loss, arg, per_sample)
                                                                             Losses.shiftCompensatedL1Loss / L2Loss   models/loss.py:55-84
   probav::shift_loss_backward(hr, mask, pred, arg, upstream, border, which) -> dpred
@@ -174,6 +176,48 @@ def _(flat, dy, ws, engine, wcache=None):
     return torch.empty_like(flat)
 
 
+def _input_shape(engine, batch):
+    """Shape of the network's input (and of d loss / d x) for `batch` samples: [B, P + maxShift, P + maxShift, T, C], read from the engine's
+    layer table (mainConv1's input channels), its plan (the normalised input's size) and the frame count that makes them agree."""
+    import ctypes
+    L = _lib.lib()
+    shp = (ctypes.c_int32 * 5)()
+    _lib.check(L.probav_layer_info(c_void_p(engine), 0, None, None, None, None, ctypes.byref(shp)), "probav_layer_info")
+    off, cnt = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(L.probav_workspace_view(c_void_p(engine), int(batch), 1, 4, 0, ctypes.byref(off), ctypes.byref(cnt)), "probav_workspace_view")
+    r1o, r1c = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(L.probav_workspace_view(c_void_p(engine), int(batch), 1, 3, 0, ctypes.byref(r1o), ctypes.byref(r1c)), "probav_workspace_view")
+    C = int(shp[3])
+    h1 = int(round((r1c.value / (9 * int(batch))) ** 0.5))             # relu(residConv1): [B, Hin - 2, Hin - 2, 9]
+    hin = h1 + 2
+    T = cnt.value // (int(batch) * hin * hin * C)
+    if h1 * h1 * 9 * int(batch) != r1c.value or T * int(batch) * hin * hin * C != cnt.value:
+        raise RuntimeError("probav_workspace_view: the plan's input and residual extents do not factor")
+    return (int(batch), hin, hin, int(T), C)
+
+
+@torch.library.custom_op("probav::wdsr_backward_input", mutates_args=(), device_types="cuda")
+def wdsr_backward_input(flat: Tensor, dy: Tensor, ws: Tensor, engine: int, wcache: Optional[Tensor] = None) -> tuple[Tensor, Tensor]:
+    """-> (d loss / d flat, d loss / d x): wdsr_backward with the input gradient as a second output (probav_backward_input).  The first
+    output has the bits wdsr_backward gives; the second costs one more launch at the end of the pass.  Functional like wdsr_backward: `ws`
+    is only read, the scratch is this call's own block from the same private pool."""
+    _dev(dy, "output gradient")
+    grads = torch.empty_like(flat)
+    B = dy.shape[0]
+    dx = torch.empty(_input_shape(engine, B), dtype=torch.float32, device=dy.device)
+    with torch.cuda.use_mem_pool(_ws_pool(dy.device, "scratch"), device=dy.device):
+        scratch = torch.empty(_scratch_floats(engine, B), dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().probav_backward_input(c_void_p(engine), _lib.ptr(flat), _lib.ptr(dy), _lib.ptr(grads), _lib.ptr(ws), ws.numel() * 4,
+                                                _lib.ptr(scratch), scratch.numel() * 4, B, _lib.ptr(wcache),
+                                                0 if wcache is None else wcache.numel() * 4, _lib.ptr(dx), _lib.current_stream()), "probav_backward_input")
+    return grads, dx
+
+
+@wdsr_backward_input.register_fake
+def _(flat, dy, ws, engine, wcache=None):
+    return torch.empty_like(flat), dy.new_empty(_input_shape(engine, int(dy.shape[0])), dtype=torch.float32)
+
+
 def _wdsr_setup(ctx, inputs, output):
     flat, x, engine, out_size, training, wcache = inputs
     ctx.wcache = wcache
@@ -192,6 +236,9 @@ def _wdsr_bwd(ctx, dy, dws):
         raise RuntimeError("backward through model(x, training=False): call the model with training=True "
                            "to keep the activations the reverse pass needs")
     flat, ws = ctx.saved_tensors
+    if ctx.needs_input_grad[1]:                # d loss / d x asked for: the same pass with one more launch and one more output
+        g, dx = torch.ops.probav.wdsr_backward_input(flat, dy.contiguous().float(), ws, ctx.engine, ctx.wcache)
+        return g, dx, None, None, None, None
     g = torch.ops.probav.wdsr_backward(flat, dy.contiguous().float(), ws, ctx.engine, ctx.wcache)
     return g, None, None, None, None, None
 
