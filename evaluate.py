@@ -10,6 +10,7 @@
     python evaluate.py --cfg C --band NIR --baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered]   # the bicubic-mean baseline, no checkpoint
     python evaluate.py --cfg C --band NIR --model --benchmark-baseline                                       # the checkpoint against that baseline
     python evaluate.py --cfg C --band NIR --model --norm computed                                            # N_i from the esa / raw baseline (a stand-in for norm.csv)
+    python evaluate.py --cfg C --band NIR --model --metrics cpsnr,cssim                                      # ... the cSSIM of the literature beside the cPSNR
 
 --toCompare scores the imgsetNNNN.png of a folder (test.py's output) against resolverDir/TRAINimgHR_<band>.npy, matching by id: train ids
 below 594 are RED, 594 .. 1159 NIR, ids from 1160 are test sets (no HR: counted, skipped).  --model resolves resolverDir/TRAINpatchesLR_<band>.npy
@@ -23,6 +24,10 @@ norm.csv (default <raw_data>/norm.csv when present; lower is better).  --baselin
 TRAIN sets (probav_amd/baseline.py; no checkpoint, no PNGs), --benchmark-baseline compares --model against it instead of a --benchmark folder, and
 --norm computed takes N_i from the esa / raw baseline's own cPSNR: a stand-in, since ESA's norm.csv was made with another interpolator
 (INTEGRATION.md).  The JSON line says where the norm came from: "norm_source": "file", "computed" or null.
+
+--metrics cpsnr,cssim adds the shift-compensated SSIM published beside the cPSNR (proba-v_amd/scoring.py, on the device): per image its maximum
+over the 49 shifts with that shift (cssim, su, sv) and the SSIM at the cPSNR's own shift (cssim_at_cpsnr_shift), their means in the JSON line; it works with
+every source and inference flag above.  --formula does not affect it (HR is always masked there), and norm.csv has no SSIM counterpart: no cSSIM score.
 
 Prints one JSON line; writes <out>/scores.csv and, when matplotlib imports and there is a --benchmark, <out>/comparison.png.
 """
@@ -49,7 +54,10 @@ def parser(argv=None):
     p.add_argument("--band", type=str, default="both", help="NIR, RED or both")
     p.add_argument("--norm", type=str, default=None, help="norm.csv (default: <raw_data>/norm.csv if present), or `computed`: N_i = the cPSNR of "
                    "this repository's own esa / raw bicubic-mean baseline (a stand-in: ESA's file was made with another interpolator)")
-    p.add_argument("--formula", type=str, default="esa", choices=("esa", "reference"))
+    p.add_argument("--formula", type=str, default="esa", choices=("esa", "reference"), help="the cPSNR's formula; it does not affect cSSIM, "
+                   "where HR is always masked")
+    p.add_argument("--metrics", type=str, default="cpsnr", help="cpsnr (default) or cpsnr,cssim: also the shift-compensated SSIM of every image "
+                   "(extra CSV columns and JSON keys; --formula does not affect it)")
     p.add_argument("--model", action="store_true", help="score the cfg's latest checkpoint on resolverDir/TRAINpatchesLR_<band>.npy")
     p.add_argument("--out", type=str, default=".", help="folder for scores.csv and comparison.png")
     add_inference_args(p, "with --model: ")
@@ -62,6 +70,10 @@ def parser(argv=None):
     p.add_argument("--border", type=int, default=3, help=argparse.SUPPRESS)
     opt = p.parse_args(argv)
     opt.band = opt.band.upper()
+    try:
+        opt.metrics = scoring.check_metrics(m.strip() for m in opt.metrics.split(","))
+    except ValueError as e:
+        p.error("--metrics: %s" % e)
     if opt.band not in ("NIR", "RED", "BOTH"):
         p.error("--band must be NIR, RED or both, got %r" % opt.band)
     if int(opt.model) + int(opt.toCompare is not None) + int(opt.baseline) != 1:
@@ -125,7 +137,7 @@ def main(opt):
     def baseline_scored(spec):
         if spec not in baseline_rows:
             baseline_rows[spec] = scoring.score_images(baseline_train_images(config, bands, spec), hr, border=opt.border, formula=opt.formula,
-                                                       removed=removed)
+                                                       removed=removed, metrics=opt.metrics)
         return baseline_rows[spec]
 
     if norm_path == "computed":
@@ -143,14 +155,17 @@ def main(opt):
     else:
         images = scoring.load_sr_dir(opt.toCompare)
     if not opt.baseline:
-        rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed)
+        rows, counts = scoring.score_images(images, hr, border=opt.border, formula=opt.formula, removed=removed, metrics=opt.metrics)
     bench_rows = None
     if opt.benchmark_baseline:
         bench_rows = baseline_scored(opt.baseline_spec)[0]
     elif opt.benchmark is not None:
-        bench_rows, _ = scoring.score_images(scoring.load_sr_dir(opt.benchmark), hr, border=opt.border, formula=opt.formula, removed=removed)
-    summary = scoring.summarize(rows, counts, norm=norm, bench_rows=bench_rows)
+        bench_rows, _ = scoring.score_images(scoring.load_sr_dir(opt.benchmark), hr, border=opt.border, formula=opt.formula, removed=removed,
+                                             metrics=opt.metrics)
+    summary = scoring.summarize(rows, counts, norm=norm, bench_rows=bench_rows, metrics=opt.metrics)
     summary["formula"] = opt.formula
+    if opt.metrics != ("cpsnr",):
+        summary["metrics"] = list(opt.metrics)
     if opt.ensemble != "none":
         summary["ensemble"] = {"geometry": opt.ensemble, "permute": opt.ensemble_permute, "seed": opt.ensemble_seed}
     if opt.weights != "raw":
@@ -164,7 +179,7 @@ def main(opt):
     summary["norm"] = norm_path
     summary["norm_source"] = norm_source
     os.makedirs(opt.out, exist_ok=True)
-    scoring.write_csv(os.path.join(opt.out, "scores.csv"), rows, norm=norm, bench_rows=bench_rows)
+    scoring.write_csv(os.path.join(opt.out, "scores.csv"), rows, norm=norm, bench_rows=bench_rows, metrics=opt.metrics)
     if bench_rows is not None:
         if scoring.plot_comparison(os.path.join(opt.out, "comparison.png"), rows, bench_rows):
             summary["comparison_png"] = os.path.join(opt.out, "comparison.png")

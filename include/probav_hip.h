@@ -408,6 +408,28 @@ int probav_score_moments(const uint16_t* sr, const uint16_t* hr, const uint8_t* 
 int probav_score_select(const int64_t* moments, int64_t n_images, int border, double* cpsnr, int32_t* shift, double* bias,
                         int64_t* n_clear, void* stream);
 
+/* The shift-compensated SSIM (cSSIM) of whole images, the number published beside the cPSNR.  Images, mask, border, L, P and the shift
+ * order as above; for every shift (u, v), all in fp64:
+ *     H = HR[u:u+L, v:v+L],  m = mask[u:u+L, v:v+L] as 0/1,  n = sum m,  s1 = sum m (H - P)    (the exact integers of probav_score_moments)
+ *     bias = s1 / n                                              (one fp64 division; n = 0: the shift is skipped, its value is NaN)
+ *     x = m (P + bias),  y = m H                                 (masked pixels are zero on BOTH sides, as the published implementations do)
+ *     g[j] = exp(-(j - 5)^2 / (2 * 1.5^2)), j = 0..10, divided by their sum: gauss11, 11 doubles computed by the caller and read as data
+ *     F(a)[i, j] = sum_{p, q} g[p] g[q] a[i+p, j+q], "valid": K x K outputs, K = L - 10
+ *     mx = F(x)  my = F(y)  vx = F(x x) - mx^2  vy = F(y y) - my^2  cxy = F(x y) - mx my,   C1 = (0.01 * 65535)^2,  C2 = (0.03 * 65535)^2
+ *     ssim(u, v) = mean over the K^2 windows of ((2 mx my + C1)(2 cxy + C2)) / ((mx^2 + my^2 + C1)(vx + vy + C2))
+ * A window that sees only masked pixels contributes exactly 1.  table [n_images][(2b+1)^2] fp64 = ssim(u, v), NaN where n = 0.  moments:
+ * the output of probav_score_moments for the same arguments.  scratch: probav_ssim_scratch_bytes(n_images, S, border) bytes (0 for an
+ * unsupported shape; PROBAV_ENOSPACE when scratch_bytes is smaller), one slot per workgroup and shift: no floating-point atomics, and an
+ * entry is a pure function of the image's crops (the same bits for any batch, position or run; equal crops give equal bits).
+ * 1 <= n_images <= 65535, 0 <= b <= 3, 2b + 11 <= S <= 2048.  Shape, exactness and cost model: csrc/kernels_ssim.hip; the statement the
+ * kernel is held to: probav_amd.scoring.cssim_table_numpy. */
+size_t probav_ssim_scratch_bytes(int64_t n_images, int S, int border);
+int probav_ssim_table(const uint16_t* sr, const uint16_t* hr, const uint8_t* mask, const int64_t* moments, const double* gauss11,
+                      int64_t n_images, int S, int border, void* scratch, size_t scratch_bytes, double* table, void* stream);
+/* From the table: per image cssim = the largest entry that is not NaN, shift [2] = (u, v) of the FIRST entry attaining it; every entry
+ * NaN: cssim = NaN, shift = (-1, -1). */
+int probav_ssim_select(const double* table, int64_t n_images, int border, double* cssim, int32_t* shift, void* stream);
+
 /* ---- batch augmentation (proba-v_amd/augment.py), an addition of ABI 7 ------------------------------------------------------------- */
 /* One launch builds a training batch from the device-resident UN-augmented patches: lr [n_base][H][H][T][C] fp32, hr [n_base][S][S] fp32,
  * mask [n_base][S][S] uint8 (copied as bytes).  recipe [batch][3 + T] int32, row b = {i, f, k, perm[0..T)}: base sample i, flip code f

@@ -106,6 +106,10 @@ SIGNATURES = {
     # scoring (csrc/kernels_score.hip)
     "probav_score_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "probav_score_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # shift-compensated SSIM (csrc/kernels_ssim.hip): added under ABI 7
+    "probav_ssim_scratch_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "probav_ssim_table": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "probav_ssim_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     # batch augmentation (csrc/kernels_augment.hip)
     "probav_augment_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),

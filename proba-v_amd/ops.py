@@ -28,6 +28,8 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
   probav::esa_shift_moments(sr, hr, mask, border) -> moments int64 [N, (2b+1)^2, 3]       (n, s1, s2) of every shift, exact
   probav::esa_shift_cpsnr(sr, hr, mask, border) -> (cpsnr f64[N], shift i32[N,2], bias f64[N], n_clear i64[N])
                                                                             the ESA cPSNR of whole images   evaluate.py:76-87 (scoring.py)
+  probav::esa_shift_ssim_table(sr, hr, mask, border) -> table f64 [N, (2b+1)^2]           the windowed SSIM of every shift, NaN where n = 0
+  probav::esa_shift_cssim(sr, hr, mask, border) -> (cssim f64[N], shift i32[N,2])         its first maximum: the cSSIM published beside the cPSNR
   probav::augment_batch(lr, hr, mask, recipe) -> (lr_b, hr_b, mask_b)      a training batch from the un-augmented patches: frame permutation,
                                                                             flip, quarter turns per sample   utils/dataGenerator.py:227-273 (augment.py)
   probav::ensemble_expand(lr, recipe) -> lr_v                              the LR variants of inference patches (flip, quarter turns, frame order)
@@ -664,6 +666,59 @@ def _(sr, hr, mask, border):
     N = sr.shape[0]
     return (sr.new_empty((N,), dtype=torch.float64), sr.new_empty((N, 2), dtype=torch.int32), sr.new_empty((N,), dtype=torch.float64),
             sr.new_empty((N,), dtype=torch.int64))
+
+
+# the shift-compensated SSIM of the same images (csrc/kernels_ssim.hip; stated in scoring.py).  The 11 Gaussian taps are scoring.gauss11():
+# made once on the host in numpy fp64 and handed to the kernel as data, so the numpy statement and the kernel use the same bit patterns.
+_GAUSS11 = {}
+
+
+def _gauss11(device):
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _GAUSS11:
+        from .scoring import gauss11
+        _GAUSS11[key] = torch.from_numpy(gauss11()).to(device)
+    return _GAUSS11[key]
+
+
+@torch.library.custom_op("probav::esa_shift_ssim_table", mutates_args=(), device_types="cuda")
+def esa_shift_ssim_table(sr: Tensor, hr: Tensor, mask: Tensor, border: int) -> Tensor:
+    sr, hr, mask = _score_args(sr, hr, mask, border)
+    N, S, ns = sr.shape[0], sr.shape[1], 2 * border + 1
+    if S < 2 * border + 11:
+        raise ValueError("esa_shift_ssim_table: the 11-tap window needs 11 rows of the crop: S >= 2 border + 11 = %d, got S = %d" % (2 * border + 11, S))
+    table = torch.empty((N, ns * ns), dtype=torch.float64, device=sr.device)
+    if N:
+        mom = esa_shift_moments(sr, hr, mask, border)
+        nbytes = _lib.lib().probav_ssim_scratch_bytes(N, S, border)
+        scratch = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=sr.device)
+        _lib.check(_lib.lib().probav_ssim_table(_lib.ptr(sr), _lib.ptr(hr), _lib.ptr(mask), _lib.ptr(mom), _lib.ptr(_gauss11(sr.device)), N, S, border,
+                                                _lib.ptr(scratch), nbytes, _lib.ptr(table), _lib.current_stream()), "probav_ssim_table")
+    return table
+
+
+@esa_shift_ssim_table.register_fake
+def _(sr, hr, mask, border):
+    ns = 2 * border + 1
+    return sr.new_empty((sr.shape[0], ns * ns), dtype=torch.float64)
+
+
+@torch.library.custom_op("probav::esa_shift_cssim", mutates_args=(), device_types="cuda")
+def esa_shift_cssim(sr: Tensor, hr: Tensor, mask: Tensor, border: int) -> tuple[Tensor, Tensor]:
+    N, dev = sr.shape[0], sr.device
+    table = esa_shift_ssim_table(sr, hr, mask, border)
+    cssim = torch.empty(N, dtype=torch.float64, device=dev)
+    shift = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    if N:
+        _lib.check(_lib.lib().probav_ssim_select(_lib.ptr(table), N, border, _lib.ptr(cssim), _lib.ptr(shift), _lib.current_stream()),
+                   "probav_ssim_select")
+    return cssim, shift
+
+
+@esa_shift_cssim.register_fake
+def _(sr, hr, mask, border):
+    N = sr.shape[0]
+    return sr.new_empty((N,), dtype=torch.float64), sr.new_empty((N, 2), dtype=torch.int32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
