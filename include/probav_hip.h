@@ -389,6 +389,30 @@ int probav_prep_patches(const float* frames, const uint8_t* masks, int S, int T,
 int probav_prep_register_masked(const uint16_t* frames, const uint8_t* masks, const int64_t* set_offsets, int n_sets, int64_t n_frames,
                                 const int32_t* ref_frame, int window, int32_t* shifts, uint8_t* registered, uint16_t* out_frames,
                                 uint8_t* out_masks, int32_t* out_counts, void* stream);
+/* Refined quality masks (csrc/kernels_refine.hip): the pixels of co-registered uint16 frames [n_frames][H][W] (any H, W >= 1) that the
+ * quality masks call clear but that lie far from the temporal median of their set's clear looks are taken out of the masks.  Per set
+ * (frames x[t], clear c[t] = masks != 0, t < T) and per pixel, all in integers:
+ *     sat[t] = c[t] and saturation >= 0 and x[t] > saturation;  c'[t] = c[t] and not sat[t];  n = #c'
+ *     med = the clear values' element (n - 1) / 2 in ascending order (the lower median);  d[t] = |x[t] - med|
+ *     mad = the element (n - 1) / 2 of the clear d in ascending order;  s = max(mad, floor_dn)
+ *     o[t] = c'[t] and n >= min_clear and 16 d[t] > k16 s        (strict; 16 d < 2^20 and k16 s < 2^26: int32)
+ *     pixel_masks [n_sets][3][H][W] uint64, bit t = frame t of the set: plane 0 = c, plane 1 = sat, plane 2 = o
+ *                                                                (an output, and the second launch's input; bits T .. 63 are zero)
+ *     g[t][p] = any (sat | o)[t][q] over |q - p|_inf <= dilate, q inside the frame (nothing wraps or reflects)
+ *     out_masks[t] = c[t] and not g[t] (0/1);  out_counts[t] = its ones;  flagged[t] = {sum sat[t], sum o[t]} (before the dilation)
+ * Host-known arguments outside their ranges return PROBAV_EINVAL and launch nothing: 0 <= k16 <= 1024, 0 <= floor_dn <= 65535,
+ * 3 <= min_clear <= 64, 0 <= dilate <= 3, -1 <= saturation <= 65535 (-1: no saturation test), 1 <= max_set_len <= 64 (the longest set;
+ * it sizes the LDS of the launch).  Preconditions on the device array as probav_prep_register: set_offsets[0] = 0, non-decreasing,
+ * set_offsets[n_sets] = n_frames, and here 1 <= set_offsets[s+1] - set_offsets[s] <= max_set_len.  A set that breaks them is neither
+ * read nor written; each of its frames f has out_counts[f] = PROBAV_PREP_BAD_COUNT and flagged[f] = {PROBAV_PREP_BAD_COUNT,
+ * PROBAV_PREP_BAD_COUNT} (probav.prep raises on it).  Frames are never changed; no scratch beside `pixel_masks` (24 n_sets H W bytes).  The statement the kernels
+ * equal bit for bit: probav_amd.prep.refine_masks_numpy.
+ *                                         the counterpart of nothing in the reference: its README names the radiometric half of the
+ *                                         problem (LR frames are never clipped to their 14-bit depth) and leaves it there */
+#define PROBAV_PREP_BAD_COUNT (-1)
+int probav_prep_refine_masks(const uint16_t* frames, const uint8_t* masks, const int64_t* set_offsets, int n_sets, int64_t n_frames, int H, int W,
+                             int max_set_len, int k16, int floor_dn, int min_clear, int dilate, int saturation, uint64_t* pixel_masks,
+                             uint8_t* out_masks, int32_t* out_counts, int32_t* flagged, void* stream);
 
 /* ---- scoring (evaluate.py; proba-v_amd/scoring.py), additions of ABI 7 ------------------------------------------------------------- */
 /* The ESA PROBA-V shift-compensated clear PSNR of whole images; it replaces the reference's unfinished evaluate.py:76-87, which calls

@@ -103,6 +103,8 @@ SIGNATURES = {
     # cloud-aware registration (csrc/kernels_prep_masked.hip): added under ABI 7
     "probav_prep_register_masked": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    # refined quality masks (csrc/kernels_refine.hip): added under ABI 7
+    "probav_prep_refine_masks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64] + [c_int] * 8 + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # scoring (csrc/kernels_score.hip)
     "probav_score_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "probav_score_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -17,8 +17,12 @@ Deliberate differences ('From the ESA download to train.py'):
   - registerFrame(tech='time'), the reference's cloud-aware registration (utils/dataGenerator.py:663-666), is a masked normalised
     correlation over a bounded window of integer shifts with a shift that does not wrap: `register_masked_numpy` is its statement,
     csrc/kernels_prep_masked.hip the kernel that equals it bit for bit.  Selected by registerImages(tech='time') /
-    main(register='masked'); the default ('freq') is the plain path above, unchanged.
+    main(register='masked'); the default ('freq') is the plain path above, unchanged;
+  - registerImages(refine=RefineSpec(...)) / main(refine=...) take temporal outliers and saturated pixels of the registered frames out of
+    their masks before anything is selected -- the counterpart of nothing in the reference.  `refine_masks_numpy` is the statement,
+    csrc/kernels_refine.hip the kernels that equal it bit for bit.  Off by default (refine=None): the masks as the quality masks give them.
 """
+import dataclasses
 import glob
 import logging
 import math
@@ -27,10 +31,13 @@ import os
 import numpy as np
 
 from . import pngio
+from .frame_windows import MAX_POOL
 
 LR_SIZE = 128          # registration geometry (PROBA-V LR frames)
 PREP_BAD_SHIFT = -2 ** 31   # PROBAV_PREP_BAD_SHIFT
 MASKED_MAX_WINDOW = 32      # largest window of the masked registration (csrc/kernels_prep_masked.hip)
+PREP_BAD_COUNT = -1          # PROBAV_PREP_BAD_COUNT
+REFINE_MAX_K16, REFINE_MAX_DILATE = 1024, 3   # the mask refinement's ranges (csrc/kernels_refine.hip); its longest set is frame_windows.MAX_POOL
 REGISTER_TECHS = ('freq', 'time')                        # registerFrame's `tech`, the reference's names
 REGISTER_MODES = {'freq': 'freq', 'masked': 'time'}      # main()'s `register` / the CLI's --register -> tech
 
@@ -218,6 +225,162 @@ def device_register_masked(frames, masks, set_offsets, ref_frame, window):
     return sh, reg.cpu().numpy(), rf.cpu().numpy(), rm.cpu().numpy().astype(bool), rc.cpu().numpy()
 
 
+# ---- refined quality masks (csrc/kernels_refine.hip) --------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class RefineSpec:
+    """What `refine_masks_numpy` / `device_refine_masks` flag.  k: outlier threshold in MADs, a multiple of 1/16 with k16 = 16 k in 0..1024;
+    floor: smallest scale in DN, 0..65535; min_clear: clear looks a pixel needs before it is judged, 3..64; dilate: radius in pixels by
+    which the flags grow, 0..3; saturation: None, or the value 0..65535 above which a clear pixel is flagged whatever the set says.
+    Anything else is a ValueError, here and wherever a spec is used."""
+    k: float = 5.0
+    floor: int = 32
+    min_clear: int = 5
+    dilate: int = 1
+    saturation: object = None
+
+    def __post_init__(self):
+        _check_refine(self)
+
+    @property
+    def k16(self):
+        return int(round(16 * self.k))
+
+
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _check_refine(spec):
+    if not isinstance(spec, RefineSpec):
+        raise ValueError("refine takes a prep.RefineSpec, got %r" % (spec,))
+    k = spec.k
+    if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)) or not math.isfinite(k) or 16 * k != round(16 * k) \
+            or not 0 <= round(16 * k) <= REFINE_MAX_K16:
+        raise ValueError("refine k must be a multiple of 1/16 in 0..%d, got %r" % (REFINE_MAX_K16 // 16, k))
+    for name, lo, hi in (("floor", 0, 65535), ("min_clear", 3, MAX_POOL), ("dilate", 0, REFINE_MAX_DILATE)):
+        v = getattr(spec, name)
+        if not _is_int(v) or not lo <= v <= hi:
+            raise ValueError("refine %s must be an integer in %d..%d, got %r" % (name, lo, hi, v))
+    if spec.saturation is not None and (not _is_int(spec.saturation) or not 0 <= spec.saturation <= 65535):
+        raise ValueError("refine saturation must be None or an integer in 0..65535, got %r" % (spec.saturation,))
+    return spec
+
+
+def _check_refine_sets(frames, masks, set_offsets):
+    frames, masks = np.asarray(frames), np.asarray(masks)
+    o = np.asarray(set_offsets, np.int64)
+    if frames.ndim != 3 or masks.shape != frames.shape or min(frames.shape) < 1:
+        raise ValueError("mask refinement takes frames and masks [F, H, W] with F, H, W >= 1, got %r / %r" % (frames.shape, masks.shape))
+    if o.ndim != 1 or len(o) < 2 or o[0] != 0 or o[-1] != len(frames) or (np.diff(o) < 1).any():
+        raise ValueError("mask refinement needs set_offsets[0] = 0, set_offsets[-1] = n_frames and no empty set")
+    if np.diff(o).max() > MAX_POOL:
+        raise ValueError("mask refinement takes sets of at most %d frames, got one of %d" % (MAX_POOL, np.diff(o).max()))
+    return frames.astype(np.uint16, copy=False), masks != 0, o
+
+
+def refine_set_numpy(x, c, spec):
+    """One set of `refine_masks_numpy`, steps 1 to 5: x uint16 [T, H, W], c bool [T, H, W] -> (sat, o, med, mad, n); med and mad are int64
+    [H, W] (0 where n = 0) whatever min_clear says."""
+    T = len(x)
+    x = x.astype(np.int64)
+    sat = c & (x > spec.saturation) if spec.saturation is not None else np.zeros_like(c)
+    cc = c & ~sat
+    n = cc.sum(0)
+    r = np.maximum(n - 1, 0) // 2
+    BIG = 1 << 20                                           # above every value and every distance: unclear looks sort last
+    pick = lambda v: np.take_along_axis(np.sort(np.where(cc, v, BIG), axis=0), r[None], 0)[0]
+    med = np.where(n > 0, pick(x), 0)
+    d = np.abs(x - med[None])
+    mad = np.where(n > 0, pick(d), 0)
+    s = np.maximum(mad, spec.floor)
+    o = cc & (n >= spec.min_clear)[None] & (16 * d > spec.k16 * s[None])
+    return sat, o, med, mad, n
+
+
+def refine_masks_numpy(frames, clear, set_offsets, spec=None):
+    """THE statement of the mask refinement (csrc/kernels_refine.hip equals it bit for bit).  frames uint16 [F, H, W] of one band AFTER
+    registration, clear [F, H, W] (nonzero = clear), set_offsets [S+1] (the ragged convention of `device_register`), a RefineSpec ->
+    (clear_out bool [F, H, W], counts int32 [F], flagged int32 [F, 2]).
+
+    Per set with frames x[t], clear flags c[t], t < T <= 64, and per pixel p, all in integers:
+      1. sat[t] = c[t] and saturation is not None and x[t] > saturation;  c'[t] = c[t] and not sat[t]
+      2. n = #{t : c'[t]};  med = the element (n - 1) // 2 of {x[t] : c'[t]} in ascending order (the lower median)
+      3. d[t] = |x[t] - med|;  mad = the element (n - 1) // 2 of {d[t] : c'[t]} in ascending order
+      4. s = max(mad, floor)
+      5. o[t] = c'[t] and n >= min_clear and 16 d[t] > k16 s      (strict; everything fits int32)
+      6. f[t] = sat[t] or o[t]
+      7. g[t][p] = any f[t][q] over |q - p|_inf <= dilate, q inside the frame (nothing wraps or reflects)
+      8. clear_out[t] = c[t] and not g[t]
+    counts = the ones of clear_out per frame, flagged = {sum sat, sum o} per frame (before the dilation).  Only values are selected, so
+    ties need no rule; a set with T < min_clear gets the saturation flags alone; the frames are never changed."""
+    spec = _check_refine(RefineSpec() if spec is None else spec)
+    frames, c, off = _check_refine_sets(frames, clear, set_offsets)
+    F, H, W = frames.shape
+    f = np.zeros((F, H, W), bool)
+    flagged = np.zeros((F, 2), np.int32)
+    for i in range(len(off) - 1):
+        sl = slice(off[i], off[i + 1])
+        sat, o = refine_set_numpy(frames[sl], c[sl], spec)[:2]
+        f[sl] = sat | o
+        flagged[sl, 0], flagged[sl, 1] = sat.sum((1, 2)), o.sum((1, 2))
+    r = spec.dilate
+    g = np.zeros_like(f)
+    pad = np.pad(f, ((0, 0), (r, r), (r, r)))              # zeros outside the frame
+    for dy in range(2 * r + 1):
+        for dx in range(2 * r + 1):
+            g |= pad[:, dy:dy + H, dx:dx + W]
+    out = c & ~g
+    return out, out.sum((1, 2)).astype(np.int32), flagged
+
+
+def device_refine_masks(frames, masks, set_offsets, spec=None):
+    """The mask refinement on the device (csrc/kernels_refine.hip): frames [F, H, W] uint16 (any H, W >= 1), masks [F, H, W] (nonzero =
+    clear), set_offsets [S+1], a RefineSpec -> (clear_out bool [F, H, W], counts int32 [F], flagged int32 [F, 2] = {saturated, outliers}
+    per frame before the dilation).  Equal to `refine_masks_numpy` bit for bit."""
+    spec = _check_refine(RefineSpec() if spec is None else spec)
+    frames, clear, o = _check_refine_sets(frames, masks, set_offsets)
+    import torch
+    from . import _lib
+    dev = _dev()
+    F, H, W = frames.shape
+    fr, mk, off = _to_dev(frames, dev), _to_dev(clear.view(np.uint8), dev), _to_dev(o, dev)
+    out = torch.empty_like(mk)
+    planes = torch.empty((len(o) - 1) * 3 * H * W, dtype=torch.int64, device=dev)      # pixel_masks: per set and pixel, one bit per frame
+    counts = torch.empty(F, dtype=torch.int32, device=dev)
+    flagged = torch.empty(F, 2, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().probav_prep_refine_masks(_lib.ptr(fr), _lib.ptr(mk), _lib.ptr(off), len(o) - 1, F, H, W, int(np.diff(o).max()), spec.k16,
+                                                   spec.floor, spec.min_clear, spec.dilate, -1 if spec.saturation is None else spec.saturation,
+                                                   _lib.ptr(planes), _lib.ptr(out), _lib.ptr(counts), _lib.ptr(flagged), _lib.current_stream()),
+               "probav_prep_refine_masks")
+    cn = counts.cpu().numpy()
+    if (cn == PREP_BAD_COUNT).any():
+        raise ValueError("probav_prep_refine_masks: set_offsets break the preconditions of include/probav_hip.h (an empty or over-long set)")
+    return out.cpu().numpy().astype(bool), cn, flagged.cpu().numpy()
+
+
+def _refine_registered(rf, rm, offsets, spec, log):
+    """registerImages' refinement of one band's registered flat arrays: the refined masks, with what they changed logged."""
+    out, counts, flagged = device_refine_masks(rf, rm, offsets, spec)
+    before = rm.reshape(len(rm), -1).sum(1).astype(np.int64)
+    lost = before - counts
+    log.info('[ INFO ] Refined masks (k %g, floor %d, min_clear %d, dilate %d, saturation %s): %d pixels newly masked of %d clear '
+             '(%d saturated, %d temporal outliers, the rest by dilation); %d of %d frames lost more than 10 %% of their clear pixels',
+             spec.k, spec.floor, spec.min_clear, spec.dilate, spec.saturation, int(lost.sum()), int(before.sum()), int(flagged[:, 0].sum()),
+             int(flagged[:, 1].sum()), int((10 * lost > before).sum()), len(rm))
+    # the number a user needs to choose `floor`: the median MAD of judged pixels, from the statement on the host over at most 8 sets
+    pick = np.linspace(0, len(offsets) - 2, min(8, len(offsets) - 1)).astype(int)
+    mads = []
+    for i in np.unique(pick):
+        sl = slice(offsets[i], offsets[i + 1])
+        _, _, _, mad, n = refine_set_numpy(rf[sl].astype(np.uint16, copy=False), rm[sl] != 0, spec)
+        mads.append(mad[n >= spec.min_clear])
+    mads = np.concatenate(mads)
+    if len(mads):
+        log.info('[ INFO ] Refined masks: median over pixels of the temporal MAD is %d DN on %d sets (floor = %d DN)',
+                 int(np.median(mads)), len(np.unique(pick)), spec.floor)
+    return out
+
+
 def device_xcorr_surface(ref, img):
     """Diagnostic: (fp32 surface [128,128], {B, c_ref, c_img, max}) the registration kernel ranks shifts by."""
     import torch
@@ -310,11 +473,15 @@ def registerFrame(img, msk, referenceImg, referenceMsk, tech='freq', window=8):
     return rf[1].astype(np.float64).reshape(shape), rm[1].reshape(shape)
 
 
-def registerImages(allImgLR, allMskLR, tech='freq', window=8):
+def registerImages(allImgLR, allMskLR, tech='freq', window=8, refine=None):
     """Per set: frames reordered by np.argsort(-clear count), the first is the reference, every other one registered against it
-    (device; tech / window as registerFrame).  Returns an object array of float64 masked arrays [T, 1, 128, 128] (mask = ~clear)."""
+    (device; tech / window as registerFrame).  Returns an object array of float64 masked arrays [T, 1, 128, 128] (mask = ~clear).
+    refine: None, or a RefineSpec: the registered frames' masks go through `device_refine_masks` (whichever `tech`) before the masked
+    arrays are built; the data are the same either way."""
     _check_tech(tech)
     window = _check_window(window)
+    if refine is not None:
+        _check_refine(refine)
     sets_img = [np.asarray(allImgLR[i]) for i in range(len(allImgLR))]
     sets_msk = [np.asarray(allMskLR[i]) for i in range(len(allMskLR))]
     for a, m in zip(sets_img, sets_msk):
@@ -332,6 +499,8 @@ def registerImages(allImgLR, allMskLR, tech='freq', window=8):
                                                 'stay where they are', window, int((reg == 0).sum()), len(reg))
     else:
         _, rf, rm, _ = device_register(frames[order], masks[order], offsets, offsets[:-1])
+    if refine is not None:
+        rm = _refine_registered(rf, rm, offsets, refine, logging.getLogger("dataGenerator"))
     out = []
     for i in range(len(sizes)):
         sl = slice(offsets[i], offsets[i + 1])
@@ -521,9 +690,11 @@ def gridPatches(imgLR, imgHR, config):
 
 
 # ---- driver (utils/dataGenerator.py:33-273) ---------------------------------------------------------------------------------------
-def main(config, band, rng=None, online_aug=False, register='freq', register_window=8, scene_split=False):
+def main(config, band, rng=None, online_aug=False, register='freq', register_window=8, scene_split=False, refine=None):
     """register: 'freq' (the default: the plain circular registration, as the reference's registerFrame default) or 'masked' (the
     cloud-aware one over [-register_window, register_window]^2, the reference's tech='time'); stage 2 only.
+    refine: None (the default: the masks as the ESA quality masks give them) or a RefineSpec: stage 2 takes temporal outliers and saturated
+    pixels of the registered TRAIN and TEST frames out of their masks (`refine_masks_numpy`) before anything is selected; stage 2 only.
     online_aug: stage 5 draws the frame permutations as ever (same rng, same order) but SAVES them beside the un-augmented training
     arrays instead of applying them -- TRAINbasepatches{LR,HR}_<band>.npy and TRAINaugperms_<band>.npy, what `train.py --online-aug` reads
     (probav_amd.augment).  The TRAINVAL dumps do not depend on it.
@@ -537,6 +708,8 @@ def main(config, band, rng=None, online_aug=False, register='freq', register_win
     if register not in REGISTER_MODES:
         raise ValueError("register must be one of %r, got %r" % (tuple(REGISTER_MODES), register))
     tech, register_window = REGISTER_MODES[register], _check_window(register_window)
+    if refine is not None:
+        _check_refine(refine)
     rawDataDir, cleanDataDir = config['raw_data'], config['preprocessing_out']
     d = {k: os.path.join(cleanDataDir, k) for k in ('arrayDir', 'trimmedArrayDir', 'patchesDir', 'trimmedPatchesDir', 'resolverDir',
                                                      'augmentedPatchesDir')}
@@ -555,7 +728,7 @@ def main(config, band, rng=None, online_aug=False, register='freq', register_win
     if 2 in ckpt:
         TRAIN, TEST = loadData(d['arrayDir'], band)
         allImgLR, allMskLR, allImgHR, allMskHR = TRAIN
-        allImgMskLR = registerImages(allImgLR, allMskLR, tech, register_window)
+        allImgMskLR = registerImages(allImgLR, allMskLR, tech, register_window, refine)
         allImgMskHR = convertToMaskedArray(allImgHR, allMskHR)
         allImgMskHR.dump(path('resolverDir', 'TRAINimgHR'))
         trmImgMskLR, trmImgMskHR, imgSetRemoved = removeCorruptedTrainImageSets(allImgMskLR, allImgMskHR, config['low_res_threshold'])
@@ -565,7 +738,7 @@ def main(config, band, rng=None, online_aug=False, register='freq', register_win
             print(f'[ WARNING ] Imgsets {imgSetRemoved} were removed')
         trmImgMskLR = pickClearLRImgsPerImgSet(trmImgMskLR, config['num_low_res_imgs_pre'], config['low_res_threshold'], rng)
         allImgLRTest, allMskLRTest = TEST
-        allImgMskLRTest = registerImages(allImgLRTest, allMskLRTest, tech, register_window)
+        allImgMskLRTest = registerImages(allImgLRTest, allMskLRTest, tech, register_window, refine)
         trmImgMskLRTest = removeCorruptedTestImageSets(allImgMskLRTest, config['low_res_threshold'])
         trmImgMskLRTest = pickClearLRImgsPerImgSet(trmImgMskLRTest, config['num_low_res_imgs_pre'], config['low_res_threshold'], rng)
         trmImgMskLR.dump(path('trimmedArrayDir', 'TRAINimgLR'))
