@@ -7,6 +7,7 @@
     python evaluate.py --cfg C --band NIR --model --tile-stride 8 [--tile-window hat|box]                    # ... its overlapped, blended tiles
     python evaluate.py --cfg C --band NIR --model --frame-windows 3 [--frame-window-step s --frame-window-weights clear|uniform]   # ... its frame-window ensemble
     python evaluate.py --cfg C --band NIR --model --weights ema                                              # ... its EMA weights (train.py --ema-momentum)
+    python evaluate.py --cfg C --band NIR --model --fuse                                                     # ... with the band's FuseNet applied to the stitched image
     python evaluate.py --cfg C --band NIR --baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered]   # the bicubic-mean baseline, no checkpoint
     python evaluate.py --cfg C --band NIR --model --benchmark-baseline                                       # the checkpoint against that baseline
     python evaluate.py --cfg C --band NIR --model --norm computed                                            # N_i from the esa / raw baseline (a stand-in for norm.csv)
@@ -40,7 +41,7 @@ import sys
 import numpy as np
 
 from probav_amd import scoring
-from probav_amd.inference import InferenceOptions, add_inference_args, inference_options, load_inputs, load_model, numbered, predict
+from probav_amd.inference import InferenceOptions, add_inference_args, fuse_images, inference_options, load_inputs, load_model, numbered, predict
 
 logging.basicConfig(format="%(asctime)s - %(message)s", level=logging.INFO, stream=sys.stderr)
 logger = logging.getLogger("probav_amd")
@@ -109,6 +110,9 @@ def model_images(config, cfg_path, band, options=InferenceOptions()):
     y_preds = predict(model, inputs, options, config)
     del model, trainer
     torch.cuda.empty_cache()
+    if options.fuse:
+        with contextlib.redirect_stdout(sys.stderr):
+            y_preds = fuse_images(y_preds, config, cfg_path, band, "evaluate.py --model --fuse")
     return {i: img[:, :, 0].astype(np.uint16) for i, img in numbered(y_preds, "TRAIN", band)}      # test.py's cast, a pixel clipped to 65536 included
 
 

@@ -593,6 +593,27 @@ int probav_crop_batch(const float* lr, const uint8_t* lr_mask, const float* hr, 
                       int P, int pad, int win, int scale, int k, int L, const int32_t* positions, int64_t n_positions, const int32_t* recipe,
                       int64_t batch, float* lr_b, float* hr_b, uint8_t* mask_b, int32_t* sel, void* stream);
 
+/* ---- FuseNet (proba-v_amd/fusenet_numpy.py), additions of ABI 7 --------------------------------------------------------------------------- */
+/* The reference's stitching network (models/modelsTF.py:391-474, FuseNetv3; INTEGRATION.md, 'FuseNet').  x [batch][H][W] fp32 (raw DN);
+ * flat = conv2d/kernel [48][48][1][64] | conv2d/bias [64] | instance_normalization/gamma [64] | beta [64], flat_count = 147648.
+ *     y[b][r][s][c] = sum_{i,j < 48} x[b][r+i-23][s+j-23] kernel[i][j][0][c]      zero outside the image (TF 'SAME': 23 before, 24 after).  The bias
+ *                     is NOT added: it cancels in y - mu below, so no kernel reads it and its gradient is exact zeros
+ *     stats[b][c]   = (mu, 1 / sqrt(var + 1e-3)): mean and biased variance of y[b][.][.][c] over the H W pixels
+ *     m[b][r][s]    = (1/64) sum_c l,  l = a if a >= 0 else 0.3 a,  a = gamma[c] (y - mu) / sqrt(var + 1e-3) + beta[c]
+ *     out           = x + m (residual != 0), or m
+ * y [batch][H][W][64] and stats [batch][64][2] are outputs of the forward and inputs of the backward.  Backward: g = d loss / d out
+ * [batch][H][W] -> dflat [147648] = d loss / d flat (bias part: zeros).  No d loss / d x.  Arithmetic: the fp32-input MFMA (an fp32 fma
+ * chain); every cross-thread reduction is fp64 in a fixed order, no floating-point atomics, so the bits depend on the arguments only and a
+ * sample's y, stats and m do not depend on its batch.  workspace: probav_fusenet_workspace_bytes(batch, H, W, backward) bytes (0 for an
+ * unsupported shape), written and read inside one call.  PROBAV_EINVAL, nothing launched: a null pointer, batch, H or W < 1, batch > 65535,
+ * H or W > 32768, batch H W 64 >= 2^31, flat_count != 147648, a workspace smaller than the query's answer, or flat / y / stats / workspace not
+ * 16-byte aligned.  Kernels: csrc/kernels_fusenet.hip. */
+size_t probav_fusenet_workspace_bytes(int batch, int H, int W, int backward);
+int probav_fusenet_forward(const float* x, const float* flat, int64_t flat_count, int batch, int H, int W, int residual, float* out, float* y,
+                           float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int probav_fusenet_backward(const float* g, const float* x, const float* y, const float* stats, const float* flat, int64_t flat_count, int batch,
+                            int H, int W, float* dflat, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

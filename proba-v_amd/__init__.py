@@ -12,7 +12,7 @@ from .parseConfig import parseConfig                    # noqa: F401
 def __getattr__(name):
     # heavy modules (torch, the HIP library) are imported on first use
     import importlib
-    lazy = {"WDSRConv3D": "modelsTF", "Losses": "loss", "ModelTrainer": "trainClass",
+    lazy = {"WDSRConv3D": "modelsTF", "FuseNetConv2D": "modelsTF", "Losses": "loss", "ModelTrainer": "trainClass",
             "Enhancer": "testClass"}
     if name in lazy:
         return getattr(importlib.import_module("." + lazy[name], __name__), name)

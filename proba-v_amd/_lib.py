@@ -130,6 +130,11 @@ SIGNATURES = {
     "probav_window_counts": (c_int, [c_void_p, c_int64] + [c_int] * 5 + [c_void_p, c_void_p]),
     "probav_crop_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 8 + [c_void_p, c_int64, c_void_p, c_int64,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # FuseNet (csrc/kernels_fusenet.hip): added under ABI 7
+    "probav_fusenet_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "probav_fusenet_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "probav_fusenet_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                        c_void_p]),
 }
 
 _lib = None

@@ -15,15 +15,17 @@ FIRST_ID = {("TEST", "NIR"): 1306, ("TEST", "RED"): 1160, ("TRAIN", "NIR"): 594,
 
 @dataclass(frozen=True)
 class InferenceOptions:
-    """How the network predicts an image: an EnsembleSpec, a TileSpec, a FrameWindowSpec (None: not asked for) and "raw" or "ema" weights."""
+    """How the network predicts an image: an EnsembleSpec, a TileSpec, a FrameWindowSpec (None: not asked for), "raw" or "ema" weights, and
+    whether the band's FuseNet is applied to the stitched image (True; None: not asked for)."""
     ensemble: object = None
     tiles: object = None
     windows: object = None
     weights: str = "raw"
+    fuse: object = None
 
 
 def add_inference_args(p, where=""):
-    """The nine flags of the network's inference options; `where` goes before the help of the four that switch an option on."""
+    """The ten flags of the network's inference options; `where` goes before the help of the five that switch an option on."""
     p.add_argument("--ensemble", type=str, default="none", choices=("none", "d8"), help=where + "test-time self-ensemble: d8 = the mean over the 4 quarter "
                    "turns x 2 flips of every patch (8 forward passes per patch); none = the plain prediction")
     p.add_argument("--ensemble-permute", type=int, default=0, help="with --ensemble d8: P further frame orders, crossed with the 8 geometric variants "
@@ -40,16 +42,18 @@ def add_inference_args(p, where=""):
                    "pixels of its frames (clear, default) or equally (uniform)")
     p.add_argument("--weights", type=str, default="raw", choices=("raw", "ema"), help=where + "which weights of the checkpoint to predict with: raw (default) or "
                    "the moving average a run with train.py --ema-momentum saved; ema on a checkpoint without one is an error")
+    p.add_argument("--fuse", action="store_true", help=where + "apply the band's latest FuseNet checkpoint (train.py --modelType fusionNet) to the "
+                   "stitched, rounded image on the device, then clip to 0..65535 and round half to even")
 
 
 def inference_options(p, opt, applies=True, needs=""):
-    """The parser errors of the nine flags (`p`: the ArgumentParser, `opt`: its result, with .cfg) -> InferenceOptions, also left in
+    """The parser errors of the ten flags (`p`: the ArgumentParser, `opt`: its result, with .cfg) -> InferenceOptions, also left in
     opt.inference.  --tile-window, --frame-window-step and --frame-window-weights are resolved to their defaults in `opt`; opt.windows is the
     FrameWindowSpec or None.  applies=False: the script is not predicting with the network, and a flag that switches an option on is an error
     naming `needs`, the flag that would make it predict."""
     if not applies:
         for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.weights != "raw", "--weights"), (opt.tile_stride != 0, "--tile-stride"),
-                            (opt.frame_windows != 0, "--frame-windows")):
+                            (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse")):
             if given:
                 p.error("%s applies to %s (a folder of PNGs is scored as it is)" % (flag, needs))
     if opt.ensemble == "none" and opt.ensemble_permute:
@@ -86,7 +90,7 @@ def inference_options(p, opt, applies=True, needs=""):
         except ValueError as e:
             p.error("--frame-windows: %s" % e)
     opt.windows = windows
-    opt.inference = InferenceOptions(ensemble, tiles, windows, opt.weights)
+    opt.inference = InferenceOptions(ensemble, tiles, windows, opt.weights, True if opt.fuse else None)
     return opt.inference
 
 
@@ -132,6 +136,38 @@ def predict(model, inputs, options, config, micro_batch=2048, launch_batch=None)
     if options.ensemble is not None:
         return testClass.evaluate_device(model, inputs, ensemble=options.ensemble, final="round")
     return testClass.evaluate_device(model, inputs, micro_batch=micro_batch, launch_batch=launch_batch)
+
+
+def fuse_ckpt_dir(config, cfg_path, band):
+    """Where train.py --modelType fusionNet keeps a band's checkpoints: <model_out>/fuseNetCkpt_<cfg>/<band>."""
+    return os.path.join(config["model_out"], "fuseNetCkpt_%s" % os.path.basename(cfg_path).split(".")[0], band)
+
+
+def load_fusenet(config, cfg_path, band, who):
+    """The band's FuseNet on the device with its latest checkpoint restored -> model.  No checkpoint: SystemExit naming the directory looked in."""
+    import glob
+    from .modelsTF import FuseNetConv2D
+    from .trainClass import ModelTrainer
+    ckpt = fuse_ckpt_dir(config, cfg_path, band)
+    if not (os.path.exists(os.path.join(ckpt, "checkpoint.pt-index")) or glob.glob(os.path.join(ckpt, "ckpt-*.pt"))):      # (asked before ModelTrainer makes the directory)
+        raise SystemExit("%s: no FuseNet checkpoint under %s (train one with train.py --modelType fusionNet)" % (who, ckpt))
+    model = FuseNetConv2D(name="fusionNet", band=band).build().to("cuda")
+    ModelTrainer(model, None, None, None, ckpt, os.path.join(config["model_out"], "fuseNetLogs_%s" % os.path.basename(cfg_path).split(".")[0], band))
+    return model
+
+
+def fuse_images(images, config, cfg_path, band, who, batch=16):
+    """--fuse: the band's FuseNet applied to the stitched, rounded images (a list of [G, G, 1] arrays, `predict`'s form) on the device, the
+    result clipped to 0..65535 and rounded half to even -> the same form."""
+    import torch
+    model = load_fusenet(config, cfg_path, band, who)
+    out = []
+    with torch.no_grad():
+        for k in range(0, len(images), batch):
+            x = torch.as_tensor(np.stack([np.asarray(im)[:, :, 0] for im in images[k:k + batch]]).astype(np.float32)).to("cuda")
+            y = torch.ops.probav.clip_round(model(x), 0.0, 65535.0)
+            out += [a[:, :, None] for a in y.cpu().double().numpy()]
+    return out
 
 
 def numbered(images, split, band, directory="."):

@@ -341,3 +341,103 @@ class WDSRConv3D:
 
     def denormalize(self, x):
         return x * self.std + self.mean
+
+
+class FuseNetModel(torch.nn.Module):
+    """What ``FuseNetConv2D.build`` returns: the reference's stitching network (models/modelsTF.py:391-474, FuseNetv3) as ONE torch custom
+    op, `torch.ops.probav.fusenet_forward`, over a single flat parameter -- the protocol ModelTrainer and the Hip* optimizers use (`flat`,
+    `parameters()`, `variable_names`, `trainable_variables`, `load_variables`, `state_dict`).  ``model(x, training=False)`` maps float32
+    [B, H, W] (or [B, H, W, 1]) in raw DN to the same shape: x + branch.  The definition: probav_amd/fusenet_numpy.py."""
+
+    def __init__(self, name, band, seed=None):
+        super().__init__()
+        from . import fusenet_numpy as fn
+        self.name, self.band = name, band
+        self._names, self._shapes = list(fn.NAMES), [tuple(s) for s in fn.SHAPES]
+        # Keras's initial values: kernel glorot_uniform (fan_in 2304, fan_out 147456), bias zeros, gamma and beta random_uniform(-0.05, 0.05)
+        gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
+        limit = (6.0 / (fn.KSIZE * fn.KSIZE * (1 + fn.FILTERS))) ** 0.5
+        flat = torch.zeros(fn.N_FLAT, dtype=torch.float32)
+        flat[:fn.N_KERNEL] = (torch.rand(fn.N_KERNEL, generator=gen) * 2.0 - 1.0) * limit
+        flat[fn.N_KERNEL + fn.FILTERS:] = (torch.rand(2 * fn.FILTERS, generator=gen) * 2.0 - 1.0) * 0.05
+        self.flat = torch.nn.Parameter(flat)
+
+    def _slices(self):
+        off = 0
+        for name, shp in zip(self._names, self._shapes):
+            n = 1
+            for d in shp:
+                n *= d
+            yield name, shp, off, off + n
+            off += n
+
+    @property
+    def variable_names(self):
+        """conv2d/kernel, conv2d/bias, instance_normalization/gamma, instance_normalization/beta: the reference model's variables, in its order."""
+        return list(self._names)
+
+    @property
+    def trainable_variables(self):
+        return [self.flat[lo:hi].view(shp) for _, shp, lo, hi in self._slices()]
+
+    def variable_gradients(self):
+        g = self.flat.grad
+        return None if g is None else [g[lo:hi].view(shp) for _, shp, lo, hi in self._slices()]
+
+    def _require_finite(self, flat, what):
+        """A non-finite parameter is refused where it enters ('Non-finite values')."""
+        finite = torch.isfinite(flat.detach().reshape(-1))
+        if bool(finite.all()):
+            return
+        i = int((~finite).nonzero()[0])
+        for name, _, lo, hi in self._slices():
+            if lo <= i < hi:
+                raise ValueError("%s: non-finite parameter in %s (%r at element %d of the flat buffer; first of %d): refused, see INTEGRATION.md "
+                                 "'Non-finite values'" % (what, name, float(flat.detach().reshape(-1)[i]), i, int((~finite).sum())))
+
+    def load_variables(self, params):
+        """params: {"conv2d": {"kernel", "bias"}, "instance_normalization": {"gamma", "beta"}} numpy / torch -> the flat buffer (what
+        ModelTrainer.save writes).  A NaN or inf is a ValueError naming the variable; the model's parameters are then unchanged."""
+        staged = torch.empty(self.flat.numel(), dtype=torch.float32)
+        for name, _, lo, hi in self._slices():
+            layer, key = name.split("/")
+            t = torch.as_tensor(params[layer][key]).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+            if t.numel() != hi - lo:
+                raise ValueError("%s: expected %d values, got %d" % (name, hi - lo, t.numel()))
+            staged[lo:hi] = t
+        self._require_finite(staged, "load_variables")
+        with torch.no_grad():
+            self.flat.copy_(staged)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        flat = state_dict.get("flat") if hasattr(state_dict, "get") else None
+        if torch.is_tensor(flat) and flat.numel() == self.flat.numel():
+            self._require_finite(flat, "load_state_dict")
+        return super().load_state_dict(state_dict, *args, **kwargs)
+
+    def forward(self, x, training=False, residual=True):
+        """residual=False returns the branch m alone (the quantity every accuracy check is made on: m is ~1e-5 of x)."""
+        x = _lib.require_device(x, "model input")
+        shape = x.shape
+        if x.dim() == 4 and shape[-1] == 1:
+            x = x.reshape(shape[:3])
+        if x.dim() != 3:
+            raise ValueError("model input must be [B, H, W] or [B, H, W, 1], got %s" % (tuple(shape),))
+        if x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(ops.FUSENET_NO_DX)
+        if self.flat.device != x.device:
+            raise RuntimeError("model parameters are on %s but the input is on %s" % (self.flat.device, x.device))
+        flat = self.flat if (training and torch.is_grad_enabled()) else self.flat.detach()
+        out, y, stats = torch.ops.probav.fusenet_forward(x.contiguous().float(), flat, bool(residual))
+        return out.reshape(shape)
+
+
+class FuseNetConv2D:
+    """models/modelsTF.py:391-400: ``FuseNetConv2D(name, band).build()``."""
+
+    def __init__(self, name, band):
+        self.name = name
+        self.band = band
+
+    def build(self, seed=None):
+        return FuseNetModel(self.name, self.band, seed=seed)

@@ -53,6 +53,10 @@ dispatcher, `torch.compile` / AOT-autograd and `torch.library.opcheck` (tests/te
                                                                             a training batch cut at arbitrary origins out of resident scenes: the
                                                                             window's frames chosen as the builder chooses them, then frame order,
                                                                             flip, quarter turns   utils/dataGenerator.py:99-174, 326-551 (crops.py)
+  probav::fusenet_forward(x, flat, residual) -> (out [B, H, W], y [B, H, W, 64], stats [B, 64, 2])
+                                                                            FuseNetConv2D: 48 x 48 convolution, instance normalisation, LeakyReLU,
+                                                                            channel mean, + x   models/modelsTF.py:391-474 (fusenet_numpy.py)
+  probav::fusenet_backward(g, x, y, stats, flat) -> dflat                   its parameter gradients (the bias part exact zeros; no input gradient)
 
 `engine` is the probav_engine* of include/probav_hip.h as an integer (the ops are stateless; the handle owns only the layer table),
 `ws` the workspace of one forward call: an OUTPUT of wdsr_forward (it carries the activations to the reverse pass, like the residuals of
@@ -1340,3 +1344,89 @@ def _wn_bwd(ctx, dweff, dweffT, dinv):
 
 
 wn_weight_fwd.register_autograd(_wn_bwd, setup_context=_wn_setup)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# FuseNet (csrc/kernels_fusenet.hip; the statement: fusenet_numpy.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+FUSENET_PARAMS = 48 * 48 * 64 + 3 * 64
+FUSENET_NO_DX = ("FuseNet computes no gradient for its input: the stitched image is data (d loss / d x is out of scope); "
+                 "pass an input that does not require grad")
+
+
+def _fusenet_args(x, flat):
+    if x.dim() != 3 or x.dtype != torch.float32 or flat.dtype != torch.float32:
+        raise ValueError("fusenet: x must be float32 [B, H, W] and flat float32, got %s %s and %s" % (x.dtype, tuple(x.shape), flat.dtype))
+    if flat.numel() != FUSENET_PARAMS:
+        raise ValueError("fusenet: flat must hold %d values (kernel, bias, gamma, beta), got %d" % (FUSENET_PARAMS, flat.numel()))
+    return int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+
+
+def _fusenet_ws(B, H, W, backward, device):
+    n = _lib.lib().probav_fusenet_workspace_bytes(B, H, W, backward)
+    if n == 0:
+        raise ValueError("fusenet: unsupported shape B=%d H=%d W=%d (all >= 1, B <= 65535, H, W <= 32768, 64 B H W < 2^31)" % (B, H, W))
+    return torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
+
+
+@torch.library.custom_op("probav::fusenet_forward", mutates_args=(), device_types="cuda")
+def fusenet_forward(x: Tensor, flat: Tensor, residual: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """-> (out [B, H, W] = x + m, or the branch m alone with residual=False; y [B, H, W, 64], the convolution without its bias; stats [B, 64, 2] =
+    (mu, 1 / sqrt(var + 1e-3))).  y and stats are what the reverse pass reads: outputs, like the residuals of any differentiable op."""
+    _dev(x, "fusenet input")
+    _dev(flat, "fusenet parameters")
+    B, H, W = _fusenet_args(x, flat)
+    x, flat = x.contiguous(), flat.contiguous()
+    out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    y = torch.empty((B, H, W, 64), dtype=torch.float32, device=x.device)
+    stats = torch.empty((B, 64, 2), dtype=torch.float32, device=x.device)
+    ws = _fusenet_ws(B, H, W, 0, x.device)
+    _lib.check(_lib.lib().probav_fusenet_forward(_lib.ptr(x), _lib.ptr(flat), flat.numel(), B, H, W, 1 if residual else 0, _lib.ptr(out), _lib.ptr(y),
+                                                 _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 8, _lib.current_stream()), "probav_fusenet_forward")
+    return out, y, stats
+
+
+@fusenet_forward.register_fake
+def _(x, flat, residual):
+    B, H, W = x.shape
+    return x.new_empty((B, H, W), dtype=torch.float32), x.new_empty((B, H, W, 64), dtype=torch.float32), x.new_empty((B, 64, 2), dtype=torch.float32)
+
+
+@torch.library.custom_op("probav::fusenet_backward", mutates_args=(), device_types="cuda")
+def fusenet_backward(g: Tensor, x: Tensor, y: Tensor, stats: Tensor, flat: Tensor) -> Tensor:
+    """d loss / d flat from g = d loss / d out; x, y, stats, flat as the matching forward took and returned them, only READ here (functional:
+    the scratch is this call's own).  The bias slots are exact zeros."""
+    _dev(g, "fusenet output gradient")
+    B, H, W = _fusenet_args(x, flat)
+    if tuple(g.shape) != (B, H, W) or tuple(y.shape) != (B, H, W, 64) or tuple(stats.shape) != (B, 64, 2):
+        raise ValueError("fusenet_backward: g %s, y %s, stats %s do not belong to x %s" % (tuple(g.shape), tuple(y.shape), tuple(stats.shape), tuple(x.shape)))
+    g, x, y, stats, flat = (t.contiguous() for t in (g.float(), x, y, stats, flat))
+    dflat = torch.empty(FUSENET_PARAMS, dtype=torch.float32, device=x.device)
+    ws = _fusenet_ws(B, H, W, 1, x.device)
+    _lib.check(_lib.lib().probav_fusenet_backward(_lib.ptr(g), _lib.ptr(x), _lib.ptr(y), _lib.ptr(stats), _lib.ptr(flat), flat.numel(), B, H, W, _lib.ptr(dflat),
+                                                  _lib.ptr(ws), ws.numel() * 8, _lib.current_stream()), "probav_fusenet_backward")
+    return dflat.view(flat.shape)
+
+
+@fusenet_backward.register_fake
+def _(g, x, y, stats, flat):
+    return torch.empty_like(flat)
+
+
+def _fusenet_setup(ctx, inputs, output):
+    x, flat, residual = inputs
+    ctx.save_for_backward(x, flat, output[1], output[2])
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.set_materialize_grads(False)
+
+
+def _fusenet_bwd(ctx, g, dy, dstats):
+    if ctx.needs_input_grad[0]:
+        raise RuntimeError(FUSENET_NO_DX)
+    if g is None:
+        return None, None, None
+    x, flat, y, stats = ctx.saved_tensors
+    return None, torch.ops.probav.fusenet_backward(g.contiguous().float(), x, y, stats, flat), None
+
+
+fusenet_forward.register_autograd(_fusenet_bwd, setup_context=_fusenet_setup)

@@ -25,10 +25,14 @@ passes; it needs num_low_res_imgs_pre >= (W - 1) s + num_low_res_imgs; combines 
 --weights ema predicts with the moving average of the weights that `train.py --ema-momentum M` keeps and saves beside the raw weights (the
 checkpoint's "ema" entry); --weights raw (default) is the path above.  A checkpoint without an "ema" entry is refused, not silently read raw.
 
+--fuse applies the band's latest FuseNet checkpoint (train.py --modelType fusionNet; <model_out>/fuseNetCkpt_<cfg>/<band>) to the stitched, rounded
+image of whichever path above produced it, on the device, and writes the result clipped to 0..65535 and rounded half to even (INTEGRATION.md,
+'FuseNet').  No checkpoint there is an error naming the directory.  Without the flag every path above is what it was, byte for byte.
+
 --method baseline [--baseline-mode esa|clear] [--baseline-frames raw|registered] writes the competition's bicubic-mean baseline instead
 (probav_amd/baseline.py): every LR frame upscaled by the Keys cubic and the frames of maximum clearance averaged, in exact
 integer arithmetic on the device.  It reads <preprocessing_out>/arrayDir (raw: every set, unregistered) or trimmedArrayDir (registered) and
-needs no checkpoint; it does not combine with --ensemble, --tile-stride, --frame-windows or --weights ema.  --method network (default) is the path above.
+needs no checkpoint; it does not combine with --ensemble, --tile-stride, --frame-windows, --weights ema or --fuse.  --method network (default) is the path above.
 """
 import argparse
 import logging
@@ -36,7 +40,7 @@ import os
 
 import numpy as np
 
-from probav_amd.inference import add_inference_args, inference_options, load_inputs, load_model, numbered, predict
+from probav_amd.inference import add_inference_args, fuse_images, inference_options, load_inputs, load_model, numbered, predict
 from probav_amd.parseConfig import parseConfig
 from probav_amd.pngio import imsave_uint16
 
@@ -61,11 +65,12 @@ def parser(argv=None):
     opt = p.parse_args(argv)
     if opt.method == "baseline":
         for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.tile_stride != 0, "--tile-stride"), (opt.weights == "ema", "--weights ema"),
-                            (opt.frame_windows != 0, "--frame-windows")):
+                            (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse")):
             if given:
                 p.error("%s predicts with the network: it cannot be combined with --method baseline" % flag)
     opt.baseline = cli_spec(p, opt, opt.method == "baseline", "--method baseline")
-    for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.tile_stride != 0, "--tile-stride"), (opt.frame_windows != 0, "--frame-windows")):
+    for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.tile_stride != 0, "--tile-stride"), (opt.frame_windows != 0, "--frame-windows"),
+                        (opt.fuse, "--fuse")):
         if given and opt.reference_loop:
             p.error("--reference-loop is the reference's plain loop: it cannot be combined with %s" % flag)
     inference_options(p, opt)
@@ -108,6 +113,10 @@ def main(config, opt):
     log_options(options)
     y_preds = (predict(model, inputs, options, config, micro_batch=16, launch_batch=16) if opt.reference_loop
                else predict(model, inputs, options, config, micro_batch=opt.micro_batch))
+    if options.fuse:
+        logger.info("[ INFO ] Applying the band's FuseNet to the stitched images...")
+        del model
+        y_preds = fuse_images(y_preds, config, opt.cfg, opt.band, "test.py --fuse")
     outDir = (config["test_out"] if opt.totest == "TEST" else config["train_out"]) + "_" + os.path.basename(opt.cfg).split(".")[0]
     os.makedirs(outDir, exist_ok=True)
     logger.info("[ SAVE ] Saving predicted images to %s..." % outDir)

@@ -6,6 +6,13 @@ Loads the augmented patch pickles the reference's preprocessing writes
 WDSR-B Conv3D network on the MI355X engine, and runs ModelTrainer.fitTrainData.  Under
 `python -m torch.distributed.run --nproc-per-node N train.py ...` every rank trains on its shard of the data and the
 flat gradient buffer is all-reduced once per step (RCCL over xGMI).
+
+--modelType fusionNet --fusion-input DIR trains the reference's stitching network instead (FuseNetConv2D, models/modelsTF.py:391-474, train.py:116-188;
+INTEGRATION.md, 'FuseNet'): DIR holds the imgsetNNNN.png that `test.py --totest TRAIN` writes, the target and mask are
+trimmedArrayDir/TRAINimgHR_<band>.npy matched by id, the split is train_test_split(test_size=split, random_state=17), the loss is the
+shift-compensated L1 on 384 x 384, the metric the cPSNR, the optimizer the cfg's; checkpoints go to <model_out>/fuseNetCkpt_<cfg>/<band>.  Unlike
+the reference: one band per run, paths from the cfg and the flags instead of the author's home directory, and all images of the folder instead
+of the first 1 160.
 """
 import argparse
 import logging
@@ -29,6 +36,8 @@ def parser(argv=None):
     p.add_argument("--cfg", default="cfg/yourcfg.cfg", type=str)
     p.add_argument("--band", type=str, default="NIR")
     p.add_argument("--modelType", type=str, default="patchNet")
+    p.add_argument("--fusion-input", dest="fusion_input", type=str, default=None,
+                   help="with --modelType fusionNet: the folder of imgsetNNNN.png that `test.py --totest TRAIN` wrote (the stitched predictions FuseNet corrects)")
     p.add_argument("--online-aug", dest="online_aug", action="store_true",
                    help="train from the un-augmented patches of `utils/dataGenerator.py --online-aug`: every batch is augmented on the GPU")
     p.add_argument("--random-crops", dest="random_crops", action="store_true",
@@ -48,6 +57,10 @@ def parser(argv=None):
     p.add_argument("--validate-on", dest="validate_on", type=str, default="raw", choices=("raw", "ema"),
                    help="the weights the validation runs on (ema needs --ema-momentum); default raw")
     opt = p.parse_args(argv)
+    if opt.fusion_input is not None and opt.modelType != "fusionNet":
+        p.error("--fusion-input needs --modelType fusionNet")
+    if opt.modelType == "fusionNet" and opt.fusion_input is None:
+        p.error("--modelType fusionNet needs --fusion-input DIR (the PNGs of test.py --totest TRAIN)")
     if opt.random_crops and opt.online_aug:
         p.error("--random-crops and --online-aug are mutually exclusive")
     if not opt.random_crops and (opt.crop_positions != "all" or opt.crop_seed != 0 or opt.crops_per_epoch is not None):
@@ -140,10 +153,65 @@ def patchNet(config, opt):
     logger.info("[ SUCCESS ] Model logs can be found in %s." % logDir)
 
 
+def fusion_data(config, band, directory):
+    """(X [n, 384, 384, 1] float32, HR [n, 384, 384, 1] float32, clear [n, 384, 384, 1] bool, ids): every imgsetNNNN.png of `directory` with the
+    HR image and mask of its id in trimmedArrayDir/TRAINimgHR_<band>.npy (ids as probav_amd.inference.numbered counts them).  A PNG whose id has
+    no partner there is an error that names it."""
+    import glob
+    import re
+    from probav_amd.inference import numbered
+    from probav_amd.pngio import imread_uint16
+    hr_path = os.path.join(config["preprocessing_out"], "trimmedArrayDir", "TRAINimgHR_%s.npy" % band)
+    hr = np.load(hr_path, allow_pickle=True)
+    index = {i: k for k, (i, _) in enumerate(numbered(range(len(hr)), "TRAIN", band))}
+    files = sorted(f for f in glob.glob(os.path.join(directory, "imgset*.png")) if re.fullmatch(r"imgset\d{4}\.png", os.path.basename(f)))
+    if not files:
+        raise SystemExit("--fusion-input: no imgsetNNNN.png in %s" % directory)
+    ids = [int(os.path.basename(f)[6:10]) for f in files]
+    for i, f in zip(ids, files):
+        if i not in index:
+            raise SystemExit("--fusion-input: %s (id %d) has no partner in %s (the %s TRAIN ids there run over %d sets)" % (f, i, hr_path, band, len(hr)))
+    rows = [index[i] for i in ids]
+    X = np.stack([imread_uint16(f) for f in files]).astype(np.float32)[..., None]
+    target = hr[rows][:, 0, 0]
+    return X, np.array(target, dtype=np.float32)[..., None], ~np.ma.getmaskarray(target)[..., None], ids
+
+
+def fusionNet(config, opt):
+    """train.py:116-188 of the reference, on the device."""
+    from probav_amd.inference import fuse_ckpt_dir
+    from probav_amd.modelsTF import FuseNetConv2D
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    logger.info("[ INFO ] Loading data...")
+    X, y, clear, ids = fusion_data(config, opt.band, opt.fusion_input)
+    n = len(X)
+    perm = np.random.RandomState(17).permutation(n)                 # train_test_split(test_size=split, random_state=17), as prep.splitPatches restates it
+    n_test = int(np.ceil(config["split"] * n))
+    test, train = perm[:n_test], perm[n_test:]
+    if len(train) < 1 or n_test < 1:
+        raise SystemExit("--fusion-input: %d images split %g leave an empty training or validation part" % (n, config["split"]))
+    logger.info("[ INFO ] %d images (%d training, %d validation). Building model..." % (n, len(train), n_test))
+    model = FuseNetConv2D(name="fusionNet", band=opt.band).build(seed=0).to(torch.device("cuda"))
+    optimizer = make_optimizer(config["optimizer"], model, config["learning_rate"])
+    loss = Losses(targetShape=(X.shape[1], X.shape[2], 1))
+    ckptDir = fuse_ckpt_dir(config, opt.cfg, opt.band)
+    logDir = os.path.join(config["model_out"], "fuseNetLogs_%s" % os.path.basename(opt.cfg).split(".")[0], opt.band)
+    trainer = ModelTrainer(model=model, loss=loss.shiftCompensatedL1Loss, metric=loss.shiftCompensatedcPSNR, optimizer=optimizer, ckptDir=ckptDir, logDir=logDir,
+                           multiGPU=False)
+    batch = min(config["batch_size"], len(train))
+    trainer.fitTrainData(X[train], [y[train], clear[train]], batch, config["epochs"], [X[test], y[test], clear[test]], saveBestOnly=False, initEpoch=0)
+    if trainer.latest_checkpoint is None:                           # fewer steps than one evaluation interval: keep what was trained
+        trainer.save()
+    logger.info("[ SUCCESS ] Model checkpoint can be found in %s." % ckptDir)
+    logger.info("[ SUCCESS ] Model logs can be found in %s." % logDir)
+
+
 if __name__ == "__main__":
     opt = parser()
     config = parseConfig(opt.cfg)
-    if opt.modelType != "patchNet":
-        raise SystemExit("--modelType %s: only the patchNet (WDSR-B Conv3D) path is implemented; the reference's fusionNet "
-                         "is a separate experimental model with hard-coded paths (train.py:116-188)" % opt.modelType)
-    patchNet(config, opt)
+    if opt.modelType == "fusionNet":
+        fusionNet(config, opt)
+    elif opt.modelType != "patchNet":
+        raise SystemExit("--modelType %s: patchNet (WDSR-B Conv3D) or fusionNet (FuseNetConv2D)" % opt.modelType)
+    else:
+        patchNet(config, opt)
