@@ -19,8 +19,9 @@
  *     stream by event and join it back into `stream` before returning: the caller sees plain
  *     stream order.  The side stream is created on the engine's first pass (make that pass outside
  *     a graph capture); PROBAV_NO_SIDE_STREAM=1 in the environment disables it.
- *   - return value: 0 = ok, PROBAV_EINVAL (-1) bad argument, PROBAV_ENOSPACE (-2) workspace too small,
- *     PROBAV_EHIP (-3) a HIP call failed; probav_last_error() gives the text (thread-local).
+ *   - return value: 0 = ok, PROBAV_EINVAL (-1) bad argument, PROBAV_ENOSPACE (-2) a workspace, scratch buffer or weight cache whose
+ *     byte-size argument is below its size query's answer (read or written, nothing is launched; the FuseNet entries alone answer
+ *     PROBAV_EINVAL), PROBAV_EHIP (-3) a HIP call failed; probav_last_error() gives the text (thread-local).
  *   - thread-safety: an engine handle and its workspace may be used by one thread at a time;
  *     distinct handles are independent (one process per GPU under data parallelism).
  *   - NaN and inf in any buffer are ordinary data.  What each entry point does with them, and the four contracts the library keeps (a
@@ -272,6 +273,8 @@ int probav_input_grad(int batch, int H, int T, int C, const float* g, const floa
 int64_t probav_weff_count(const probav_engine* e);
 int64_t probav_cout_total(const probav_engine* e);
 int probav_wn_forward(probav_engine* e, const float* params, float* weff, float* weffT, float* inv_norm, void* stream);
+/* grads[param_count]: the g and v entries of every layer are written (d loss / d g, d loss / d v); the bias entries are left as they were
+ * (a bias is no function of weff: the passes write its gradient themselves)                                                          */
 int probav_wn_backward(probav_engine* e, const float* params, const float* dweff, const float* inv_norm,
                        float* grads, void* stream);
 

@@ -869,7 +869,8 @@ int probav_forward(probav_engine* e, const float* params, const float* x, float*
 int probav_forward_wc(probav_engine* e, const float* params, const float* x, float* y, void* ws, size_t ws_bytes,
                       int B, int training, const void* wcache, size_t wcache_bytes, void* stream)
 {
-    if (!e || !wcache || wcache_bytes < make_wc_plan(e).total * sizeof(float)) { set_error("probav_forward_wc: weight cache missing / too small", hipSuccess); return PROBAV_EINVAL; }
+    if (!e || !wcache) { set_error("probav_forward_wc: null engine / weight cache", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache_bytes < make_wc_plan(e).total * sizeof(float)) { set_error("probav_forward_wc: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
     return forward_impl(e, params, x, y, ws, ws_bytes, B, training, (const float*)wcache, stream);
 }
 
@@ -1062,14 +1063,16 @@ int probav_backward_split(probav_engine* e, const float* params, const float* dy
                           void* scratch, size_t scratch_bytes, int B, const void* wcache, size_t wcache_bytes, void* stream)
 {
     if (!scratch) { set_error("probav_backward_split: null scratch", hipSuccess); return PROBAV_EINVAL; }
-    if (wcache && (!e || wcache_bytes < make_wc_plan(e).total * sizeof(float))) { set_error("probav_backward_split: weight cache too small", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache && !e) { set_error("probav_backward_split: null engine", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache && wcache_bytes < make_wc_plan(e).total * sizeof(float)) { set_error("probav_backward_split: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
     return backward_impl(e, params, dy, grads, saved, saved_bytes, scratch, scratch_bytes, B, (const float*)wcache, stream);
 }
 int probav_backward_input(probav_engine* e, const float* params, const float* dy, float* grads, const void* saved, size_t saved_bytes,
                           void* scratch, size_t scratch_bytes, int B, const void* wcache, size_t wcache_bytes, float* dx, void* stream)
 {
     if (!scratch || !dx) { set_error("probav_backward_input: null scratch / dx", hipSuccess); return PROBAV_EINVAL; }
-    if (wcache && (!e || wcache_bytes < make_wc_plan(e).total * sizeof(float))) { set_error("probav_backward_input: weight cache too small", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache && !e) { set_error("probav_backward_input: null engine", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache && wcache_bytes < make_wc_plan(e).total * sizeof(float)) { set_error("probav_backward_input: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
     return backward_impl(e, params, dy, grads, saved, saved_bytes, scratch, scratch_bytes, B, (const float*)wcache, stream, dx);
 }
 int probav_input_grad(int batch, int H, int T, int C, const float* g, const float* act0, const float* wmain, const float* d1,
@@ -1088,7 +1091,8 @@ int probav_workspace_split(const probav_engine* e, int batch, size_t* saved_byte
 int probav_backward_wc(probav_engine* e, const float* params, const float* dy, float* grads, void* ws, size_t ws_bytes, int B,
                        const void* wcache, size_t wcache_bytes, void* stream)
 {
-    if (!e || !wcache || wcache_bytes < make_wc_plan(e).total * sizeof(float)) { set_error("probav_backward_wc: weight cache missing / too small", hipSuccess); return PROBAV_EINVAL; }
+    if (!e || !wcache) { set_error("probav_backward_wc: null engine / weight cache", hipSuccess); return PROBAV_EINVAL; }
+    if (wcache_bytes < make_wc_plan(e).total * sizeof(float)) { set_error("probav_backward_wc: weight cache too small", hipSuccess); return PROBAV_ENOSPACE; }
     return backward_impl(e, params, dy, grads, ws, ws_bytes, nullptr, 0, B, (const float*)wcache, stream);
 }
 
