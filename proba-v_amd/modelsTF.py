@@ -188,6 +188,7 @@ class WDSRModel(torch.nn.Module):
         4 (default) = the same kernels with the H3 arithmetic (three products of fp16 piece pairs, operands scaled by a power
         of two per sample / per filter column).  Every family computes a sample independently of its batch mates, bit for bit."""
         _lib.check(_lib.lib().probav_engine_set_impl(self._handle(), int(impl)), "probav_engine_set_impl")
+        ops.forget_engine(self._handle().value)            # (the sizes the ops cache per handle are asked for again)
         self._impl = int(impl)
 
     @property
@@ -308,6 +309,7 @@ class WDSRModel(torch.nn.Module):
     def __del__(self):
         try:
             if self._engine is not None:
+                ops.forget_engine(self._engine.value)      # (the address may be handed to the next engine)
                 _lib.lib().probav_engine_destroy(self._engine)
         except Exception:
             pass
