@@ -349,6 +349,46 @@ int probav_debug_hidden_from_forward_kernel(int on);
 int probav_plan_conv(const int32_t geom[17], int impl, int gated, int has_skip, int op, int32_t report[8]);
 int probav_plan_pw(int64_t nvox, int64_t vox_per_sample, int D, int impl, int backward, int32_t report[8]);
 
+/* ---- the general matrix route (csrc/kernels_gemm.hip), additions made under ABI 7 ------------------------------------------------------ */
+/* Every tuned kernel above exists for the shipped channel counts (32 filters, expansion 8, 25 channels behind the decay convolution); at any other
+ * count the engine falls to the generic direct (VALU) kernels.  The general matrix route runs those launches -- convolution forward / backward-data
+ * and backward-filter, 1x1x1 and 3x3x3, any Cin and Cout -- as implicit GEMMs on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: the direct kernels'
+ * arithmetic, an exact fp32 fma chain, on the matrix cores).  It is a SWITCH on the engine, off by default, kept apart from the kernel family:
+ * probav_engine_set_impl keeps it.  With it on, at family >= 1, a launch goes to the route exactly when it would otherwise run the generic direct
+ * kernel on a geometry that kernel's own callers do not call exotic (5x5x5, mirrored depth pads, zero pads above 2, mirrored pads above 1 stay
+ * direct) -- nothing a matrix, split-operand or dedicated small kernel (upscale pair, one-channel input, fused residual path, the tuned one-channel
+ * backward-filter) serves changes hands; family 0 is the direct kernels with or without it.  The backward-filter's slab regions differ in size, so
+ * probav_workspace_bytes / probav_workspace_split change with the switch: size the buffers after setting it.  Results of a sample do not depend on
+ * its batch mates and are bitwise reproducible; they differ from the direct kernels' by fp32 rounding (another order of additions).
+ * PROBAV_GEMM_ROUTE (set, non-zero) at probav_engine_create turns it on, as PROBAV_IMPL chooses the family.                                  */
+int probav_engine_set_gemm_route(probav_engine* e, int on);
+int probav_engine_gemm_route(const probav_engine* e);      /* 1 / 0 */
+/* The single operators: arguments as probav_conv3d_forward / probav_conv3d_wgrad without `impl`.  A geometry the route does not take (see above; the
+ * backward-filter takes pads <= 1 only) is refused with PROBAV_EINVAL and nothing is written; probav_gemm_conv3d_wgrad_scratch_bytes is 0 for it.
+ * A scratch smaller than probav_gemm_conv3d_wgrad_scratch_bytes: PROBAV_ENOSPACE, nothing written.                                           */
+int probav_gemm_conv3d_forward(const int32_t geom[17], const float* x, const float* gate, const float* w,
+                               const float* bias, const float* skip, float* y, void* stream);
+size_t probav_gemm_conv3d_wgrad_scratch_bytes(const int32_t geom[17]);
+int probav_gemm_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy, const float* gate,
+                             float* dw, float* db, void* scratch, size_t scratch_bytes, void* stream);
+/* probav_plan_conv for an engine with the route ON (host only): PROBAV_PLAN_GEMM / PROBAV_PLAN_WGRAD_GEMM where that engine's launch of the
+ * geometry goes to the route, probav_plan_conv's report everywhere else (refusals of impl included).
+ * GEMM: report[1] = tiles along Cout, [2] = tiles along the output voxels, [3] = voxels per tile, [4] = output channels per tile, [5] = grid =
+ *   [1] x [2], [6] = input channels per K chunk, [7] = K chunks per filter tap.
+ * WGRAD_GEMM: report[1] = slabs (a function of the geometry alone, never of the device), [2] = voxels per slab, [3] x [4] = the Cin x Cout tile of
+ *   a workgroup, [5] = grid = slabs x taps x tiles; the scratch is [1] x 4 x (taps Cin Cout + Cout) bytes.                                     */
+#define PROBAV_PLAN_GEMM 11          /* gemm_conv_fwd_kernel */
+#define PROBAV_PLAN_WGRAD_GEMM 12    /* gemm_conv_wgrad_kernel */
+int probav_plan_conv_gemm(const int32_t geom[17], int impl, int gated, int has_skip, int op, int32_t report[8]);
+/* The launches of ONE training step of `batch` patches (forward with training != 0, then backward) by route, from the functions the passes route
+ * with (host only): counts[0] convolution launches (forward, backward-data, the recomputed hidden tensor) on the generic direct kernel, [1] on the
+ * general matrix route, [2] backward-filter launches on the generic direct kernel, [3] on the route.  Launches of the matrix, split-operand and
+ * dedicated small kernels and of the fused residual path / pointwise pair are not counted.                                                     */
+int probav_engine_route_counts(const probav_engine* e, int batch, int32_t counts[4]);
+/* The same four counts of what the engine's passes have ACTUALLY launched since the last reset, incremented where the launches are issued: after one
+ * training step they equal probav_engine_route_counts (tests/test_gpu_gemm_route.py holds the census to them).  reset != 0 clears them after the read.  */
+int probav_engine_launched_counts(probav_engine* e, int32_t counts[4], int reset);
+
 /* ---- dataset builder (utils/dataGenerator.py; proba-v_amd/prep.py), additions of ABI 7 ------------------------------------------------ */
 /* Frames are one flat [n_frames][H][W] array; a ragged list of image sets is that array plus set_offsets[n_sets+1] (int64, ascending,
  * set_offsets[0] = 0).  Masks are uint8, nonzero = set.  Kernels and the registration error bound: csrc/kernels_prep.hip.

@@ -84,6 +84,15 @@ SIGNATURES = {
     # plan report (csrc/engine.hip): added under ABI 7, host only
     "probav_plan_conv": (c_int, [POINTER(c_int32 * 17), c_int, c_int, c_int, c_int, POINTER(c_int32 * 8)]),
     "probav_plan_pw": (c_int, [c_int64, c_int64, c_int, c_int, c_int, POINTER(c_int32 * 8)]),
+    # the general matrix route (csrc/kernels_gemm.hip): added under ABI 7
+    "probav_engine_set_gemm_route": (c_int, [c_void_p, c_int]),
+    "probav_engine_gemm_route": (c_int, [c_void_p]),
+    "probav_gemm_conv3d_forward": (c_int, [POINTER(c_int32 * 17), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "probav_gemm_conv3d_wgrad_scratch_bytes": (c_size_t, [POINTER(c_int32 * 17)]),
+    "probav_gemm_conv3d_wgrad": (c_int, [POINTER(c_int32 * 17), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "probav_plan_conv_gemm": (c_int, [POINTER(c_int32 * 17), c_int, c_int, c_int, c_int, POINTER(c_int32 * 8)]),
+    "probav_engine_route_counts": (c_int, [c_void_p, c_int, POINTER(c_int32 * 4)]),
+    "probav_engine_launched_counts": (c_int, [c_void_p, POINTER(c_int32 * 4), c_int]),
     "probav_workspace_split": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "probav_backward_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
     # input gradients (csrc/kernels_input_grad.hip): added under ABI 7

@@ -14,6 +14,7 @@ using namespace probav;
 
 #include "kernels_mfma.h"
 #include "kernels_x6.h"
+#include "kernels_gemm.h"
 
 // MFMA operand fragments: offsets into the workspace's wpack region (-1 = none)
 struct ConvFrags { long f32 = -1, x6 = -1, h3 = -1, h3t = -1; };   // one direction of a 3x3x3 layer; h3t: per-tap H3 fragments of a 25-channel layer
@@ -35,12 +36,16 @@ struct Family {
     bool x6;                  // split-operand kernels
     int arith;                // their arithmetic: 0 none, 1 X6, 2 H3
     bool pw_fused;            // the fused pointwise pair (expConv + ReLU + decConv in one launch each way)
+    bool gemm;                // the general matrix route (kernels_gemm.hip) wherever a launch would otherwise fall to the generic direct kernels
 };
-static Family make_family(int impl, bool pw_mfma)
+// gemm: the engine's switch (probav_engine_set_gemm_route), kept on the engine apart from the family and folded in here, so that a change of family keeps it;
+// it needs the matrix kernels' family (impl >= 1): family 0 stays the direct kernels everywhere
+static Family make_family(int impl, bool pw_mfma, bool gemm = false)
 {
     Family f;
     f.mfma = impl >= 1; f.strip = impl >= 2; f.x6 = impl >= 3; f.arith = impl >= 4 ? 2 : (impl >= 3 ? 1 : 0);
     f.pw_fused = f.mfma && pw_mfma;
+    f.gemm = f.mfma && gemm;
     return f;
 }
 
@@ -50,6 +55,9 @@ struct probav_engine {
     int64_t nparams = 0, weff_count = 0, cout_total = 0, cin_total = 0;
     WnLayer* d_layers = nullptr;
     Family fam = {};
+    int impl = 4;                                   // what fam was made from (probav_engine_set_impl)
+    bool gemm = false;                              // probav_engine_set_gemm_route: folded into fam by make_family
+    int32_t launched[4] = {0, 0, 0, 0};             // what conv_fwd / conv_wgrad have launched, as probav_engine_route_counts counts (probav_engine_launched_counts)
     int iMain = -1, iResid1 = -1, iResid2 = -1, iResid3 = -1, iUp = -1;
     std::vector<int> iExp, iDec, iNorm, iRed;
     ReduceSide side = {};                           // side stream of the slab sums (probav_common.h), created on first use
@@ -216,7 +224,7 @@ static bool resid_path_fused(const probav_engine* e)
 
 // The kernel that serves a backward-filter launch: the one decision both make_plan (slab region sizes) and conv_wgrad (launch) read.
 // am.x / am.w: per-sample amax slots of x and of dy (the H3 kernel needs both)
-enum class WgradKernel { direct, x6, mfma };
+enum class WgradKernel { direct, x6, mfma, gemm };
 struct WgradRoute { WgradKernel k; int cls; int arith; };
 static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Amax& am)
 {
@@ -226,11 +234,13 @@ static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Amax& am
     const int cls = g.kh * g.kw * g.kt == 1 ? CLS_PW_WGRAD : (x6 ? CLS_CONV3_WGRAD_X6 : CLS_CONV3_WGRAD);
     if (x6) return {WgradKernel::x6, cls, f.arith == 2 && am.x && am.w ? 2 : 1};
     if (f.mfma && mfma_wgrad_supported(g)) return {WgradKernel::mfma, cls, 0};
+    if (f.gemm && gemm_wgrad_supported(g)) return {WgradKernel::gemm, cls, 0};      // the general matrix route: only what would be the generic direct kernel's
     return {WgradKernel::direct, cls, 0};
 }
 // slab floats the routed kernel writes
 static size_t wgrad_slab_floats(const WgradRoute& r, const ConvGeom& g)
 {
+    if (r.k == WgradKernel::gemm) return gemm_wgrad_partial_floats(g);
     return r.k == WgradKernel::x6 ? x6_wgrad_partial_floats(g) : (r.k == WgradKernel::mfma ? mfma_wgrad_partial_floats(g) : wgrad_partial_floats(g));
 }
 static size_t wgrad_need(const Family& f, const ConvGeom& g) { return wgrad_slab_floats(wgrad_route(f, g, Amax()), g); }
@@ -299,11 +309,15 @@ static Plan make_plan(const probav_engine* e, int B, int training)
             const Family& f = e->fam;
             size_t acc = 0;
             auto region = [&](size_t q) { Plan::Region r; r.off = acc; r.floats = q; acc += align_up(q); return r; };
-            size_t resid3 = wgrad_need(f, n.resid3);
+            // (the residual path's three regions: where the path runs fused nothing is launched through wgrad_route, and the regions keep the sizes they have
+            // always had, with or without the general matrix route)
+            Family fr = f;
+            if (resid_path_fused(e)) fr.gemm = false;
+            size_t resid3 = wgrad_need(fr, n.resid3);
             if (resid_path_fused(e)) resid3 = std::max(resid3, resid_path_slab_floats(B, n.resid1.Cin));     // (the fused reverse pass: one slab per patch, in the first region)
             p.slab.resid3 = region(resid3);
-            p.slab.resid2 = region(wgrad_need(f, n.resid2));
-            p.slab.resid1 = region(wgrad_need(f, n.resid1));
+            p.slab.resid2 = region(wgrad_need(fr, n.resid2));
+            p.slab.resid1 = region(wgrad_need(fr, n.resid1));
             p.slab.up = region(wgrad_need(f, n.up));
             p.slab.red.resize(nred);
             for (int k = nred - 1; k >= 0; --k) p.slab.red[k] = region(wgrad_need(f, n.red[k]));
@@ -377,7 +391,7 @@ struct AmaxSlots {
 
 // The kernel that serves a convolution launch of the engine (forward, or backward-data when bias == nullptr): with the launch's profiling class,
 // whether the kernel writes am.y itself, and for the MFMA / x6 kernels the filter fragments they read (x6: in arithmetic 1 X6 or 2 H3)
-enum class ConvKernel { direct, up, up_bwd_data, cin1, x6_strip, x6_rowtile, mfma_strip, mfma_rowtile };
+enum class ConvKernel { direct, up, up_bwd_data, cin1, x6_strip, x6_rowtile, mfma_strip, mfma_rowtile, gemm };
 struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; const float* wfrag; StripSel strip; };     // strip: the strip kernels' selection (strip_select), made here once
 // `dedicated`: the engine's policy in front of the matrix kernels (small dedicated kernels, exotic geometries on the direct one); the single-operator entry point,
 // whose tests hold the matrix kernels to the oracle on those geometries too, routes without it
@@ -408,6 +422,8 @@ static ConvRoute conv_route(const Family& f, const ConvGeom& g, const float* gat
     const StripSel s32 = (f.strip && wf.f32 && !split) ? strip_select(g, gate, 0) : StripSel();      // (split: no strip kernel took g above, so the fp32 one does not either)
     if (s32.k != StripKernel::none) return {ConvKernel::mfma_strip, cls, true, 0, wf.f32, s32};
     if (f.mfma && wf.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, wf.f32, {}};
+    // the general matrix route: what no matrix, split-operand or dedicated kernel took above (an exotic geometry returned before).  It does not report amax
+    if (f.gemm && dedicated && gemm_conv_supported(g)) return {ConvKernel::gemm, cls, false, 0, nullptr, {}};
     return {ConvKernel::direct, cls, false, 0, nullptr, {}};
 }
 // the routed launch (w: the filter as the direct kernels read it)
@@ -421,6 +437,7 @@ static int conv_launch(const ConvRoute& r, const ConvGeom& g, const float* x, co
     case ConvKernel::x6_strip: case ConvKernel::mfma_strip: return conv_strip_forward(r.strip, x, gate, r.wfrag, bias, skip, y, am, s);
     case ConvKernel::x6_rowtile: return x6_conv_rowtile_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s);
     case ConvKernel::mfma_rowtile: return mfma_conv_forward(g, x, gate, r.wfrag, bias, skip, y, am, s);
+    case ConvKernel::gemm: return gemm_conv_forward(g, x, gate, w, bias, skip, y, s);
     default: return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
     }
 }
@@ -429,6 +446,7 @@ static int conv_fwd(const probav_engine* e, const ConvGeom& g, const float* x, c
                     const Frags& wf, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s)
 {
     const ConvRoute r = conv_route(e->fam, g, gate, bias, skip, wf, am);
+    if (r.k == ConvKernel::direct || r.k == ConvKernel::gemm) ++const_cast<probav_engine*>(e)->launched[r.k == ConvKernel::gemm ? 1 : 0];
     int rc;
     { ProfScope ps(e, r.cls, geom_macs(g), s); rc = conv_launch(r, g, x, gate, w, bias, skip, y, am, s); }
     if (rc == PROBAV_OK && am.y && !r.reports) rc = amax_tensor(y, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, am.y, s);
@@ -454,10 +472,13 @@ static int conv_wgrad(const probav_engine* e, const ConvGeom& g, const float* x,
 {
     const WgradRoute r = wgrad_route(e->fam, g, am);
     CK(slab_fits(part, wgrad_slab_floats(r, g)));
+    if (r.k == WgradKernel::gemm) ++const_cast<probav_engine*>(e)->launched[3];
+    else if (r.k == WgradKernel::direct && !(e->fam.mfma && conv3d_direct_wgrad_is_tuned(g))) ++const_cast<probav_engine*>(e)->launched[2];
     ProfScope ps(e, r.cls, geom_macs(g), s);
     switch (r.k) {
     case WgradKernel::x6: return x6_conv_wgrad(g, x, dy, gate, dw, db, part.p, r.arith, am, s);
     case WgradKernel::mfma: return mfma_conv_wgrad(g, x, dy, gate, dw, db, part.p, s);
+    case WgradKernel::gemm: return gemm_conv_wgrad(g, x, dy, gate, dw, db, part.p, s);
     default: return conv3d_direct_wgrad(g, x, dy, gate, dw, db, part.p, s);
     }
 }
@@ -654,7 +675,10 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
     }
     // (the layer and packing tables go to the device with the first call that launches with them: device_tables)
     const char* env = getenv("PROBAV_IMPL");
-    e->fam = make_family(env ? atoi(env) : 4, e->pw_mfma);
+    const char* genv = getenv("PROBAV_GEMM_ROUTE");                // set and non-zero: the general matrix route is on from the start
+    e->impl = env ? atoi(env) : 4;
+    e->gemm = genv && atoi(genv) != 0;
+    e->fam = make_family(e->impl, e->pw_mfma, e->gemm);
     *out = e;
     return PROBAV_OK;
 }
@@ -752,9 +776,19 @@ int probav_layer_info(const probav_engine* e, int i, char name[32], int64_t* g_o
 int probav_engine_set_impl(probav_engine* e, int impl)
 {
     if (!e || impl < 0 || impl > 4) { set_error("probav_engine_set_impl: bad argument", hipSuccess); return PROBAV_EINVAL; }
-    e->fam = make_family(impl, e->pw_mfma);
+    e->impl = impl;
+    e->fam = make_family(impl, e->pw_mfma, e->gemm);
     return PROBAV_OK;
 }
+
+int probav_engine_set_gemm_route(probav_engine* e, int on)
+{
+    if (!e) { set_error("probav_engine_set_gemm_route: null engine", hipSuccess); return PROBAV_EINVAL; }
+    e->gemm = on != 0;
+    e->fam = make_family(e->impl, e->pw_mfma, e->gemm);
+    return PROBAV_OK;
+}
+int probav_engine_gemm_route(const probav_engine* e) { return e && e->gemm ? 1 : 0; }
 
 size_t probav_workspace_bytes(const probav_engine* e, int batch, int training)
 {
@@ -1472,6 +1506,131 @@ int probav_plan_conv(const int32_t geom[17], int impl, int gated, int has_skip, 
     kernel = sel.k == StripKernel::pp ? PROBAV_PLAN_PP : (sel.k == StripKernel::pstrip ? PROBAV_PLAN_PSTRIP : PROBAV_PLAN_STRIP);
     nsplit = sel.plan.a.nsplit; nstrips = sel.plan.a.nstrips; SR = sel.plan.a.SR; grid = sel.plan.grid;
     if (sel.k == StripKernel::pp) { nslot = sel.plan.a.nslot; rvp = sel.rvp; }
+    return PROBAV_OK;
+}
+
+// ---- the general matrix route (kernels_gemm.hip): single operators, plan report, launch census ----
+int probav_gemm_conv3d_forward(const int32_t geom[17], const float* x, const float* gate, const float* w, const float* bias,
+                               const float* skip, float* y, void* stream)
+{
+    if (!geom || !x || !w || !y) { set_error("probav_gemm_conv3d_forward: null argument", hipSuccess); return PROBAV_EINVAL; }
+    const ConvGeom g = geom_from(geom);
+    if (!geom_ok(g)) { set_error("probav_gemm_conv3d_forward: bad geometry", hipSuccess); return PROBAV_EINVAL; }
+    if (!gemm_conv_supported(g)) { set_error("probav_gemm_conv3d_forward: geometry not supported by the general matrix route", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_conv_forward(g, x, gate, w, bias, skip, y, (hipStream_t)stream);
+}
+
+size_t probav_gemm_conv3d_wgrad_scratch_bytes(const int32_t geom[17])
+{
+    if (!geom) return 0;
+    const ConvGeom g = geom_from(geom);
+    if (!geom_ok(g) || !gemm_wgrad_supported(g)) return 0;
+    return gemm_wgrad_partial_floats(g) * sizeof(float);
+}
+
+int probav_gemm_conv3d_wgrad(const int32_t geom[17], const float* x, const float* dy, const float* gate, float* dw, float* db,
+                             void* scratch, size_t scratch_bytes, void* stream)
+{
+    if (!geom || !x || !dy || !dw || !scratch) { set_error("probav_gemm_conv3d_wgrad: null argument", hipSuccess); return PROBAV_EINVAL; }
+    const ConvGeom g = geom_from(geom);
+    if (!geom_ok(g)) { set_error("probav_gemm_conv3d_wgrad: bad geometry", hipSuccess); return PROBAV_EINVAL; }
+    if (!gemm_wgrad_supported(g)) { set_error("probav_gemm_conv3d_wgrad: geometry not supported by the general matrix route", hipSuccess); return PROBAV_EINVAL; }
+    if (scratch_bytes < gemm_wgrad_partial_floats(g) * sizeof(float)) { set_error("probav_gemm_conv3d_wgrad: scratch too small", hipSuccess); return PROBAV_ENOSPACE; }
+    return gemm_conv_wgrad(g, x, dy, gate, dw, db, (float*)scratch, (hipStream_t)stream);
+}
+
+// What probav_plan_conv reports, for an engine with the route on: GEMM / WGRAD_GEMM where conv_route / wgrad_route of that engine's family hand the launch to the
+// general matrix route, probav_plan_conv's answer everywhere else
+int probav_plan_conv_gemm(const int32_t geom[17], int impl, int gated, int has_skip, int op, int32_t report[8])
+{
+    const int rc = probav_plan_conv(geom, impl, gated, has_skip, op, report);
+    if (rc) return rc;
+    const ConvGeom g = geom_from(geom);
+    const Family f = make_family(impl, false, true);
+    static const float some = 0.f;
+    Amax am;
+    if (impl == 4) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
+    if (op == PROBAV_PLAN_OP_WGRAD) {
+        if (wgrad_route(f, g, am).k != WgradKernel::gemm) return PROBAV_OK;
+        int v[5];
+        if (!gemm_wgrad_plan_ints(g, v)) return PROBAV_OK;
+        for (int i = 0; i < 8; ++i) report[i] = 0;
+        report[0] = PROBAV_PLAN_WGRAD_GEMM; report[1] = v[0]; report[2] = v[1]; report[3] = v[2]; report[4] = v[3]; report[5] = v[4];
+        return PROBAV_OK;
+    }
+    if (report[0] != PROBAV_PLAN_NONE) return PROBAV_OK;       // a kernel serves the single-operator call (impl 0: direct; the dedicated upscale pair, which that call takes with a bias too)
+    // (every filter fragment exists as far as the route can tell, as in op_conv_route: a geometry a matrix kernel serves stays with it)
+    const ConvRoute r = conv_route(f, g, gated ? &some : nullptr, op == PROBAV_PLAN_OP_FORWARD ? &some : nullptr, has_skip ? &some : nullptr,
+                                   Frags{&some, &some, &some, &some}, am, true);
+    if (r.k != ConvKernel::gemm) return PROBAV_OK;
+    int v[6];
+    if (!gemm_conv_plan_ints(g, v)) return PROBAV_OK;
+    for (int i = 0; i < 8; ++i) report[i] = 0;
+    report[0] = PROBAV_PLAN_GEMM; report[1] = v[3]; report[2] = v[2]; report[3] = v[0]; report[4] = v[1]; report[5] = v[2] * v[3]; report[6] = v[4]; report[7] = v[5];
+    return PROBAV_OK;
+}
+
+// The launches of one training step by route, walked over make_net in the order, and with the operands, of forward_impl / backward_impl
+int probav_engine_route_counts(const probav_engine* e, int batch, int32_t counts[4])
+{
+    if (!e || !counts || batch < 1) { set_error("probav_engine_route_counts: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    for (int i = 0; i < 4; ++i) counts[i] = 0;
+    const Net n = make_net(e, batch);
+    static const float some = 0.f;
+    const float* const P = &some;
+    Amax am;
+    if (e->fam.arith == 2) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
+    auto fr = [&](int li, int dir) {
+        const ConvFrags& o = e->layers[li].pk[dir];
+        return Frags{o.f32 >= 0 ? P : nullptr, o.x6 >= 0 ? P : nullptr, o.h3 >= 0 ? P : nullptr, o.h3t >= 0 ? P : nullptr};
+    };
+    auto conv = [&](const ConvGeom& g, bool gate, bool bias, bool skip, const Frags& wf, bool reports_y) {
+        Amax m = am;
+        if (reports_y && e->fam.arith == 2) m.y = const_cast<unsigned*>(reinterpret_cast<const unsigned*>(&some));
+        const ConvKernel k = conv_route(e->fam, g, gate ? P : nullptr, bias ? P : nullptr, skip ? P : nullptr, wf, m).k;
+        if (k == ConvKernel::direct) ++counts[0];
+        if (k == ConvKernel::gemm) ++counts[1];
+    };
+    auto wgrad = [&](const ConvGeom& g) {
+        const WgradKernel k = wgrad_route(e->fam, g, am).k;
+        if (k == WgradKernel::direct && !(e->fam.mfma && conv3d_direct_wgrad_is_tuned(g))) ++counts[2];
+        if (k == WgradKernel::gemm) ++counts[3];
+    };
+    const bool fusedp = e->fam.pw_fused, fusedr = resid_path_fused(e);
+    const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
+    // forward
+    if (!fusedr) { conv(n.resid1, false, true, false, fr(e->iResid1, 0), false); conv(n.resid2, false, true, false, fr(e->iResid2, 0), false); conv(n.resid3, false, true, false, fr(e->iResid3, 0), false); }
+    conv(n.main, false, true, false, fr(e->iMain, 0), true);
+    for (int i = 0; i < R; ++i) {
+        if (!fusedp) { conv(n.exp, false, true, false, fr(e->iExp[i], 0), false); conv(n.dec, false, true, false, fr(e->iDec[i], 0), true); }
+        conv(n.norm, false, true, true, fr(e->iNorm[i], 0), true);
+    }
+    for (int k = 0; k < nred; ++k) conv(n.red[k], false, true, false, fr(e->iRed[k], 0), true);
+    conv(n.up, false, true, false, fr(e->iUp, 0), false);
+    // backward
+    if (!fusedr) {
+        wgrad(n.resid3); conv(bwd_data_geom(n.resid3), false, false, false, fr(e->iResid3, 1), false);
+        wgrad(n.resid2); conv(bwd_data_geom(n.resid2), false, false, false, fr(e->iResid2, 1), false);
+        wgrad(n.resid1);
+    }
+    wgrad(n.up); conv(bwd_data_geom(n.up), false, false, false, fr(e->iUp, 1), true);
+    for (int k = nred - 1; k >= 0; --k) { wgrad(n.red[k]); conv(bwd_data_geom(n.red[k]), true, false, false, fr(e->iRed[k], 1), true); }
+    for (int i = R - 1; i >= 0; --i) {
+        wgrad(n.norm); conv(bwd_data_geom(n.norm), false, false, false, fr(e->iNorm[i], 1), true);
+        if (fusedp) continue;
+        conv(n.exp, false, true, false, Frags(), false);                       // the recomputed hidden tensor
+        wgrad(n.dec); conv(bwd_data_geom(n.dec), false, false, false, fr(e->iDec[i], 1), false);
+        wgrad(n.exp); conv(bwd_data_geom(n.exp), true, false, true, fr(e->iExp[i], 1), true);
+    }
+    wgrad(n.main);
+    return PROBAV_OK;
+}
+
+// What the passes have actually launched since the last reset, counted where they launch (conv_fwd / conv_wgrad): the check of the census above
+int probav_engine_launched_counts(probav_engine* e, int32_t counts[4], int reset)
+{
+    if (!e || !counts) { set_error("probav_engine_launched_counts: null argument", hipSuccess); return PROBAV_EINVAL; }
+    for (int i = 0; i < 4; ++i) { counts[i] = e->launched[i]; if (reset) e->launched[i] = 0; }
     return PROBAV_OK;
 }
 

@@ -25,7 +25,8 @@ class InferenceOptions:
 
 
 def add_inference_args(p, where=""):
-    """The ten flags of the network's inference options; `where` goes before the help of the five that switch an option on."""
+    """The ten flags of the network's inference options, and --gemm-route, a switch of the engine the network runs on (it stays in the parse result, opt.gemm_route,
+    for load_model: it is no option of the prediction); `where` goes before the help of those that switch something on."""
     p.add_argument("--ensemble", type=str, default="none", choices=("none", "d8"), help=where + "test-time self-ensemble: d8 = the mean over the 4 quarter "
                    "turns x 2 flips of every patch (8 forward passes per patch); none = the plain prediction")
     p.add_argument("--ensemble-permute", type=int, default=0, help="with --ensemble d8: P further frame orders, crossed with the 8 geometric variants "
@@ -44,6 +45,9 @@ def add_inference_args(p, where=""):
                    "the moving average a run with train.py --ema-momentum saved; ema on a checkpoint without one is an error")
     p.add_argument("--fuse", action="store_true", help=where + "apply the band's latest FuseNet checkpoint (train.py --modelType fusionNet) to the "
                    "stitched, rounded image on the device, then clip to 0..65535 and round half to even")
+    p.add_argument("--gemm-route", dest="gemm_route", action="store_true", help=where + "the engine's general matrix route (WDSRModel.set_gemm_route): "
+                   "launches that would run the generic VALU kernels -- a cfg whose num_filters, exp_rate or decay_rate are not the shipped ones -- run on "
+                   "the fp32-input MFMA instead; any checkpoint, results equal to fp32 rounding")
 
 
 def inference_options(p, opt, applies=True, needs=""):
@@ -53,7 +57,7 @@ def inference_options(p, opt, applies=True, needs=""):
     naming `needs`, the flag that would make it predict."""
     if not applies:
         for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.weights != "raw", "--weights"), (opt.tile_stride != 0, "--tile-stride"),
-                            (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse")):
+                            (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse"), (opt.gemm_route, "--gemm-route")):
             if given:
                 p.error("%s applies to %s (a folder of PNGs is scored as it is)" % (flag, needs))
     if opt.ensemble == "none" and opt.ensemble_permute:
@@ -94,9 +98,9 @@ def inference_options(p, opt, applies=True, needs=""):
     return opt.inference
 
 
-def load_model(config, cfg_path, band, weights, who):
+def load_model(config, cfg_path, band, weights, who, gemm_route=False):
     """The cfg's network on the device with its latest checkpoint restored (`weights`: "raw" or "ema") -> (model, trainer).  `who` names the
-    command in the error of a checkpoint without an "ema" entry."""
+    command in the error of a checkpoint without an "ema" entry.  gemm_route: the engine's general matrix route (--gemm-route)."""
     from .modelsTF import WDSRConv3D
     from .trainClass import ModelTrainer
     mean, std = BAND_STATS["NIR" if band == "NIR" else "RED"]
@@ -105,6 +109,8 @@ def load_model(config, cfg_path, band, weights, who):
         scale=config["scale"], numFilters=config["num_filters"], kernelSize=(k, k, k), numResBlocks=config["num_res_blocks"],
         expRate=config["exp_rate"], decayRate=config["decay_rate"], numImgLR=config["num_low_res_imgs"],
         patchSizeLR=config["patch_size"], isGrayScale=config["is_grayscale"]).to("cuda")
+    if gemm_route:
+        model.set_gemm_route(True)
     basename = os.path.basename(cfg_path).split(".")[0]
     try:
         trainer = ModelTrainer(model, None, None, None, os.path.join(config["model_out"], "ckpt_%s" % basename, band),

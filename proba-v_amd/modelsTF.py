@@ -196,6 +196,20 @@ class WDSRModel(torch.nn.Module):
         """The engine's kernel family: what `set_impl` chose, else the engine's own default (PROBAV_IMPL in the environment, else 4)."""
         return self._impl if self._impl is not None else int(os.environ.get("PROBAV_IMPL", 4))
 
+    def set_gemm_route(self, on):
+        """probav_engine_set_gemm_route: the general matrix route (csrc/kernels_gemm.hip).  On, every launch that would otherwise run the generic direct
+        (VALU) kernels on an ordinary geometry -- which is most of a network whose numFilters, expRate or decayRate are not the shipped ones -- runs as an
+        implicit GEMM on the fp32-input MFMA instead; the shipped configuration launches what it launched.  Off by default (PROBAV_GEMM_ROUTE=1 in the
+        environment turns it on at engine creation); `set_impl` keeps it.  Checkpoints do not depend on it; results agree with the direct kernels' to fp32
+        rounding, not bit for bit.  The reverse pass's scratch changes size, so the sizes the ops cache per engine are asked for again."""
+        _lib.check(_lib.lib().probav_engine_set_gemm_route(self._handle(), int(bool(on))), "probav_engine_set_gemm_route")
+        ops.forget_engine(self._handle().value)
+
+    @property
+    def gemm_route(self):
+        """Whether the engine's general matrix route is on (`set_gemm_route`, or PROBAV_GEMM_ROUTE at engine creation)."""
+        return bool(_lib.lib().probav_engine_gemm_route(self._handle()))
+
     def set_side_stream_mode(self, mode):
         """probav_engine_side_stream: 0 = everything on the caller's stream; 1 = the slab sums, the residual path and the upscale layer's backward-filter on the
         engine's low-priority side stream; 2 = also the blocks' backward-filter kernels (the engine's default)."""

@@ -2,20 +2,29 @@
 instances for the shipped configuration only (patch 16 -> 22 x 22 rows, 9 or 7 frames in the residual blocks, decay 0.8 -> 25 channels, 32 filters); every other value
 runs the general kernels of rounds 2 - 4 -- correct (tests/test_gpu_parity.py::test_other_patch_sizes_agree_across_engines), slower per voxel.  This prints, per
 configuration, ms per training step (forward + shift-L1 + backward), patches/s, and the throughput per VOXEL-MAC relative to the shipped configuration.
-    python tools/cfg_cliff.py            (on the GPU box, from the repo root)"""
+    python tools/cfg_cliff.py            (on the GPU box, from the repo root)
+    --gemm-route       the table with the engine's general matrix route on (WDSRModel.set_gemm_route; INTEGRATION.md, 'The general matrix route')
+    --filters F        only the num_filters = F row (batch 128, 12 blocks, expansion --exp, default 8)
+    --ab               per row, the route off and on ALTERNATED in one process on one model: --windows windows per leg (default 3) of --steps steps each, timed
+                       with device events; ms per step off / on, their ratio, the off leg's own window-to-window spread, the training workspace bytes off / on,
+                       and the TFLOP/s of the fp32 kernel classes (probav_engine_profile: what the route's launches are booked under) with the route on"""
+import argparse
+import ctypes
 import json
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
+from probav_amd import _lib as L
 from probav_amd import synth
 from probav_amd.loss import Losses
 from probav_amd.modelsTF import WDSRConv3D
 
 dev = torch.device("cuda:0")
+FP32_PEAK_TFLOPS = 157.3          # MI355X fp32 matrix peak, as published (not measured here)
+FP32_CLASSES = (2, 3, 4, 5, 6, 7)   # engine.hip: conv3 fwd / bwd-data / wgrad, 1x1x1 fwd / bwd-data / wgrad -- the fp32 (VALU, fp32-MFMA, general matrix route) launches
 
 
 def macs_per_patch(P, T, F=32, E=8, decay=0.8, R=12):
@@ -26,9 +35,11 @@ def macs_per_patch(P, T, F=32, E=8, decay=0.8, R=12):
     return R * V * (F * F * E + F * E * D + 27 * D * F)
 
 
-def run(P, T, B, decay=0.8, F=32, steps=30):
-    model = WDSRConv3D("cliff", "NIR", synth.NIR_MEAN, synth.NIR_STD, 6).build(3, F, (3, 3, 3), 12, 8, decay, T, P, True, seed=0)
+def build(P, T, B, decay, F, E, gemm):
+    model = WDSRConv3D("cliff", "NIR", synth.NIR_MEAN, synth.NIR_STD, 6).build(3, F, (3, 3, 3), 12, E, decay, T, P, True, seed=0)
     model = model.to(dev)
+    if gemm:
+        model.set_gemm_route(True)
     rng = np.random.default_rng(1)
     H = P + 6
     x = torch.as_tensor(np.clip(rng.normal(synth.NIR_MEAN, synth.NIR_STD, (B, H, H, T, 1)), 0, 16383).astype(np.float32)).to(dev)
@@ -41,8 +52,11 @@ def run(P, T, B, decay=0.8, F=32, steps=30):
         loss = losses.shiftCompensatedL1Loss(hr, mask, pred)
         model.flat.grad = None
         loss.backward()
-    for _ in range(5):
-        step()
+    return model, step
+
+
+def timed(step, steps):
+    """ms of each of `steps` steps, by device events."""
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     torch.cuda.synchronize()
     evs[0].record()
@@ -50,34 +64,111 @@ def run(P, T, B, decay=0.8, F=32, steps=30):
         step()
         evs[i + 1].record()
     torch.cuda.synchronize()
-    ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
-    med = ms[len(ms) // 2]
+    return [evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]
+
+
+def release(model):
     model._ws.clear()
     del model
     torch.cuda.empty_cache()
-    return med
+
+
+def run(P, T, B, decay=0.8, F=32, steps=30, E=8, gemm=False):
+    model, step = build(P, T, B, decay, F, E, gemm)
+    for _ in range(5):
+        step()
+    ms = sorted(timed(step, steps))
+    release(model)
+    return ms[len(ms) // 2]
+
+
+def fp32_class_tflops(model, step):
+    """TFLOP/s (2 x algorithmic MACs / bracketed time) of the fp32 classes over one step, everything on the launch stream."""
+    h = model._handle()
+    n = 13
+    model.set_side_stream_mode(0)
+    L.check(L.lib().probav_engine_profile(h, 1, 4096), "probav_engine_profile")
+    try:
+        step()
+        torch.cuda.synchronize()
+        ms, macs, cnt = (ctypes.c_double * n)(), (ctypes.c_double * n)(), (ctypes.c_int64 * n)()
+        L.check(L.lib().probav_engine_profile_read(h, n, ms, macs, cnt), "probav_engine_profile_read")
+    finally:
+        L.check(L.lib().probav_engine_profile(h, 0, 0), "probav_engine_profile")
+        model.set_side_stream_mode(2)
+    t, m, k = (sum(a[c] for c in FP32_CLASSES) for a in (ms, macs, cnt))
+    return (2.0 * m / (t * 1e-3) / 1e12 if t > 0 else 0.0), t, int(k)
+
+
+def run_ab(P, T, B, decay, F, E, steps, windows):
+    model, step = build(P, T, B, decay, F, E, False)
+    h = model._handle()
+    legs, ws = {False: [], True: []}, {}
+    for w in range(windows):
+        for on in (False, True):
+            model.set_gemm_route(on)
+            ws[on] = int(L.lib().probav_workspace_bytes(h, B, 1))
+            step()
+            step()                                              # (the switch resizes the reverse pass's scratch: the first steps allocate)
+            legs[on].append(sum(timed(step, steps)) / steps)
+    counts = (ctypes.c_int32 * 4)()
+    model.set_gemm_route(True)
+    L.check(L.lib().probav_engine_route_counts(h, B, ctypes.byref(counts)), "probav_engine_route_counts")
+    tf, tms, launches = fp32_class_tflops(model, step)
+    release(model)
+    med = lambda v: sorted(v)[len(v) // 2]
+    off, on = med(legs[False]), med(legs[True])
+    return {"ms_per_step_off": round(off, 3), "ms_per_step_on": round(on, 3), "on_over_off": round(on / off, 4),
+            "off_windows_ms": [round(v, 3) for v in legs[False]], "on_windows_ms": [round(v, 3) for v in legs[True]],
+            "off_spread": round((max(legs[False]) - min(legs[False])) / off, 4),
+            "train_workspace_bytes_off": ws[False], "train_workspace_bytes_on": ws[True], "route_launches_conv_wgrad": [counts[1], counts[3]],
+            "valu_launches_left_conv_wgrad": [counts[0], counts[2]],
+            "fp32_classes_on": {"launches": launches, "ms": round(tms, 3), "tflops": round(tf, 2), "of_fp32_matrix_peak_157.3": round(tf / FP32_PEAK_TFLOPS, 4)}}
+
+
+# name, P, T, B, decay, F, E
+TABLE = (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8, 32, 8),
+         ("7 frames", 16, 7, 128, 0.8, 32, 8),
+         ("13 frames (reducer v3)", 16, 13, 128, 0.8, 32, 8),
+         ("19 frames (experimental reducer)", 16, 19, 64, 0.8, 32, 8),
+         ("patch 32 (38 x 38 rows)", 32, 9, 40, 0.8, 32, 8),
+         ("patch 24 (30 x 30 rows)", 24, 9, 64, 0.8, 32, 8),
+         ("decay 0.5 (16 channels)", 16, 9, 128, 0.5, 32, 8),
+         ("decay 0.9 (28 channels)", 16, 9, 128, 0.9, 32, 8),
+         ("filters 64 (51 channels)", 16, 9, 128, 0.8, 64, 8),
+         ("filters 48 / exp 6 (43 channels)", 16, 9, 128, 0.9, 48, 6))
+# the rows of --ab: the shipped one (which must not move), the cfg values the route is for, 13 frames at 64 filters
+AB_TABLE = (TABLE[0], TABLE[6], TABLE[7], TABLE[8], TABLE[9], ("filters 64, 13 frames", 16, 13, 128, 0.8, 64, 8))
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--gemm-route", dest="gemm_route", action="store_true")
+    ap.add_argument("--filters", type=int, default=None)
+    ap.add_argument("--exp", type=int, default=8)
+    ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--windows", type=int, default=3)
+    opt = ap.parse_args()
+    table = AB_TABLE if opt.ab else TABLE
+    if opt.filters is not None:
+        table = (("filters %d / exp %d" % (opt.filters, opt.exp), 16, 9, 128, 0.8, opt.filters, opt.exp),)
     rows = []
     base = None
-    for name, P, T, B, decay in (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8),
-                                 ("7 frames", 16, 7, 128, 0.8),
-                                 ("13 frames (reducer v3)", 16, 13, 128, 0.8),
-                                 ("19 frames (experimental reducer)", 16, 19, 64, 0.8),
-                                 ("patch 32 (38 x 38 rows)", 32, 9, 40, 0.8),
-                                 ("patch 24 (30 x 30 rows)", 24, 9, 64, 0.8),
-                                 ("decay 0.5 (16 channels)", 16, 9, 128, 0.5),
-                                 ("decay 0.9 (28 channels)", 16, 9, 128, 0.9)):
+    for name, P, T, B, decay, F, E in table:
         try:
-            med = run(P, T, B, decay)
+            if opt.ab:
+                rows.append(dict({"config": name, "batch": B}, **run_ab(P, T, B, decay, F, E, opt.steps or 4, opt.windows)))
+                print(json.dumps(rows[-1]), flush=True)
+                continue
+            med = run(P, T, B, decay, F, opt.steps or 30, E, opt.gemm_route)
         except Exception as ex:                                   # a configuration the engine refuses is a row of the table too
             rows.append({"config": name, "error": str(ex)[:200]})
             print(json.dumps(rows[-1]), flush=True)
             continue
-        gmacs = macs_per_patch(P, T, decay=decay) * B / (med * 1e-3) / 1e9
+        gmacs = macs_per_patch(P, T, F, E, decay) * B / (med * 1e-3) / 1e9
         if base is None:
             base = gmacs
-        rows.append({"config": name, "batch": B, "ms_per_step_median": round(med, 3), "patches_per_s": round(B / (med * 1e-3), 1),
+        rows.append({"config": name, "batch": B, "gemm_route": bool(opt.gemm_route), "ms_per_step_median": round(med, 3), "patches_per_s": round(B / (med * 1e-3), 1),
                      "block_GMAC_per_s": round(gmacs, 1), "per_mac_throughput_vs_shipped": round(gmacs / base, 3)})
         print(json.dumps(rows[-1]), flush=True)

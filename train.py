@@ -56,11 +56,16 @@ def parser(argv=None):
                    help="Keras use_ema / ema_momentum: keep a moving average of the weights with this momentum (e.g. 0.99); checkpoints gain an 'ema' entry")
     p.add_argument("--validate-on", dest="validate_on", type=str, default="raw", choices=("raw", "ema"),
                    help="the weights the validation runs on (ema needs --ema-momentum); default raw")
+    p.add_argument("--gemm-route", dest="gemm_route", action="store_true",
+                   help="the engine's general matrix route (WDSRModel.set_gemm_route): launches that would run the generic VALU kernels -- a cfg whose "
+                        "num_filters, exp_rate or decay_rate are not the shipped ones, e.g. cfg/p16t9c85r12f64.cfg -- run on the fp32-input MFMA instead")
     opt = p.parse_args(argv)
     if opt.fusion_input is not None and opt.modelType != "fusionNet":
         p.error("--fusion-input needs --modelType fusionNet")
     if opt.modelType == "fusionNet" and opt.fusion_input is None:
         p.error("--modelType fusionNet needs --fusion-input DIR (the PNGs of test.py --totest TRAIN)")
+    if opt.gemm_route and opt.modelType == "fusionNet":
+        p.error("--gemm-route is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
     if opt.random_crops and opt.online_aug:
         p.error("--random-crops and --online-aug are mutually exclusive")
     if not opt.random_crops and (opt.crop_positions != "all" or opt.crop_seed != 0 or opt.crops_per_epoch is not None):
@@ -74,6 +79,12 @@ def parser(argv=None):
     if opt.validate_on == "ema" and opt.ema_momentum is None:
         p.error("--validate-on ema needs --ema-momentum")
     return opt
+
+
+def apply_engine_options(model, opt):
+    """The engine switches among the flags, set on the freshly built model: --gemm-route."""
+    if opt.gemm_route:
+        model.set_gemm_route(True)
 
 
 def training_scenes(dataDir, band):
@@ -126,6 +137,7 @@ def patchNet(config, opt):
         scale=config["scale"], numFilters=config["num_filters"], kernelSize=(k, k, k), numResBlocks=config["num_res_blocks"],
         expRate=config["exp_rate"], decayRate=config["decay_rate"], numImgLR=config["num_low_res_imgs"],
         patchSizeLR=config["patch_size"], isGrayScale=config["is_grayscale"], seed=0).to(torch.device("cuda", local))
+    apply_engine_options(model, opt)
     if opt.global_clipnorm is None and not opt.skip_nonfinite and opt.ema_momentum is None:
         optimizer = make_optimizer(config["optimizer"], model, config["learning_rate"])
     else:
