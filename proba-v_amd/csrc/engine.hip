@@ -142,22 +142,49 @@ static size_t in_floats(const ConvGeom& g) { return (size_t)g.N * g.Hi * g.Wi * 
 static size_t out_floats(const ConvGeom& g) { return (size_t)g.N * g.Ho * g.Wo * g.To * g.Cout; }
 static long in_voxels(const ConvGeom& g) { return (long)g.N * g.Hi * g.Wi * g.Ti; }
 
+// Which operands a launch has: all that the route functions (conv_route, wgrad_route) need to know of them
+struct Operands {
+    bool gate = false, bias = false, skip = false;
+    bool f32 = false, x6 = false, h3 = false, h3t = false;    // the filter fragments that exist (h3t: per-tap H3 fragments of a 25-channel layer)
+    bool am_in = false;                                       // the launch gets the amax slots of its inputs (Amax: x and w)
+    bool am_out = false;                                      // ... and must leave its output's amax (Amax: y)
+};
+
+// One routed launch of a training step.  step_launches lists them, forward then backward, in issue order: the one statement of which launches a step consists
+// of.  make_plan lays the slab regions out and counts the amax slots over it, probav_engine_route_counts routes it, and the passes fetch every launch here by its site
+enum class Role { resid1, resid2, resid3, resid_path, main, exp, dec, pair, norm, red, up, hidden };   // pair / resid_path: the fused launches; hidden: expConv's output recomputed by the un-fused reverse pass
+enum class LaunchKind { none, conv, wgrad, fused };          // conv: forward, or in the reverse pass backward-data (hidden: forward); wgrad: backward-filter; fused: the pointwise pair or the residual path, one launch each way
+struct Region { static constexpr size_t none = ~(size_t)0; size_t off = none, floats = 0; };     // of the scratch's slab area: offset relative to Plan::partial, size
+struct Launch {
+    Role role = Role::main; int i = 0;                        // the site: whose launch (i: block or reducer) ...
+    LaunchKind kind = LaunchKind::none; bool back = false;    // ... and which of them, of which pass
+    ConvGeom g;                                               // the geometry launched (backward-data: bwd_data_geom of the layer's; fused: of the pair's / the path's first layer)
+    int li = -1, dir = -1;                                    // the layer and the direction of its fragments (0 forward, 1 backward-data, -1: the launch has none)
+    Operands o;                                               // as the pass hands them over
+    int slots = 0, slot = -1;                                 // reverse pass: per-sample amax slot arrays its output takes (2: one more for the fold of its mirrored pads), the first's index
+    Region slab;                                              // backward-filter and fused reverse launches: the slab region
+};
+
 struct Plan {
     Net net;
+    std::vector<Launch> launches;
     size_t weff, weffT, invn, xn, mn;
     size_t amax; int n_amax, amax_bwd, amax_fwd, B;   // amax slots (one 32-bit word each, x6_device.h): region offset, count, first slot of the backward / forward per-sample arrays
-    int n_back;                               // per-sample slot arrays the reverse pass takes (new_slot); the region behind amax_bwd holds at least as many
+    int n_back;                               // per-sample slot arrays the reverse pass takes (Launch::slots); the region behind amax_bwd holds at least as many
     std::vector<size_t> act, dec, red;
     size_t up, r1, r2, r3, H, wpack;
     // --- what only the reverse pass writes (offsets relative to the SCRATCH base: the tail of a one-piece workspace, or the caller's second buffer) ---
     size_t bamax, dweff2, Hb, dH, gA, gB, gDec, dtail, dr2, dr1, partial;
     size_t fwd_total, bwd_total, total;       // floats: the saved state of a forward pass | the reverse pass's scratch | both
     std::vector<size_t> gblk, gred;
-    // the slab region of each backward-filter launch of a backward pass, by the layer it serves (offset relative to `partial`, size; off == none:
-    // this plan has no such launch).  pair[i]: the fused pointwise pair of block i; dec[i], exp[i]: its two layers un-fused
-    struct Region { static constexpr size_t none = ~(size_t)0; size_t off = none, floats = 0; };
-    struct { Region resid3, resid2, resid1, up, main; std::vector<Region> red, norm, pair, dec, exp; } slab;
 };
+// the launch at a site, or an entry of kind none (which conv_fwd / conv_wgrad refuse): by value, so that a queued launch may keep it
+static Launch launch_at(const Plan& p, Role role, LaunchKind kind, bool back, int i = 0)
+{
+    for (const Launch& L : p.launches) if (L.role == role && L.kind == kind && L.back == back && L.i == i) return L;
+    Launch none; none.role = role; none.back = back; none.i = i;
+    return none;
+}
 
 static ConvGeom make_geom(int N, int Hi, int Ti, int Cin, int Ho, int To, int Cout, int kh, int kw, int kt,
                           int ph, int pt, int reflect, int relu)
@@ -223,32 +250,106 @@ static bool resid_path_fused(const probav_engine* e)
 }
 
 // The kernel that serves a backward-filter launch: the one decision both make_plan (slab region sizes) and conv_wgrad (launch) read.
-// am.x / am.w: per-sample amax slots of x and of dy (the H3 kernel needs both)
+// o.am_in: the launch has the per-sample amax slots of x and of dy (the H3 kernel needs both).  tuned: the direct kernel's dedicated small instance
 enum class WgradKernel { direct, x6, mfma, gemm };
-struct WgradRoute { WgradKernel k; int cls; int arith; };
-static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Amax& am)
+struct WgradRoute { WgradKernel k; int cls; int arith; bool tuned; };
+static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Operands& o)
 {
     const bool exotic = g.reflect_t || g.ph > 1 || g.pw > 1 || g.pt > 1 || (g.kh != 3 && g.kh != 1);
-    if (exotic || (f.mfma && conv3d_direct_wgrad_is_tuned(g))) return {WgradKernel::direct, CLS_CONV3_WGRAD, 0};
+    const bool tuned = f.mfma && conv3d_direct_wgrad_is_tuned(g);
+    if (exotic || tuned) return {WgradKernel::direct, CLS_CONV3_WGRAD, 0, tuned};
     const bool x6 = f.x6 && x6_wgrad_supported(g);
     const int cls = g.kh * g.kw * g.kt == 1 ? CLS_PW_WGRAD : (x6 ? CLS_CONV3_WGRAD_X6 : CLS_CONV3_WGRAD);
-    if (x6) return {WgradKernel::x6, cls, f.arith == 2 && am.x && am.w ? 2 : 1};
-    if (f.mfma && mfma_wgrad_supported(g)) return {WgradKernel::mfma, cls, 0};
-    if (f.gemm && gemm_wgrad_supported(g)) return {WgradKernel::gemm, cls, 0};      // the general matrix route: only what would be the generic direct kernel's
-    return {WgradKernel::direct, cls, 0};
+    if (x6) return {WgradKernel::x6, cls, f.arith == 2 && o.am_in ? 2 : 1, false};
+    if (f.mfma && mfma_wgrad_supported(g)) return {WgradKernel::mfma, cls, 0, false};
+    if (f.gemm && gemm_wgrad_supported(g)) return {WgradKernel::gemm, cls, 0, false};      // the general matrix route: only what would be the generic direct kernel's
+    return {WgradKernel::direct, cls, 0, false};
 }
+// the slot of the launch census (probav_engine_route_counts, probav_engine_launched_counts) a routed backward-filter counts in, or -1
+static int census_slot(const WgradRoute& r) { return r.k == WgradKernel::gemm ? 3 : (r.k == WgradKernel::direct && !r.tuned ? 2 : -1); }
 // slab floats the routed kernel writes
 static size_t wgrad_slab_floats(const WgradRoute& r, const ConvGeom& g)
 {
     if (r.k == WgradKernel::gemm) return gemm_wgrad_partial_floats(g);
     return r.k == WgradKernel::x6 ? x6_wgrad_partial_floats(g) : (r.k == WgradKernel::mfma ? mfma_wgrad_partial_floats(g) : wgrad_partial_floats(g));
 }
-static size_t wgrad_need(const Family& f, const ConvGeom& g) { return wgrad_slab_floats(wgrad_route(f, g, Amax()), g); }
+static size_t wgrad_need(const Family& f, const ConvGeom& g, const Operands& o = Operands()) { return wgrad_slab_floats(wgrad_route(f, g, o), g); }
+
+// The launches of one training step on the network n.  The family-dependent shape of the step is stated here and nowhere else: the residual path and the
+// pointwise pair fused or layer by layer, and under the H3 arithmetic which launches get their inputs' amax slots and which leave their output's
+static std::vector<Launch> step_launches(const probav_engine* e, const Net& n)
+{
+    const bool h3 = e->fam.arith == 2, fusedp = e->fam.pw_fused, fusedr = resid_path_fused(e);
+    const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
+    std::vector<Launch> v;
+    v.reserve(16 + 12 * R + 4 * nred);
+    auto add = [&](Role role, int i, LaunchKind kind, bool back, const ConvGeom& g, int li, int dir) -> Launch& {
+        Launch L; L.role = role; L.i = i; L.kind = kind; L.back = back; L.g = g; L.li = li; L.dir = dir;
+        v.push_back(L);
+        return v.back();
+    };
+    // dir 0: the layer's forward; 1: its backward-data; -1: its forward again, without fragments.  in / out: the amax slots under H3
+    auto conv = [&](Role role, int i, const ConvGeom& g, int li, int dir, bool gate, bool skip, bool in, bool out, int slots = 0) {
+        Launch& L = add(role, i, LaunchKind::conv, dir != 0, dir == 1 ? bwd_data_geom(g) : g, li, dir);
+        if (dir >= 0) { const ConvFrags& c = e->layers[li].pk[dir]; L.o.f32 = c.f32 >= 0; L.o.x6 = c.x6 >= 0; L.o.h3 = c.h3 >= 0; L.o.h3t = c.h3t >= 0; }
+        L.o.gate = gate; L.o.bias = dir != 1; L.o.skip = skip; L.o.am_in = h3 && in; L.o.am_out = h3 && out; L.slots = slots;
+    };
+    auto wgrad = [&](Role role, int i, const ConvGeom& g, int li, bool gate, bool in) {
+        Launch& L = add(role, i, LaunchKind::wgrad, true, g, li, -1);
+        L.o.gate = gate; L.o.am_in = h3 && in;
+    };
+    // forward (forward_impl)
+    if (fusedr) add(Role::resid_path, 0, LaunchKind::fused, false, n.resid1, -1, -1);
+    else {
+        conv(Role::resid1, 0, n.resid1, e->iResid1, 0, false, false, false, false);
+        conv(Role::resid2, 0, n.resid2, e->iResid2, 0, false, false, false, false);
+        conv(Role::resid3, 0, n.resid3, e->iResid3, 0, false, false, false, false);
+    }
+    conv(Role::main, 0, n.main, e->iMain, 0, false, false, false, true);
+    for (int i = 0; i < R; ++i) {
+        if (fusedp) add(Role::pair, i, LaunchKind::fused, false, n.exp, -1, -1);
+        else {
+            conv(Role::exp, i, n.exp, e->iExp[i], 0, false, false, false, false);
+            conv(Role::dec, i, n.dec, e->iDec[i], 0, false, false, false, true);
+        }
+        conv(Role::norm, i, n.norm, e->iNorm[i], 0, false, true, true, true);
+    }
+    for (int k = 0; k < nred; ++k) conv(Role::red, k, n.red[k], e->iRed[k], 0, false, false, true, true);
+    conv(Role::up, 0, n.up, e->iUp, 0, false, false, true, false);
+    // backward (backward_impl): the residual path last layer first, upscale layer, reducers, blocks, mainConv1 (input-facing: no backward-data)
+    if (fusedr) add(Role::resid_path, 0, LaunchKind::fused, true, n.resid1, -1, -1);
+    else {
+        wgrad(Role::resid3, 0, n.resid3, e->iResid3, false, false);
+        conv(Role::resid3, 0, n.resid3, e->iResid3, 1, false, false, false, false);
+        wgrad(Role::resid2, 0, n.resid2, e->iResid2, false, false);
+        conv(Role::resid2, 0, n.resid2, e->iResid2, 1, false, false, false, false);
+        wgrad(Role::resid1, 0, n.resid1, e->iResid1, true, false);
+    }
+    wgrad(Role::up, 0, n.up, e->iUp, false, false);
+    conv(Role::up, 0, n.up, e->iUp, 1, false, false, false, true, 1);
+    for (int k = nred - 1; k >= 0; --k) {
+        wgrad(Role::red, k, n.red[k], e->iRed[k], true, true);
+        conv(Role::red, k, n.red[k], e->iRed[k], 1, true, false, true, true, n.red[k].reflect_hw ? 2 : 1);     // (the folded gradient of mirrored pads is a new tensor)
+    }
+    for (int i = R - 1; i >= 0; --i) {
+        wgrad(Role::norm, i, n.norm, e->iNorm[i], false, true);
+        conv(Role::norm, i, n.norm, e->iNorm[i], 1, false, false, true, true, 1);
+        if (fusedp) { add(Role::pair, i, LaunchKind::fused, true, n.exp, -1, -1).slots = 1; continue; }
+        conv(Role::hidden, i, n.exp, e->iExp[i], -1, false, false, false, false);
+        wgrad(Role::dec, i, n.dec, e->iDec[i], false, false);
+        conv(Role::dec, i, n.dec, e->iDec[i], 1, false, false, false, false);
+        wgrad(Role::exp, i, n.exp, e->iExp[i], true, false);
+        conv(Role::exp, i, n.exp, e->iExp[i], 1, true, true, false, true, 1);
+    }
+    wgrad(Role::main, 0, n.main, e->iMain, true, false);
+    return v;
+}
 
 static Plan make_plan(const probav_engine* e, int B, int training)
 {
     Plan p;
     p.net = make_net(e, B);
+    p.launches = step_launches(e, p.net);
     const Net& n = p.net;
     const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
     size_t off = 0;
@@ -261,8 +362,8 @@ static Plan make_plan(const probav_engine* e, int B, int training)
         p.B = B;
         p.amax_fwd = 2 * L + (int)e->cout_total + (int)e->cin_total;
         p.amax_bwd = p.amax_fwd + B * (2 * R + 1 + nred);
-        p.n_back = 1 + 2 * R;
-        for (const ConvGeom& g : n.red) p.n_back += g.reflect_hw ? 2 : 1;
+        p.n_back = 0;
+        for (Launch& L : p.launches) if (L.slots) { L.slot = p.n_back; p.n_back += L.slots; }
         p.n_amax = p.amax_bwd + (training ? B * (2 * R + 2 * nred + 8) : 0);     // (reserved: n_back and a margin that the workspace sizes have always carried)
         p.amax = take((size_t)p.amax_bwd);
     }
@@ -303,33 +404,23 @@ static Plan make_plan(const probav_engine* e, int B, int training)
         p.dr2 = take(out_floats(n.resid2));
         p.dr1 = take(out_floats(n.resid1));
         p.dH = take(unfused ? out_floats(n.exp) : 0);
-        // one slab region per backward-filter launch, laid out in the order backward_impl issues them: the slabs of a launch are summed on the side
-        // stream while the main chain has moved on, so no two launches may share a region
-        {
-            const Family& f = e->fam;
-            size_t acc = 0;
-            auto region = [&](size_t q) { Plan::Region r; r.off = acc; r.floats = q; acc += align_up(q); return r; };
-            // (the residual path's three regions: where the path runs fused nothing is launched through wgrad_route, and the regions keep the sizes they have
-            // always had, with or without the general matrix route)
-            Family fr = f;
-            if (resid_path_fused(e)) fr.gemm = false;
-            size_t resid3 = wgrad_need(fr, n.resid3);
-            if (resid_path_fused(e)) resid3 = std::max(resid3, resid_path_slab_floats(B, n.resid1.Cin));     // (the fused reverse pass: one slab per patch, in the first region)
-            p.slab.resid3 = region(resid3);
-            p.slab.resid2 = region(wgrad_need(fr, n.resid2));
-            p.slab.resid1 = region(wgrad_need(fr, n.resid1));
-            p.slab.up = region(wgrad_need(f, n.up));
-            p.slab.red.resize(nred);
-            for (int k = nred - 1; k >= 0; --k) p.slab.red[k] = region(wgrad_need(f, n.red[k]));
-            p.slab.norm.resize(R); p.slab.pair.resize(R); p.slab.dec.resize(R); p.slab.exp.resize(R);
-            for (int i = R - 1; i >= 0; --i) {
-                p.slab.norm[i] = region(wgrad_need(f, n.norm));
-                if (!unfused) p.slab.pair[i] = region(mfma_pw_backward_slab_floats(n.dec.Cout));
-                else { p.slab.dec[i] = region(wgrad_need(f, n.dec)); p.slab.exp[i] = region(wgrad_need(f, n.exp)); }
+        // one slab region per launch of the reverse pass that writes slabs, in list order: the slabs of a launch are summed on the side stream while the
+        // main chain has moved on, so no two launches may share a region
+        size_t acc = 0;
+        auto region = [&](size_t q) { Region r; r.off = acc; r.floats = q; acc += align_up(q); return r; };
+        for (Launch& L : p.launches) {
+            if (!L.back) continue;
+            if (L.kind == LaunchKind::wgrad) L.slab = region(wgrad_need(e->fam, L.g, L.o));
+            else if (L.kind == LaunchKind::fused && L.role == Role::pair) L.slab = region(mfma_pw_backward_slab_floats(n.dec.Cout));
+            else if (L.kind == LaunchKind::fused) {
+                // the fused residual path: one slab per patch in the first of the three regions its layers would have, which keep the sizes they have always had,
+                // with or without the general matrix route
+                Family fr = e->fam; fr.gemm = false;
+                L.slab = region(std::max(wgrad_need(fr, n.resid3), resid_path_slab_floats(B, n.resid1.Cin)));
+                region(wgrad_need(fr, n.resid2)); region(wgrad_need(fr, n.resid1));
             }
-            p.slab.main = region(wgrad_need(f, n.main));
-            p.partial = take(acc);
         }
+        p.partial = take(acc);
     }
     p.bwd_total = off;
     p.total = p.fwd_total + p.bwd_total;
@@ -352,15 +443,6 @@ static WcPlan make_wc_plan(const probav_engine* e)
 }
 
 // ---------------------------------------------------------------------------------------------------
-struct Frags { const float* f32 = nullptr; const float* x6 = nullptr; const float* h3 = nullptr; const float* h3t = nullptr; };   // h3t: per-tap H3 fragments of a 25-channel layer
-// the conv fragments of layer li in direction dir (0 forward, 1 backward-data) inside the packed region `wpack`
-static Frags frags(const probav_engine* e, const float* wpack, int li, int dir)
-{
-    const ConvFrags& o = e->layers[li].pk[dir];
-    auto at = [wpack](long off) -> const float* { return off >= 0 ? wpack + off : nullptr; };
-    return {at(o.f32), at(o.x6), at(o.h3), at(o.h3t)};
-}
-
 // Where the parameter-derived tensors of a pass live: in the caller's weight cache (WC), or in the workspace W, where the forward pass recomputes them.
 // wslots: the weights' amax slots (the head of the workspace's amax region, or the cache's)
 struct Derived { const float *weff, *weffT, *invn, *wpack; unsigned* wslots; };
@@ -389,97 +471,112 @@ struct AmaxSlots {
     unsigned* back(int j) const { return bbase + B * j; }                             // j-th tensor produced by the backward pass
 };
 
-// The kernel that serves a convolution launch of the engine (forward, or backward-data when bias == nullptr): with the launch's profiling class,
-// whether the kernel writes am.y itself, and for the MFMA / x6 kernels the filter fragments they read (x6: in arithmetic 1 X6 or 2 H3)
+// The kernel that serves a convolution launch of the engine (forward, or backward-data when it has no bias): with the launch's profiling class,
+// whether the kernel writes am.y itself, and for the MFMA / x6 kernels the kind of filter fragments they read (x6: in arithmetic 1 X6 or 2 H3)
 enum class ConvKernel { direct, up, up_bwd_data, cin1, x6_strip, x6_rowtile, mfma_strip, mfma_rowtile, gemm };
-struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; const float* wfrag; StripSel strip; };     // strip: the strip kernels' selection (strip_select), made here once
+enum class FragKind { none, f32, x6, h3, h3t };
+struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; FragKind frag; StripSel strip; };     // strip: the strip kernels' selection (strip_select), made here once
 // `dedicated`: the engine's policy in front of the matrix kernels (small dedicated kernels, exotic geometries on the direct one); the single-operator entry point,
 // whose tests hold the matrix kernels to the oracle on those geometries too, routes without it
-static ConvRoute conv_route(const Family& f, const ConvGeom& g, const float* gate, const float* bias, const float* skip, const Frags& wf, const Amax& am, bool dedicated = true)
+static ConvRoute conv_route(const Family& f, const ConvGeom& g, const Operands& o, bool dedicated = true)
 {
     const bool pw = g.kh * g.kw * g.kt == 1;
-    const bool bwd = (bias == nullptr);              // only backward-data launches run without a bias
+    const bool bwd = !o.bias;                        // only backward-data launches run without a bias
     if (dedicated) {
         // the experimental 19-frame reducer: 5x5x5 kernels, pads of 2, mirrored depth pads (and their backward-data forms): generic kernels
         const bool exotic = g.reflect_t || g.ph > 2 || g.pw > 2 || g.pt > 2 || (!pw && g.kh != 3) || (g.reflect_hw && g.ph > 1);
         // upscaleConv1 and its backward-data (0.2 % of the work): dedicated small VALU kernels instead of 32x32 matrix tiles around a 32x9 product
-        if (f.mfma && !gate && !skip && bwd && conv3d_up_bwd_data_supported(g)) return {ConvKernel::up_bwd_data, CLS_CONV3_BWD_DATA, true, 0, nullptr, {}};
-        if (exotic) return {ConvKernel::direct, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, false, 0, nullptr, {}};
-        if (f.mfma && !gate && !skip && bias && !am.y && conv3d_up_forward_supported(g)) return {ConvKernel::up, CLS_CONV3_FWD, false, 0, nullptr, {}};
-        if (f.mfma && !gate && !skip && bias && conv3d_cin1_forward_supported(g)) return {ConvKernel::cin1, CLS_CONV3_FWD, true, 0, nullptr, {}};
+        if (f.mfma && !o.gate && !o.skip && bwd && conv3d_up_bwd_data_supported(g)) return {ConvKernel::up_bwd_data, CLS_CONV3_BWD_DATA, true, 0, FragKind::none, {}};
+        if (exotic) return {ConvKernel::direct, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, false, 0, FragKind::none, {}};
+        if (f.mfma && !o.gate && !o.skip && o.bias && !o.am_out && conv3d_up_forward_supported(g)) return {ConvKernel::up, CLS_CONV3_FWD, false, 0, FragKind::none, {}};
+        if (f.mfma && !o.gate && !o.skip && o.bias && conv3d_cin1_forward_supported(g)) return {ConvKernel::cin1, CLS_CONV3_FWD, true, 0, FragKind::none, {}};
     }
-    const bool h3 = f.arith == 2 && wf.h3 && am.x && am.w;
-    const float* wsplit = h3 ? wf.h3 : wf.x6;
+    const bool h3 = f.arith == 2 && o.h3 && o.am_in;
+    const FragKind wsplit = h3 ? FragKind::h3 : FragKind::x6;
     const int arith = h3 ? 2 : 1;
-    const bool split = f.x6 && wsplit;
-    const StripSel sel = split ? strip_select(g, gate, arith) : StripSel();
+    const bool split = f.x6 && (h3 || o.x6);
+    const StripSel sel = split ? strip_select(g, o.gate, arith) : StripSel();
     const bool x6s = sel.k != StripKernel::none;
     const bool x6r = split && !x6s && x6_conv_rowtile_supported(g);
     const bool x6 = x6s || x6r;
     const int cls = pw ? (bwd ? CLS_PW_BWD_DATA : CLS_PW_FWD) : (bwd ? (x6 ? CLS_CONV3_BWD_DATA_X6 : CLS_CONV3_BWD_DATA) : (x6 ? CLS_CONV3_FWD_X6 : CLS_CONV3_FWD));
-    if (x6s) return {ConvKernel::x6_strip, cls, true, arith, (sel.taps && g.Cin == 25 && wf.h3t) ? wf.h3t : wsplit, sel};
+    if (x6s) return {ConvKernel::x6_strip, cls, true, arith, (sel.taps && g.Cin == 25 && o.h3t) ? FragKind::h3t : wsplit, sel};
     if (x6r) return {ConvKernel::x6_rowtile, cls, true, arith, wsplit, {}};
-    const StripSel s32 = (f.strip && wf.f32 && !split) ? strip_select(g, gate, 0) : StripSel();      // (split: no strip kernel took g above, so the fp32 one does not either)
-    if (s32.k != StripKernel::none) return {ConvKernel::mfma_strip, cls, true, 0, wf.f32, s32};
-    if (f.mfma && wf.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, wf.f32, {}};
+    const StripSel s32 = (f.strip && o.f32 && !split) ? strip_select(g, o.gate, 0) : StripSel();      // (split: no strip kernel took g above, so the fp32 one does not either)
+    if (s32.k != StripKernel::none) return {ConvKernel::mfma_strip, cls, true, 0, FragKind::f32, s32};
+    if (f.mfma && o.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, FragKind::f32, {}};
     // the general matrix route: what no matrix, split-operand or dedicated kernel took above (an exotic geometry returned before).  It does not report amax
-    if (f.gemm && dedicated && gemm_conv_supported(g)) return {ConvKernel::gemm, cls, false, 0, nullptr, {}};
-    return {ConvKernel::direct, cls, false, 0, nullptr, {}};
+    if (f.gemm && dedicated && gemm_conv_supported(g)) return {ConvKernel::gemm, cls, false, 0, FragKind::none, {}};
+    return {ConvKernel::direct, cls, false, 0, FragKind::none, {}};
 }
-// the routed launch (w: the filter as the direct kernels read it)
-static int conv_launch(const ConvRoute& r, const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias,
+static int census_slot(const ConvRoute& r) { return r.k == ConvKernel::direct ? 0 : (r.k == ConvKernel::gemm ? 1 : -1); }      // (as census_slot of a backward-filter route)
+// the routed launch (w: the filter as the direct kernels read it; wfrag: its fragments of the kind the route chose)
+static int conv_launch(const ConvRoute& r, const ConvGeom& g, const float* x, const float* gate, const float* w, const float* wfrag, const float* bias,
                        const float* skip, float* y, const Amax& am, hipStream_t s)
 {
     switch (r.k) {
     case ConvKernel::up_bwd_data: return conv3d_up_bwd_data(g, x, w, nullptr, y, am.y, s);
     case ConvKernel::up: return conv3d_up_forward(g, x, w, bias, y, s);
     case ConvKernel::cin1: return conv3d_cin1_forward(g, x, w, bias, y, am.y, s);
-    case ConvKernel::x6_strip: case ConvKernel::mfma_strip: return conv_strip_forward(r.strip, x, gate, r.wfrag, bias, skip, y, am, s);
-    case ConvKernel::x6_rowtile: return x6_conv_rowtile_forward(g, x, gate, r.wfrag, bias, skip, y, r.arith, am, s);
-    case ConvKernel::mfma_rowtile: return mfma_conv_forward(g, x, gate, r.wfrag, bias, skip, y, am, s);
+    case ConvKernel::x6_strip: case ConvKernel::mfma_strip: return conv_strip_forward(r.strip, x, gate, wfrag, bias, skip, y, am, s);
+    case ConvKernel::x6_rowtile: return x6_conv_rowtile_forward(g, x, gate, wfrag, bias, skip, y, r.arith, am, s);
+    case ConvKernel::mfma_rowtile: return mfma_conv_forward(g, x, gate, wfrag, bias, skip, y, am, s);
     case ConvKernel::gemm: return gemm_conv_forward(g, x, gate, w, bias, skip, y, s);
     default: return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
     }
 }
-// am.x / am.w: amax slots of x (one per sample) and of the layer's filter columns (H3 kernels); am.y: per-sample slots that must hold the output's amax afterwards
-static int conv_fwd(const probav_engine* e, const ConvGeom& g, const float* x, const float* gate, const float* w,
-                    const Frags& wf, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s)
-{
-    const ConvRoute r = conv_route(e->fam, g, gate, bias, skip, wf, am);
-    if (r.k == ConvKernel::direct || r.k == ConvKernel::gemm) ++const_cast<probav_engine*>(e)->launched[r.k == ConvKernel::gemm ? 1 : 0];
-    int rc;
-    { ProfScope ps(e, r.cls, geom_macs(g), s); rc = conv_launch(r, g, x, gate, w, bias, skip, y, am, s); }
-    if (rc == PROBAV_OK && am.y && !r.reports) rc = amax_tensor(y, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, am.y, s);
-    return rc;
-}
 
 #define CK(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-// a slab region of the backward pass (make_plan: Plan::slab) inside the scratch S; p == nullptr: the pass asked for a region that the plan did not lay out
-struct Slab { float* p; size_t floats; };
-static Slab slab_at(const Plan& p, float* S, const Plan::Region& r)
+// What a pass hands over with a launch must be what its entry of the launch list states: the plan and the census have routed and sized the launch by the entry
+// (weights, bias and fragments are the entry's own: conv_fwd / conv_wgrad take them from its layer).  A host comparison, made before anything is launched
+static int operands_agree(const Launch& L, LaunchKind kind, const float* gate, const float* skip, const Amax& am)
 {
-    return r.off == Plan::Region::none ? Slab{nullptr, 0} : Slab{S + p.partial + r.off, r.floats};
+    const Operands& o = L.o;
+    if (L.kind == kind && (gate != nullptr) == o.gate && (skip != nullptr) == o.skip && (am.x && am.w) == o.am_in && (am.y != nullptr) == o.am_out) return PROBAV_OK;
+    static const char* const roles[] = {"residConv1", "residConv2", "residConv3", "the residual path", "mainConv1", "expConv", "decConv", "the pointwise pair", "normConv", "convReducer", "upscaleConv1", "expConv (recomputed)"};
+    set_error((std::string("probav engine: the ") + (L.back ? "reverse" : "forward") + " pass's " + (kind == LaunchKind::wgrad ? "backward-filter" : "convolution") + " launch of " + roles[(int)L.role] +
+               " [" + std::to_string(L.i) + "] " + (L.kind == LaunchKind::none ? "is not in the launch list" : "has other operands than the launch list states")).c_str(), hipSuccess);
+    return PROBAV_EINVAL;
 }
-static int slab_fits(const Slab& r, size_t need)
+// Where a pass's launches find what the layer tables determine: the parameter-derived tensors and, reverse pass, the gradient and slab areas.  Copied into queued launches
+struct PassBufs { const probav_engine* e; Derived dv; const float* params; float *dweff2, *grads, *slabs; };
+// am.x / am.w: amax slots of x (one per sample) and of the layer's filter columns (H3 kernels); am.y: per-sample slots that must hold the output's amax afterwards
+static int conv_fwd(const PassBufs& b, const Launch& L, const float* x, const float* gate, const float* skip, float* y, const Amax& am, hipStream_t s)
 {
-    if (!r.p) { set_error("probav_backward: more backward-filter launches than make_plan laid out slab regions for", hipSuccess); return PROBAV_EINVAL; }
-    if (need > r.floats) { set_error("probav_backward: a backward-filter launch needs a larger slab region than make_plan laid out", hipSuccess); return PROBAV_EINVAL; }
-    return PROBAV_OK;
+    const probav_engine* e = b.e;
+    const ConvGeom& g = L.g;
+    CK(operands_agree(L, LaunchKind::conv, gate, skip, am));
+    const WnLayer& wn = e->layers[L.li].wn;
+    const float* w = (L.dir == 1 ? b.dv.weffT : b.dv.weff) + wn.w_off;
+    const float* bias = L.o.bias ? b.params + wn.b_off : nullptr;
+    const ConvRoute r = conv_route(e->fam, g, L.o);
+    if (census_slot(r) >= 0) ++const_cast<probav_engine*>(e)->launched[census_slot(r)];
+    // the fragments of the kind the route chose, in the packed region (a route only chooses a kind that L.o states, so the layer has it in direction L.dir)
+    const ConvFrags nofrags, &c = L.dir < 0 ? nofrags : e->layers[L.li].pk[L.dir];
+    const long foff = r.frag == FragKind::f32 ? c.f32 : (r.frag == FragKind::x6 ? c.x6 : (r.frag == FragKind::h3 ? c.h3 : (r.frag == FragKind::h3t ? c.h3t : -1)));
+    const float* wfrag = foff >= 0 ? b.dv.wpack + foff : nullptr;
+    int rc;
+    { ProfScope ps(e, r.cls, geom_macs(g), s); rc = conv_launch(r, g, x, gate, w, wfrag, bias, skip, y, am, s); }
+    if (rc == PROBAV_OK && am.y && !r.reports) rc = amax_tensor(y, (size_t)g.Ho * g.Wo * g.To * g.Cout, g.N, am.y, s);
+    return rc;
 }
-static int conv_wgrad(const probav_engine* e, const ConvGeom& g, const float* x, const float* dy, const float* gate,
-                      float* dw, float* db, const Slab& part, const Amax& am, hipStream_t s)
+static int conv_wgrad(const PassBufs& b, const Launch& L, const float* x, const float* dy, const float* gate, const Amax& am, hipStream_t s)
 {
-    const WgradRoute r = wgrad_route(e->fam, g, am);
-    CK(slab_fits(part, wgrad_slab_floats(r, g)));
-    if (r.k == WgradKernel::gemm) ++const_cast<probav_engine*>(e)->launched[3];
-    else if (r.k == WgradKernel::direct && !(e->fam.mfma && conv3d_direct_wgrad_is_tuned(g))) ++const_cast<probav_engine*>(e)->launched[2];
+    const probav_engine* e = b.e;
+    const ConvGeom& g = L.g;
+    CK(operands_agree(L, LaunchKind::wgrad, gate, nullptr, am));
+    const WgradRoute r = wgrad_route(e->fam, g, L.o);
+    if (wgrad_slab_floats(r, g) > L.slab.floats) { set_error("probav_backward: a backward-filter launch needs a larger slab region than make_plan laid out", hipSuccess); return PROBAV_EINVAL; }
+    if (census_slot(r) >= 0) ++const_cast<probav_engine*>(e)->launched[census_slot(r)];
+    const WnLayer& wn = e->layers[L.li].wn;
+    float *dw = b.dweff2 + wn.w_off, *db = b.grads + wn.b_off, *part = b.slabs + L.slab.off;
     ProfScope ps(e, r.cls, geom_macs(g), s);
     switch (r.k) {
-    case WgradKernel::x6: return x6_conv_wgrad(g, x, dy, gate, dw, db, part.p, r.arith, am, s);
-    case WgradKernel::mfma: return mfma_conv_wgrad(g, x, dy, gate, dw, db, part.p, s);
-    case WgradKernel::gemm: return gemm_conv_wgrad(g, x, dy, gate, dw, db, part.p, s);
-    default: return conv3d_direct_wgrad(g, x, dy, gate, dw, db, part.p, s);
+    case WgradKernel::x6: return x6_conv_wgrad(g, x, dy, gate, dw, db, part, r.arith, am, s);
+    case WgradKernel::mfma: return mfma_conv_wgrad(g, x, dy, gate, dw, db, part, s);
+    case WgradKernel::gemm: return gemm_conv_wgrad(g, x, dy, gate, dw, db, part, s);
+    default: return conv3d_direct_wgrad(g, x, dy, gate, dw, db, part, s);
     }
 }
 
@@ -546,17 +643,18 @@ static int pw_forward_launch(const probav_engine* e, int i, const float* wpack, 
 }
 // backward of block i: dT = d loss / d dec_i, dOut = d loss / d act[i+1] (the skip path) -> dX, the weight (into dweff2) and bias (into grads)
 // gradients of expConv_i and decConv_i; adt / ay: amax slots of dT / dX (H3)
-static int pw_backward_launch(const probav_engine* e, int i, const float* wpack, const AmaxSlots& A, const float* params, float* grads,
-                              float* dweff2, const float* x, const float* dT, const float* dOut, float* dX, const Slab& part, long nvox,
+static int pw_backward_launch(const PassBufs& b, const Launch& L, const AmaxSlots& A, const float* x, const float* dT, const float* dOut, float* dX,
                               unsigned* adt, unsigned* ay, hipStream_t s)
 {
-    const int D = e->cfg.dec_channels;
-    CK(slab_fits(part, mfma_pw_backward_slab_floats(D)));
+    const probav_engine* e = b.e;
+    const int i = L.i, D = e->cfg.dec_channels;
+    const long nvox = in_voxels(L.g);
+    if (L.kind != LaunchKind::fused || mfma_pw_backward_slab_floats(D) > L.slab.floats) { set_error("probav_backward: the fused pointwise pair's launch is not in the launch list, or its slab region is too small", hipSuccess); return PROBAV_EINVAL; }
     const WnLayer &we = e->layers[e->iExp[i]].wn, &wd = e->layers[e->iDec[i]].wn;
     PwAmax m;
     if (e->fam.arith == 2) { m.x = A.act(i); m.w1 = A.w(e->iExp[i]); m.w2 = A.w(e->iDec[i]); m.w1r = A.wrow(e->iExp[i]); m.b1 = A.b(e->iExp[i]); m.dt = adt; m.y = ay; }
-    return pw_backward(e->fam.arith, block_frags(e, wpack, i), x, dT, dOut, params + we.b_off, dX, dweff2 + we.w_off, dweff2 + wd.w_off,
-                       grads + we.b_off, grads + wd.b_off, part.p, nvox, nvox / A.B, D, m, s);
+    return pw_backward(e->fam.arith, block_frags(e, b.dv.wpack, i), x, dT, dOut, b.params + we.b_off, dX, b.dweff2 + we.w_off, b.dweff2 + wd.w_off,
+                       b.grads + we.b_off, b.grads + wd.b_off, b.slabs + L.slab.off, nvox, nvox / A.B, D, m, s);
 }
 
 extern "C" {
@@ -842,7 +940,8 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     const int R = c.num_res_blocks;
     auto weff = [&](int li) { return dv.weff + e->layers[li].wn.w_off; };
     auto bias = [&](int li) { return params + e->layers[li].wn.b_off; };
-    auto frag = [&](int li) { return frags(e, dv.wpack, li, 0); };
+    const PassBufs pb = {e, dv, params, nullptr, nullptr, nullptr};
+    auto fwd = [&](Role role, int i = 0) { return launch_at(p, role, LaunchKind::conv, false, i); };
     // amax slots (H3 arithmetic, impl 4): every tensor an H3 kernel reads has its largest magnitude in a slot by then
     const bool h3 = e->fam.arith == 2;
     const AmaxSlots A(e, p, W, dv.wslots);
@@ -861,35 +960,36 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     SideGuard side_guard((side_stream_disabled() || e->side_mode == 0) ? nullptr : engine_side(e), s);
     {
         hipStream_t rs = reduce_fork(s);
-        if (resid_path_fused(e)) {                         // the three layers as one launch (kernels_direct.hip); family 0 keeps the generic direct kernels
-            CK(resid_path_forward(B, n.resid1.Hi, n.resid1.Cin, W + p.mn, weff(e->iResid1), bias(e->iResid1), weff(e->iResid2), bias(e->iResid2), weff(e->iResid3), bias(e->iResid3),
+        const Launch path = launch_at(p, Role::resid_path, LaunchKind::fused, false);
+        if (path.kind == LaunchKind::fused) {              // the three layers as one launch (kernels_direct.hip); family 0 keeps the generic direct kernels
+            CK(resid_path_forward(B, path.g.Hi, path.g.Cin, W + p.mn, weff(e->iResid1), bias(e->iResid1), weff(e->iResid2), bias(e->iResid2), weff(e->iResid3), bias(e->iResid3),
                                   W + p.r1, W + p.r2, W + p.r3, rs));
         } else {
-        CK(conv_fwd(e, n.resid1, W + p.mn, nullptr, weff(e->iResid1), frag(e->iResid1), bias(e->iResid1), nullptr, W + p.r1, Amax(), rs));
-        CK(conv_fwd(e, n.resid2, W + p.r1, nullptr, weff(e->iResid2), frag(e->iResid2), bias(e->iResid2), nullptr, W + p.r2, Amax(), rs));
-        CK(conv_fwd(e, n.resid3, W + p.r2, nullptr, weff(e->iResid3), frag(e->iResid3), bias(e->iResid3), nullptr, W + p.r3, Amax(), rs));
+        CK(conv_fwd(pb, fwd(Role::resid1), W + p.mn, nullptr, nullptr, W + p.r1, Amax(), rs));
+        CK(conv_fwd(pb, fwd(Role::resid2), W + p.r1, nullptr, nullptr, W + p.r2, Amax(), rs));
+        CK(conv_fwd(pb, fwd(Role::resid3), W + p.r2, nullptr, nullptr, W + p.r3, Amax(), rs));
         }
     }
-    CK(conv_fwd(e, n.main, W + p.xn, nullptr, weff(e->iMain), frag(e->iMain), bias(e->iMain), nullptr, W + p.act[0], amx(nullptr, e->iMain, A.act(0)), s));
+    CK(conv_fwd(pb, fwd(Role::main), W + p.xn, nullptr, nullptr, W + p.act[0], amx(nullptr, e->iMain, A.act(0)), s));
     for (int i = 0; i < R; ++i) {
-        if (e->fam.pw_fused) {
+        const Launch pair = launch_at(p, Role::pair, LaunchKind::fused, false, i);
+        if (pair.kind == LaunchKind::fused) {
             // fused expConv + ReLU + decConv: the 256-channel tensor never leaves the accumulators
-            const long nvox = in_voxels(n.exp);
             ProfScope ps(e, e->fam.x6 ? CLS_PW_FWD_X6 : CLS_PW_FWD, geom_macs(n.exp) + geom_macs(n.dec), s);
-            CK(pw_forward_launch(e, i, dv.wpack, A, params, W + p.act[i], W + p.dec[i], nvox, A.dec(i), s));
+            CK(pw_forward_launch(e, i, dv.wpack, A, params, W + p.act[i], W + p.dec[i], in_voxels(pair.g), A.dec(i), s));
         } else {
-            CK(conv_fwd(e, n.exp, W + p.act[i], nullptr, weff(e->iExp[i]), frag(e->iExp[i]), bias(e->iExp[i]), nullptr, W + p.H, Amax(), s));
-            CK(conv_fwd(e, n.dec, W + p.H, nullptr, weff(e->iDec[i]), frag(e->iDec[i]), bias(e->iDec[i]), nullptr, W + p.dec[i], amx(nullptr, e->iDec[i], A.dec(i)), s));
+            CK(conv_fwd(pb, fwd(Role::exp, i), W + p.act[i], nullptr, nullptr, W + p.H, Amax(), s));
+            CK(conv_fwd(pb, fwd(Role::dec, i), W + p.H, nullptr, nullptr, W + p.dec[i], amx(nullptr, e->iDec[i], A.dec(i)), s));
         }
-        CK(conv_fwd(e, n.norm, W + p.dec[i], nullptr, weff(e->iNorm[i]), frag(e->iNorm[i]), bias(e->iNorm[i]), W + p.act[i], W + p.act[i + 1], amx(A.dec(i), e->iNorm[i], A.act(i + 1)), s));
+        CK(conv_fwd(pb, fwd(Role::norm, i), W + p.dec[i], nullptr, W + p.act[i], W + p.act[i + 1], amx(A.dec(i), e->iNorm[i], A.act(i + 1)), s));
     }
     const float* cur = W + p.act[R];
     const unsigned* acur = A.act(R);
-    for (size_t k = 0; k < n.red.size(); ++k) {
-        CK(conv_fwd(e, n.red[k], cur, nullptr, weff(e->iRed[k]), frag(e->iRed[k]), bias(e->iRed[k]), nullptr, W + p.red[k], amx(acur, e->iRed[k], A.red((int)k)), s));
-        cur = W + p.red[k]; acur = A.red((int)k);
+    for (int k = 0; k < (int)n.red.size(); ++k) {
+        CK(conv_fwd(pb, fwd(Role::red, k), cur, nullptr, nullptr, W + p.red[k], amx(acur, e->iRed[k], A.red(k)), s));
+        cur = W + p.red[k]; acur = A.red(k);
     }
-    CK(conv_fwd(e, n.up, cur, nullptr, weff(e->iUp), frag(e->iUp), bias(e->iUp), nullptr, W + p.up, amx(acur, e->iUp, nullptr), s));
+    CK(conv_fwd(pb, fwd(Role::up), cur, nullptr, nullptr, W + p.up, amx(acur, e->iUp, nullptr), s));
     CK(reduce_join(s));                                                       // the residual path has arrived
     CK(tail_forward(W + p.up, W + p.r3, y, B, n.up.Ho, c.scale, c.mean, c.std, s));
     return PROBAV_OK;
@@ -930,17 +1030,13 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     const Derived dv = derived(e, p, W, WC);
     const int R = e->cfg.num_res_blocks;
     auto weff = [&](int li) { return dv.weff + e->layers[li].wn.w_off; };
-    auto weffT = [&](int li) { return dv.weffT + e->layers[li].wn.w_off; };
-    auto fragT = [&](int li) { return frags(e, dv.wpack, li, 1); };
-    // amax slots of the gradient tensors, in launch order (the forward pass left those of the weights and activations)
+    const PassBufs pb = {e, dv, params, S + p.dweff2, grads, S + p.partial};
+    auto filter = [&](Role role, int i = 0) { return launch_at(p, role, LaunchKind::wgrad, true, i); };
+    auto data = [&](Role role, int i = 0) { return launch_at(p, role, LaunchKind::conv, true, i); };
+    // amax slots of the gradient tensors, in list order (the forward pass left those of the weights and activations): k-th of the arrays the launch's output takes
     const bool h3 = e->fam.arith == 2;
     const AmaxSlots A(e, p, W, dv.wslots, S);
-    int nback = 0;
-    auto new_slot = [&](unsigned*& slot) -> int {
-        if (h3 && nback >= p.n_back) { set_error("probav_backward: the pass takes more per-sample amax slots than make_plan counted", hipSuccess); return PROBAV_EINVAL; }
-        slot = h3 ? A.back(nback++) : nullptr;
-        return PROBAV_OK;
-    };
+    auto slot_of = [&](const Launch& L, int k = 0) -> unsigned* { return h3 && k < L.slots ? A.back(L.slot + k) : nullptr; };
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wrow(li); m.y = ay; } return m; };   // backward-data: the matrix' columns are the layer's INPUT channels
     if (e->fwd_unfused != !e->fam.pw_fused) {
         set_error("probav_backward: the kernel family changed between forward and backward in a way that changes the workspace layout (impl 0 <-> >= 1)", hipSuccess);
@@ -953,7 +1049,6 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     // (the reverse pass's per-sample amax slots are cleared by tail_bwd_kernel, its first launch)
     auto dweff = [&](int li) { return S + p.dweff2 + e->layers[li].wn.w_off; };
     auto dbias = [&](int li) { return grads + e->layers[li].wn.b_off; };
-    auto slab = [&](const Plan::Region& r) { return slab_at(p, S, r); };
     // (defer: the slab sums and the small launches that only the weight-norm backward waits for are queued and leave in a few flushes -- one event record
     // on the launch stream per flush instead of one per launch, probav_common.h)
     SideGuard side_guard((side_stream_disabled() || e->side_mode == 0) ? nullptr : engine_side(e), s, 1);
@@ -961,57 +1056,59 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     CK(tail_backward(dy, S + p.dtail, B, n.up.Ho, e->cfg.scale, e->cfg.std, s, h3 ? A.back(0) : nullptr, h3 ? p.n_amax - p.amax_bwd : 0));
     // low-frequency residual path (models/modelsTF.py:45-53), last layer first: beside the main chain, nothing below depends on it until the weight-norm
     // backward -- queued and launched at the first flush, when the launch stream has its next kernels
+    const Launch path = launch_at(p, Role::resid_path, LaunchKind::fused, true);
     {
-        const Slab rp3 = slab(p.slab.resid3), rp2 = slab(p.slab.resid2), rp1 = slab(p.slab.resid1);
-        // (the queued launch runs later, from reduce_flush: everything it needs is captured BY VALUE -- pointers, geometries and extents, nothing of this frame)
-        const ConvGeom g3 = n.resid3, g2 = n.resid2, g1 = n.resid1;
-        const float *r2 = W + p.r2, *r1 = W + p.r1, *mn = W + p.mn, *wT3 = weffT(e->iResid3), *wT2 = weffT(e->iResid2);
-        const Frags fT3 = fragT(e->iResid3), fT2 = fragT(e->iResid2);
+        // (the queued launch runs later, from reduce_flush: everything it needs is captured BY VALUE -- pointers, launch-list entries and extents, nothing of this frame)
+        const float *r2 = W + p.r2, *r1 = W + p.r1, *mn = W + p.mn;
         float *dtail = S + p.dtail, *dr2 = S + p.dr2, *dr1 = S + p.dr1;
-        float *dw3 = dweff(e->iResid3), *db3 = dbias(e->iResid3), *dw2 = dweff(e->iResid2), *db2 = dbias(e->iResid2), *dw1 = dweff(e->iResid1), *db1 = dbias(e->iResid1);
-        const float *w2r = weff(e->iResid2), *w3r = weff(e->iResid3);
-        if (resid_path_fused(e)) {
-            CK(slab_fits(rp3, resid_path_slab_floats(B, g1.Cin)));
+        if (path.kind == LaunchKind::fused) {
+            if (resid_path_slab_floats(B, path.g.Cin) > path.slab.floats) { set_error("probav_backward: the fused residual path needs a larger slab region than make_plan laid out", hipSuccess); return PROBAV_EINVAL; }
+            float *dw3 = dweff(e->iResid3), *db3 = dbias(e->iResid3), *dw2 = dweff(e->iResid2), *db2 = dbias(e->iResid2), *dw1 = dweff(e->iResid1), *db1 = dbias(e->iResid1);
+            const float *w2r = weff(e->iResid2), *w3r = weff(e->iResid3);
+            float* const slabs = pb.slabs + path.slab.off;
             float* const dr1_out = dx ? dr1 : nullptr;         // the gated gradient at residConv1, which the kernel otherwise keeps in LDS: only the input gradient reads it
-            CK(reduce_later(s, [=](hipStream_t rs) -> int {    // one launch + one slab sum (residConv3's region holds the patches' slabs: make_plan sized it)
-                return resid_path_backward(B, g1.Hi, g1.Cin, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, rp3.p, rs, dr1_out); }));
-        } else
+            CK(reduce_later(s, [=](hipStream_t rs) -> int {    // one launch + one slab sum (the region holds the patches' slabs: make_plan sized it)
+                return resid_path_backward(B, path.g.Hi, path.g.Cin, mn, r1, r2, dtail, w2r, w3r, dw1, db1, dw2, db2, dw3, db3, slabs, rs, dr1_out); }));
+        } else {
+        const Launch f3 = filter(Role::resid3), d3 = data(Role::resid3), f2 = filter(Role::resid2), d2 = data(Role::resid2), f1 = filter(Role::resid1);
         CK(reduce_later(s, [=](hipStream_t rs) -> int {
-            CK(conv_wgrad(e, g3, r2, dtail, nullptr, dw3, db3, rp3, Amax(), rs));
-            CK(conv_fwd(e, bwd_data_geom(g3), dtail, nullptr, wT3, fT3, nullptr, nullptr, dr2, Amax(), rs));
-            CK(conv_wgrad(e, g2, r1, dr2, nullptr, dw2, db2, rp2, Amax(), rs));
-            CK(conv_fwd(e, bwd_data_geom(g2), dr2, nullptr, wT2, fT2, nullptr, nullptr, dr1, Amax(), rs));
-            CK(conv_wgrad(e, g1, mn, dr1, r1, dw1, db1, rp1, Amax(), rs));
+            CK(conv_wgrad(pb, f3, r2, dtail, nullptr, Amax(), rs));
+            CK(conv_fwd(pb, d3, dtail, nullptr, nullptr, dr2, Amax(), rs));
+            CK(conv_wgrad(pb, f2, r1, dr2, nullptr, Amax(), rs));
+            CK(conv_fwd(pb, d2, dr2, nullptr, nullptr, dr1, Amax(), rs));
+            CK(conv_wgrad(pb, f1, mn, dr1, r1, Amax(), rs));
             return PROBAV_OK;
         }));
+        }
     }
     // upscale + reducers (models/modelsTF.py:152-164)
     const int nred = (int)n.red.size();
     float* cur = S + p.gA;
     float* oth = S + p.gB;                          // (the unfused block path below ping-pongs between `cur` and this)
-    unsigned* acur; CK(new_slot(acur));             // amax slot of the tensor `cur` holds
+    unsigned* acur;                                 // amax slot of the tensor `cur` holds
     {
-        const ConvGeom gu = n.up;
-        const Slab up_part = slab(p.slab.up);
+        const Launch fu = filter(Role::up), du = data(Role::up);
         const float* const upx = W + p.red[nred - 1];
-        float *const updy = S + p.dtail, *const updw = dweff(e->iUp), *const updb = dbias(e->iUp);
+        float* const updy = S + p.dtail;
         CK(reduce_later(s, [=](hipStream_t rs) -> int {       // (only the weight-norm backward reads it; captured by value: it runs from a later flush)
-            return conv_wgrad(e, gu, upx, updy, nullptr, updw, updb, up_part, Amax(), rs); }));
-        CK(conv_fwd(e, bwd_data_geom(gu), S + p.dtail, nullptr, weffT(e->iUp), fragT(e->iUp), nullptr, nullptr, cur, amx(nullptr, e->iUp, acur), s));
+            return conv_wgrad(pb, fu, upx, updy, nullptr, Amax(), rs); }));
+        acur = slot_of(du);
+        CK(conv_fwd(pb, du, S + p.dtail, nullptr, nullptr, cur, amx(nullptr, e->iUp, acur), s));
     }
     for (int k = nred - 1; k >= 0; --k) {
+        const Launch dr = data(Role::red, k);
         const ConvGeom& gr = n.red[k];
         const float* xin = k ? W + p.red[k - 1] : W + p.act[R];
         // the backward-filter only feeds the weight-norm backward at the very end: side stream; every tensor it reads stays untouched
         // (each stage of the chain writes a buffer of its own)
         { Amax m; if (h3) { m.x = k ? A.red(k - 1) : A.act(R); m.w = acur; }
-          CK(conv_wgrad(e, gr, xin, cur, W + p.red[k], dweff(e->iRed[k]), dbias(e->iRed[k]), slab(p.slab.red[k]), m, e->side_mode >= 2 ? reduce_fork(s) : s)); }
+          CK(conv_wgrad(pb, filter(Role::red, k), xin, cur, W + p.red[k], m, e->side_mode >= 2 ? reduce_fork(s) : s)); }
         float* outA = S + p.gred[2 * k];
         float* outB = S + p.gred[2 * k + 1];
-        unsigned* aoth; CK(new_slot(aoth));
-        CK(conv_fwd(e, bwd_data_geom(gr), cur, W + p.red[k], weffT(e->iRed[k]), fragT(e->iRed[k]), nullptr, nullptr, outA, amx(acur, e->iRed[k], aoth), s));
-        if (gr.reflect_hw) {
-            CK(new_slot(acur));                     // the folded gradient is a new tensor
+        unsigned* aoth = slot_of(dr);
+        CK(conv_fwd(pb, dr, cur, W + p.red[k], nullptr, outA, amx(acur, e->iRed[k], aoth), s));
+        if (dr.slots == 2) {                        // mirrored pads: the folded gradient is a new tensor
+            acur = slot_of(dr, 1);
             if (gr.ph == 1 && !gr.reflect_t) CK(reflect_fold(outA, outB, B, gr.Hi, gr.Wi, gr.Ti * gr.Cin, acur, s));
             else {
                 CK(reflect_fold3(outA, outB, B, gr.Hi, gr.Wi, gr.Ti, gr.Cin, gr.ph, gr.pw, gr.reflect_t ? gr.pt : 0, s));
@@ -1024,29 +1121,28 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         }
     }
     // residual blocks (models/modelsTF.py:177-189), last first.  cur = d loss / d act[i+1]
-    const ConvGeom &ge = n.exp, &gd = n.dec, &gn = n.norm;
+    const ConvGeom &ge = n.exp, &gd = n.dec;
     CK(reduce_flush(s));                                   // the residual path, the upscale layer's backward-filter, the reducers' slab sums: one fork
     for (int i = R - 1; i >= 0; --i) {
         float* gDec = S + p.gDec;
         float* Hbuf = S + p.Hb;
         float* dH = S + p.dH;
-        const int le = e->iExp[i], ld = e->iDec[i], ln = e->iNorm[i];
         // normConv_i: d loss/d w, then d loss/d dec_i
-        const bool fusedp = e->fam.pw_fused;
+        const Launch pair = launch_at(p, Role::pair, LaunchKind::fused, true, i), dn = data(Role::norm, i);
+        const bool fusedp = pair.kind == LaunchKind::fused;
         { Amax m; if (h3) { m.x = A.dec(i); m.w = acur; }
           // (from the second block on, the last thing enqueued on s was the previous block's pointwise backward, whose slab sums forked right behind it)
-          CK(conv_wgrad(e, gn, W + p.dec[i], cur, nullptr, dweff(ln), dbias(ln), slab(p.slab.norm[i]), m,
+          CK(conv_wgrad(pb, filter(Role::norm, i), W + p.dec[i], cur, nullptr, m,
                         (fusedp && e->side_mode >= 2) ? (i < R - 1 ? reduce_fork_adjacent(s) : reduce_fork(s)) : s)); }
         if (fusedp) oth = S + p.gblk[i];                   // this block's dX goes to its own buffer: `cur` stays intact for the late backward-filter
-        unsigned* agdec; CK(new_slot(agdec));
-        CK(conv_fwd(e, bwd_data_geom(gn), cur, nullptr, weffT(ln), fragT(ln), nullptr, nullptr, gDec, amx(acur, ln, agdec), s));
+        unsigned* agdec = slot_of(dn);
+        CK(conv_fwd(pb, dn, cur, nullptr, nullptr, gDec, amx(acur, e->iNorm[i], agdec), s));
         if (fusedp) {
             // fused: H recompute, dH, ReLU gate, dX (+ skip), dW1, dW2, db1, db2 -- nothing 256-wide touches HBM
-            const long nvox = in_voxels(ge);
-            unsigned* anew; CK(new_slot(anew));              // amax slot of dX
+            unsigned* anew = slot_of(pair);                  // amax slot of dX
             {   // (the class's bracket ends HERE: the flush below launches the batched slab sums on this stream, and they are no part of this class)
             ProfScope ps(e, e->fam.x6 ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, 2.0 * (geom_macs(ge) + geom_macs(gd)), s);   // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work
-            CK(pw_backward_launch(e, i, dv.wpack, A, params, grads, S + p.dweff2, W + p.act[i], gDec, cur, oth, slab(p.slab.pair[i]), nvox, agdec, anew, s));
+            CK(pw_backward_launch(pb, pair, A, W + p.act[i], gDec, cur, oth, agdec, anew, s));
             }
             float* tmp2 = cur; cur = oth; oth = tmp2;
             acur = anew;
@@ -1056,14 +1152,15 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
             continue;
         }
         // recompute H = relu(expConv_i(act[i])): the 256-channel tensor is never kept (1 KB/voxel/block)
-        CK(conv_fwd(e, ge, W + p.act[i], nullptr, weff(le), Frags(), params + e->layers[le].wn.b_off, nullptr, Hbuf, Amax(), s));
+        CK(conv_fwd(pb, data(Role::hidden, i), W + p.act[i], nullptr, nullptr, Hbuf, Amax(), s));
         // decConv_i
-        CK(conv_wgrad(e, gd, Hbuf, gDec, nullptr, dweff(ld), dbias(ld), slab(p.slab.dec[i]), Amax(), s));
-        CK(conv_fwd(e, bwd_data_geom(gd), gDec, nullptr, weffT(ld), fragT(ld), nullptr, nullptr, dH, Amax(), s));
+        CK(conv_wgrad(pb, filter(Role::dec, i), Hbuf, gDec, nullptr, Amax(), s));
+        CK(conv_fwd(pb, data(Role::dec, i), gDec, nullptr, nullptr, dH, Amax(), s));
         // expConv_i: ReLU gate (H > 0) applied where dH is consumed; skip path adds d loss/d act[i+1]
-        CK(conv_wgrad(e, ge, W + p.act[i], dH, Hbuf, dweff(le), dbias(le), slab(p.slab.exp[i]), Amax(), s));
-        unsigned* aoth; CK(new_slot(aoth));
-        CK(conv_fwd(e, bwd_data_geom(ge), dH, Hbuf, weffT(le), fragT(le), nullptr, cur, oth, amx(nullptr, le, aoth), s));
+        CK(conv_wgrad(pb, filter(Role::exp, i), W + p.act[i], dH, Hbuf, Amax(), s));
+        const Launch de = data(Role::exp, i);
+        unsigned* aoth = slot_of(de);
+        CK(conv_fwd(pb, de, dH, Hbuf, cur, oth, amx(nullptr, e->iExp[i], aoth), s));
         float* tmp = cur; cur = oth; oth = tmp;
         acur = aoth;
     }
@@ -1073,7 +1170,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     {
         ReduceSide* const ctx = side_guard.c;
         reduce_side_activate(nullptr);
-        const int rc = conv_wgrad(e, n.main, W + p.xn, cur, W + p.act[0], dweff(e->iMain), dbias(e->iMain), slab(p.slab.main), Amax(), s);
+        const int rc = conv_wgrad(pb, filter(Role::main), W + p.xn, cur, W + p.act[0], Amax(), s);
         reduce_side_activate(ctx);
         if (rc) return rc;
     }
@@ -1083,7 +1180,7 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
         // d r1 -- which has arrived with the join -- spread over the frames.  Fused residual path: dr1 holds the gated gradient; un-fused: the plain
         // backward-data output, gated here by r1 as its backward-filter gates it
         CK(input_grad(B, e->Hin, e->cfg.num_img_lr, e->cfg.in_channels, cur, W + p.act[0], weff(e->iMain), S + p.dr1,
-                      resid_path_fused(e) ? nullptr : W + p.r1, weff(e->iResid1), e->cfg.std, dx, s));
+                      path.kind == LaunchKind::fused ? nullptr : W + p.r1, weff(e->iResid1), e->cfg.std, dx, s));
     }
     { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_backward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, params, S + p.dweff2, dv.invn, grads, s)); }
     return PROBAV_OK;
@@ -1295,6 +1392,13 @@ static int op_pack(const ConvGeom& g, const float* w, hipStream_t s, int arith, 
 // skip exist matters.  impl 0 the direct kernel; impl 1 the MFMA row-tile kernel, 2 the strip kernel, 3 / 4 the x6 strip kernel (X6 / H3; the piece-ring form where it applies) or,
 // where the strip kernels do not apply, its row-tile form: what conv_route gives family `impl` behind the engine's dedicated kernels, anything else is refused
 enum class OpConvKernel { up, up_bwd_data, direct, routed, refused };
+// the operands of a single-operator call as the routes see them: every kind of filter fragment (the caller packs what the route chooses), and under impl 4 the inputs' amax
+static Operands op_operands(bool gate, bool bias, bool skip, int impl)
+{
+    Operands o;
+    o.gate = gate; o.bias = bias; o.skip = skip; o.f32 = o.x6 = o.h3 = o.h3t = true; o.am_in = impl == 4;
+    return o;
+}
 struct OpConvRoute { OpConvKernel k; ConvRoute r; };
 static OpConvRoute op_conv_route(const ConvGeom& g, bool gate, bool bias, bool skip, int impl)
 {
@@ -1302,11 +1406,7 @@ static OpConvRoute op_conv_route(const ConvGeom& g, bool gate, bool bias, bool s
     if (impl >= 1 && !gate && !skip && bias && conv3d_up_forward_supported(g)) return {OpConvKernel::up, {}};
     if (impl >= 1 && !gate && !skip && !g.relu && conv3d_up_bwd_data_supported(g)) return {OpConvKernel::up_bwd_data, {}};
     if (impl == 0) return {OpConvKernel::direct, {}};
-    // The route only asks WHICH operands exist (any address will do): the caller packs them
-    static const float some = 0.f;
-    Amax am;
-    if (impl == 4) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
-    const ConvRoute r = conv_route(make_family(impl, false), g, gate ? &some : nullptr, bias ? &some : nullptr, skip ? &some : nullptr, Frags{&some, &some, &some, &some}, am, false);
+    const ConvRoute r = conv_route(make_family(impl, false), g, op_operands(gate, bias, skip, impl), false);
     const bool documented = impl == 1 ? r.k == ConvKernel::mfma_rowtile : (impl == 2 ? r.k == ConvKernel::mfma_strip : r.k == ConvKernel::x6_strip || r.k == ConvKernel::x6_rowtile);
     return {documented ? OpConvKernel::routed : OpConvKernel::refused, r};
 }
@@ -1324,7 +1424,7 @@ int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* g
     if (o.k == OpConvKernel::up_bwd_data) return conv3d_up_bwd_data(g, x, w, bias, y, nullptr, s);
     if (o.k == OpConvKernel::direct) return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
     if (o.k == OpConvKernel::refused) { set_error("probav_conv3d_forward: geometry not supported by this MFMA kernel", hipSuccess); return PROBAV_EINVAL; }
-    ConvRoute r = o.r;
+    const ConvRoute& r = o.r;
     Amax am;
     CK(op_scratch());
     if (impl == 4) {
@@ -1333,8 +1433,7 @@ int probav_conv3d_forward(const int32_t geom[17], const float* x, const float* g
         am.x = g_op.amax; am.w = g_op.amax + 2 * g.N; am.y = g_op.amax + g.N;
     }
     CK(op_pack(g, w, s, r.arith, r.strip.taps));
-    r.wfrag = g_op.frag;
-    return conv_launch(r, g, x, gate, w, bias, skip, y, am, s);
+    return conv_launch(r, g, x, gate, w, g_op.frag, bias, skip, y, am, s);
 }
 
 // The kernel family that serves a single-operator backward-filter call (impl names a kernel here, not an engine family: 2 is the direct kernel, so the call does not go
@@ -1472,14 +1571,12 @@ int probav_plan_conv(const int32_t geom[17], int impl, int gated, int has_skip, 
     if (!geom_ok(g)) { set_error("probav_plan_conv: bad geometry", hipSuccess); return PROBAV_EINVAL; }
     for (int i = 0; i < 8; ++i) report[i] = 0;
     int32_t &kernel = report[0], &nsplit = report[1], &nstrips = report[2], &SR = report[3], &nslot = report[4], &grid = report[5], &rvp = report[6];
-    static const float some = 0.f;
-    const float* gate = gated ? &some : nullptr;
     if (op == PROBAV_PLAN_OP_WGRAD) {
         int v[4] = {0, 0, 0, 0};
         switch (op_wgrad_kernel(g, impl)) {
         case OpWgradKernel::x6: {
             static const int32_t names[4] = {PROBAV_PLAN_NONE, PROBAV_PLAN_WG4, PROBAV_PLAN_WGRAD_X6_H3, PROBAV_PLAN_WGRAD_X6};
-            kernel = names[x6_wgrad_plan_ints(g, gate, impl == 4 ? 2 : 1, v)];
+            kernel = names[x6_wgrad_plan_ints(g, gated != 0, impl == 4 ? 2 : 1, v)];
             nsplit = v[0]; nstrips = v[1]; SR = v[2]; grid = v[3];
             break;
         }
@@ -1500,7 +1597,7 @@ int probav_plan_conv(const int32_t geom[17], int impl, int gated, int has_skip, 
     const StripSel& sel = o.r.strip;
     if (sel.k == StripKernel::cw4) {
         int v[5];
-        if (cw4_conv_plan_ints(g, gate, v)) { kernel = PROBAV_PLAN_CW4; nsplit = v[0]; nstrips = v[1]; SR = v[2]; nslot = v[3]; grid = v[4]; }
+        if (cw4_conv_plan_ints(g, gated != 0, v)) { kernel = PROBAV_PLAN_CW4; nsplit = v[0]; nstrips = v[1]; SR = v[2]; nslot = v[3]; grid = v[4]; }
         return PROBAV_OK;
     }
     kernel = sel.k == StripKernel::pp ? PROBAV_PLAN_PP : (sel.k == StripKernel::pstrip ? PROBAV_PLAN_PSTRIP : PROBAV_PLAN_STRIP);
@@ -1547,11 +1644,10 @@ int probav_plan_conv_gemm(const int32_t geom[17], int impl, int gated, int has_s
     if (rc) return rc;
     const ConvGeom g = geom_from(geom);
     const Family f = make_family(impl, false, true);
-    static const float some = 0.f;
-    Amax am;
-    if (impl == 4) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
+    // (every filter fragment exists as far as the route can tell, as in op_conv_route: a geometry a matrix kernel serves stays with it)
+    const Operands o = op_operands(gated != 0, op == PROBAV_PLAN_OP_FORWARD, has_skip != 0, impl);
     if (op == PROBAV_PLAN_OP_WGRAD) {
-        if (wgrad_route(f, g, am).k != WgradKernel::gemm) return PROBAV_OK;
+        if (wgrad_route(f, g, o).k != WgradKernel::gemm) return PROBAV_OK;
         int v[5];
         if (!gemm_wgrad_plan_ints(g, v)) return PROBAV_OK;
         for (int i = 0; i < 8; ++i) report[i] = 0;
@@ -1559,10 +1655,7 @@ int probav_plan_conv_gemm(const int32_t geom[17], int impl, int gated, int has_s
         return PROBAV_OK;
     }
     if (report[0] != PROBAV_PLAN_NONE) return PROBAV_OK;       // a kernel serves the single-operator call (impl 0: direct; the dedicated upscale pair, which that call takes with a bias too)
-    // (every filter fragment exists as far as the route can tell, as in op_conv_route: a geometry a matrix kernel serves stays with it)
-    const ConvRoute r = conv_route(f, g, gated ? &some : nullptr, op == PROBAV_PLAN_OP_FORWARD ? &some : nullptr, has_skip ? &some : nullptr,
-                                   Frags{&some, &some, &some, &some}, am, true);
-    if (r.k != ConvKernel::gemm) return PROBAV_OK;
+    if (conv_route(f, g, o, true).k != ConvKernel::gemm) return PROBAV_OK;
     int v[6];
     if (!gemm_conv_plan_ints(g, v)) return PROBAV_OK;
     for (int i = 0; i < 8; ++i) report[i] = 0;
@@ -1570,59 +1663,15 @@ int probav_plan_conv_gemm(const int32_t geom[17], int impl, int gated, int has_s
     return PROBAV_OK;
 }
 
-// The launches of one training step by route, walked over make_net in the order, and with the operands, of forward_impl / backward_impl
+// The launches of one training step by route: the launch list (step_launches), each entry routed as the passes route it
 int probav_engine_route_counts(const probav_engine* e, int batch, int32_t counts[4])
 {
     if (!e || !counts || batch < 1) { set_error("probav_engine_route_counts: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
     for (int i = 0; i < 4; ++i) counts[i] = 0;
-    const Net n = make_net(e, batch);
-    static const float some = 0.f;
-    const float* const P = &some;
-    Amax am;
-    if (e->fam.arith == 2) am.x = am.w = reinterpret_cast<const unsigned*>(&some);
-    auto fr = [&](int li, int dir) {
-        const ConvFrags& o = e->layers[li].pk[dir];
-        return Frags{o.f32 >= 0 ? P : nullptr, o.x6 >= 0 ? P : nullptr, o.h3 >= 0 ? P : nullptr, o.h3t >= 0 ? P : nullptr};
-    };
-    auto conv = [&](const ConvGeom& g, bool gate, bool bias, bool skip, const Frags& wf, bool reports_y) {
-        Amax m = am;
-        if (reports_y && e->fam.arith == 2) m.y = const_cast<unsigned*>(reinterpret_cast<const unsigned*>(&some));
-        const ConvKernel k = conv_route(e->fam, g, gate ? P : nullptr, bias ? P : nullptr, skip ? P : nullptr, wf, m).k;
-        if (k == ConvKernel::direct) ++counts[0];
-        if (k == ConvKernel::gemm) ++counts[1];
-    };
-    auto wgrad = [&](const ConvGeom& g) {
-        const WgradKernel k = wgrad_route(e->fam, g, am).k;
-        if (k == WgradKernel::direct && !(e->fam.mfma && conv3d_direct_wgrad_is_tuned(g))) ++counts[2];
-        if (k == WgradKernel::gemm) ++counts[3];
-    };
-    const bool fusedp = e->fam.pw_fused, fusedr = resid_path_fused(e);
-    const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
-    // forward
-    if (!fusedr) { conv(n.resid1, false, true, false, fr(e->iResid1, 0), false); conv(n.resid2, false, true, false, fr(e->iResid2, 0), false); conv(n.resid3, false, true, false, fr(e->iResid3, 0), false); }
-    conv(n.main, false, true, false, fr(e->iMain, 0), true);
-    for (int i = 0; i < R; ++i) {
-        if (!fusedp) { conv(n.exp, false, true, false, fr(e->iExp[i], 0), false); conv(n.dec, false, true, false, fr(e->iDec[i], 0), true); }
-        conv(n.norm, false, true, true, fr(e->iNorm[i], 0), true);
+    for (const Launch& L : step_launches(e, make_net(e, batch))) {
+        const int slot = L.kind == LaunchKind::conv ? census_slot(conv_route(e->fam, L.g, L.o)) : (L.kind == LaunchKind::wgrad ? census_slot(wgrad_route(e->fam, L.g, L.o)) : -1);
+        if (slot >= 0) ++counts[slot];
     }
-    for (int k = 0; k < nred; ++k) conv(n.red[k], false, true, false, fr(e->iRed[k], 0), true);
-    conv(n.up, false, true, false, fr(e->iUp, 0), false);
-    // backward
-    if (!fusedr) {
-        wgrad(n.resid3); conv(bwd_data_geom(n.resid3), false, false, false, fr(e->iResid3, 1), false);
-        wgrad(n.resid2); conv(bwd_data_geom(n.resid2), false, false, false, fr(e->iResid2, 1), false);
-        wgrad(n.resid1);
-    }
-    wgrad(n.up); conv(bwd_data_geom(n.up), false, false, false, fr(e->iUp, 1), true);
-    for (int k = nred - 1; k >= 0; --k) { wgrad(n.red[k]); conv(bwd_data_geom(n.red[k]), true, false, false, fr(e->iRed[k], 1), true); }
-    for (int i = R - 1; i >= 0; --i) {
-        wgrad(n.norm); conv(bwd_data_geom(n.norm), false, false, false, fr(e->iNorm[i], 1), true);
-        if (fusedp) continue;
-        conv(n.exp, false, true, false, Frags(), false);                       // the recomputed hidden tensor
-        wgrad(n.dec); conv(bwd_data_geom(n.dec), false, false, false, fr(e->iDec[i], 1), false);
-        wgrad(n.exp); conv(bwd_data_geom(n.exp), true, false, true, fr(e->iExp[i], 1), true);
-    }
-    wgrad(n.main);
     return PROBAV_OK;
 }
 

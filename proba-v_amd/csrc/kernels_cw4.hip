@@ -658,20 +658,20 @@ static bool cw4_plan(const ConvGeom& g, Cw4Args& p, size_t& lds_bytes, int& grid
     return false;
 }
 
-bool cw4_conv_supported(const ConvGeom& g, const float* gate)
+bool cw4_conv_supported(const ConvGeom& g, bool gated)
 {
     Cw4Args p;
     size_t lds_bytes;
     int grid;
-    return gate == nullptr && cw4_plan(g, p, lds_bytes, grid);
+    return !gated && cw4_plan(g, p, lds_bytes, grid);
 }
 
-bool cw4_conv_plan_ints(const ConvGeom& g, const float* gate, int out[5])
+bool cw4_conv_plan_ints(const ConvGeom& g, bool gated, int out[5])
 {
     Cw4Args p;
     size_t lds_bytes;
     int grid;
-    if (gate != nullptr || !cw4_plan(g, p, lds_bytes, grid)) return false;
+    if (gated || !cw4_plan(g, p, lds_bytes, grid)) return false;
     out[0] = p.nsplit; out[1] = p.nstrips; out[2] = p.SR; out[3] = p.nslot; out[4] = grid;
     return true;
 }

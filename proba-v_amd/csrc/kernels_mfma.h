@@ -55,7 +55,7 @@ struct StripPlan { bool ok; int CC, KS; size_t lds_bytes; int grid; StripArgs a;
 // W4::conv is on and it takes the layer, else conv3_pp_kernel (rvp staging items per thread), else conv3_pstrip_kernel.  Everything else: conv3_strip_kernel (25 channels: PACK_*_CONVK)
 enum class StripKernel { none, cw4, pp, pstrip, strip };
 struct StripSel { StripKernel k = StripKernel::none; int arith = 0, rvp = 2; bool taps = false; StripPlan plan = {}; };     // plan: of pp / pstrip / strip (cw4: the piece-ring plan; plan.a.g = g)
-StripSel strip_select(const ConvGeom& g, const float* gate, int arith);
+StripSel strip_select(const ConvGeom& g, bool gated, int arith);
 int conv_strip_forward(const StripSel& sel, const float* x, const float* gate, const float* wfrag, const float* bias,
                        const float* skip, float* y, const Amax& am, hipStream_t s);
 // row-tile kernel with a split-operand tap loop (32-channel inputs: reducers, upscale; any pads / reflect).  arith 1: X6,
@@ -90,9 +90,9 @@ int mfma_pw_backward_grid();
 // 3x3x3 'same' convolution of the residual blocks (25 -> 32 channels, and its backward-data 32 -> 25 / 32) as ONE-WAVE-PER-SIMD kernel (kernels_cw4.hip; H3
 // arithmetic only): the filter's first pieces stay in registers for the whole launch.  strip_select takes it when cw4_conv_supported(); with W4::conv off conv3_pp_kernel stays.
 // wfrag: PACK_H3_CONVP (25 input channels) / PACK_H3_CONV (32) fragments, as conv3_pp_kernel reads them
-bool cw4_conv_supported(const ConvGeom& g, const float* gate);
+bool cw4_conv_supported(const ConvGeom& g, bool gated);
 // introspection (probav_plan_conv): the plan cw4_conv_forward launches.  out = {nsplit, nstrips, SR, nslot, grid}; false = the kernel does not take g
-bool cw4_conv_plan_ints(const ConvGeom& g, const float* gate, int out[5]);
+bool cw4_conv_plan_ints(const ConvGeom& g, bool gated, int out[5]);
 int cw4_conv_forward(const ConvGeom& g, const float* x, const float* wfrag, const float* bias, const float* skip, float* y, const Amax& am, hipStream_t s);
 
 }  // namespace probav

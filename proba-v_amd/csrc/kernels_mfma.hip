@@ -2454,13 +2454,13 @@ static StripPlan strip_plan(const ConvGeom& g)
 }
 
 // today's precedence, each plan computed at most once (kernels_mfma.h)
-StripSel strip_select(const ConvGeom& g, const float* gate, int arith)
+StripSel strip_select(const ConvGeom& g, bool gated, int arith)
 {
     StripSel r; r.arith = arith;
     if (arith == 2) {
         const bool pp = pp_plan(g, r.plan, r.rvp);
         r.taps = pp || pstrip_plan(g, r.plan);
-        if (r.taps) r.k = w4_enabled(W4::conv) && cw4_conv_supported(g, gate) ? StripKernel::cw4 : (pp ? StripKernel::pp : StripKernel::pstrip);
+        if (r.taps) r.k = w4_enabled(W4::conv) && cw4_conv_supported(g, gated) ? StripKernel::cw4 : (pp ? StripKernel::pp : StripKernel::pstrip);
     }
     if (!r.taps) { r.plan = strip_plan(g); if (r.plan.ok) r.k = StripKernel::strip; }
     return r;

@@ -574,20 +574,20 @@ WG4_PART2(WG4_DEF)
 
 #if WG4_PART == 0
 // ---- host side ----
-static bool wg4_plan(const ConvGeom& g, const float* gate, Wg4Args& p, int& grid)
+static bool wg4_plan(const ConvGeom& g, bool gated, Wg4Args& p, int& grid)
 {
     if (g.kh != 3 || g.kw != 3 || g.kt != 3 || g.reflect_t || g.Cout != 32) return false;
     int nsplit = 1;
     if (g.Cin == 25) {                                                   // normConv: 'same' padding with zeros, no gate (depth 13: column halves)
         if (g.Wo != 22 || g.Wi != 22 || g.Ho != g.Hi || g.ph != 1 || g.pw != 1) return false;
-        if (g.reflect_hw || g.pt != 1 || g.To != g.Ti || gate || (g.To != 13 && g.To != 9 && g.To != 7)) return false;
+        if (g.reflect_hw || g.pt != 1 || g.To != g.Ti || gated || (g.To != 13 && g.To != 9 && g.To != 7)) return false;
         if (g.To == 13) nsplit = 2;
     } else if (g.Cin == 32 && g.reflect_hw) {                            // the mirrored-pad reducers: tf.pad(REFLECT) in rows / columns, no depth pads, dY masked by the layer's output (depth 13 -> 11: column halves)
         if (g.Wo != 22 || g.Wi != 22 || g.Ho != g.Hi || g.ph != 1 || g.pw != 1) return false;
-        if (g.pt != 0 || g.To != g.Ti - 2 || !gate || g.Hi < 2 || (g.To != 11 && g.To != 9 && g.To != 7 && g.To != 5 && g.To != 3)) return false;
+        if (g.pt != 0 || g.To != g.Ti - 2 || !gated || g.Hi < 2 || (g.To != 11 && g.To != 9 && g.To != 7 && g.To != 5 && g.To != 3)) return false;
         if (g.To == 11) nsplit = 2;
     } else if (g.Cin == 32) {                                            // the reducers behind it: no pads at all, dY masked
-        if (g.ph != 0 || g.pw != 0 || g.pt != 0 || g.Ho != g.Hi - 2 || g.Wo != g.Wi - 2 || g.To != g.Ti - 2 || !gate) return false;
+        if (g.ph != 0 || g.pw != 0 || g.pt != 0 || g.Ho != g.Hi - 2 || g.Wo != g.Wi - 2 || g.To != g.Ti - 2 || !gated) return false;
         if (!((g.Wo == 20 && g.To == 5) || (g.Wo == 18 && g.To == 3))) return false;
     } else return false;
     if (g.N < 1 || g.N * nsplit > 256 || g.Ho < 1) return false;         // one slab per workgroup, at most 256 of them (x6_wgrad_partial_floats)
@@ -600,18 +600,18 @@ static bool wg4_plan(const ConvGeom& g, const float* gate, Wg4Args& p, int& grid
     return true;
 }
 
-bool wg4_wgrad_supported(const ConvGeom& g, const float* gate)
+bool wg4_wgrad_supported(const ConvGeom& g, bool gated)
 {
     Wg4Args p;
     int grid;
-    return wg4_plan(g, gate, p, grid);
+    return wg4_plan(g, gated, p, grid);
 }
 
-bool wg4_wgrad_plan_ints(const ConvGeom& g, const float* gate, int out[4])
+bool wg4_wgrad_plan_ints(const ConvGeom& g, bool gated, int out[4])
 {
     Wg4Args p;
     int grid;
-    if (!wg4_plan(g, gate, p, grid)) return false;
+    if (!wg4_plan(g, gated, p, grid)) return false;
     out[0] = p.nsplit; out[1] = p.nstrips; out[2] = p.SR; out[3] = grid;
     return true;
 }
@@ -620,7 +620,7 @@ int wg4_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const flo
 {
     Wg4Args p;
     int grid;
-    if (!wg4_plan(g, gate, p, grid)) { set_error("wg4_conv_wgrad: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
+    if (!wg4_plan(g, gate != nullptr, p, grid)) { set_error("wg4_conv_wgrad: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (!am.x || !am.w) { set_error("wg4_conv_wgrad: H3 arithmetic needs the per-sample amax slots of x (am.x) and dY (am.w)", hipSuccess); return PROBAV_EINVAL; }
     const long nw = (long)27 * g.Cin * g.Cout;
     float* partial_b = partial + (size_t)grid * nw;

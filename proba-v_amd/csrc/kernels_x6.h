@@ -55,13 +55,13 @@ int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const floa
 // (kernels_wg4.hip; H3 arithmetic only): a conflict-free piece image of the input ring, dY straight from memory, one instruction stream per output row.
 // x6_wgrad_select takes it when wg4_wgrad_supported(); with W4::wgrad off conv3_wgrad_x6_kernel stays.
 // partial: x6_wgrad_partial_floats(g) floats, as for the general form
-bool wg4_wgrad_supported(const ConvGeom& g, const float* gate);
-bool wg4_wgrad_plan_ints(const ConvGeom& g, const float* gate, int out[4]);      // introspection: {nsplit, nstrips, SR, grid} of the launch; false = the kernel does not take g
+bool wg4_wgrad_supported(const ConvGeom& g, bool gated);
+bool wg4_wgrad_plan_ints(const ConvGeom& g, bool gated, int out[4]);      // introspection: {nsplit, nstrips, SR, grid} of the launch; false = the kernel does not take g
 int wg4_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, const Amax& am, hipStream_t s);
 
 // introspection (probav_plan_conv / probav_plan_pw): what x6_conv_wgrad / x6_pw_forward / x6_pw_backward launch, from the selections they make themselves.
 // x6_wgrad_plan_ints: 0 none, 1 conv3_wgrad_w4_kernel, 2 conv3_wgrad_x6_kernel<H3>, 3 conv3_wgrad_x6_kernel<X6>; out = {nsplit, nstrips, SR, grid} (the general form has no strips: 0)
-int x6_wgrad_plan_ints(const ConvGeom& g, const float* gate, int arith, int out[4]);
+int x6_wgrad_plan_ints(const ConvGeom& g, bool gated, int arith, int out[4]);
 // x6_pw_plan_kernel: forward 1 pw_fwd_w4_kernel, 2 pw_fwd_h3k_kernel, 3 pw_fwd_x6_kernel<X6>; backward 1 pw_bwd_w4_kernel (*wps = its waves per sample), 2 pw_bwd_x6_kernel<H3>, 3 pw_bwd_x6_kernel<X6>
 int x6_pw_plan_kernel(long nvox, long vps, int D, int arith, bool backward, int* wps);
 

@@ -1421,20 +1421,20 @@ size_t x6_wgrad_partial_floats(const ConvGeom& g)
 // H3 on the general form has PLAIN second pieces (one scale per operand tensor: a channel 2^-24 below its mates is resolved to 7e-5), so a layer without an instance of
 // the new kernel runs the unscaled x6 arithmetic on it; its H3 instance stays for A/B runs (W4::wgrad off: H3 wherever the dY image also fits, as before that kernel)
 enum class WgradX6Kernel { none, w4, x6_h3, x6 };
-static WgradX6Kernel x6_wgrad_select(const ConvGeom& g, const float* gate, int arith)
+static WgradX6Kernel x6_wgrad_select(const ConvGeom& g, bool gated, int arith)
 {
     if (!x6_wgrad_supported(g)) return WgradX6Kernel::none;
     if (arith != 2) return WgradX6Kernel::x6;
-    if (w4_enabled(W4::wgrad)) return wg4_wgrad_supported(g, gate) ? WgradX6Kernel::w4 : WgradX6Kernel::x6;
+    if (w4_enabled(W4::wgrad)) return wg4_wgrad_supported(g, gated) ? WgradX6Kernel::w4 : WgradX6Kernel::x6;
     return x6_wgrad_split(g, 2) ? WgradX6Kernel::x6_h3 : WgradX6Kernel::x6;
 }
 
-int x6_wgrad_plan_ints(const ConvGeom& g, const float* gate, int arith, int out[4])
+int x6_wgrad_plan_ints(const ConvGeom& g, bool gated, int arith, int out[4])
 {
-    const WgradX6Kernel k = x6_wgrad_select(g, gate, arith);
+    const WgradX6Kernel k = x6_wgrad_select(g, gated, arith);
     out[0] = out[1] = out[2] = out[3] = 0;
     if (k == WgradX6Kernel::none) return 0;
-    if (k == WgradX6Kernel::w4) return wg4_wgrad_plan_ints(g, gate, out) ? 1 : 0;
+    if (k == WgradX6Kernel::w4) return wg4_wgrad_plan_ints(g, gated, out) ? 1 : 0;
     const int a = k == WgradX6Kernel::x6_h3 ? 2 : 1;
     out[0] = x6_wgrad_split(g, a); out[3] = x6_wgrad_grid(g, a);
     return a == 2 ? 2 : 3;
@@ -1456,7 +1456,7 @@ int x6_pw_plan_kernel(long nvox, long vps, int D, int arith, bool backward, int*
 int x6_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial,
                   int arith, const Amax& am, hipStream_t s)
 {
-    const WgradX6Kernel k = x6_wgrad_select(g, gate, arith);
+    const WgradX6Kernel k = x6_wgrad_select(g, gate != nullptr, arith);
     if (k == WgradX6Kernel::none) { set_error("x6_conv_wgrad: unsupported geometry", hipSuccess); return PROBAV_EINVAL; }
     if (arith == 2 && (!am.x || !am.w)) { set_error("x6_conv_wgrad: H3 arithmetic needs the per-sample amax slots of x (am.x) and dY (am.w)", hipSuccess); return PROBAV_EINVAL; }
     if (k == WgradX6Kernel::w4) return wg4_conv_wgrad(g, x, dy, gate, dw, db, partial, am, s);

@@ -308,9 +308,9 @@ def test_whole_network_on_the_route_matches_the_oracle(dev, case, impl, monkeypa
 @pytest.mark.parametrize("case", NET_CASES + [((32, 12, 8, 0.8, 25), 9, True, 2)],
                          ids=lambda c: "f%d-r%d-e%d-d%d-t%d" % (c[0][0], c[0][1], c[0][2], c[0][4], c[1]) if isinstance(c, tuple) else None)
 def test_the_census_is_what_a_step_launches(dev, case, impl):
-    """probav_engine_route_counts walks the network by hand; probav_engine_launched_counts counts where forward and backward actually launch.  After one training
-    step the two agree, switch off and on -- at the cfg values above and the shipped network -- so a pass that changes its launches moves
-    the census or fails here."""
+    """probav_engine_route_counts routes the engine's launch list; probav_engine_launched_counts counts where forward and backward actually launch, each launch
+    fetched from that list.  After one training step the two agree, switch off and on -- at the cfg values above and the shipped network -- so a pass that
+    skips a launch of the list, or issues one twice, fails here."""
     row, T, gray, B = case
     lib = _L().lib()
     m = _model(dev, row, T, gray)

@@ -54,13 +54,13 @@ int main(int argc, char** argv)
         const size_t ny = (size_t)c.B * c.H * c.W * c.T * c.Cout;
         std::vector<float> ya(ny), yb(ny);
         std::vector<unsigned> sa(c.B), sb(c.B);
-        if (!cw4_conv_supported(g, nullptr)) { printf("B %3d %dx%dx%d %d->%d: not taken by the new kernel\n", c.B, c.H, c.W, c.T, c.Cin, c.Cout); continue; }
+        if (!cw4_conv_supported(g, false)) { printf("B %3d %dx%dx%d %d->%d: not taken by the new kernel\n", c.B, c.H, c.W, c.T, c.Cin, c.Cout); continue; }
         for (int k = 0; k < 2; ++k) {
             w4_set_enabled(W4::conv, k);
             hipMemset(y, 0xff, nvmax * 32 * 4);
             hipMemcpy(am_, slots.data(), 8192 * 4, hipMemcpyHostToDevice);
             hipMemset(am_ + 4096, 0, 2048 * 4);
-            if (conv_strip_forward(strip_select(g, nullptr, 2), x, nullptr, wf, c.bias ? bias : nullptr, c.skip ? sk : nullptr, y, am, 0)) { printf("launch failed: %s\n", last_error()); return 1; }
+            if (conv_strip_forward(strip_select(g, false, 2), x, nullptr, wf, c.bias ? bias : nullptr, c.skip ? sk : nullptr, y, am, 0)) { printf("launch failed: %s\n", last_error()); return 1; }
             hipDeviceSynchronize();
             if (hipGetLastError() != hipSuccess) { printf("HIP error\n"); return 1; }
             hipMemcpy(k ? yb.data() : ya.data(), y, ny * 4, hipMemcpyDeviceToHost);
@@ -93,7 +93,7 @@ int main(int argc, char** argv)
         for (int pass = 0; pass < 4; ++pass)
             for (int k = 0; k < 2; ++k) {
                 w4_set_enabled(W4::conv, k);
-                auto run = [&] { conv_strip_forward(strip_select(g, nullptr, 2), x, nullptr, wf, bias, dir ? nullptr : sk, y, am, 0); };
+                auto run = [&] { conv_strip_forward(strip_select(g, false, 2), x, nullptr, wf, bias, dir ? nullptr : sk, y, am, 0); };
                 for (int i = 0; i < 3; ++i) run();
                 hipDeviceSynchronize();
                 hipEventRecord(ea, 0);

@@ -21,9 +21,9 @@ int main()
         for (int arith = 1; arith <= 2; ++arith) {
             Amax m; m.x = am; m.w = am + 1024; m.y = am + 2048;
             hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-            for (int it = 0; it < 3; ++it) conv_strip_forward(strip_select(g, nullptr, arith), x, nullptr, wf, bias, cin == 25 ? skp : nullptr, y, m, 0);
+            for (int it = 0; it < 3; ++it) conv_strip_forward(strip_select(g, false, arith), x, nullptr, wf, bias, cin == 25 ? skp : nullptr, y, m, 0);
             hipEventRecord(e0, 0);
-            for (int it = 0; it < 20; ++it) conv_strip_forward(strip_select(g, nullptr, arith), x, nullptr, wf, bias, cin == 25 ? skp : nullptr, y, m, 0);
+            for (int it = 0; it < 20; ++it) conv_strip_forward(strip_select(g, false, arith), x, nullptr, wf, bias, cin == 25 ? skp : nullptr, y, m, 0);
             hipEventRecord(e1, 0); hipEventSynchronize(e1);
             float ms; hipEventElapsedTime(&ms, e0, e1);
             printf("strip cin %d arith %d: %.1f us\n", cin, arith, ms * 1000 / 20);

@@ -50,8 +50,8 @@ int main()
         hipMemset(bias, 0, 32 * 4);
         ConvGeom gb{B, 22, 22, 9, 32, 22, 22, 9, 25, 3, 3, 3, 1, 1, 1, 0, 0, 0};
         for (int it = 0; it < 3; ++it) {
-            if (dir == 0) conv_strip_forward(strip_select(g, nullptr, ARITH), x, nullptr, wf, bias, dy, y, am, 0);
-            else conv_strip_forward(strip_select(gb, nullptr, ARITH), dy, nullptr, wf, nullptr, nullptr, y, am, 0);
+            if (dir == 0) conv_strip_forward(strip_select(g, false, ARITH), x, nullptr, wf, bias, dy, y, am, 0);
+            else conv_strip_forward(strip_select(gb, false, ARITH), dy, nullptr, wf, nullptr, nullptr, y, am, 0);
         }
         hipDeviceSynchronize();
         hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_stamps), st.size() * 8);

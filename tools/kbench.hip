@@ -142,11 +142,11 @@ int main(int argc, char** argv)
             char nm[96];
             const double gfl = (double)B * hs[k + 1] * hs[k + 1] * ts[k + 1] * 27 * 32 * 32 * 2e-9;
             snprintf(nm, sizeof(nm), "reducer %d forward  (%dx%dx%d out)", k + 1, hs[k + 1], hs[k + 1], ts[k + 1]);
-            timeit(nm, iters, gfl, [&] { conv_strip_forward(strip_select(f, nullptr, 2), x32, nullptr, wfr, bias, nullptr, y32, am, 0); });
+            timeit(nm, iters, gfl, [&] { conv_strip_forward(strip_select(f, false, 2), x32, nullptr, wfr, bias, nullptr, y32, am, 0); });
             snprintf(nm, sizeof(nm), "reducer %d backward-data, gated", k + 1);
-            timeit(nm, iters, gfl, [&] { conv_strip_forward(strip_select(bd, z32, 2), y32, z32, wfr, nullptr, nullptr, x32, am, 0); });
+            timeit(nm, iters, gfl, [&] { conv_strip_forward(strip_select(bd, true, 2), y32, z32, wfr, nullptr, nullptr, x32, am, 0); });
             snprintf(nm, sizeof(nm), "reducer %d backward-data, no gate", k + 1);
-            timeit(nm, iters, gfl, [&] { conv_strip_forward(strip_select(bd, nullptr, 2), y32, nullptr, wfr, nullptr, nullptr, x32, am, 0); });
+            timeit(nm, iters, gfl, [&] { conv_strip_forward(strip_select(bd, false, 2), y32, nullptr, wfr, nullptr, nullptr, x32, am, 0); });
             snprintf(nm, sizeof(nm), "reducer %d backward-filter, gated", k + 1);
             timeit(nm, iters, gfl, [&] { x6_conv_wgrad(f, x32, y32, z32, dw, db, partr, 2, am, 0); });
         }
@@ -154,8 +154,8 @@ int main(int argc, char** argv)
     continue;
 #endif
 #ifdef KB_ONLY_STRIP
-    timeit("conv3_w4<25> normConv forward + skip", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gf, nullptr, 2), x25, nullptr, wf, bias, y32, z32, am, 0); });
-    timeit("conv3_w4<32> normConv backward-data", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gb, nullptr, 2), x32, nullptr, wf, nullptr, nullptr, y25, am, 0); });
+    timeit("conv3_w4<25> normConv forward + skip", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gf, false, 2), x25, nullptr, wf, bias, y32, z32, am, 0); });
+    timeit("conv3_w4<32> normConv backward-data", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gb, false, 2), x32, nullptr, wf, nullptr, nullptr, y25, am, 0); });
     continue;
 #endif
 #ifdef KB_ONLY_WG
@@ -180,8 +180,8 @@ int main(int argc, char** argv)
     timeit("pw_fwd  one sample (vps = nvox)", iters, gv * 14592, [&] { x6_pw_forward(x32, w, w + X6_PW_FRAG_WORDS, b1, b2, y25, nvox, nvox, D, 2, pam, 0); });
     timeit("pw_bwd  one sample (vps = nvox)", iters, gv * 29184, [&] { x6_pw_backward(x32, x25, y32, w, w + X6_PW_FRAG_WORDS, w + 2 * X6_PW_FRAG_WORDS, b1, z32, dW1, dW2, db1, db2, slabs, nvox, nvox, D, 2, pam, 0); });
 #endif
-    timeit("conv3_w4<25> normConv forward + skip", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gf, nullptr, 2), x25, nullptr, wf, bias, y32, z32, am, 0); });
-    timeit("conv3_w4<32> normConv backward-data", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gb, nullptr, 2), x32, nullptr, wf, nullptr, nullptr, y25, am, 0); });
+    timeit("conv3_w4<25> normConv forward + skip", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gf, false, 2), x25, nullptr, wf, bias, y32, z32, am, 0); });
+    timeit("conv3_w4<32> normConv backward-data", iters, gv * 21600, [&] { conv_strip_forward(strip_select(gb, false, 2), x32, nullptr, wf, nullptr, nullptr, y25, am, 0); });
     timeit("wgrad<25> normConv backward-filter", iters, gv * 21600, [&] { x6_conv_wgrad(gf, x25, y32, nullptr, dw, db, part, 2, am, 0); });
     }
     return 0;

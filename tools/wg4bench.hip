@@ -41,7 +41,7 @@ int main(int argc, char** argv)
         ConvGeom g = c.red ? ConvGeom{c.B, c.H, 22, c.T + 2, 32, c.H, 22, c.T, 32, 3, 3, 3, 1, 1, 0, 1, 1, 0} : ConvGeom{c.B, c.H, 22, c.T, 25, c.H, 22, c.T, 32, 3, 3, 3, 1, 1, 1, 0, 0, 0};
         const float* gate = c.red ? gt : nullptr;
         const long nw = 27L * g.Cin * 32;
-        if (!wg4_wgrad_supported(g, gate)) { printf("B %3d %dx22x%d%s: not taken by the new kernel\n", c.B, c.H, c.T, c.red ? " reducer" : ""); continue; }
+        if (!wg4_wgrad_supported(g, gate != nullptr)) { printf("B %3d %dx22x%d%s: not taken by the new kernel\n", c.B, c.H, c.T, c.red ? " reducer" : ""); continue; }
         std::vector<float> wa(nw), wb(nw), ba(32), bb(32);
         for (int k = 0; k < 2; ++k) {
             w4_set_enabled(W4::wgrad, k);
