@@ -10,9 +10,16 @@
  *   - activations [N][H][W][T][C], C innermost (the reference's layout; models/modelsTF.py:19);
  *     kernels [kh][kw][kt][Cin][Cout] (Keras).  All buffers contiguous, 16-byte aligned.
  *   - every call only ENQUEUES work on `stream` and returns; it never synchronises, allocates or
- *     frees device memory (so calls can be captured in a hipGraph).  The one exception is an engine's
- *     first call that launches with its layer table (a pass, a weight-norm or optimizer call): it uploads
- *     that table, a few KB, once -- make it outside a graph capture.  probav_engine_create itself touches
+ *     frees device memory (so calls can be captured in a hipGraph).  The exceptions, each of which waits on the
+ *     host, allocates or frees and therefore belongs outside a graph capture (tests/test_gpu_bands.py, HOST_WAIT_EXEMPT):
+ *       (1) an engine's first call that launches with its layer table (a pass, a weight-norm or optimizer call) uploads that table, a few KB, once;
+ *       (2) the single-operator entries probav_conv3d_forward (impl 1-4), probav_pw_forward and probav_pw_backward pack their filter into a scratch the library owns: every such call waits for `stream` to drain and uploads its packing jobs with a blocking copy (the first one also allocates the scratch);
+ *       (3) their H3 form (impl 4, probav_conv3d_wgrad included) frees and allocates the library's amax table when a call needs more slots than any call before it;
+ *       (4) probav_shift_loss_forward frees and allocates the library's candidate table when its batch times (2 border + 1)^2 exceeds that of every call before it.
+ *     The packing scratch, the amax table and the candidate table are the library's own, one of each per process: calls of the entry
+ *     points of (2)-(4) that overlap on two streams or two threads are unsafe (the second call repacks, resets or frees what the first
+ *     one's kernels still read) -- keep them on one stream, or order them with events.  Everything else, the engine included, only
+ *     enqueues.  probav_engine_create itself touches
  *     no device: the size and layout queries of a configuration answer on a host without one.
  *     probav_forward / probav_backward additionally fork work that is off the critical path (the
  *     low-frequency residual path, the sums of the backward-filter slabs) onto one engine-owned side

@@ -21,6 +21,11 @@ A buffer starts 16-byte aligned; a band is at least BAND_MIN bytes and at least 
 frame) of the buffer it guards, so a whole extra strip or sample still lands in a band.  The bytes that round a band up belong to the band
 and are checked with it.  Works on CPU tensors too (tests/test_bands_host.py).
 
+On a device a fourth run follows (`_late_run`): the same launch on a stream that is still busy with a delay (tests/late_stream.py), the arena
+filled and its inputs delivered on that stream behind the delay.  The header's "every call only ENQUEUES work on `stream` and returns" is what
+it holds: work that is not on (or forked from) the stream it was given runs before its inputs arrive and the result differs from run A's; a
+call that waits on the host returns after the delay ('sync').  It is inert on CPU tensors, for refusals and for expect_rc != 0.
+
 What this cannot see: a READ past the end of an input whose value never reaches the result.  Nothing here proves reads in bounds.
 """
 import numpy as np
@@ -110,7 +115,8 @@ def carve(bufs):
 
 class Violation:
     """One failed check: buffer name, side ('before' / 'after': a band; 'in': an input changed; 'kept': an element that had to keep its fill;
-    'differs': an output differs between two runs; 'rc': the return code), the fill's label, first and last offending byte offset."""
+    'differs': an output differs between two runs; 'rc': the return code; 'sync': the call waited on the host), the fill's label ('late': the run on the
+    late stream), first and last offending byte offset."""
 
     def __init__(self, buffer, side, fill, first=None, last=None, note=""):
         self.buffer, self.side, self.fill, self.first, self.last, self.note = buffer, side, fill, first, last, note
@@ -129,25 +135,34 @@ def _span(bad):
 
 
 class Arena:
-    def __init__(self, bufs, device, fill):
+    def __init__(self, bufs, device, fill, deliver=True):
         self.bufs, self.fill, self.device = list(bufs), fill, torch.device(device)
         names = [b.name for b in self.bufs]
         assert len(set(names)) == len(names), "buffer names must differ"
         self.plan, total = carve(self.bufs)
         self.mem = _arena_bytes(self.device, total)
-        self.mem.fill_(fill.byte)
         self.tensors, self.views = {}, {}
         for b, (before, start, after, end) in zip(self.bufs, self.plan):
             v = self.mem[start:start + b.nbytes]
-            if b.init is not None:
-                v.copy_(b.init.to(self.device))
-            elif b.name in fill.preset:
+            if b.init is None and b.name in fill.preset:
                 p = fill.preset[b.name]
                 assert p.numel() == b.nbytes, "%s: preset of %d bytes for %d" % (b.name, p.numel(), b.nbytes)
-                v.copy_(p.to(self.device))
             self.views[b.name] = v
             self.tensors[b.name] = v.view(b.dtype)
             assert self.tensors[b.name].data_ptr() % ALIGN == 0
+        if deliver:
+            self.deliver(self.staged())
+
+    def staged(self):
+        """[(view, bytes on the arena's device)]: the initial data of the in / inout buffers and the fill's presets, ready to be delivered."""
+        src = [(b.name, b.init if b.init is not None else self.fill.preset.get(b.name)) for b in self.bufs]
+        return [(self.views[n], d.to(self.device)) for n, d in src if d is not None]
+
+    def deliver(self, staged):
+        """The fill of the whole arena, then the staged bytes (device to device): enqueued on the current stream."""
+        self.mem.fill_(self.fill.byte)
+        for v, d in staged:
+            v.copy_(d)
 
     def checks(self, untouched=False):
         """[(buffer, side, bad-bytes tensor)]: the bands, the inputs, the kept elements; with untouched, every out / scratch buffer whole."""
@@ -225,6 +240,7 @@ FILLS = (Fill(0xFF), Fill(0x00))
 class Report:
     def __init__(self):
         self.violations, self.rcs, self.outputs = [], {}, {}
+        self.late_exempt = None          # why the late run's host-wait check was skipped (host_wait_exempt's answer), or None
 
     def ok(self):
         return not self.violations
@@ -233,10 +249,63 @@ class Report:
         return "\n".join(repr(v) for v in self.violations) or "clean"
 
 
-def run(bufs, call, device, fills=FILLS, plain=True, expect_rc=0, compare=True):
+host_wait_exempt = None          # set by a test module: callable([(entry point, args)] of the late launch, the same of every call before it) -> the reason it may wait on the host, or None
+
+
+def _late_run(bufs, call, device, fill, first, rep):
+    """The launch once more, on the late stream of tests/late_stream.py.  The arena still holds the complete, valid state the last fill's run left
+    (a kernel that escapes to another stream runs at once and must read valid inputs).  Enqueued on the stream, behind its delay: the fill of the
+    whole arena, the delivery of the staged inputs and presets, `call` (its `current_stream()` is the late stream).  Whatever did not wait for the
+    delay wrote before the fill and is erased.  Checked through that stream alone: bands, inputs and kept elements as after every run, every
+    output bitwise against the first run's ('differs', fill '<first> vs late'), and that the call came back while the delay was still running
+    ('sync'; repeated once with RETRY_FACTOR times the delay before it is reported)."""
+    from tests import late_stream
+    dev = torch.device(device)
+    a = Arena(bufs, dev, fill, deliver=False)
+    staged = a.staged()
+    s = late_stream.stream(dev)
+    for factor in (1, late_stream.RETRY_FACTOR):
+        found = []
+        torch.cuda.synchronize(dev)
+        mark = len(late_stream.history)
+        gate = late_stream.begin(dev, factor)
+        with torch.cuda.stream(s):
+            a.deliver(staged)
+            rc = call(a.tensors)
+            early = gate.returned(", ".join(sorted({n for n, _ in late_stream.history[mark:]})))
+            reason = host_wait_exempt(late_stream.history[mark:], late_stream.history[:mark]) if host_wait_exempt else None
+            if rc != 0:
+                found.append(Violation("(call)", "rc", "late", note="returned %r, expected 0" % (rc,)))
+            found += a.violations()
+            for v in found:
+                v.fill = "late"
+            res = []
+            for b in bufs:
+                if b.role in ("out", "inout"):
+                    bad = first[b.name] != a.views[b.name]
+                    res.append((b.name, bad if b.keep is None else bad & ~b.keep.to(dev)))
+            flags = torch.stack([bad.any() for _, bad in res]).cpu().tolist() if res and rc == 0 else []
+            found += [Violation(n, "differs", "%s vs late" % fill.label, *_span(bad)) for (n, bad), f in zip(res, flags) if f]
+        s.synchronize()
+        if not early and reason:
+            late_stream.note_wait(reason.split(":")[0])
+        if early or reason:
+            break
+        if factor == 1:
+            late_stream.stats["retries"] += 1
+        else:
+            found.append(Violation("(call)", "sync", "late", note="the call returned only after a delay of %d x %.1f ms on its stream had passed: it waited on the host (%s)"
+                                   % (factor, late_stream.delay_ms(dev), gate.what or "entry points not recorded")))
+    rep.rcs["late"] = rc
+    rep.late_exempt = reason
+    rep.violations += found
+    del a
+
+
+def run(bufs, call, device, fills=FILLS, plain=True, expect_rc=0, compare=True, late=True):
     """Run the launch under every fill and once on plain tensors; returns a Report (see the module docstring for the checks).
     report.outputs: {name: uint8 tensor} the out / inout buffers of the first run (copies), for a caller that wants to hold the values to
-    something else too."""
+    something else too.  late: one more run on a late stream (_late_run; device tensors and accepted launches only)."""
     rep, runs = Report(), []
     results = [b.name for b in bufs if b.role in ("out", "inout")]
     for f in fills:
@@ -270,6 +339,8 @@ def run(bufs, call, device, fills=FILLS, plain=True, expect_rc=0, compare=True):
                 res.append((b.name, "%s vs %s" % (label0, label), bad if live is None else bad & live))
         flags = torch.stack([bad.any() for _, _, bad in res]).cpu().tolist() if res else []
         rep.violations += [Violation(n, "differs", lab, *_span(bad)) for (n, lab, bad), f in zip(res, flags) if f]
+    if late and torch.device(device).type == "cuda" and expect_rc == 0 and all(rc == 0 for rc in rep.rcs.values()):
+        _late_run(bufs, call, device, fills[0], runs[0][1], rep)
     return rep
 
 

@@ -195,3 +195,69 @@ def test_arena_memory_is_kept_and_reused_then_released():
     assert float(rep.outputs["y"].view(torch.float32)[5]) == 5.0
     bands.release(CPU)
     assert CPU not in bands._storage
+
+
+# ---- the stream runs: every streamed entry point has a test, every exemption quotes the header ---------------------------------------------
+def _header():
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "probav_hip.h")) as fh:
+        text = fh.read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    streamed = {m.group(1) for m in re.finditer(r"\b(probav_\w+)\s*\(([^;{}()]*)\)\s*;", code) if re.search(r"void\s*\*\s*stream\s*$", m.group(2).strip())}
+    return " ".join(text.split()), streamed
+
+
+def test_every_streamed_entry_point_is_held_by_a_test_that_exists():
+    from tests import test_gpu_bands as tb, test_gpu_gemm_route as tg
+    _, streamed = _header()
+    assert len(streamed) == 52 and not set(tb.STREAMED) & set(tg.STREAMED)
+    assert set(tb.STREAMED) | set(tg.STREAMED) == streamed, sorted(streamed ^ (set(tb.STREAMED) | set(tg.STREAMED)))
+    assert sorted(tg.STREAMED) == ["probav_gemm_conv3d_forward", "probav_gemm_conv3d_wgrad"]
+    for mod, table in ((tb, tb.STREAMED), (tg, tg.STREAMED)):
+        for entry, test in table.items():
+            assert test.startswith("test_") and callable(getattr(mod, test, None)), (entry, test)
+            src = __import__("inspect").getsource(getattr(mod, test))
+            helpers = "".join(__import__("inspect").getsource(getattr(mod, h)) for h in ("_conv_forward", "_conv_wgrad") if hasattr(mod, h) and h + "(" in src)
+            assert entry + "(" in src + helpers, "%s does not call %s" % (test, entry)
+
+
+def test_every_host_wait_exemption_quotes_the_header():
+    from tests import test_gpu_bands as tb
+    text, streamed = _header()
+    text = text.replace(" * ", " ")                        # (the comment's line prefix)
+    assert set(tb.HOST_WAIT_EXEMPT) <= set(tb.STREAMED)
+    for entry, (sentence, applies) in tb.HOST_WAIT_EXEMPT.items():
+        assert " ".join(sentence.split()) in text, "%s: not a sentence of include/probav_hip.h: %s" % (entry, sentence)
+        assert callable(applies)
+
+
+def test_host_wait_exemptions_apply_to_the_calls_the_header_names_and_no_others():
+    import ctypes
+    from tests import test_gpu_bands as tb
+    ex = tb._host_wait_exempt
+    h1, h2 = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x2000)
+    fwd = lambda h: ("probav_forward", (h, None, None, None, None, 0, 1, 0, None))
+    assert ex([fwd(h1)], []) and ex([fwd(h2)], [fwd(h1)])              # an engine's first call
+    assert ex([fwd(ctypes.c_void_p(0x1000))], [fwd(h1)]) is None        # the same engine again (another handle object of the same value)
+    assert ex([fwd(h1), fwd(h1)], []) and ex([("probav_clip_round", (None,) * 6)], []) is None
+    conv = lambda impl: ("probav_conv3d_forward", (None,) * 7 + (impl, None))
+    assert ex([conv(0)], []) is None and all(ex([conv(i)], [conv(i)]) for i in (1, 2, 3, 4))
+    assert ex([("probav_pw_forward", (None,) * 11)], []) and ex([("probav_pw_backward", (None,) * 18)], [])
+    loss = lambda B, border: ("probav_shift_loss_forward", (None, None, None, B, 48, border) + (None,) * 9)
+    assert ex([loss(2, 3)], []) and ex([loss(2, 3)], [loss(2, 3)]) is None and ex([loss(3, 3)], [loss(2, 3)]) and ex([loss(5, 2)], [loss(3, 3)]) is None
+    g = lambda N: ctypes.byref((ctypes.c_int32 * 17)(N))
+    wgrad = lambda N, impl: ("probav_conv3d_wgrad", (g(N),) + (None,) * 7 + (impl, None))
+    assert ex([wgrad(2, 4)], []) and ex([wgrad(2, 4)], [wgrad(2, 4)]) is None and ex([wgrad(3, 4)], [wgrad(2, 4), wgrad(9, 3)]) and ex([wgrad(9, 3)], []) is None
+
+
+def test_the_recording_library_notes_calls_in_order():
+    from tests import late_stream
+
+    class Lib:
+        def probav_a(self, x):
+            return x + 1
+    rec = late_stream.recording(Lib())
+    mark = len(late_stream.history)
+    assert rec.probav_a(1) == 2 and rec.probav_a(5) == 6 and late_stream.history[mark:] == [("probav_a", (1,)), ("probav_a", (5,))]
+    assert late_stream.recording(rec._cdll) is rec

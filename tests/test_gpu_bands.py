@@ -7,32 +7,13 @@ What this cannot see: a read past the end of an input whose value never reaches 
 load).  Nobody should read this module as a proof of in-bounds reads; it proves in-bounds WRITES at these shapes and results that are
 functions of the arguments alone.
 
-Entry points of include/probav_hip.h that write device memory -> the test that holds them:
-    probav_forward (training 0 / 1), probav_backward                          test_engine_one_piece
-    probav_workspace_split, probav_backward_split, probav_backward_input      test_engine_split
-    probav_weight_cache_build, probav_forward_wc, probav_backward_wc          test_engine_weight_cache
-    probav_optimizer_step_fused, probav_optimizer_step_fused_guarded          test_engine_fused_optimizer
-    probav_wn_forward, probav_wn_backward                                     test_engine_weight_norm
-    probav_debug_hidden                                                       test_engine_debug_hidden
-    probav_conv3d_forward                                                     test_conv3d_forward, test_conv3d_plan_rows
-    probav_conv3d_wgrad (+ probav_conv3d_wgrad_scratch_bytes)                 test_conv3d_wgrad, test_conv3d_plan_rows
-    probav_pw_forward, probav_pw_backward (+ its scratch query)               test_pointwise_pair
-    probav_shift_loss_forward / _backward, probav_shift_l1edge_forward / _backward, probav_revssim_forward / _backward
-                                                                              test_losses
-    probav_nadam_step, probav_grad_guard, probav_nadam_step_guarded           test_optimizer
-    probav_clip_round                                                         test_clip_round (and the harness's self-test)
-    probav_input_grad                                                         test_input_grad
-    probav_score_moments, probav_score_select, probav_ssim_table, probav_ssim_select
-                                                                              test_scoring
-    probav_prep_count_nonzero, probav_prep_register, probav_prep_xcorr_surface, probav_prep_patches, probav_prep_register_masked,
-    probav_prep_refine_masks                                                  test_prep_*
-    probav_augment_batch, probav_ensemble_expand, probav_ensemble_reduce      test_augment_and_ensemble
-    probav_tile_blend, probav_baseline_upscale_mean (both modes)              test_tile_blend, test_baseline
-    probav_frame_windows_gather / _reduce, probav_window_counts, probav_crop_batch
-                                                                              test_frame_windows, test_crops
-    probav_fusenet_forward / _backward (+ probav_fusenet_workspace_bytes)     test_fusenet
-    probav_mfma_probe, probav_mfma_probe_shape (the measurement aid's `sink`)  test_mfma_probe
-Left out: nothing that writes device memory.  The host-only entries (engine create / destroy, set_impl, side_stream, the size, layout,
+Every run is followed by one on a late stream (tests/bands.py, `_late_run`; tests/late_stream.py): the same launch on a stream that is still busy
+with a delay, its inputs delivered behind the delay.  The result must be the first run's bit for bit -- every launch, memset, fork and join of an
+entry point is on, or from, the stream it was given -- and the call must come back while the delay is still running: it only enqueues.
+HOST_WAIT_EXEMPT lists the calls the header allows to wait; they are held to the first half alone.
+
+Entry points of include/probav_hip.h that take a stream -> the test that holds them: STREAMED below (tests/test_bands_host.py holds the table to
+the header).  Left out: nothing that writes device memory.  The host-only entries (engine create / destroy, set_impl, side_stream, the size, layout,
 view, plan and profile queries, probav_debug_hidden_from_forward_kernel) write none.
 
 Rows of tests/plan_cases.py: the classes with a short last strip or more than one column range run at their own N.  Skipped, because a
@@ -56,9 +37,113 @@ pytestmark = pytest.mark.gpu
 F32, I32, I64, U8, U16, F64 = torch.float32, torch.int32, torch.int64, torch.uint8, torch.uint16, torch.float64
 
 
+# entry point that takes a stream -> the test of this module that holds it (the two probav_gemm_* operators: tests/test_gpu_gemm_route.py)
+STREAMED = {
+    "probav_forward": "test_engine_one_piece",                            # training 0 / 1
+    "probav_backward": "test_engine_one_piece",
+    "probav_backward_split": "test_engine_split",                         # (+ probav_workspace_split)
+    "probav_backward_input": "test_engine_split",
+    "probav_weight_cache_build": "test_engine_weight_cache",
+    "probav_forward_wc": "test_engine_weight_cache",
+    "probav_backward_wc": "test_engine_weight_cache",
+    "probav_optimizer_step_fused": "test_engine_fused_optimizer",
+    "probav_optimizer_step_fused_guarded": "test_engine_fused_optimizer",
+    "probav_wn_forward": "test_engine_weight_norm",
+    "probav_wn_backward": "test_engine_weight_norm",
+    "probav_debug_hidden": "test_engine_debug_hidden",
+    "probav_conv3d_forward": "test_conv3d_forward",                       # and test_conv3d_plan_rows
+    "probav_conv3d_wgrad": "test_conv3d_wgrad",                           # (+ probav_conv3d_wgrad_scratch_bytes) and test_conv3d_plan_rows
+    "probav_pw_forward": "test_pointwise_pair",
+    "probav_pw_backward": "test_pointwise_pair",                          # (+ its scratch query)
+    "probav_shift_loss_forward": "test_losses",
+    "probav_shift_loss_backward": "test_losses",
+    "probav_shift_l1edge_forward": "test_losses",
+    "probav_shift_l1edge_backward": "test_losses",
+    "probav_revssim_forward": "test_losses",
+    "probav_revssim_backward": "test_losses",
+    "probav_nadam_step": "test_optimizer",
+    "probav_grad_guard": "test_optimizer",
+    "probav_nadam_step_guarded": "test_optimizer",
+    "probav_clip_round": "test_clip_round",                               # and the harness's self-tests
+    "probav_input_grad": "test_input_grad",
+    "probav_score_moments": "test_scoring",
+    "probav_score_select": "test_scoring",
+    "probav_ssim_table": "test_scoring",
+    "probav_ssim_select": "test_scoring",
+    "probav_prep_count_nonzero": "test_prep_count_nonzero",
+    "probav_prep_register": "test_prep_register",
+    "probav_prep_xcorr_surface": "test_prep_xcorr_surface",
+    "probav_prep_patches": "test_prep_patches",
+    "probav_prep_register_masked": "test_prep_register_masked",
+    "probav_prep_refine_masks": "test_prep_refine_masks",
+    "probav_augment_batch": "test_augment_and_ensemble",
+    "probav_ensemble_expand": "test_augment_and_ensemble",
+    "probav_ensemble_reduce": "test_augment_and_ensemble",
+    "probav_tile_blend": "test_tile_blend",
+    "probav_baseline_upscale_mean": "test_baseline",                      # both modes
+    "probav_frame_windows_gather": "test_frame_windows",
+    "probav_frame_windows_reduce": "test_frame_windows",
+    "probav_window_counts": "test_crops",
+    "probav_crop_batch": "test_crops",
+    "probav_fusenet_forward": "test_fusenet",                             # (+ probav_fusenet_workspace_bytes)
+    "probav_fusenet_backward": "test_fusenet",
+    "probav_mfma_probe": "test_mfma_probe",                               # the measurement aid's `sink`
+    "probav_mfma_probe_shape": "test_mfma_probe",
+}
+
+# The calls that may wait on the host, allocate or free: skipped for the late run's host-wait check, never for its comparison.  Each row quotes the sentence of
+# include/probav_hip.h (Conventions) that grants it.  entry point -> (the header's sentence, which of its calls: args of the call, calls of the session before it -> bool)
+_FIRST = "an engine's first call that launches with its layer table (a pass, a weight-norm or optimizer call) uploads that table, a few KB, once"
+_SINGLE_OP = ("the single-operator entries probav_conv3d_forward (impl 1-4), probav_pw_forward and probav_pw_backward pack their filter into a scratch the library owns: "
+              "every such call waits for `stream` to drain and uploads its packing jobs with a blocking copy")
+_AMAX = "their H3 form (impl 4, probav_conv3d_wgrad included) frees and allocates the library's amax table when a call needs more slots than any call before it"
+_CAND = "probav_shift_loss_forward frees and allocates the library's candidate table when its batch times (2 border + 1)^2 exceeds that of every call before it"
+
+
+def _first_of_its_engine(args, before):
+    handle = lambda a: getattr(a[0], "value", a[0])
+    return not any(handle(a) == handle(args) for n, a in before if n in _ENGINE_ENTRIES)
+
+
+def _larger_than_before(entry, need):
+    return lambda args, before: need(args) > max([need(a) for n, a in before if n == entry], default=0)
+
+
+_ENGINE_ENTRIES = ("probav_forward", "probav_backward", "probav_backward_split", "probav_backward_input", "probav_weight_cache_build", "probav_forward_wc", "probav_backward_wc",
+                   "probav_optimizer_step_fused", "probav_optimizer_step_fused_guarded", "probav_wn_forward", "probav_wn_backward")
+HOST_WAIT_EXEMPT = dict(
+    [(n, (_FIRST, _first_of_its_engine)) for n in _ENGINE_ENTRIES] +
+    [("probav_conv3d_forward", (_SINGLE_OP, lambda args, before: args[7] >= 1)),
+     ("probav_pw_forward", (_SINGLE_OP, lambda args, before: True)),
+     ("probav_pw_backward", (_SINGLE_OP, lambda args, before: True)),
+     ("probav_conv3d_wgrad", (_AMAX, lambda args, before: args[8] == 4 and _larger_than_before("probav_conv3d_wgrad", lambda a: a[0]._obj[0] if a[8] == 4 else 0)(args, before))),
+     ("probav_shift_loss_forward", (_CAND, _larger_than_before("probav_shift_loss_forward", lambda a: a[3] * (2 * a[5] + 1) ** 2)))])
+
+
+def _host_wait_exempt(calls, before):
+    """bands.host_wait_exempt: the header's sentence if one of the late launch's calls may wait on the host.  before: every recorded call of the session ahead of them."""
+    for i, (name, args) in enumerate(calls):
+        row = HOST_WAIT_EXEMPT.get(name)
+        if row and row[1](args, before + calls[:i]):
+            return "%s: %s" % (name, row[0])
+    return None
+
+
+class _Recorded:
+    """probav_amd._lib with every entry-point call noted (tests/late_stream.py, `recording`): how the late run knows which entry points a launch went through."""
+
+    def __getattr__(self, name):
+        from probav_amd import _lib
+        return getattr(_lib, name)
+
+    def lib(self):
+        from probav_amd import _lib
+        from tests import late_stream
+        return late_stream.recording(_lib.lib())
+
+
 def _L():
-    from probav_amd import _lib
-    return _lib
+    return _Recorded()
 
 
 def P(t):
@@ -87,9 +172,9 @@ def test_harness_reports_a_planted_overrun(dev):
     rep = bands.run(bufs, lambda t: _L().lib().probav_clip_round(P(t["in"]), P(t["out"]), n, ctypes.c_float(1.0), ctypes.c_float(65535.0), S()), dev,
                     plain=False)
     print(rep)
-    assert sorted((v.buffer, v.side, v.fill) for v in rep.violations) == [("out", "after", "0x00"), ("out", "after", "0xFF")]
+    assert sorted((v.buffer, v.side, v.fill) for v in rep.violations) == [("out", "after", "0x00"), ("out", "after", "0xFF"), ("out", "after", "late")]
     found = {v.fill: (v.first, v.last) for v in rep.violations}
-    assert found["0xFF"] == (0, 15)                        # four floats in [1, 65535]: no byte of theirs is 0xFF
+    assert found["0xFF"] == (0, 15) and found["late"] == (0, 15)            # four floats in [1, 65535]: no byte of theirs is 0xFF (the late run fills with 0xFF)
     assert found["0x00"][1] == 15 and found["0x00"][0] <= 3            # their low mantissa bytes may be zero, their exponent bytes are not
 
 
@@ -103,6 +188,33 @@ def test_harness_reports_a_planted_unwritten_element(dev):
                     plain=False)
     print(rep)
     assert [(v.buffer, v.side, v.first, v.last) for v in rep.violations] == [("out", "differs", 4 * n, 4 * n + 3)]
+
+
+def test_harness_reports_a_planted_launch_on_the_null_stream(dev):
+    """probav_clip_round handed a NULL stream.  In the ordinary runs the null stream is the current one and nothing shows.  In the late run the kernel does not wait for the
+    delay: it writes `out` (inside the arena, from the valid input the run before left there) before the fill and the inputs arrive on the late stream, and the fill erases it.
+    The harness must report exactly that: `out` differs on the late run, nothing else."""
+    n = 1025
+    x = _f32(np.random.default_rng(3), n, scale=300.0)
+    bufs = [bands.inp("in", x), bands.out("out", F32, n)]
+    rep = bands.run(bufs, lambda t: _L().lib().probav_clip_round(P(t["in"]), P(t["out"]), n, ctypes.c_float(1.0), ctypes.c_float(65535.0), None), dev)
+    print(rep)
+    assert [(v.buffer, v.side, v.fill, v.first, v.last) for v in rep.violations] == [("out", "differs", "0xFF vs late", 0, 4 * n - 1)]      # (values in [1, 65535]: no byte is 0xFF)
+
+
+def test_harness_reports_a_planted_host_wait(dev):
+    """A launch that synchronises its stream before it returns: correct bits, but the call comes back only after the delay -- also after ten times the delay."""
+    n = 255
+    x = _f32(np.random.default_rng(4), n, scale=300.0)
+    bufs = [bands.inp("in", x), bands.out("out", F32, n)]
+
+    def call(t):
+        rc = _L().lib().probav_clip_round(P(t["in"]), P(t["out"]), n, ctypes.c_float(0.0), ctypes.c_float(65535.0), S())
+        torch.cuda.current_stream().synchronize()
+        return rc
+    rep = bands.run(bufs, call, dev)
+    print(rep)
+    assert [(v.buffer, v.side, v.fill) for v in rep.violations] == [("(call)", "sync", "late")]
 
 
 # ---- single convolutions ---------------------------------------------------------------------------------------------------------------
@@ -234,7 +346,11 @@ _models, _stale = {}, {}
 @pytest.fixture(scope="module", autouse=True)
 def _give_the_device_back():
     """The engines and the stale state live as long as the module's tests need them, no longer: the modules that run afterwards get the memory back."""
+    from tests import late_stream
+    bands.host_wait_exempt = _host_wait_exempt
     yield
+    bands.host_wait_exempt = None
+    print("\n" + late_stream.summary())
     _models.clear()
     _stale.clear()
     if torch.cuda.is_available():

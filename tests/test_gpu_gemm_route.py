@@ -43,6 +43,10 @@ FWD_CASES = [c for c in CONV_CASES if not _exotic_conv(c)] + EXTRA
 BWF_CASES = WGRAD_CASES + [c for c in EXTRA if max(c[6]) <= 1]
 
 
+# entry point that takes a stream -> the test of this module that runs it in the arena, late stream included (tests/test_gpu_bands.py: STREAMED holds the other 50)
+STREAMED = {"probav_gemm_conv3d_forward": "test_bands_forward_and_backward_data", "probav_gemm_conv3d_wgrad": "test_bands_backward_filter"}
+
+
 def _L():
     from probav_amd import _lib as L
     return L

@@ -7,7 +7,9 @@ tests/ops_contract.py:
   autograd paths  an upstream gradient that arrives expanded (the gradient of .sum()) or strided gives the parameter and input gradients of the
                   same graph fed a contiguous gradient, bit for bit;
   refusal rows    through torch.ops (the dispatcher path).  The host check of the row runs first; the device call is made only if that refused
-                  the row before any entry point, and afterwards the operands the op writes are bitwise what they were.
+                  the row before any entry point, and afterwards the operands the op writes are bitwise what they were;
+  late stream     each op's well-formed row, and one whole training step through autograd, while the current stream is a stream still busy
+                  with a delay (tests/late_stream.py): the bits of the default stream, and the call back on the host before the delay has passed.
 
 Shapes: the engine at T = 9, B = 2 (22 x 22 x 9 x 1 in, 48 x 48 out) in its default family, the rest as tests/ops_contract.py states them."""
 import numpy as np
@@ -64,7 +66,9 @@ class RealEngine:
 
 @pytest.fixture(scope="module")
 def env(dev):
-    return oc.Env("cuda", RealEngine(dev))
+    yield oc.Env("cuda", RealEngine(dev))
+    from tests import late_stream
+    print("\n" + late_stream.summary())
 
 
 def _bytes(t):
@@ -242,3 +246,87 @@ def test_weight_norm_gradients_under_expanded_and_strided_upstream(env):
     flat = g.flat().requires_grad_(True)
     out = _grads_under(lambda: torch.ops.probav.wn_weight_fwd(flat, g.handle)[0], [flat])
     _assert_same_grads(out, ["flat"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# late stream: every op, and one whole step through autograd, while the current stream is not the default one (tests/late_stream.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _held_back(args):
+    """The operands of a row that arrive late: its floating tensors hold zeros until their values are copied in behind the delay (zeros are ordinary data for every
+    op); integer and boolean operands hold their values from the start, so indices stay valid.  An op without a floating operand (scoring, the baseline, the window
+    counts) would prove nothing that way: there the uint16 images and uint8 masks -- pixel data, never an index -- arrive late instead."""
+    tensors = [(n, v) for n, v in args if isinstance(v, torch.Tensor)]
+    held = [n for n, v in tensors if v.is_floating_point()]
+    return held or [n for n, v in tensors if v.dtype in (torch.uint16, torch.uint8)]
+
+
+def _single_operator_entries():
+    """The entry points whose every call the header lets wait on the host: the one table, tests/test_gpu_bands.py."""
+    from tests import test_gpu_bands as tb
+    return {n for n, (sentence, _) in tb.HOST_WAIT_EXEMPT.items() if sentence is tb._SINGLE_OP}
+
+
+@pytest.mark.parametrize("case", oc.CASES, ids=lambda c: c.id)
+def test_accepted_row_on_a_late_stream(env, case):
+    """The well-formed row of the case while the current stream is a stream that is still busy: the op must hand THAT stream to the library, and every launch behind it must
+    be on it -- the outputs are the default stream's bit for bit although the operands' values arrive only behind the delay -- and, after one warm-up call on the stream
+    (allocator pools, first-call uploads, table growth), the op must come back before the delay has passed."""
+    from tests import late_stream
+    dev = env.device
+    real = case.args(env)
+    held = _held_back(real)
+    snapshot = lambda ts: [t.detach().clone() for t in ts]
+    zeroed = lambda: [(n, (torch.zeros_like(v) if n in held else v.clone()) if isinstance(v, torch.Tensor) else v) for n, v in real]
+    want = snapshot(_call(case, _fresh(real)))
+    proof = snapshot(_call(case, zeroed()))
+    torch.cuda.synchronize()
+    assert held and not all(_same(p, w) for p, w in zip(proof, want)), "%s: the row proves nothing, zeroed operands %s give the real outputs" % (case.id, held)
+    s = late_stream.stream(dev)
+    with torch.cuda.stream(s):
+        _call(case, _fresh(real))
+    s.synchronize()
+    values = {n: v.clone() for n, v in real if n in held}
+    for factor in (1, late_stream.RETRY_FACTOR):
+        args = zeroed()
+        torch.cuda.synchronize()
+        gate = late_stream.begin(dev, factor, case.id)
+        with torch.cuda.stream(s):
+            for n, v in args:
+                if n in held:
+                    v.copy_(values[n])
+            got = _call(case, args)
+            early = gate.returned()
+            same = len(got) == len(want) and all(_same(g, w) for g, w in zip(got, want))        # (read through the stream: torch.equal waits for it alone)
+        s.synchronize()
+        if early:
+            break
+        late_stream.stats["retries"] += factor == 1
+    if not early and set(case.entries) & _single_operator_entries():
+        late_stream.note_wait("op " + case.id)
+    assert same, "%s: on a late stream the outputs are not those of the default stream" % case.id
+    assert early or set(case.entries) & _single_operator_entries(), "%s: the op came back only after a delay of %d x %.1f ms had passed on its stream" % (
+        case.id, factor, late_stream.delay_ms(dev))
+
+
+@pytest.mark.parametrize("impl", [0, 4])
+def test_training_step_on_a_late_stream(dev, impl):
+    """tests/late_step.py with the engine's default side-stream mode (2): the fork to the side stream is from the late stream and the join is back into it."""
+    from tests import late_step
+    failures, early = late_step.run(impl)
+    assert not failures, "family %d: on a late stream %s differ from the default stream's" % (impl, failures)
+    assert early, "family %d: the step came back only after the delay on its stream had passed" % impl
+
+
+@pytest.mark.parametrize("impl", [0, 4])
+def test_training_step_on_a_late_stream_without_the_side_stream(dev, impl):
+    """The same with PROBAV_NO_SIDE_STREAM=1, which the library reads once per process: a child process."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PROBAV_NO_SIDE_STREAM="1")
+    out = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from tests import late_step; late_step.main()" % root, str(impl)],
+                         env=env, capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    print(out.stdout)
+    assert "LATE_STEP failures=none early=True" in out.stdout, out.stdout[-2000:]
