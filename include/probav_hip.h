@@ -395,6 +395,27 @@ int probav_engine_route_counts(const probav_engine* e, int batch, int32_t counts
 /* The same four counts of what the engine's passes have ACTUALLY launched since the last reset, incremented where the launches are issued: after one
  * training step they equal probav_engine_route_counts (tests/test_gpu_gemm_route.py holds the census to them).  reset != 0 clears them after the read.  */
 int probav_engine_launched_counts(probav_engine* e, int32_t counts[4], int reset);
+/* The route's fused pointwise pair (csrc/kernels_gemm_pw.hip; host-only entry points, additions made under ABI 7).  On the route a residual block's
+ * expConv -> ReLU -> decConv runs as separate launches whose hidden tensor ([voxels][F x expRate]) passes through memory: written and read once in
+ * the forward pass, recomputed, written and read again with its gradient in the reverse pass.  A SECOND SWITCH, off by default, fuses the pair into
+ * one launch each way for F <= 64 filters, D <= 64 decay channels and any hidden count: the hidden tile stays in registers, and the workspace loses
+ * its three hidden-sized tensors (H of the saved state, Hb and dH of the reverse scratch) for one slab region per block -- size the buffers after
+ * setting it.  It takes effect exactly when the family is >= 1, the route is on, the shape has no tuned pair (the shipped 32 -> 256 -> D <= 26 keeps its
+ * own, whatever the switches) and the shape is in range; everywhere else the wish is kept and changes nothing.  probav_engine_set_impl and
+ * probav_engine_set_gemm_route keep the wish; PROBAV_GEMM_PAIR (set, non-zero) at probav_engine_create sets it.
+ * Forward results are those of the un-fused route BIT FOR BIT (each element is the same k-ordered fp32 fma chain); the reverse pass recomputes the
+ * hidden tile with that chain (the forward's ReLU gates), sums dX in a fixed order per voxel and the weight gradients over slabs whose count follows
+ * from the voxel count alone: reproducible, a sample independent of its batch mates, gradients equal to the un-fused route's to fp32 rounding.
+ * A switch flipped between a training forward and its backward is refused by the backward (PROBAV_EINVAL, nothing written).  The launch census
+ * (probav_engine_route_counts) does not count the fused pair: per block [1] drops by 5 and [3] by 2.
+ * probav_debug_hidden serves the general fused pair in every family >= 1.                                                                       */
+int probav_engine_set_gemm_pair(probav_engine* e, int on);
+int probav_engine_gemm_pair(const probav_engine* e);       /* the wish: 1 / 0 */
+int probav_engine_pair_kind(const probav_engine* e);       /* what the engine runs now: 0 un-fused, 1 the tuned fused pair, 2 the general fused pair */
+/* The general pair's launch plan, from the functions its launches call: report[0] = voxels per workgroup tile (0: shape not supported, all zero),
+ * [1] = tiles, [2] = hidden channels per chunk, [3] = chunks, [4] = workgroups of the launch (backward: the input-gradient kernel's tiles + slabs x
+ * groups of eight chunks of the weight-gradient kernel), [5] = slabs and [6] = voxels per slab (backward only; functions of nvox alone), [7] = 0.   */
+int probav_plan_pw_gemm(int F, int H, int D, int64_t nvox, int backward, int32_t report[8]);
 
 /* ---- dataset builder (utils/dataGenerator.py; proba-v_amd/prep.py), additions of ABI 7 ------------------------------------------------ */
 /* Frames are one flat [n_frames][H][W] array; a ragged list of image sets is that array plus set_offsets[n_sets+1] (int64, ascending,

@@ -15,6 +15,7 @@ using namespace probav;
 #include "kernels_mfma.h"
 #include "kernels_x6.h"
 #include "kernels_gemm.h"
+#include "kernels_gemm_pw.h"
 
 // MFMA operand fragments: offsets into the workspace's wpack region (-1 = none)
 struct ConvFrags { long f32 = -1, x6 = -1, h3 = -1, h3t = -1; };   // one direction of a 3x3x3 layer; h3t: per-tap H3 fragments of a 25-channel layer
@@ -30,22 +31,24 @@ struct LayerRec {
 // what a kernel family (probav_engine_set_impl) may use: 0 direct kernels, 1 MFMA row-tile kernels, 2 MFMA + strip convolution where it
 // applies, 3 = 2 with the x6 kernels (fp32 products as six bf16-piece MFMA products) where they exist, 4 = 3 with the H3 arithmetic (three
 // products of scaled fp16 piece pairs) where it exists
+enum class PairKind { none = 0, tuned = 1, gemm = 2 };      // un-fused | the tuned pair of the shipped shape (kernels_mfma / kernels_x6) | the general matrix route's (kernels_gemm_pw.hip)
 struct Family {
     bool mfma;                // MFMA kernels, and the dedicated small kernels (upscale layer, one-channel input, fused residual path, tuned direct backward-filter)
     bool strip;               // MFMA strip convolution
     bool x6;                  // split-operand kernels
     int arith;                // their arithmetic: 0 none, 1 X6, 2 H3
-    bool pw_fused;            // the fused pointwise pair (expConv + ReLU + decConv in one launch each way)
+    PairKind pw_fused;        // the fused pointwise pair (expConv + ReLU + decConv in one launch each way): which kernels run it, if any
     bool gemm;                // the general matrix route (kernels_gemm.hip) wherever a launch would otherwise fall to the generic direct kernels
 };
 // gemm: the engine's switch (probav_engine_set_gemm_route), kept on the engine apart from the family and folded in here, so that a change of family keeps it;
-// it needs the matrix kernels' family (impl >= 1): family 0 stays the direct kernels everywhere
-static Family make_family(int impl, bool pw_mfma, bool gemm = false)
+// it needs the matrix kernels' family (impl >= 1): family 0 stays the direct kernels everywhere.  pair_gemm: the second switch (probav_engine_set_gemm_pair) on a block
+// geometry that gemm_pw_supported takes; it fuses the pair only on the route, and only where the tuned pair does not exist
+static Family make_family(int impl, bool pw_mfma, bool gemm = false, bool pair_gemm = false)
 {
     Family f;
     f.mfma = impl >= 1; f.strip = impl >= 2; f.x6 = impl >= 3; f.arith = impl >= 4 ? 2 : (impl >= 3 ? 1 : 0);
-    f.pw_fused = f.mfma && pw_mfma;
     f.gemm = f.mfma && gemm;
+    f.pw_fused = !f.mfma ? PairKind::none : (pw_mfma ? PairKind::tuned : (f.gemm && pair_gemm ? PairKind::gemm : PairKind::none));
     return f;
 }
 
@@ -57,6 +60,8 @@ struct probav_engine {
     Family fam = {};
     int impl = 4;                                   // what fam was made from (probav_engine_set_impl)
     bool gemm = false;                              // probav_engine_set_gemm_route: folded into fam by make_family
+    bool gemm_pair = false;                         // probav_engine_set_gemm_pair: the wish; folded into fam (with pw_gemm) by make_family
+    bool pw_gemm = false;                           // the block geometry has a general fused pointwise pair (gemm_pw_supported)
     int32_t launched[4] = {0, 0, 0, 0};             // what conv_fwd / conv_wgrad have launched, as probav_engine_route_counts counts (probav_engine_launched_counts)
     int iMain = -1, iResid1 = -1, iResid2 = -1, iResid3 = -1, iUp = -1;
     std::vector<int> iExp, iDec, iNorm, iRed;
@@ -73,7 +78,7 @@ struct probav_engine {
     std::vector<std::array<PwFrags, 3>> pkBlk;   // per residual block, per arithmetic (fp32, X6, H3)
     bool pw_mfma = false;     // the block geometry has a fused pointwise pair
     bool fwd_amax = false;    // the last training forward filled the amax slots of the saved activations (H3 kernels, impl 4)
-    bool fwd_unfused = false; // ... and laid its workspace out for the unfused pointwise pair (impl 0): the backward pass must agree
+    PairKind fwd_pair = PairKind::none; // ... and ran the pointwise pair in this form, with this workspace layout: the backward pass must agree
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg)
     bool prof_on = false;
     unsigned prof_mask = ~0u;   // kernel classes whose launches are bracketed (bit = class index)
@@ -82,6 +87,9 @@ struct probav_engine {
     std::vector<double> prof_macs;
     size_t prof_used = 0;
 };
+
+// the family of the engine's impl and its two switches: every setter makes it here, so each keeps what the others set
+static Family engine_family(const probav_engine* e) { return make_family(e->impl, e->pw_mfma, e->gemm, e->gemm_pair && e->pw_gemm); }
 
 enum { CLS_WN = 0, CLS_SMALL, CLS_CONV3_FWD, CLS_CONV3_BWD_DATA, CLS_CONV3_WGRAD, CLS_PW_FWD, CLS_PW_BWD_DATA, CLS_PW_WGRAD,
        // launches served by an x6 kernel (bf16 MFMA pipe) are timed apart from the fp32-MFMA / VALU ones: they price against another peak
@@ -279,7 +287,7 @@ static size_t wgrad_need(const Family& f, const ConvGeom& g, const Operands& o =
 // pointwise pair fused or layer by layer, and under the H3 arithmetic which launches get their inputs' amax slots and which leave their output's
 static std::vector<Launch> step_launches(const probav_engine* e, const Net& n)
 {
-    const bool h3 = e->fam.arith == 2, fusedp = e->fam.pw_fused, fusedr = resid_path_fused(e);
+    const bool h3 = e->fam.arith == 2, fusedp = e->fam.pw_fused != PairKind::none, fusedr = resid_path_fused(e);
     const int R = e->cfg.num_res_blocks, nred = (int)n.red.size();
     std::vector<Launch> v;
     v.reserve(16 + 12 * R + 4 * nred);
@@ -345,6 +353,13 @@ static std::vector<Launch> step_launches(const probav_engine* e, const Net& n)
     return v;
 }
 
+// slab floats of the fused pair's reverse launch (g: expConv's geometry), by the kind that runs it
+static size_t pair_slab_floats(const probav_engine* e, const ConvGeom& g)
+{
+    if (e->fam.pw_fused == PairKind::gemm) return gemm_pw_backward_slab_floats(g.Cin, g.Cout, e->cfg.dec_channels, in_voxels(g));
+    return mfma_pw_backward_slab_floats(e->cfg.dec_channels);
+}
+
 static Plan make_plan(const probav_engine* e, int B, int training)
 {
     Plan p;
@@ -383,7 +398,7 @@ static Plan make_plan(const probav_engine* e, int B, int training)
     p.r2 = take(out_floats(n.resid2));
     p.r3 = take(out_floats(n.resid3));
     // the 256-channel hidden tensor (1 KB per voxel) only exists in memory when the pointwise pair runs UNfused (generic kernels, impl 0)
-    const bool unfused = !e->fam.pw_fused;
+    const bool unfused = e->fam.pw_fused == PairKind::none;
     p.H = take(unfused ? out_floats(n.exp) : 0);
     p.fwd_total = off;
     off = 0;
@@ -411,7 +426,7 @@ static Plan make_plan(const probav_engine* e, int B, int training)
         for (Launch& L : p.launches) {
             if (!L.back) continue;
             if (L.kind == LaunchKind::wgrad) L.slab = region(wgrad_need(e->fam, L.g, L.o));
-            else if (L.kind == LaunchKind::fused && L.role == Role::pair) L.slab = region(mfma_pw_backward_slab_floats(n.dec.Cout));
+            else if (L.kind == LaunchKind::fused && L.role == Role::pair) L.slab = region(pair_slab_floats(e, L.g));
             else if (L.kind == LaunchKind::fused) {
                 // the fused residual path: one slab per patch in the first of the three regions its layers would have, which keep the sizes they have always had,
                 // with or without the general matrix route
@@ -657,6 +672,30 @@ static int pw_backward_launch(const PassBufs& b, const Launch& L, const AmaxSlot
                        b.grads + we.b_off, b.grads + wd.b_off, b.slabs + L.slab.off, nvox, nvox / A.B, D, m, s);
 }
 
+// the general matrix route's pair (kernels_gemm_pw.hip) of block i: the effective weights as the route's other launches read them.  It does not report amax: where the
+// launch list's neighbours are H3 kernels, ay (per-sample slots of the output) is filled by amax_tensor behind the launch, as conv_fwd does for the route
+static int gemm_pair_forward_launch(const probav_engine* e, int i, const Derived& dv, const float* params, const float* x, float* dec, const ConvGeom& g,
+                                    unsigned* ay, hipStream_t s, float* hidden = nullptr)
+{
+    const WnLayer &we = e->layers[e->iExp[i]].wn, &wd = e->layers[e->iDec[i]].wn;
+    const int D = e->cfg.dec_channels;
+    CK(gemm_pw_forward(x, dv.weff + we.w_off, params + we.b_off, dv.weff + wd.w_off, params + wd.b_off, dec, hidden, in_voxels(g), g.Cin, g.Cout, D, s));
+    if (ay) CK(amax_tensor(dec, (size_t)g.Ho * g.Wo * g.To * D, g.N, ay, s));
+    return PROBAV_OK;
+}
+static int gemm_pair_backward_launch(const PassBufs& b, const Launch& L, const float* x, const float* dT, const float* dOut, float* dX, unsigned* ay, hipStream_t s)
+{
+    const probav_engine* e = b.e;
+    const ConvGeom& g = L.g;
+    const int i = L.i, D = e->cfg.dec_channels;
+    if (L.kind != LaunchKind::fused || gemm_pw_backward_slab_floats(g.Cin, g.Cout, D, in_voxels(g)) > L.slab.floats) { set_error("probav_backward: the general fused pointwise pair's launch is not in the launch list, or its slab region is too small", hipSuccess); return PROBAV_EINVAL; }
+    const WnLayer &we = e->layers[e->iExp[i]].wn, &wd = e->layers[e->iDec[i]].wn;
+    CK(gemm_pw_backward(x, dT, dOut, b.dv.weff + we.w_off, b.params + we.b_off, b.dv.weff + wd.w_off, dX, b.dweff2 + we.w_off, b.dweff2 + wd.w_off,
+                        b.grads + we.b_off, b.grads + wd.b_off, b.slabs + L.slab.off, in_voxels(g), g.Cin, g.Cout, D, s));
+    if (ay) CK(amax_tensor(dX, (size_t)g.Hi * g.Wi * g.Ti * g.Cin, g.N, ay, s));
+    return PROBAV_OK;
+}
+
 extern "C" {
 
 int probav_abi_version(void) { return PROBAV_ABI_VERSION; }
@@ -774,9 +813,12 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
     // (the layer and packing tables go to the device with the first call that launches with them: device_tables)
     const char* env = getenv("PROBAV_IMPL");
     const char* genv = getenv("PROBAV_GEMM_ROUTE");                // set and non-zero: the general matrix route is on from the start
+    const char* penv = getenv("PROBAV_GEMM_PAIR");                 // set and non-zero: the wish for the route's fused pointwise pair is on from the start
     e->impl = env ? atoi(env) : 4;
     e->gemm = genv && atoi(genv) != 0;
-    e->fam = make_family(e->impl, e->pw_mfma, e->gemm);
+    e->gemm_pair = penv && atoi(penv) != 0;
+    e->pw_gemm = gemm_pw_supported(F, E, D, (long)e->Hin * e->Hin * T);
+    e->fam = engine_family(e);
     *out = e;
     return PROBAV_OK;
 }
@@ -875,7 +917,7 @@ int probav_engine_set_impl(probav_engine* e, int impl)
 {
     if (!e || impl < 0 || impl > 4) { set_error("probav_engine_set_impl: bad argument", hipSuccess); return PROBAV_EINVAL; }
     e->impl = impl;
-    e->fam = make_family(impl, e->pw_mfma, e->gemm);
+    e->fam = engine_family(e);
     return PROBAV_OK;
 }
 
@@ -883,10 +925,29 @@ int probav_engine_set_gemm_route(probav_engine* e, int on)
 {
     if (!e) { set_error("probav_engine_set_gemm_route: null engine", hipSuccess); return PROBAV_EINVAL; }
     e->gemm = on != 0;
-    e->fam = make_family(e->impl, e->pw_mfma, e->gemm);
+    e->fam = engine_family(e);
     return PROBAV_OK;
 }
 int probav_engine_gemm_route(const probav_engine* e) { return e && e->gemm ? 1 : 0; }
+
+int probav_engine_set_gemm_pair(probav_engine* e, int on)
+{
+    if (!e) { set_error("probav_engine_set_gemm_pair: null engine", hipSuccess); return PROBAV_EINVAL; }
+    e->gemm_pair = on != 0;
+    e->fam = engine_family(e);
+    return PROBAV_OK;
+}
+int probav_engine_gemm_pair(const probav_engine* e) { return e && e->gemm_pair ? 1 : 0; }
+int probav_engine_pair_kind(const probav_engine* e) { return e ? (int)e->fam.pw_fused : 0; }
+
+int probav_plan_pw_gemm(int F, int H, int D, int64_t nvox, int backward, int32_t report[8])
+{
+    if (!report) { set_error("probav_plan_pw_gemm: null report", hipSuccess); return PROBAV_EINVAL; }
+    int v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!gemm_pw_plan_ints(F, H, D, (long)nvox, backward != 0, v)) for (int i = 0; i < 8; ++i) v[i] = 0;
+    for (int i = 0; i < 8; ++i) report[i] = v[i];
+    return PROBAV_OK;
+}
 
 size_t probav_workspace_bytes(const probav_engine* e, int batch, int training)
 {
@@ -948,7 +1009,7 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wcol(li); m.y = ay; } return m; };
     // (the per-sample amax slots -- the atomicMax targets -- are cleared by head_kernel below; the weight slots in front of them are plain stores of wn_forward_kernel /
     // wn_rowmax_kernel, every one of them written before anything reads it)
-    if (training) { e->fwd_amax = h3; e->fwd_unfused = !e->fam.pw_fused; }
+    if (training) { e->fwd_amax = h3; e->fwd_pair = e->fam.pw_fused; }
 
     if (!WC) {
         { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, W + p.weff, W + p.weffT, W + p.invn, h3 ? A.base : nullptr, s)); }
@@ -973,7 +1034,11 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     CK(conv_fwd(pb, fwd(Role::main), W + p.xn, nullptr, nullptr, W + p.act[0], amx(nullptr, e->iMain, A.act(0)), s));
     for (int i = 0; i < R; ++i) {
         const Launch pair = launch_at(p, Role::pair, LaunchKind::fused, false, i);
-        if (pair.kind == LaunchKind::fused) {
+        if (pair.kind == LaunchKind::fused && e->fam.pw_fused == PairKind::gemm) {
+            // the general matrix route's pair: any channel counts, the route's operands (fp32 class, the pair's algorithmic MACs)
+            ProfScope ps(e, CLS_PW_FWD, geom_macs(n.exp) + geom_macs(n.dec), s);
+            CK(gemm_pair_forward_launch(e, i, dv, params, W + p.act[i], W + p.dec[i], pair.g, h3 ? A.dec(i) : nullptr, s));
+        } else if (pair.kind == LaunchKind::fused) {
             // fused expConv + ReLU + decConv: the 256-channel tensor never leaves the accumulators
             ProfScope ps(e, e->fam.x6 ? CLS_PW_FWD_X6 : CLS_PW_FWD, geom_macs(n.exp) + geom_macs(n.dec), s);
             CK(pw_forward_launch(e, i, dv.wpack, A, params, W + p.act[i], W + p.dec[i], in_voxels(pair.g), A.dec(i), s));
@@ -1038,8 +1103,8 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     const AmaxSlots A(e, p, W, dv.wslots, S);
     auto slot_of = [&](const Launch& L, int k = 0) -> unsigned* { return h3 && k < L.slots ? A.back(L.slot + k) : nullptr; };
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wrow(li); m.y = ay; } return m; };   // backward-data: the matrix' columns are the layer's INPUT channels
-    if (e->fwd_unfused != !e->fam.pw_fused) {
-        set_error("probav_backward: the kernel family changed between forward and backward in a way that changes the workspace layout (impl 0 <-> >= 1)", hipSuccess);
+    if (e->fwd_pair != e->fam.pw_fused) {
+        set_error("probav_backward: the pointwise pair's form changed between forward and backward (the kernel family, impl 0 <-> >= 1, or a route switch): the workspace layout differs", hipSuccess);
         return PROBAV_EINVAL;
     }
     if (h3 && !e->fwd_amax) {
@@ -1141,8 +1206,12 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
             // fused: H recompute, dH, ReLU gate, dX (+ skip), dW1, dW2, db1, db2 -- nothing 256-wide touches HBM
             unsigned* anew = slot_of(pair);                  // amax slot of dX
             {   // (the class's bracket ends HERE: the flush below launches the batched slab sums on this stream, and they are no part of this class)
-            ProfScope ps(e, e->fam.x6 ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, 2.0 * (geom_macs(ge) + geom_macs(gd)), s);   // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work
-            CK(pw_backward_launch(pb, pair, A, W + p.act[i], gDec, cur, oth, agdec, anew, s));
+            const bool gp = e->fam.pw_fused == PairKind::gemm;
+            // bwd-data + bwd-filter of expConv and decConv; the recompute of H (F*E more) is not algorithmic work of the tuned pair.  The general pair books it
+            // (3 F H + 2 H D per voxel), as the un-fused route's recomputing launch does
+            ProfScope ps(e, (e->fam.x6 && !gp) ? CLS_PW_BWD_DATA_X6 : CLS_PW_BWD_DATA, (gp ? 3.0 : 2.0) * geom_macs(ge) + 2.0 * geom_macs(gd), s);
+            if (gp) CK(gemm_pair_backward_launch(pb, pair, W + p.act[i], gDec, cur, oth, anew, s));
+            else CK(pw_backward_launch(pb, pair, A, W + p.act[i], gDec, cur, oth, agdec, anew, s));
             }
             float* tmp2 = cur; cur = oth; oth = tmp2;
             acur = anew;
@@ -1303,7 +1372,14 @@ int probav_workspace_view(const probav_engine* e, int batch, int training, int k
 int probav_debug_hidden(probav_engine* e, const float* params, const void* ws, size_t ws_bytes, int B, int block, float* hidden, float* dec_scratch, const void* wcache, void* stream)
 {
     if (!e || !params || !ws || !hidden || !dec_scratch || B < 1 || block < 0 || block >= e->cfg.num_res_blocks) { set_error("probav_debug_hidden: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
-    if (!e->fam.x6 || !e->fam.pw_fused) { set_error("probav_debug_hidden: only the split-operand kernel families (impl 3, 4) expose their hidden tile", hipSuccess); return PROBAV_EINVAL; }
+    if (e->fam.pw_fused == PairKind::gemm) {
+        // the general fused pair, in every family that has it: its forward launch again with the dump pointer, into the caller's scratch; the saved state is only read
+        const Plan p = make_plan(e, B, 1);
+        if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_debug_hidden: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
+        const float* W = (const float*)ws;
+        return gemm_pair_forward_launch(e, block, derived(e, p, W, (const float*)wcache), params, W + p.act[block], dec_scratch, p.net.exp, nullptr, (hipStream_t)stream, hidden);
+    }
+    if (!e->fam.x6 || e->fam.pw_fused != PairKind::tuned) { set_error("probav_debug_hidden: only the split-operand kernel families (impl 3, 4) expose their hidden tile", hipSuccess); return PROBAV_EINVAL; }
     const Plan p = make_plan(e, B, 1);
     if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_debug_hidden: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
     const float* W = (const float*)ws;

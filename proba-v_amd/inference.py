@@ -48,6 +48,8 @@ def add_inference_args(p, where=""):
     p.add_argument("--gemm-route", dest="gemm_route", action="store_true", help=where + "the engine's general matrix route (WDSRModel.set_gemm_route): "
                    "launches that would run the generic VALU kernels -- a cfg whose num_filters, exp_rate or decay_rate are not the shipped ones -- run on "
                    "the fp32-input MFMA instead; any checkpoint, results equal to fp32 rounding")
+    p.add_argument("--gemm-pair", dest="gemm_pair", action="store_true", help=where + "with --gemm-route: the route's fused pointwise pair "
+                   "(WDSRModel.set_gemm_pair): a block's expConv, ReLU and decConv in one launch, the hidden tensor never in memory; the same bits")
 
 
 def inference_options(p, opt, applies=True, needs=""):
@@ -57,9 +59,11 @@ def inference_options(p, opt, applies=True, needs=""):
     naming `needs`, the flag that would make it predict."""
     if not applies:
         for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.weights != "raw", "--weights"), (opt.tile_stride != 0, "--tile-stride"),
-                            (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse"), (opt.gemm_route, "--gemm-route")):
+                            (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse"), (opt.gemm_route, "--gemm-route"), (opt.gemm_pair, "--gemm-pair")):
             if given:
                 p.error("%s applies to %s (a folder of PNGs is scored as it is)" % (flag, needs))
+    if opt.gemm_pair and not opt.gemm_route:
+        p.error("--gemm-pair needs --gemm-route")
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
     if opt.tile_stride == 0 and opt.tile_window is not None:
@@ -98,9 +102,9 @@ def inference_options(p, opt, applies=True, needs=""):
     return opt.inference
 
 
-def load_model(config, cfg_path, band, weights, who, gemm_route=False):
+def load_model(config, cfg_path, band, weights, who, gemm_route=False, gemm_pair=False):
     """The cfg's network on the device with its latest checkpoint restored (`weights`: "raw" or "ema") -> (model, trainer).  `who` names the
-    command in the error of a checkpoint without an "ema" entry.  gemm_route: the engine's general matrix route (--gemm-route)."""
+    command in the error of a checkpoint without an "ema" entry.  gemm_route: the engine's general matrix route (--gemm-route); gemm_pair: its fused pointwise pair (--gemm-pair)."""
     from .modelsTF import WDSRConv3D
     from .trainClass import ModelTrainer
     mean, std = BAND_STATS["NIR" if band == "NIR" else "RED"]
@@ -111,6 +115,8 @@ def load_model(config, cfg_path, band, weights, who, gemm_route=False):
         patchSizeLR=config["patch_size"], isGrayScale=config["is_grayscale"]).to("cuda")
     if gemm_route:
         model.set_gemm_route(True)
+    if gemm_pair:
+        model.set_gemm_pair(True)
     basename = os.path.basename(cfg_path).split(".")[0]
     try:
         trainer = ModelTrainer(model, None, None, None, os.path.join(config["model_out"], "ckpt_%s" % basename, band),

@@ -12,11 +12,11 @@ from . import _lib
 
 
 def pointwise_pair_is_fused(m):
-    """Whether the engine of `m` runs expConv + ReLU + decConv as ONE launch each way in its current kernel family: every family but 0, at the channel
-    counts the fused kernels take (mfma_pw_supported, csrc/kernels_mfma.hip: 32 -> 256 -> D <= 26).  Otherwise the hidden tensor passes through memory
-    and each 1x1x1 layer is a launch of its own (csrc/engine.hip: Family::pw_fused)."""
-    F, E, D = m.numFilters, m.numFilters * m.expRate, int(m.numFilters * m.decayRate)
-    return m.impl >= 1 and F == 32 and E == 256 and 1 <= D <= 26
+    """Whether the engine of `m` runs expConv + ReLU + decConv as ONE launch each way now (`probav_engine_pair_kind`, csrc/engine.hip: Family::pw_fused):
+    in every family but 0 at the channel counts the tuned kernels take (mfma_pw_supported, csrc/kernels_mfma.hip: 32 -> 256 -> D <= 26; kind 1), or, with
+    the general matrix route and its pair switch on, at the counts gemm_pw_supported takes (csrc/kernels_gemm_pw.hip; kind 2).  Otherwise the hidden tensor
+    passes through memory and each 1x1x1 layer is a launch of its own."""
+    return _lib.lib().probav_engine_pair_kind(m._handle()) != 0
 
 
 def _effective_weights(m, flat_used, wc):
@@ -57,8 +57,8 @@ def _unfused_hidden(m, flat_used, weff, x, B, T, block):
 def device_gates(m, flat_used, B, T=9, samples=None):
     """{layer: bool array}: the ReLU decisions of the last training forward of `m` (batch B, T frames), read from the saved activations
     (a post-ReLU value is > 0 exactly where the gate is open: `probav_workspace_view`) and, for the hidden tiles of the fused pointwise pair, which
-    never reach memory, recomputed by the forward kernel itself (`probav_debug_hidden`; kernel families 3 and 4 -- the fp32-MFMA families do not expose
-    theirs, and the call raises).  Where the pair runs un-fused (family 0; any family at channel counts other than 32 -> 256 -> D <= 26:
+    never reach memory, recomputed by the forward kernel itself (`probav_debug_hidden`; the tuned pair: kernel families 3 and 4 -- the fp32-MFMA families
+    do not expose theirs, and the call raises; the general matrix route's pair: every family).  Where the pair runs un-fused (family 0; any family at channel counts other than 32 -> 256 -> D <= 26:
     `pointwise_pair_is_fused`) the hidden tensor is rebuilt from the saved block input with the launch the reverse pass itself recomputes it with
     (`_unfused_hidden`).  Needs the pass's workspace alive: run the forward with PROBAV_KEEP_WS=1, or call this before the backward pass releases it.
     samples (optional): only these samples of the batch, in this order -- the gates of a sub-batch of a large batch (every saved tensor is

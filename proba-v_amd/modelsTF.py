@@ -210,6 +210,19 @@ class WDSRModel(torch.nn.Module):
         """Whether the engine's general matrix route is on (`set_gemm_route`, or PROBAV_GEMM_ROUTE at engine creation)."""
         return bool(_lib.lib().probav_engine_gemm_route(self._handle()))
 
+    def set_gemm_pair(self, on):
+        """probav_engine_set_gemm_pair: the route's fused pointwise pair (csrc/kernels_gemm_pw.hip).  With the route on (`set_gemm_route`) and no tuned pair
+        for the shape, a block's expConv -> ReLU -> decConv runs as one launch each way and its hidden tensor never reaches memory: the forward bits are the
+        un-fused route's, the workspace loses three hidden-sized tensors.  Off by default (PROBAV_GEMM_PAIR=1 turns the wish on at engine creation);
+        `set_impl` and `set_gemm_route` keep it.  The workspace changes size, so the sizes the ops cache per engine are asked for again."""
+        _lib.check(_lib.lib().probav_engine_set_gemm_pair(self._handle(), int(bool(on))), "probav_engine_set_gemm_pair")
+        ops.forget_engine(self._handle().value)
+
+    @property
+    def gemm_pair(self):
+        """Whether the wish for the route's fused pointwise pair is on (`set_gemm_pair`, or PROBAV_GEMM_PAIR at engine creation)."""
+        return bool(_lib.lib().probav_engine_gemm_pair(self._handle()))
+
     def set_side_stream_mode(self, mode):
         """probav_engine_side_stream: 0 = everything on the caller's stream; 1 = the slab sums, the residual path and the upscale layer's backward-filter on the
         engine's low-priority side stream; 2 = also the blocks' backward-filter kernels (the engine's default)."""

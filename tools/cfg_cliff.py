@@ -7,7 +7,11 @@ configuration, ms per training step (forward + shift-L1 + backward), patches/s, 
     --filters F        only the num_filters = F row (batch 128, 12 blocks, expansion --exp, default 8)
     --ab               per row, the route off and on ALTERNATED in one process on one model: --windows windows per leg (default 3) of --steps steps each, timed
                        with device events; ms per step off / on, their ratio, the off leg's own window-to-window spread, the training workspace bytes off / on,
-                       and the TFLOP/s of the fp32 kernel classes (probav_engine_profile: what the route's launches are booked under) with the route on"""
+                       and the TFLOP/s of the fp32 kernel classes (probav_engine_profile: what the route's launches are booked under) with the route on
+    --gemm-route --pair   the table with the route and its fused pointwise pair on
+    --ab --pair        the same A/B with the route ON in both legs and the route's fused pointwise pair (WDSRModel.set_gemm_pair) alternated: ms per step pair off / on,
+                       the off leg's spread, probav_workspace_bytes(e, B, 1) and the device memory in use at the end of each leg (workspace blocks released between legs), and the TFLOP/s of the pair's two launches
+                       (classes pw_fwd / pw_bwd_data, algorithmic MACs F H + H D forward and 3 F H + 2 H D in reverse per voxel)"""
 import argparse
 import ctypes
 import json
@@ -18,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from probav_amd import _lib as L
-from probav_amd import synth
+from probav_amd import ops, synth
 from probav_amd.loss import Losses
 from probav_amd.modelsTF import WDSRConv3D
 
@@ -35,11 +39,13 @@ def macs_per_patch(P, T, F=32, E=8, decay=0.8, R=12):
     return R * V * (F * F * E + F * E * D + 27 * D * F)
 
 
-def build(P, T, B, decay, F, E, gemm):
+def build(P, T, B, decay, F, E, gemm, pair=False):
     model = WDSRConv3D("cliff", "NIR", synth.NIR_MEAN, synth.NIR_STD, 6).build(3, F, (3, 3, 3), 12, E, decay, T, P, True, seed=0)
     model = model.to(dev)
     if gemm:
         model.set_gemm_route(True)
+    if pair:
+        model.set_gemm_pair(True)
     rng = np.random.default_rng(1)
     H = P + 6
     x = torch.as_tensor(np.clip(rng.normal(synth.NIR_MEAN, synth.NIR_STD, (B, H, H, T, 1)), 0, 16383).astype(np.float32)).to(dev)
@@ -73,8 +79,8 @@ def release(model):
     torch.cuda.empty_cache()
 
 
-def run(P, T, B, decay=0.8, F=32, steps=30, E=8, gemm=False):
-    model, step = build(P, T, B, decay, F, E, gemm)
+def run(P, T, B, decay=0.8, F=32, steps=30, E=8, gemm=False, pair=False):
+    model, step = build(P, T, B, decay, F, E, gemm, pair)
     for _ in range(5):
         step()
     ms = sorted(timed(step, steps))
@@ -126,6 +132,54 @@ def run_ab(P, T, B, decay, F, E, steps, windows):
             "fp32_classes_on": {"launches": launches, "ms": round(tms, 3), "tflops": round(tf, 2), "of_fp32_matrix_peak_157.3": round(tf / FP32_PEAK_TFLOPS, 4)}}
 
 
+def class_tflops(model, step, classes):
+    """{class: (TFLOP/s, ms, launches)} of one step with every launch on the launch stream (probav_engine_profile)."""
+    h, n = model._handle(), 13
+    model.set_side_stream_mode(0)
+    L.check(L.lib().probav_engine_profile(h, 1, 4096), "probav_engine_profile")
+    try:
+        step()
+        torch.cuda.synchronize()
+        ms, macs, cnt = (ctypes.c_double * n)(), (ctypes.c_double * n)(), (ctypes.c_int64 * n)()
+        L.check(L.lib().probav_engine_profile_read(h, n, ms, macs, cnt), "probav_engine_profile_read")
+    finally:
+        L.check(L.lib().probav_engine_profile(h, 0, 0), "probav_engine_profile")
+        model.set_side_stream_mode(2)
+    return {c: ((2.0 * macs[c] / (ms[c] * 1e-3) / 1e12 if ms[c] > 0 else 0.0), ms[c], int(cnt[c])) for c in classes}
+
+
+def run_ab_pair(P, T, B, decay, F, E, steps, windows):
+    """run_ab with the route on in both legs and the fused pointwise pair alternated."""
+    model, step = build(P, T, B, decay, F, E, True)
+    h = model._handle()
+    legs, ws, peak, kind = {False: [], True: []}, {}, {False: 0, True: 0}, {}
+    for w in range(windows):
+        for on in (False, True):
+            model.set_gemm_pair(on)
+            kind[on] = int(L.lib().probav_engine_pair_kind(h))
+            ws[on] = int(L.lib().probav_workspace_bytes(h, B, 1))
+            model._ws.clear()
+            ops.release_workspaces(dev)                         # (the other leg's blocks go back to the driver, so that what the device holds below is this leg's own)
+            step()
+            step()
+            legs[on].append(sum(timed(step, steps)) / steps)
+            free, total = torch.cuda.mem_get_info(dev)          # nothing is handed back during a leg: what the process holds now is the most it held
+            peak[on] = max(peak[on], int(total - free))
+    model.set_gemm_pair(True)
+    cls = class_tflops(model, step, (5, 6))
+    release(model)
+    med = lambda v: sorted(v)[len(v) // 2]
+    off, on = med(legs[False]), med(legs[True])
+    spread = (max(legs[False]) - min(legs[False])) / off
+    pair = {name: {"launches": cls[c][2], "ms": round(cls[c][1], 3), "tflops": round(cls[c][0], 2), "of_fp32_matrix_peak_157.3": round(cls[c][0] / FP32_PEAK_TFLOPS, 4)}
+            for name, c in (("pw_fwd", 5), ("pw_bwd_data", 6))}
+    return {"pair_kind_off_on": [kind[False], kind[True]], "ms_per_step_pair_off": round(off, 3), "ms_per_step_pair_on": round(on, 3), "on_over_off": round(on / off, 4),
+            "off_windows_ms": [round(v, 3) for v in legs[False]], "on_windows_ms": [round(v, 3) for v in legs[True]], "off_spread": round(spread, 4),
+            "faster_by_more_than_the_spread": bool(off - on > spread * off),
+            "train_workspace_bytes_off": ws[False], "train_workspace_bytes_on": ws[True], "device_bytes_in_use_off": peak[False], "device_bytes_in_use_on": peak[True],
+            "pair_classes_on": pair}
+
+
 # name, P, T, B, decay, F, E
 TABLE = (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8, 32, 8),
          ("7 frames", 16, 7, 128, 0.8, 32, 8),
@@ -139,6 +193,8 @@ TABLE = (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8, 32, 8),
          ("filters 48 / exp 6 (43 channels)", 16, 9, 128, 0.9, 48, 6))
 # the rows of --ab: the shipped one (which must not move), the cfg values the route is for, 13 frames at 64 filters
 AB_TABLE = (TABLE[0], TABLE[6], TABLE[7], TABLE[8], TABLE[9], ("filters 64, 13 frames", 16, 13, 128, 0.8, 64, 8))
+# the rows of --ab --pair: the shapes the general pair takes, and the shipped one (which keeps its tuned pair and must not move)
+PAIR_TABLE = (TABLE[8], TABLE[9], TABLE[7], AB_TABLE[5], TABLE[0])
 
 
 if __name__ == "__main__":
@@ -147,10 +203,13 @@ if __name__ == "__main__":
     ap.add_argument("--filters", type=int, default=None)
     ap.add_argument("--exp", type=int, default=8)
     ap.add_argument("--ab", action="store_true")
+    ap.add_argument("--pair", action="store_true")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--windows", type=int, default=3)
     opt = ap.parse_args()
-    table = AB_TABLE if opt.ab else TABLE
+    if opt.pair and not (opt.ab or opt.gemm_route):
+        ap.error("--pair needs --ab or --gemm-route")
+    table = (PAIR_TABLE if opt.pair else AB_TABLE) if opt.ab else TABLE
     if opt.filters is not None:
         table = (("filters %d / exp %d" % (opt.filters, opt.exp), 16, 9, 128, 0.8, opt.filters, opt.exp),)
     rows = []
@@ -158,10 +217,10 @@ if __name__ == "__main__":
     for name, P, T, B, decay, F, E in table:
         try:
             if opt.ab:
-                rows.append(dict({"config": name, "batch": B}, **run_ab(P, T, B, decay, F, E, opt.steps or 4, opt.windows)))
+                rows.append(dict({"config": name, "batch": B}, **(run_ab_pair if opt.pair else run_ab)(P, T, B, decay, F, E, opt.steps or 4, opt.windows)))
                 print(json.dumps(rows[-1]), flush=True)
                 continue
-            med = run(P, T, B, decay, F, opt.steps or 30, E, opt.gemm_route)
+            med = run(P, T, B, decay, F, opt.steps or 30, E, opt.gemm_route, opt.pair)
         except Exception as ex:                                   # a configuration the engine refuses is a row of the table too
             rows.append({"config": name, "error": str(ex)[:200]})
             print(json.dumps(rows[-1]), flush=True)
@@ -169,6 +228,6 @@ if __name__ == "__main__":
         gmacs = macs_per_patch(P, T, F, E, decay) * B / (med * 1e-3) / 1e9
         if base is None:
             base = gmacs
-        rows.append({"config": name, "batch": B, "gemm_route": bool(opt.gemm_route), "ms_per_step_median": round(med, 3), "patches_per_s": round(B / (med * 1e-3), 1),
+        rows.append({"config": name, "batch": B, "gemm_route": bool(opt.gemm_route), "gemm_pair": bool(opt.pair), "ms_per_step_median": round(med, 3), "patches_per_s": round(B / (med * 1e-3), 1),
                      "block_GMAC_per_s": round(gmacs, 1), "per_mac_throughput_vs_shipped": round(gmacs / base, 3)})
         print(json.dumps(rows[-1]), flush=True)

@@ -59,6 +59,9 @@ def parser(argv=None):
     p.add_argument("--gemm-route", dest="gemm_route", action="store_true",
                    help="the engine's general matrix route (WDSRModel.set_gemm_route): launches that would run the generic VALU kernels -- a cfg whose "
                         "num_filters, exp_rate or decay_rate are not the shipped ones, e.g. cfg/p16t9c85r12f64.cfg -- run on the fp32-input MFMA instead")
+    p.add_argument("--gemm-pair", dest="gemm_pair", action="store_true",
+                   help="with --gemm-route: the route's fused pointwise pair (WDSRModel.set_gemm_pair): a block's expConv, ReLU and decConv in one launch "
+                        "each way, the hidden tensor never in memory (F <= 64, decay channels <= 64; the shipped shape keeps its tuned pair)")
     opt = p.parse_args(argv)
     if opt.fusion_input is not None and opt.modelType != "fusionNet":
         p.error("--fusion-input needs --modelType fusionNet")
@@ -66,6 +69,10 @@ def parser(argv=None):
         p.error("--modelType fusionNet needs --fusion-input DIR (the PNGs of test.py --totest TRAIN)")
     if opt.gemm_route and opt.modelType == "fusionNet":
         p.error("--gemm-route is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
+    if opt.gemm_pair and opt.modelType == "fusionNet":
+        p.error("--gemm-pair is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
+    if opt.gemm_pair and not opt.gemm_route:
+        p.error("--gemm-pair needs --gemm-route")
     if opt.random_crops and opt.online_aug:
         p.error("--random-crops and --online-aug are mutually exclusive")
     if not opt.random_crops and (opt.crop_positions != "all" or opt.crop_seed != 0 or opt.crops_per_epoch is not None):
@@ -82,9 +89,11 @@ def parser(argv=None):
 
 
 def apply_engine_options(model, opt):
-    """The engine switches among the flags, set on the freshly built model: --gemm-route."""
+    """The engine switches among the flags, set on the freshly built model: --gemm-route, --gemm-pair."""
     if opt.gemm_route:
         model.set_gemm_route(True)
+    if opt.gemm_pair:
+        model.set_gemm_pair(True)
 
 
 def training_scenes(dataDir, band):
