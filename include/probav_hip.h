@@ -314,7 +314,9 @@ int probav_mfma_probe_shape(const void* seed, float* sink, int iters, int launch
 int probav_workspace_view(const probav_engine* e, int batch, int training, int kind, int index, int64_t* offset_floats, int64_t* count);
 /* the post-ReLU hidden tile relu(expConv_block(x)) [B*(P+s)^2*T][256] (models/modelsTF.py:179-180) exactly as the fused forward kernel
  * of the current kernel family (3 or 4) evaluates it -- that tensor never reaches memory otherwise.  Call after probav_forward(training=1)
- * with the same workspace; the ReLU gates of the reverse pass are the signs of these values.                                          */
+ * with the same workspace; the ReLU gates of the reverse pass are the signs of these values.  On an engine whose un-fused route runs in
+ * x6 arithmetic (probav_engine_gemm_arith == 1, no fused pair) it is the route's expConv launch again, as the reverse pass recomputes
+ * the hidden tensor: [..][F x expRate], dec_scratch is not written.                                                                    */
 int probav_debug_hidden(probav_engine* e, const float* params, const void* ws /* saved state: read only */, size_t ws_bytes, int batch, int block, float* hidden,
                         float* dec_scratch /* [voxels][dec channels] floats: the launch's regular output, discarded */,
                         const void* wcache /* the weight cache the forward pass ran from, or NULL */, void* stream);
@@ -416,6 +418,29 @@ int probav_engine_pair_kind(const probav_engine* e);       /* what the engine ru
  * [1] = tiles, [2] = hidden channels per chunk, [3] = chunks, [4] = workgroups of the launch (backward: the input-gradient kernel's tiles + slabs x
  * groups of eight chunks of the weight-gradient kernel), [5] = slabs and [6] = voxels per slab (backward only; functions of nvox alone), [7] = 0.   */
 int probav_plan_pw_gemm(int F, int H, int D, int64_t nvox, int backward, int32_t report[8]);
+/* The route on the 16-bit matrix pipe (csrc/kernels_gemm_x6.hip; host-only entry points, additions made under ABI 7).  The route's un-fused launches
+ * above evaluate their products on v_mfma_f32_32x32x2_f32.  A THIRD SWITCH, off by default, runs every CONVOLUTION launch that conv_route hands to the
+ * route -- forward, backward-data and the reverse pass's recomputed expConv, 1x1x1 and 3x3x3, any Cin and Cout -- in x6 arithmetic instead: each fp32 operand cut into three
+ * bf16 truncation pieces, the six largest piece products on v_mfma_f32_32x32x16_bf16, smallest terms first, fp32 accumulation (the arithmetic of the
+ * family-3 kernels: no operand scaling, no amax slots, no dependence on dynamic range).  Nothing else changes hands: the route's BACKWARD-FILTER stays
+ * fp32 (an x6 form of it was measured slower than gemm_conv_wgrad_kernel: INTEGRATION.md, 'The general matrix route'), the fused pair stays fp32, tuned,
+ * split-operand, dedicated and VALU launches stay where they are, family 0 never sees the switch.  Tiles and grids are the fp32 route's and no scratch
+ * is involved, so probav_workspace_bytes / probav_workspace_split and probav_engine_route_counts do not move with the switch.
+ * It takes effect exactly when the family is >= 1, the route is on and the wish is set (probav_engine_gemm_arith); probav_engine_set_impl,
+ * probav_engine_set_gemm_route and probav_engine_set_gemm_pair keep the wish; PROBAV_GEMM_X6 (set, non-zero) at probav_engine_create sets it.
+ * Results are reproducible bit for bit, a sample does not depend on its batch mates, and they differ from the fp32 route's by rounding (each product to
+ * about 2^-24 relative).  With the switch on, pair on and pair off no longer give the same forward bits: the un-fused 1x1x1 launches are then x6 and the
+ * pair is fp32; both are held to the oracle.  The recomputed expConv of the reverse pass must take the forward's gates, so a switch flipped between a
+ * training forward and its backward is refused by the backward (PROBAV_EINVAL, nothing written) -- whenever probav_engine_gemm_arith differs between the
+ * two, also on a network none of whose launches are the route's (the shipped one): the refusal is the engine state's, as the pair's is.        */
+int probav_engine_set_gemm_x6(probav_engine* e, int on);
+int probav_engine_gemm_x6(const probav_engine* e);         /* the wish: 1 / 0 */
+int probav_engine_gemm_arith(const probav_engine* e);      /* what the route's convolution launches run now: 0 fp32, 1 x6 */
+/* The x6 launch's plan for a geometry the route takes (host only), in the shape of probav_plan_conv_gemm's GEMM report: report[0] =
+ * PROBAV_PLAN_GEMM_X6 (op forward / backward-data), [1..7] as there.  All zero (PROBAV_PLAN_NONE) for a geometry the route's kernel does not
+ * take, and for op backward-filter, which has no x6 kernel (probav_plan_conv_gemm reports the fp32 one).                                       */
+#define PROBAV_PLAN_GEMM_X6 13       /* gemm_conv_fwd_x6_kernel */
+int probav_plan_conv_gemm_x6(const int32_t geom[17], int gated, int has_skip, int op, int32_t report[8]);
 
 /* ---- dataset builder (utils/dataGenerator.py; proba-v_amd/prep.py), additions of ABI 7 ------------------------------------------------ */
 /* Frames are one flat [n_frames][H][W] array; a ragged list of image sets is that array plus set_offsets[n_sets+1] (int64, ascending,

@@ -98,6 +98,11 @@ SIGNATURES = {
     "probav_engine_gemm_pair": (c_int, [c_void_p]),
     "probav_engine_pair_kind": (c_int, [c_void_p]),
     "probav_plan_pw_gemm": (c_int, [c_int, c_int, c_int, c_int64, c_int, POINTER(c_int32 * 8)]),
+    # the route on the 16-bit matrix pipe (csrc/kernels_gemm_x6.hip): added under ABI 7, host only
+    "probav_engine_set_gemm_x6": (c_int, [c_void_p, c_int]),
+    "probav_engine_gemm_x6": (c_int, [c_void_p]),
+    "probav_engine_gemm_arith": (c_int, [c_void_p]),
+    "probav_plan_conv_gemm_x6": (c_int, [POINTER(c_int32 * 17), c_int, c_int, c_int, POINTER(c_int32 * 8)]),
     "probav_workspace_split": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "probav_backward_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
     # input gradients (csrc/kernels_input_grad.hip): added under ABI 7

@@ -16,6 +16,7 @@ using namespace probav;
 #include "kernels_x6.h"
 #include "kernels_gemm.h"
 #include "kernels_gemm_pw.h"
+#include "kernels_gemm_x6.h"
 
 // MFMA operand fragments: offsets into the workspace's wpack region (-1 = none)
 struct ConvFrags { long f32 = -1, x6 = -1, h3 = -1, h3t = -1; };   // one direction of a 3x3x3 layer; h3t: per-tap H3 fragments of a 25-channel layer
@@ -39,15 +40,18 @@ struct Family {
     int arith;                // their arithmetic: 0 none, 1 X6, 2 H3
     PairKind pw_fused;        // the fused pointwise pair (expConv + ReLU + decConv in one launch each way): which kernels run it, if any
     bool gemm;                // the general matrix route (kernels_gemm.hip) wherever a launch would otherwise fall to the generic direct kernels
+    int gemm_arith;           // the arithmetic of the route's convolution launches (forward, backward-data): 0 fp32 (kernels_gemm.hip), 1 X6 (kernels_gemm_x6.hip)
 };
 // gemm: the engine's switch (probav_engine_set_gemm_route), kept on the engine apart from the family and folded in here, so that a change of family keeps it;
 // it needs the matrix kernels' family (impl >= 1): family 0 stays the direct kernels everywhere.  pair_gemm: the second switch (probav_engine_set_gemm_pair) on a block
-// geometry that gemm_pw_supported takes; it fuses the pair only on the route, and only where the tuned pair does not exist
-static Family make_family(int impl, bool pw_mfma, bool gemm = false, bool pair_gemm = false)
+// geometry that gemm_pw_supported takes; it fuses the pair only on the route, and only where the tuned pair does not exist.  gemm_x6: the third switch
+// (probav_engine_set_gemm_x6): the route's convolution launches in x6 arithmetic; it changes nothing but those launches' kernel
+static Family make_family(int impl, bool pw_mfma, bool gemm = false, bool pair_gemm = false, bool gemm_x6 = false)
 {
     Family f;
     f.mfma = impl >= 1; f.strip = impl >= 2; f.x6 = impl >= 3; f.arith = impl >= 4 ? 2 : (impl >= 3 ? 1 : 0);
     f.gemm = f.mfma && gemm;
+    f.gemm_arith = f.gemm && gemm_x6 ? 1 : 0;
     f.pw_fused = !f.mfma ? PairKind::none : (pw_mfma ? PairKind::tuned : (f.gemm && pair_gemm ? PairKind::gemm : PairKind::none));
     return f;
 }
@@ -61,6 +65,7 @@ struct probav_engine {
     int impl = 4;                                   // what fam was made from (probav_engine_set_impl)
     bool gemm = false;                              // probav_engine_set_gemm_route: folded into fam by make_family
     bool gemm_pair = false;                         // probav_engine_set_gemm_pair: the wish; folded into fam (with pw_gemm) by make_family
+    bool gemm_x6 = false;                           // probav_engine_set_gemm_x6: the wish; folded into fam (with gemm) by make_family
     bool pw_gemm = false;                           // the block geometry has a general fused pointwise pair (gemm_pw_supported)
     int32_t launched[4] = {0, 0, 0, 0};             // what conv_fwd / conv_wgrad have launched, as probav_engine_route_counts counts (probav_engine_launched_counts)
     int iMain = -1, iResid1 = -1, iResid2 = -1, iResid3 = -1, iUp = -1;
@@ -79,6 +84,7 @@ struct probav_engine {
     bool pw_mfma = false;     // the block geometry has a fused pointwise pair
     bool fwd_amax = false;    // the last training forward filled the amax slots of the saved activations (H3 kernels, impl 4)
     PairKind fwd_pair = PairKind::none; // ... and ran the pointwise pair in this form, with this workspace layout: the backward pass must agree
+    int fwd_gemm_arith = 0;   // ... and the general matrix route in this arithmetic: the reverse pass recomputes expConv and must get the forward's gates
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg)
     bool prof_on = false;
     unsigned prof_mask = ~0u;   // kernel classes whose launches are bracketed (bit = class index)
@@ -88,8 +94,8 @@ struct probav_engine {
     size_t prof_used = 0;
 };
 
-// the family of the engine's impl and its two switches: every setter makes it here, so each keeps what the others set
-static Family engine_family(const probav_engine* e) { return make_family(e->impl, e->pw_mfma, e->gemm, e->gemm_pair && e->pw_gemm); }
+// the family of the engine's impl and its three switches: every setter makes it here, so each keeps what the others set
+static Family engine_family(const probav_engine* e) { return make_family(e->impl, e->pw_mfma, e->gemm, e->gemm_pair && e->pw_gemm, e->gemm_x6); }
 
 enum { CLS_WN = 0, CLS_SMALL, CLS_CONV3_FWD, CLS_CONV3_BWD_DATA, CLS_CONV3_WGRAD, CLS_PW_FWD, CLS_PW_BWD_DATA, CLS_PW_WGRAD,
        // launches served by an x6 kernel (bf16 MFMA pipe) are timed apart from the fp32-MFMA / VALU ones: they price against another peak
@@ -270,7 +276,9 @@ static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Operands
     const int cls = g.kh * g.kw * g.kt == 1 ? CLS_PW_WGRAD : (x6 ? CLS_CONV3_WGRAD_X6 : CLS_CONV3_WGRAD);
     if (x6) return {WgradKernel::x6, cls, f.arith == 2 && o.am_in ? 2 : 1, false};
     if (f.mfma && mfma_wgrad_supported(g)) return {WgradKernel::mfma, cls, 0, false};
-    if (f.gemm && gemm_wgrad_supported(g)) return {WgradKernel::gemm, cls, 0, false};      // the general matrix route: only what would be the generic direct kernel's
+    // the general matrix route: only what would be the generic direct kernel's.  fp32 whatever the route's third switch says (Family::gemm_arith covers its
+    // convolution launches only: an x6 backward-filter was measured slower than this kernel)
+    if (f.gemm && gemm_wgrad_supported(g)) return {WgradKernel::gemm, cls, 0, false};
     return {WgradKernel::direct, cls, 0, false};
 }
 // the slot of the launch census (probav_engine_route_counts, probav_engine_launched_counts) a routed backward-filter counts in, or -1
@@ -521,7 +529,11 @@ static ConvRoute conv_route(const Family& f, const ConvGeom& g, const Operands& 
     if (s32.k != StripKernel::none) return {ConvKernel::mfma_strip, cls, true, 0, FragKind::f32, s32};
     if (f.mfma && o.f32 && mfma_conv_supported(g)) return {ConvKernel::mfma_rowtile, cls, true, 0, FragKind::f32, {}};
     // the general matrix route: what no matrix, split-operand or dedicated kernel took above (an exotic geometry returned before).  It does not report amax
-    if (f.gemm && dedicated && gemm_conv_supported(g)) return {ConvKernel::gemm, cls, false, 0, FragKind::none, {}};
+    // In x6 arithmetic (arith 1, the _X6 profiling classes) where the third switch is on
+    if (f.gemm && dedicated && gemm_conv_supported(g)) {
+        const int xcls = pw ? (bwd ? CLS_PW_BWD_DATA_X6 : CLS_PW_FWD_X6) : (bwd ? CLS_CONV3_BWD_DATA_X6 : CLS_CONV3_FWD_X6);
+        return {ConvKernel::gemm, f.gemm_arith ? xcls : cls, false, f.gemm_arith, FragKind::none, {}};
+    }
     return {ConvKernel::direct, cls, false, 0, FragKind::none, {}};
 }
 static int census_slot(const ConvRoute& r) { return r.k == ConvKernel::direct ? 0 : (r.k == ConvKernel::gemm ? 1 : -1); }      // (as census_slot of a backward-filter route)
@@ -536,7 +548,7 @@ static int conv_launch(const ConvRoute& r, const ConvGeom& g, const float* x, co
     case ConvKernel::x6_strip: case ConvKernel::mfma_strip: return conv_strip_forward(r.strip, x, gate, wfrag, bias, skip, y, am, s);
     case ConvKernel::x6_rowtile: return x6_conv_rowtile_forward(g, x, gate, wfrag, bias, skip, y, r.arith, am, s);
     case ConvKernel::mfma_rowtile: return mfma_conv_forward(g, x, gate, wfrag, bias, skip, y, am, s);
-    case ConvKernel::gemm: return gemm_conv_forward(g, x, gate, w, bias, skip, y, s);
+    case ConvKernel::gemm: return r.arith ? gemm_x6_conv_forward(g, x, gate, w, bias, skip, y, s) : gemm_conv_forward(g, x, gate, w, bias, skip, y, s);
     default: return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
     }
 }
@@ -817,6 +829,8 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
     e->impl = env ? atoi(env) : 4;
     e->gemm = genv && atoi(genv) != 0;
     e->gemm_pair = penv && atoi(penv) != 0;
+    const char* xenv = getenv("PROBAV_GEMM_X6");                   // set and non-zero: the wish for the route's x6 arithmetic is on from the start
+    e->gemm_x6 = xenv && atoi(xenv) != 0;
     e->pw_gemm = gemm_pw_supported(F, E, D, (long)e->Hin * e->Hin * T);
     e->fam = engine_family(e);
     *out = e;
@@ -940,6 +954,16 @@ int probav_engine_set_gemm_pair(probav_engine* e, int on)
 int probav_engine_gemm_pair(const probav_engine* e) { return e && e->gemm_pair ? 1 : 0; }
 int probav_engine_pair_kind(const probav_engine* e) { return e ? (int)e->fam.pw_fused : 0; }
 
+int probav_engine_set_gemm_x6(probav_engine* e, int on)
+{
+    if (!e) { set_error("probav_engine_set_gemm_x6: null engine", hipSuccess); return PROBAV_EINVAL; }
+    e->gemm_x6 = on != 0;
+    e->fam = engine_family(e);
+    return PROBAV_OK;
+}
+int probav_engine_gemm_x6(const probav_engine* e) { return e && e->gemm_x6 ? 1 : 0; }
+int probav_engine_gemm_arith(const probav_engine* e) { return e ? e->fam.gemm_arith : 0; }
+
 int probav_plan_pw_gemm(int F, int H, int D, int64_t nvox, int backward, int32_t report[8])
 {
     if (!report) { set_error("probav_plan_pw_gemm: null report", hipSuccess); return PROBAV_EINVAL; }
@@ -1009,7 +1033,7 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wcol(li); m.y = ay; } return m; };
     // (the per-sample amax slots -- the atomicMax targets -- are cleared by head_kernel below; the weight slots in front of them are plain stores of wn_forward_kernel /
     // wn_rowmax_kernel, every one of them written before anything reads it)
-    if (training) { e->fwd_amax = h3; e->fwd_pair = e->fam.pw_fused; }
+    if (training) { e->fwd_amax = h3; e->fwd_pair = e->fam.pw_fused; e->fwd_gemm_arith = e->fam.gemm_arith; }
 
     if (!WC) {
         { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, W + p.weff, W + p.weffT, W + p.invn, h3 ? A.base : nullptr, s)); }
@@ -1103,6 +1127,10 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     const AmaxSlots A(e, p, W, dv.wslots, S);
     auto slot_of = [&](const Launch& L, int k = 0) -> unsigned* { return h3 && k < L.slots ? A.back(L.slot + k) : nullptr; };
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wrow(li); m.y = ay; } return m; };   // backward-data: the matrix' columns are the layer's INPUT channels
+    if (e->fwd_gemm_arith != e->fam.gemm_arith) {
+        set_error("probav_backward: the general matrix route's arithmetic changed between forward and backward (probav_engine_set_gemm_x6, or a switch it depends on): the recomputed expConv would not take the forward's gates", hipSuccess);
+        return PROBAV_EINVAL;
+    }
     if (e->fwd_pair != e->fam.pw_fused) {
         set_error("probav_backward: the pointwise pair's form changed between forward and backward (the kernel family, impl 0 <-> >= 1, or a route switch): the workspace layout differs", hipSuccess);
         return PROBAV_EINVAL;
@@ -1378,6 +1406,19 @@ int probav_debug_hidden(probav_engine* e, const float* params, const void* ws, s
         if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_debug_hidden: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
         const float* W = (const float*)ws;
         return gemm_pair_forward_launch(e, block, derived(e, p, W, (const float*)wcache), params, W + p.act[block], dec_scratch, p.net.exp, nullptr, (hipStream_t)stream, hidden);
+    }
+    if (e->fam.pw_fused == PairKind::none && e->fam.gemm_arith == 1) {
+        // the un-fused route in x6 arithmetic: the launch the reverse pass recomputes the hidden tensor with (Role::hidden), which is the forward's expConv launch
+        // again -- the gates the gradient was taken at.  (In fp32 arithmetic the route's bits are the direct kernel's, and probav_conv3d_forward gives them.)
+        const Plan p = make_plan(e, B, 1);
+        if (ws_bytes < p.fwd_total * sizeof(float)) { set_error("probav_debug_hidden: workspace too small", hipSuccess); return PROBAV_ENOSPACE; }
+        const Launch L = launch_at(p, Role::hidden, LaunchKind::conv, true, block);
+        const ConvRoute r = conv_route(e->fam, L.g, L.o);
+        if (L.kind != LaunchKind::conv || r.k != ConvKernel::gemm || r.arith != 1) { set_error("probav_debug_hidden: the recomputed expConv is not a launch of the x6 route", hipSuccess); return PROBAV_EINVAL; }
+        const float* W = (const float*)ws;
+        const Derived dv = derived(e, p, W, (const float*)wcache);
+        const WnLayer& wn = e->layers[e->iExp[block]].wn;
+        return gemm_x6_conv_forward(L.g, W + p.act[block], nullptr, dv.weff + wn.w_off, params + wn.b_off, nullptr, hidden, (hipStream_t)stream);
     }
     if (!e->fam.x6 || e->fam.pw_fused != PairKind::tuned) { set_error("probav_debug_hidden: only the split-operand kernel families (impl 3, 4) expose their hidden tile", hipSuccess); return PROBAV_EINVAL; }
     const Plan p = make_plan(e, B, 1);
@@ -1736,6 +1777,21 @@ int probav_plan_conv_gemm(const int32_t geom[17], int impl, int gated, int has_s
     if (!gemm_conv_plan_ints(g, v)) return PROBAV_OK;
     for (int i = 0; i < 8; ++i) report[i] = 0;
     report[0] = PROBAV_PLAN_GEMM; report[1] = v[3]; report[2] = v[2]; report[3] = v[0]; report[4] = v[1]; report[5] = v[2] * v[3]; report[6] = v[4]; report[7] = v[5];
+    return PROBAV_OK;
+}
+
+// The x6 launches' plan for a geometry the route's kernels take: the fp32 route's tiles, grid and slabs under the x6 kernels' names
+int probav_plan_conv_gemm_x6(const int32_t geom[17], int gated, int has_skip, int op, int32_t report[8])
+{
+    if (!geom || !report || op < PROBAV_PLAN_OP_FORWARD || op > PROBAV_PLAN_OP_WGRAD) { set_error("probav_plan_conv_gemm_x6: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    const ConvGeom g = geom_from(geom);
+    if (!geom_ok(g)) { set_error("probav_plan_conv_gemm_x6: bad geometry", hipSuccess); return PROBAV_EINVAL; }
+    (void)gated; (void)has_skip;                                   // (one launch plan for every operand set: the gate is a select, bias and skip are the epilogue's)
+    for (int i = 0; i < 8; ++i) report[i] = 0;
+    if (op == PROBAV_PLAN_OP_WGRAD) return PROBAV_OK;            // no x6 kernel: the backward-filter stays the fp32 route's (probav_plan_conv_gemm reports it)
+    int v[6];
+    if (!gemm_x6_conv_plan_ints(g, v)) return PROBAV_OK;
+    report[0] = PROBAV_PLAN_GEMM_X6; report[1] = v[3]; report[2] = v[2]; report[3] = v[0]; report[4] = v[1]; report[5] = v[2] * v[3]; report[6] = v[4]; report[7] = v[5];
     return PROBAV_OK;
 }
 

@@ -24,4 +24,7 @@ int gemm_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const fl
 // launch plan: v = {slabs, voxels per slab, tile input channels, tile output channels, workgroups}; the slab count depends on the geometry alone
 bool gemm_wgrad_plan_ints(const ConvGeom& g, int v[5]);
 
+// the forward's accumulator tiles per wave (1, 2 or 4, from Cout): shared with the route's x6 form (kernels_gemm_x6.hip)
+int gemm_fwd_nt(const ConvGeom& g);
+
 }  // namespace probav

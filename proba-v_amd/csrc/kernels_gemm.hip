@@ -168,7 +168,7 @@ static bool gemm_common_supported(const ConvGeom& g, int maxpad)
 
 bool gemm_conv_supported(const ConvGeom& g) { return gemm_common_supported(g, 2); }
 
-static int gemm_fwd_nt(const ConvGeom& g) { return g.Cout <= 32 ? 1 : (g.Cout <= 64 ? 2 : 4); }
+int gemm_fwd_nt(const ConvGeom& g) { return g.Cout <= 32 ? 1 : (g.Cout <= 64 ? 2 : 4); }
 
 bool gemm_conv_plan_ints(const ConvGeom& g, int v[6])
 {

@@ -82,7 +82,9 @@ def device_gates(m, flat_used, B, T=9, samples=None):
         return t.view(B, -1)[torch.as_tensor(list(samples), device=t.device)].reshape(-1)
     gates = {"mainConv1": (pick(view(0, 0)) > 0).cpu().numpy(), "residConv1": (pick(view(3, 0)) > 0).cpu().numpy()}
     nvox = B * hin * hin * T
-    if pointwise_pair_is_fused(m):
+    # (the un-fused route in x6 arithmetic, `probav_engine_gemm_arith` == 1: its bits are not the direct kernel's, so the hidden tensor is recomputed by the
+    # route's own expConv launch, the one the reverse pass runs -- probav_debug_hidden serves that too)
+    if pointwise_pair_is_fused(m) or (m.numResBlocks and L.probav_engine_gemm_arith(h) == 1):
         hid = torch.empty(nvox * m.numFilters * m.expRate, device=ws.device)
         dec = torch.empty(nvox * int(m.numFilters * m.decayRate), device=ws.device)      # the launch's regular output (decConv), discarded
         for i in range(m.numResBlocks):

@@ -223,6 +223,20 @@ class WDSRModel(torch.nn.Module):
         """Whether the wish for the route's fused pointwise pair is on (`set_gemm_pair`, or PROBAV_GEMM_PAIR at engine creation)."""
         return bool(_lib.lib().probav_engine_gemm_pair(self._handle()))
 
+    def set_gemm_x6(self, on):
+        """probav_engine_set_gemm_x6: the route's convolution launches on the 16-bit matrix pipe (csrc/kernels_gemm_x6.hip).  With the route on
+        (`set_gemm_route`), every convolution launch it takes -- forward and backward-data, 1x1x1 and 3x3x3 -- runs in x6 arithmetic (three bf16 pieces
+        per fp32 operand, six piece products); its backward-filter and the fused pair (`set_gemm_pair`) stay fp32 and nothing else changes hands.  Off by default
+        (PROBAV_GEMM_X6=1 turns the wish on at engine creation); `set_impl`, `set_gemm_route` and `set_gemm_pair` keep it.  No workspace size depends on it;
+        results agree with the fp32 route's to rounding, not bit for bit."""
+        _lib.check(_lib.lib().probav_engine_set_gemm_x6(self._handle(), int(bool(on))), "probav_engine_set_gemm_x6")
+        ops.forget_engine(self._handle().value)
+
+    @property
+    def gemm_x6(self):
+        """Whether the wish for the route's x6 arithmetic is on (`set_gemm_x6`, or PROBAV_GEMM_X6 at engine creation)."""
+        return bool(_lib.lib().probav_engine_gemm_x6(self._handle()))
+
     def set_side_stream_mode(self, mode):
         """probav_engine_side_stream: 0 = everything on the caller's stream; 1 = the slab sums, the residual path and the upscale layer's backward-filter on the
         engine's low-priority side stream; 2 = also the blocks' backward-filter kernels (the engine's default)."""

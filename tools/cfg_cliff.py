@@ -9,9 +9,14 @@ configuration, ms per training step (forward + shift-L1 + backward), patches/s, 
                        with device events; ms per step off / on, their ratio, the off leg's own window-to-window spread, the training workspace bytes off / on,
                        and the TFLOP/s of the fp32 kernel classes (probav_engine_profile: what the route's launches are booked under) with the route on
     --gemm-route --pair   the table with the route and its fused pointwise pair on
+    --gemm-route [--pair] --x6   the table with the route's convolution launches in x6 arithmetic (WDSRModel.set_gemm_x6)
     --ab --pair        the same A/B with the route ON in both legs and the route's fused pointwise pair (WDSRModel.set_gemm_pair) alternated: ms per step pair off / on,
                        the off leg's spread, probav_workspace_bytes(e, B, 1) and the device memory in use at the end of each leg (workspace blocks released between legs), and the TFLOP/s of the pair's two launches
-                       (classes pw_fwd / pw_bwd_data, algorithmic MACs F H + H D forward and 3 F H + 2 H D in reverse per voxel)"""
+                       (classes pw_fwd / pw_bwd_data, algorithmic MACs F H + H D forward and 3 F H + 2 H D in reverse per voxel)
+    --ab --x6          the same A/B with the route AND the pair on in both legs (the last row: the pair off) and the route's x6 arithmetic (WDSRModel.set_gemm_x6)
+                       alternated: ms per step x6 off / on -- the off leg is the fp32 route, the yardstick of the same run --, the off leg's spread, whether on is
+                       below off by more than three times that spread, and the TFLOP/s of the route's kernel classes in each leg (fp32 classes off, _x6 classes on)
+                       against the published peaks: 157.3 TFLOP/s fp32 matrix, 2500 / 6 = 417 TFLOP/s of fp32-equivalent products in x6"""
 import argparse
 import ctypes
 import json
@@ -39,13 +44,15 @@ def macs_per_patch(P, T, F=32, E=8, decay=0.8, R=12):
     return R * V * (F * F * E + F * E * D + 27 * D * F)
 
 
-def build(P, T, B, decay, F, E, gemm, pair=False):
+def build(P, T, B, decay, F, E, gemm, pair=False, x6=False):
     model = WDSRConv3D("cliff", "NIR", synth.NIR_MEAN, synth.NIR_STD, 6).build(3, F, (3, 3, 3), 12, E, decay, T, P, True, seed=0)
     model = model.to(dev)
     if gemm:
         model.set_gemm_route(True)
     if pair:
         model.set_gemm_pair(True)
+    if x6:
+        model.set_gemm_x6(True)
     rng = np.random.default_rng(1)
     H = P + 6
     x = torch.as_tensor(np.clip(rng.normal(synth.NIR_MEAN, synth.NIR_STD, (B, H, H, T, 1)), 0, 16383).astype(np.float32)).to(dev)
@@ -79,8 +86,8 @@ def release(model):
     torch.cuda.empty_cache()
 
 
-def run(P, T, B, decay=0.8, F=32, steps=30, E=8, gemm=False, pair=False):
-    model, step = build(P, T, B, decay, F, E, gemm, pair)
+def run(P, T, B, decay=0.8, F=32, steps=30, E=8, gemm=False, pair=False, x6=False):
+    model, step = build(P, T, B, decay, F, E, gemm, pair, x6)
     for _ in range(5):
         step()
     ms = sorted(timed(step, steps))
@@ -180,6 +187,39 @@ def run_ab_pair(P, T, B, decay, F, E, steps, windows):
             "pair_classes_on": pair}
 
 
+X6_PEAK_TFLOPS = 2500.0 / 6        # MI355X dense bf16 matrix peak, as published, over the six piece products of one fp32 product (not measured here)
+CLASS_NAMES = ("wn", "small", "conv3_fwd", "conv3_bwd_data", "conv3_wgrad", "pw_fwd", "pw_bwd_data", "pw_wgrad", "conv3_fwd_x6", "conv3_bwd_data_x6", "conv3_wgrad_x6",
+               "pw_fwd_x6", "pw_bwd_data_x6")
+
+
+def run_ab_x6(P, T, B, decay, F, E, steps, windows, pair=True):
+    """run_ab with the route (and, pair=True, its fused pair) on in both legs and the route's x6 arithmetic alternated.  No size moves with the switch."""
+    model, step = build(P, T, B, decay, F, E, True, pair)
+    h = model._handle()
+    legs, arith, cls = {False: [], True: []}, {}, {}
+    for w in range(windows):
+        for on in (False, True):
+            model.set_gemm_x6(on)
+            arith[on] = int(L.lib().probav_engine_gemm_arith(h))
+            step()
+            step()
+            legs[on].append(sum(timed(step, steps)) / steps)
+    for on in (False, True):
+        model.set_gemm_x6(on)
+        got = class_tflops(model, step, range(2, 13))
+        # (the backward-filter classes are the fp32 route's in both legs)
+        cls[on] = {CLASS_NAMES[c]: {"launches": v[2], "ms": round(v[1], 3), "tflops": round(v[0], 2),
+                                    "of_peak": round(v[0] / (X6_PEAK_TFLOPS if c >= 8 else FP32_PEAK_TFLOPS), 4)} for c, v in got.items() if v[2]}
+    kind = int(L.lib().probav_engine_pair_kind(h))
+    release(model)
+    med = lambda v: sorted(v)[len(v) // 2]
+    off, on = med(legs[False]), med(legs[True])
+    spread = (max(legs[False]) - min(legs[False])) / off
+    return {"pair_kind": kind, "gemm_arith_off_on": [arith[False], arith[True]], "ms_per_step_x6_off": round(off, 3), "ms_per_step_x6_on": round(on, 3), "on_over_off": round(on / off, 4),
+            "off_windows_ms": [round(v, 3) for v in legs[False]], "on_windows_ms": [round(v, 3) for v in legs[True]], "off_spread": round(spread, 4),
+            "faster_by_more_than_three_spreads": bool(off - on > 3 * spread * off), "classes_off": cls[False], "classes_on": cls[True]}
+
+
 # name, P, T, B, decay, F, E
 TABLE = (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8, 32, 8),
          ("7 frames", 16, 7, 128, 0.8, 32, 8),
@@ -195,6 +235,8 @@ TABLE = (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8, 32, 8),
 AB_TABLE = (TABLE[0], TABLE[6], TABLE[7], TABLE[8], TABLE[9], ("filters 64, 13 frames", 16, 13, 128, 0.8, 64, 8))
 # the rows of --ab --pair: the shapes the general pair takes, and the shipped one (which keeps its tuned pair and must not move)
 PAIR_TABLE = (TABLE[8], TABLE[9], TABLE[7], AB_TABLE[5], TABLE[0])
+# the rows of --ab --x6: the pair's rows with the pair on, and the 64-filter row with the pair off, where the pointwise launches change hands too
+X6_TABLE = tuple(r + (True,) for r in PAIR_TABLE) + ((TABLE[8][0] + ", pair off",) + TABLE[8][1:] + (False,),)
 
 
 if __name__ == "__main__":
@@ -204,12 +246,22 @@ if __name__ == "__main__":
     ap.add_argument("--exp", type=int, default=8)
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--pair", action="store_true")
+    ap.add_argument("--x6", action="store_true")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--windows", type=int, default=3)
     opt = ap.parse_args()
     if opt.pair and not (opt.ab or opt.gemm_route):
         ap.error("--pair needs --ab or --gemm-route")
+    if opt.x6 and not (opt.ab or opt.gemm_route):
+        ap.error("--x6 needs --ab or --gemm-route")
+    if opt.x6 and opt.ab and opt.pair:
+        ap.error("--ab --x6 has the pair on in its legs: no --pair")
     table = (PAIR_TABLE if opt.pair else AB_TABLE) if opt.ab else TABLE
+    if opt.x6 and opt.ab:
+        table = tuple(r for r in X6_TABLE if opt.filters is None or r[5] == opt.filters)
+        for name, P, T, B, decay, F, E, pair in table:
+            print(json.dumps(dict({"config": name, "batch": B}, **run_ab_x6(P, T, B, decay, F, E, opt.steps or 4, opt.windows, pair))), flush=True)
+        sys.exit(0)
     if opt.filters is not None:
         table = (("filters %d / exp %d" % (opt.filters, opt.exp), 16, 9, 128, 0.8, opt.filters, opt.exp),)
     rows = []
@@ -220,7 +272,7 @@ if __name__ == "__main__":
                 rows.append(dict({"config": name, "batch": B}, **(run_ab_pair if opt.pair else run_ab)(P, T, B, decay, F, E, opt.steps or 4, opt.windows)))
                 print(json.dumps(rows[-1]), flush=True)
                 continue
-            med = run(P, T, B, decay, F, opt.steps or 30, E, opt.gemm_route, opt.pair)
+            med = run(P, T, B, decay, F, opt.steps or 30, E, opt.gemm_route, opt.pair, opt.x6)
         except Exception as ex:                                   # a configuration the engine refuses is a row of the table too
             rows.append({"config": name, "error": str(ex)[:200]})
             print(json.dumps(rows[-1]), flush=True)

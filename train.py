@@ -62,6 +62,9 @@ def parser(argv=None):
     p.add_argument("--gemm-pair", dest="gemm_pair", action="store_true",
                    help="with --gemm-route: the route's fused pointwise pair (WDSRModel.set_gemm_pair): a block's expConv, ReLU and decConv in one launch "
                         "each way, the hidden tensor never in memory (F <= 64, decay channels <= 64; the shipped shape keeps its tuned pair)")
+    p.add_argument("--gemm-x6", dest="gemm_x6", action="store_true",
+                   help="with --gemm-route: the route's convolution launches (forward, backward-data) on the 16-bit matrix pipe (WDSRModel.set_gemm_x6): six bf16 piece products per "
+                        "fp32 product, results equal to rounding; combines freely with --gemm-pair, which stays fp32")
     opt = p.parse_args(argv)
     if opt.fusion_input is not None and opt.modelType != "fusionNet":
         p.error("--fusion-input needs --modelType fusionNet")
@@ -73,6 +76,10 @@ def parser(argv=None):
         p.error("--gemm-pair is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
     if opt.gemm_pair and not opt.gemm_route:
         p.error("--gemm-pair needs --gemm-route")
+    if opt.gemm_x6 and opt.modelType == "fusionNet":
+        p.error("--gemm-x6 is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
+    if opt.gemm_x6 and not opt.gemm_route:
+        p.error("--gemm-x6 needs --gemm-route")
     if opt.random_crops and opt.online_aug:
         p.error("--random-crops and --online-aug are mutually exclusive")
     if not opt.random_crops and (opt.crop_positions != "all" or opt.crop_seed != 0 or opt.crops_per_epoch is not None):
@@ -89,11 +96,13 @@ def parser(argv=None):
 
 
 def apply_engine_options(model, opt):
-    """The engine switches among the flags, set on the freshly built model: --gemm-route, --gemm-pair."""
+    """The engine switches among the flags, set on the freshly built model: --gemm-route, --gemm-pair, --gemm-x6."""
     if opt.gemm_route:
         model.set_gemm_route(True)
     if opt.gemm_pair:
         model.set_gemm_pair(True)
+    if opt.gemm_x6:
+        model.set_gemm_x6(True)
 
 
 def training_scenes(dataDir, band):
