@@ -98,13 +98,13 @@ def parser(argv=None):
     return opt
 
 
-def model_images(config, cfg_path, band, options=InferenceOptions(), gemm_route=False, gemm_pair=False, gemm_x6=False):
+def model_images(config, cfg_path, band, options=InferenceOptions(), gemm_route=False, gemm_pair=False, gemm_x6=False, gemm_exotic=False):
     """{id: uint16 image} of the latest checkpoint on the band's TRAIN sets: test.py's main with --totest TRAIN and the same `options` (an
-    InferenceOptions: the self-ensemble, the blended overlapping tiles, the frame windows, the raw or EMA weights), without the PNGs.  gemm_route: --gemm-route, the engine's general matrix route; gemm_pair: --gemm-pair, its fused pointwise pair; gemm_x6: --gemm-x6, its convolution launches in x6 arithmetic."""
+    InferenceOptions: the self-ensemble, the blended overlapping tiles, the frame windows, the raw or EMA weights), without the PNGs.  gemm_route: --gemm-route, the engine's general matrix route; gemm_pair: --gemm-pair, its fused pointwise pair; gemm_x6: --gemm-x6, its convolution launches in x6 arithmetic; gemm_exotic: --gemm-exotic, the 19-frame reducer's exotic launches on the route."""
     import torch
     inputs = load_inputs(config, "TRAIN", band, options)
     with contextlib.redirect_stdout(sys.stderr):            # the restore messages: stdout carries the JSON line only
-        model, trainer = load_model(config, cfg_path, band, options.weights, "evaluate.py --model", gemm_route=gemm_route, gemm_pair=gemm_pair, gemm_x6=gemm_x6)
+        model, trainer = load_model(config, cfg_path, band, options.weights, "evaluate.py --model", gemm_route=gemm_route, gemm_pair=gemm_pair, gemm_x6=gemm_x6, gemm_exotic=gemm_exotic)
     if trainer.latest_checkpoint is None and trainer._tf_latest() is None:
         raise SystemExit("evaluate.py --model: no checkpoint under %s" % trainer.ckptDir)
     y_preds = predict(model, inputs, options, config)
@@ -155,7 +155,7 @@ def main(opt):
     elif opt.model:
         images = {}
         for b in bands:
-            images.update(model_images(config, opt.cfg, b, opt.inference, gemm_route=opt.gemm_route, gemm_pair=opt.gemm_pair, gemm_x6=opt.gemm_x6))
+            images.update(model_images(config, opt.cfg, b, opt.inference, gemm_route=opt.gemm_route, gemm_pair=opt.gemm_pair, gemm_x6=opt.gemm_x6, gemm_exotic=opt.gemm_exotic))
     else:
         images = scoring.load_sr_dir(opt.toCompare)
     if not opt.baseline:

@@ -365,7 +365,7 @@ int probav_plan_pw(int64_t nvox, int64_t vox_per_sample, int D, int impl, int ba
  * arithmetic, an exact fp32 fma chain, on the matrix cores).  It is a SWITCH on the engine, off by default, kept apart from the kernel family:
  * probav_engine_set_impl keeps it.  With it on, at family >= 1, a launch goes to the route exactly when it would otherwise run the generic direct
  * kernel on a geometry that kernel's own callers do not call exotic (5x5x5, mirrored depth pads, zero pads above 2, mirrored pads above 1 stay
- * direct) -- nothing a matrix, split-operand or dedicated small kernel (upscale pair, one-channel input, fused residual path, the tuned one-channel
+ * direct, unless the fourth switch below, probav_engine_set_gemm_exotic, hands them over) -- nothing a matrix, split-operand or dedicated small kernel (upscale pair, one-channel input, fused residual path, the tuned one-channel
  * backward-filter) serves changes hands; family 0 is the direct kernels with or without it.  The backward-filter's slab regions differ in size, so
  * probav_workspace_bytes / probav_workspace_split change with the switch: size the buffers after setting it.  Results of a sample do not depend on
  * its batch mates and are bitwise reproducible; they differ from the direct kernels' by fp32 rounding (another order of additions).
@@ -441,6 +441,32 @@ int probav_engine_gemm_arith(const probav_engine* e);      /* what the route's c
  * take, and for op backward-filter, which has no x6 kernel (probav_plan_conv_gemm reports the fp32 one).                                       */
 #define PROBAV_PLAN_GEMM_X6 13       /* gemm_conv_fwd_x6_kernel */
 int probav_plan_conv_gemm_x6(const int32_t geom[17], int gated, int has_skip, int op, int32_t report[8]);
+/* The route's exotic launches (host-only entry points, additions made under ABI 7).  The switches above leave what conv_route / wgrad_route call EXOTIC
+ * on the generic direct kernels: a mirrored depth pad, kernel size 5, mirrored H/W pads of 2, zero pads above 2 and, for the backward-filter, any pad
+ * above 1.  Only the 19-frame network (the reference's ConvReduceAndUpscaleEx) has such launches: forward and backward-filter of its reducers 1-4 (a
+ * 5x5x5 layer on a pad of 2 mirrored on H, W and T; 3x3x3 layers on mirrored pads (2,2,1), (2,2,0), (2,2,0)) and the backward-data of the 5x5x5 layer, a
+ * zero-pad correlation with pads of 4 -- five convolution and four backward-filter launches per step.  A FOURTH SWITCH, off by default, hands them to
+ * the route's kernels: the same gemm_conv_fwd_kernel / gemm_conv_fwd_x6_kernel (following probav_engine_gemm_arith) and gemm_conv_wgrad_kernel (fp32),
+ * through wider support predicates -- k x k x k and k x k x 1 for k in {1, 3, 5}; zero pads up to k - 1 per axis (backward-filter: up to 2); mirrored
+ * H/W pads and a mirrored depth pad up to 2, each on an extent above the pad.  A tap on zero padding (the pads-of-4 backward-data) is multiplied by
+ * its zero, not skipped, as elsewhere on the route; the mirrored layers have no zero padding.  The route does not report amax: where the neighbours
+ * are H3 kernels (family 4 at 32 filters) the engine fills the output's slots behind the launch, as for the route's other launches.
+ * It takes effect exactly when the family is >= 1, the route is on and the wish is set; probav_engine_set_impl, probav_engine_set_gemm_route,
+ * probav_engine_set_gemm_pair and probav_engine_set_gemm_x6 keep the wish; PROBAV_GEMM_EXOTIC (set, non-zero) at probav_engine_create sets it.  On an
+ * engine without exotic launches (7, 9 and 13 frames) nothing moves.  At 19 frames probav_engine_route_counts becomes {0, +5, 0, +4} and the four
+ * backward-filter slab regions change size (slabs x (taps Cin Cout + Cout) floats, taps up to 125), so probav_workspace_bytes /
+ * probav_workspace_split change with the switch: size the buffers after setting it.  A switch flipped between a training forward and its backward
+ * is refused by the backward (PROBAV_EINVAL, nothing written), as for the pair and x6.  Results are reproducible bit for bit and a sample does
+ * not depend on its batch mates; they differ from the direct kernels' by fp32 rounding.                                                         */
+int probav_engine_set_gemm_exotic(probav_engine* e, int on);
+int probav_engine_gemm_exotic(const probav_engine* e);     /* the wish: 1 / 0 */
+/* The route's launch plans for a wide geometry, from the functions the launches call.  geom[17] has no field for the mirrored depth pad: reflect_t
+ * states it.  op forward / backward-data: probav_plan_conv_gemm's GEMM report, report[0] = PROBAV_PLAN_GEMM (x6 == 0) or PROBAV_PLAN_GEMM_X6; op
+ * backward-filter: its WGRAD_GEMM report (x6 ignored: the backward-filter is fp32).  All zero for a geometry the wide predicates refuse (k = 7, a pad
+ * above k - 1, a mirrored pad of 3 or one not below its extent).  probav_gemm_wgrad_wide_scratch_bytes: the backward-filter's scratch, slabs x 4 x
+ * (taps Cin Cout + Cout) bytes, 0 for a refused geometry.  probav_gemm_conv3d_* and probav_plan_conv_gemm* above answer what they always did.    */
+int probav_plan_conv_gemm_wide(const int32_t geom[17], int reflect_t, int x6, int op, int32_t report[8]);
+size_t probav_gemm_wgrad_wide_scratch_bytes(const int32_t geom[17], int reflect_t);
 
 /* ---- dataset builder (utils/dataGenerator.py; proba-v_amd/prep.py), additions of ABI 7 ------------------------------------------------ */
 /* Frames are one flat [n_frames][H][W] array; a ragged list of image sets is that array plus set_offsets[n_sets+1] (int64, ascending,

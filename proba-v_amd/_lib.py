@@ -103,6 +103,11 @@ SIGNATURES = {
     "probav_engine_gemm_x6": (c_int, [c_void_p]),
     "probav_engine_gemm_arith": (c_int, [c_void_p]),
     "probav_plan_conv_gemm_x6": (c_int, [POINTER(c_int32 * 17), c_int, c_int, c_int, POINTER(c_int32 * 8)]),
+    # the route's exotic launches (the 19-frame reducer's geometries on the kernels of csrc/kernels_gemm.hip / kernels_gemm_x6.hip): added under ABI 7, host only
+    "probav_engine_set_gemm_exotic": (c_int, [c_void_p, c_int]),
+    "probav_engine_gemm_exotic": (c_int, [c_void_p]),
+    "probav_plan_conv_gemm_wide": (c_int, [POINTER(c_int32 * 17), c_int, c_int, c_int, POINTER(c_int32 * 8)]),
+    "probav_gemm_wgrad_wide_scratch_bytes": (c_size_t, [POINTER(c_int32 * 17), c_int]),
     "probav_workspace_split": (c_int, [c_void_p, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "probav_backward_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
     # input gradients (csrc/kernels_input_grad.hip): added under ABI 7

@@ -41,17 +41,20 @@ struct Family {
     PairKind pw_fused;        // the fused pointwise pair (expConv + ReLU + decConv in one launch each way): which kernels run it, if any
     bool gemm;                // the general matrix route (kernels_gemm.hip) wherever a launch would otherwise fall to the generic direct kernels
     int gemm_arith;           // the arithmetic of the route's convolution launches (forward, backward-data): 0 fp32 (kernels_gemm.hip), 1 X6 (kernels_gemm_x6.hip)
+    bool gemm_exotic;         // the route also takes the launches conv_route / wgrad_route call exotic (the 19-frame reducer's), on the wide predicates of kernels_gemm.h
 };
 // gemm: the engine's switch (probav_engine_set_gemm_route), kept on the engine apart from the family and folded in here, so that a change of family keeps it;
 // it needs the matrix kernels' family (impl >= 1): family 0 stays the direct kernels everywhere.  pair_gemm: the second switch (probav_engine_set_gemm_pair) on a block
 // geometry that gemm_pw_supported takes; it fuses the pair only on the route, and only where the tuned pair does not exist.  gemm_x6: the third switch
-// (probav_engine_set_gemm_x6): the route's convolution launches in x6 arithmetic; it changes nothing but those launches' kernel
-static Family make_family(int impl, bool pw_mfma, bool gemm = false, bool pair_gemm = false, bool gemm_x6 = false)
+// (probav_engine_set_gemm_x6): the route's convolution launches in x6 arithmetic; it changes nothing but those launches' kernel.  gemm_exotic: the fourth switch
+// (probav_engine_set_gemm_exotic): the exotic geometries, which return to the direct kernel before the route is asked, go to the route instead; only a 19-frame network has any
+static Family make_family(int impl, bool pw_mfma, bool gemm = false, bool pair_gemm = false, bool gemm_x6 = false, bool gemm_exotic = false)
 {
     Family f;
     f.mfma = impl >= 1; f.strip = impl >= 2; f.x6 = impl >= 3; f.arith = impl >= 4 ? 2 : (impl >= 3 ? 1 : 0);
     f.gemm = f.mfma && gemm;
     f.gemm_arith = f.gemm && gemm_x6 ? 1 : 0;
+    f.gemm_exotic = f.gemm && gemm_exotic;
     f.pw_fused = !f.mfma ? PairKind::none : (pw_mfma ? PairKind::tuned : (f.gemm && pair_gemm ? PairKind::gemm : PairKind::none));
     return f;
 }
@@ -66,6 +69,7 @@ struct probav_engine {
     bool gemm = false;                              // probav_engine_set_gemm_route: folded into fam by make_family
     bool gemm_pair = false;                         // probav_engine_set_gemm_pair: the wish; folded into fam (with pw_gemm) by make_family
     bool gemm_x6 = false;                           // probav_engine_set_gemm_x6: the wish; folded into fam (with gemm) by make_family
+    bool gemm_exotic = false;                       // probav_engine_set_gemm_exotic: the wish; folded into fam (with gemm) by make_family
     bool pw_gemm = false;                           // the block geometry has a general fused pointwise pair (gemm_pw_supported)
     int32_t launched[4] = {0, 0, 0, 0};             // what conv_fwd / conv_wgrad have launched, as probav_engine_route_counts counts (probav_engine_launched_counts)
     int iMain = -1, iResid1 = -1, iResid2 = -1, iResid3 = -1, iUp = -1;
@@ -85,6 +89,7 @@ struct probav_engine {
     bool fwd_amax = false;    // the last training forward filled the amax slots of the saved activations (H3 kernels, impl 4)
     PairKind fwd_pair = PairKind::none; // ... and ran the pointwise pair in this form, with this workspace layout: the backward pass must agree
     int fwd_gemm_arith = 0;   // ... and the general matrix route in this arithmetic: the reverse pass recomputes expConv and must get the forward's gates
+    bool fwd_gemm_exotic = false;   // ... and the exotic launches on this side of the fourth switch: the slab regions of the reverse scratch follow it
     // optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg)
     bool prof_on = false;
     unsigned prof_mask = ~0u;   // kernel classes whose launches are bracketed (bit = class index)
@@ -94,8 +99,8 @@ struct probav_engine {
     size_t prof_used = 0;
 };
 
-// the family of the engine's impl and its three switches: every setter makes it here, so each keeps what the others set
-static Family engine_family(const probav_engine* e) { return make_family(e->impl, e->pw_mfma, e->gemm, e->gemm_pair && e->pw_gemm, e->gemm_x6); }
+// the family of the engine's impl and its four switches: every setter makes it here, so each keeps what the others set
+static Family engine_family(const probav_engine* e) { return make_family(e->impl, e->pw_mfma, e->gemm, e->gemm_pair && e->pw_gemm, e->gemm_x6, e->gemm_exotic); }
 
 enum { CLS_WN = 0, CLS_SMALL, CLS_CONV3_FWD, CLS_CONV3_BWD_DATA, CLS_CONV3_WGRAD, CLS_PW_FWD, CLS_PW_BWD_DATA, CLS_PW_WGRAD,
        // launches served by an x6 kernel (bf16 MFMA pipe) are timed apart from the fp32-MFMA / VALU ones: they price against another peak
@@ -266,11 +271,13 @@ static bool resid_path_fused(const probav_engine* e)
 // The kernel that serves a backward-filter launch: the one decision both make_plan (slab region sizes) and conv_wgrad (launch) read.
 // o.am_in: the launch has the per-sample amax slots of x and of dy (the H3 kernel needs both).  tuned: the direct kernel's dedicated small instance
 enum class WgradKernel { direct, x6, mfma, gemm };
-struct WgradRoute { WgradKernel k; int cls; int arith; bool tuned; };
+struct WgradRoute { WgradKernel k; int cls; int arith; bool tuned; bool wide = false; };     // wide: the route's kernel through its wide predicate (an exotic geometry)
 static WgradRoute wgrad_route(const Family& f, const ConvGeom& g, const Operands& o)
 {
     const bool exotic = g.reflect_t || g.ph > 1 || g.pw > 1 || g.pt > 1 || (g.kh != 3 && g.kh != 1);
     const bool tuned = f.mfma && conv3d_direct_wgrad_is_tuned(g);
+    // the fourth switch: an exotic geometry on the route's kernel where the wide predicate takes it (fp32, as the route's other backward-filters)
+    if (exotic && !tuned && f.gemm_exotic && gemm_wgrad_supported_wide(g)) return {WgradKernel::gemm, CLS_CONV3_WGRAD, 0, false, true};
     if (exotic || tuned) return {WgradKernel::direct, CLS_CONV3_WGRAD, 0, tuned};
     const bool x6 = f.x6 && x6_wgrad_supported(g);
     const int cls = g.kh * g.kw * g.kt == 1 ? CLS_PW_WGRAD : (x6 ? CLS_CONV3_WGRAD_X6 : CLS_CONV3_WGRAD);
@@ -498,7 +505,7 @@ struct AmaxSlots {
 // whether the kernel writes am.y itself, and for the MFMA / x6 kernels the kind of filter fragments they read (x6: in arithmetic 1 X6 or 2 H3)
 enum class ConvKernel { direct, up, up_bwd_data, cin1, x6_strip, x6_rowtile, mfma_strip, mfma_rowtile, gemm };
 enum class FragKind { none, f32, x6, h3, h3t };
-struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; FragKind frag; StripSel strip; };     // strip: the strip kernels' selection (strip_select), made here once
+struct ConvRoute { ConvKernel k; int cls; bool reports; int arith; FragKind frag; StripSel strip; bool wide = false; };     // strip: the strip kernels' selection (strip_select), made here once
 // `dedicated`: the engine's policy in front of the matrix kernels (small dedicated kernels, exotic geometries on the direct one); the single-operator entry point,
 // whose tests hold the matrix kernels to the oracle on those geometries too, routes without it
 static ConvRoute conv_route(const Family& f, const ConvGeom& g, const Operands& o, bool dedicated = true)
@@ -510,6 +517,9 @@ static ConvRoute conv_route(const Family& f, const ConvGeom& g, const Operands& 
         const bool exotic = g.reflect_t || g.ph > 2 || g.pw > 2 || g.pt > 2 || (!pw && g.kh != 3) || (g.reflect_hw && g.ph > 1);
         // upscaleConv1 and its backward-data (0.2 % of the work): dedicated small VALU kernels instead of 32x32 matrix tiles around a 32x9 product
         if (f.mfma && !o.gate && !o.skip && bwd && conv3d_up_bwd_data_supported(g)) return {ConvKernel::up_bwd_data, CLS_CONV3_BWD_DATA, true, 0, FragKind::none, {}};
+        // the fourth switch: an exotic geometry on the route's kernels where the wide predicate takes it, in the route's arithmetic
+        if (exotic && f.gemm_exotic && gemm_conv_supported_wide(g))
+            return {ConvKernel::gemm, f.gemm_arith ? (bwd ? CLS_CONV3_BWD_DATA_X6 : CLS_CONV3_FWD_X6) : (bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD), false, f.gemm_arith, FragKind::none, {}, true};
         if (exotic) return {ConvKernel::direct, bwd ? CLS_CONV3_BWD_DATA : CLS_CONV3_FWD, false, 0, FragKind::none, {}};
         if (f.mfma && !o.gate && !o.skip && o.bias && !o.am_out && conv3d_up_forward_supported(g)) return {ConvKernel::up, CLS_CONV3_FWD, false, 0, FragKind::none, {}};
         if (f.mfma && !o.gate && !o.skip && o.bias && conv3d_cin1_forward_supported(g)) return {ConvKernel::cin1, CLS_CONV3_FWD, true, 0, FragKind::none, {}};
@@ -548,7 +558,9 @@ static int conv_launch(const ConvRoute& r, const ConvGeom& g, const float* x, co
     case ConvKernel::x6_strip: case ConvKernel::mfma_strip: return conv_strip_forward(r.strip, x, gate, wfrag, bias, skip, y, am, s);
     case ConvKernel::x6_rowtile: return x6_conv_rowtile_forward(g, x, gate, wfrag, bias, skip, y, r.arith, am, s);
     case ConvKernel::mfma_rowtile: return mfma_conv_forward(g, x, gate, wfrag, bias, skip, y, am, s);
-    case ConvKernel::gemm: return r.arith ? gemm_x6_conv_forward(g, x, gate, w, bias, skip, y, s) : gemm_conv_forward(g, x, gate, w, bias, skip, y, s);
+    case ConvKernel::gemm:
+        if (r.wide) return r.arith ? gemm_x6_conv_forward_wide(g, x, gate, w, bias, skip, y, s) : gemm_conv_forward_wide(g, x, gate, w, bias, skip, y, s);
+        return r.arith ? gemm_x6_conv_forward(g, x, gate, w, bias, skip, y, s) : gemm_conv_forward(g, x, gate, w, bias, skip, y, s);
     default: return conv3d_direct_forward(g, x, gate, w, bias, skip, y, s);
     }
 }
@@ -602,7 +614,7 @@ static int conv_wgrad(const PassBufs& b, const Launch& L, const float* x, const 
     switch (r.k) {
     case WgradKernel::x6: return x6_conv_wgrad(g, x, dy, gate, dw, db, part, r.arith, am, s);
     case WgradKernel::mfma: return mfma_conv_wgrad(g, x, dy, gate, dw, db, part, s);
-    case WgradKernel::gemm: return gemm_conv_wgrad(g, x, dy, gate, dw, db, part, s);
+    case WgradKernel::gemm: return r.wide ? gemm_conv_wgrad_wide(g, x, dy, gate, dw, db, part, s) : gemm_conv_wgrad(g, x, dy, gate, dw, db, part, s);
     default: return conv3d_direct_wgrad(g, x, dy, gate, dw, db, part, s);
     }
 }
@@ -831,6 +843,8 @@ int probav_engine_create(const probav_net_cfg* cfg, probav_engine** out)
     e->gemm_pair = penv && atoi(penv) != 0;
     const char* xenv = getenv("PROBAV_GEMM_X6");                   // set and non-zero: the wish for the route's x6 arithmetic is on from the start
     e->gemm_x6 = xenv && atoi(xenv) != 0;
+    const char* eenv = getenv("PROBAV_GEMM_EXOTIC");               // set and non-zero: the wish for the route's exotic launches is on from the start
+    e->gemm_exotic = eenv && atoi(eenv) != 0;
     e->pw_gemm = gemm_pw_supported(F, E, D, (long)e->Hin * e->Hin * T);
     e->fam = engine_family(e);
     *out = e;
@@ -964,6 +978,15 @@ int probav_engine_set_gemm_x6(probav_engine* e, int on)
 int probav_engine_gemm_x6(const probav_engine* e) { return e && e->gemm_x6 ? 1 : 0; }
 int probav_engine_gemm_arith(const probav_engine* e) { return e ? e->fam.gemm_arith : 0; }
 
+int probav_engine_set_gemm_exotic(probav_engine* e, int on)
+{
+    if (!e) { set_error("probav_engine_set_gemm_exotic: null engine", hipSuccess); return PROBAV_EINVAL; }
+    e->gemm_exotic = on != 0;
+    e->fam = engine_family(e);
+    return PROBAV_OK;
+}
+int probav_engine_gemm_exotic(const probav_engine* e) { return e && e->gemm_exotic ? 1 : 0; }
+
 int probav_plan_pw_gemm(int F, int H, int D, int64_t nvox, int backward, int32_t report[8])
 {
     if (!report) { set_error("probav_plan_pw_gemm: null report", hipSuccess); return PROBAV_EINVAL; }
@@ -1033,7 +1056,7 @@ static int forward_impl(probav_engine* e, const float* params, const float* x, f
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wcol(li); m.y = ay; } return m; };
     // (the per-sample amax slots -- the atomicMax targets -- are cleared by head_kernel below; the weight slots in front of them are plain stores of wn_forward_kernel /
     // wn_rowmax_kernel, every one of them written before anything reads it)
-    if (training) { e->fwd_amax = h3; e->fwd_pair = e->fam.pw_fused; e->fwd_gemm_arith = e->fam.gemm_arith; }
+    if (training) { e->fwd_amax = h3; e->fwd_pair = e->fam.pw_fused; e->fwd_gemm_arith = e->fam.gemm_arith; e->fwd_gemm_exotic = e->fam.gemm_exotic; }
 
     if (!WC) {
         { ProfScope ps(e, CLS_WN, 0.0, s); CK(wn_forward(e->d_layers, (int)e->layers.size(), (int)e->cout_total, (int)e->cin_total, params, W + p.weff, W + p.weffT, W + p.invn, h3 ? A.base : nullptr, s)); }
@@ -1129,6 +1152,10 @@ static int backward_impl(probav_engine* e, const float* params, const float* dy,
     auto amx = [&](const unsigned* ax, int li, unsigned* ay) { Amax m; if (h3) { m.x = ax; m.w = A.wrow(li); m.y = ay; } return m; };   // backward-data: the matrix' columns are the layer's INPUT channels
     if (e->fwd_gemm_arith != e->fam.gemm_arith) {
         set_error("probav_backward: the general matrix route's arithmetic changed between forward and backward (probav_engine_set_gemm_x6, or a switch it depends on): the recomputed expConv would not take the forward's gates", hipSuccess);
+        return PROBAV_EINVAL;
+    }
+    if (e->fwd_gemm_exotic != e->fam.gemm_exotic) {
+        set_error("probav_backward: the route's exotic launches changed hands between forward and backward (probav_engine_set_gemm_exotic, or a switch it depends on): the reverse scratch was sized for the forward's", hipSuccess);
         return PROBAV_EINVAL;
     }
     if (e->fwd_pair != e->fam.pw_fused) {
@@ -1793,6 +1820,35 @@ int probav_plan_conv_gemm_x6(const int32_t geom[17], int gated, int has_skip, in
     if (!gemm_x6_conv_plan_ints(g, v)) return PROBAV_OK;
     report[0] = PROBAV_PLAN_GEMM_X6; report[1] = v[3]; report[2] = v[2]; report[3] = v[0]; report[4] = v[1]; report[5] = v[2] * v[3]; report[6] = v[4]; report[7] = v[5];
     return PROBAV_OK;
+}
+
+// The route's plans for a wide geometry (what the fourth switch hands it): geom[17] has no field for the mirrored depth pad, so it is an argument.  x6: the report
+// under the x6 kernel's name (the tiles are shared).  All zero for a geometry the wide predicates refuse
+int probav_plan_conv_gemm_wide(const int32_t geom[17], int reflect_t, int x6, int op, int32_t report[8])
+{
+    if (!geom || !report || op < PROBAV_PLAN_OP_FORWARD || op > PROBAV_PLAN_OP_WGRAD) { set_error("probav_plan_conv_gemm_wide: null/invalid argument", hipSuccess); return PROBAV_EINVAL; }
+    ConvGeom g = geom_from(geom);
+    g.reflect_t = reflect_t != 0;
+    for (int i = 0; i < 8; ++i) report[i] = 0;
+    if (op == PROBAV_PLAN_OP_WGRAD) {
+        int v[5];
+        if (!gemm_wgrad_plan_ints_wide(g, v)) return PROBAV_OK;
+        report[0] = PROBAV_PLAN_WGRAD_GEMM; report[1] = v[0]; report[2] = v[1]; report[3] = v[2]; report[4] = v[3]; report[5] = v[4];
+        return PROBAV_OK;
+    }
+    int v[6];
+    if (!(x6 ? gemm_x6_conv_plan_ints_wide(g, v) : gemm_conv_plan_ints_wide(g, v))) return PROBAV_OK;
+    report[0] = x6 ? PROBAV_PLAN_GEMM_X6 : PROBAV_PLAN_GEMM; report[1] = v[3]; report[2] = v[2]; report[3] = v[0]; report[4] = v[1]; report[5] = v[2] * v[3]; report[6] = v[4]; report[7] = v[5];
+    return PROBAV_OK;
+}
+
+size_t probav_gemm_wgrad_wide_scratch_bytes(const int32_t geom[17], int reflect_t)
+{
+    if (!geom) return 0;
+    ConvGeom g = geom_from(geom);
+    g.reflect_t = reflect_t != 0;
+    if (!gemm_wgrad_supported_wide(g)) return 0;
+    return gemm_wgrad_partial_floats(g) * sizeof(float);
 }
 
 // The launches of one training step by route: the launch list (step_launches), each entry routed as the passes route it

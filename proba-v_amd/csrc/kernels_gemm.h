@@ -24,6 +24,18 @@ int gemm_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const fl
 // launch plan: v = {slabs, voxels per slab, tile input channels, tile output channels, workgroups}; the slab count depends on the geometry alone
 bool gemm_wgrad_plan_ints(const ConvGeom& g, int v[5]);
 
+// The wide geometries -- what the engine calls exotic, the 19-frame reducer's layers and their backward-data forms -- on the SAME kernels (probav_engine_set_gemm_exotic):
+// k x k x k and k x k x 1 for k in {1, 3, 5}; zero pads up to k - 1 per axis (backward-filter: up to 2); mirrored H/W pads and a mirrored depth pad (g.reflect_t)
+// up to 2, each on an extent above the pad.  Beside the predicates above, which answer what they always did.  The kernels branch on the uniform g.reflect_t for the
+// mirrored depth index; taps, tiles, slabs and the scratch layout follow from the geometry as before (taps up to 125).  A forward launch of more than 27 taps sums in two
+// levels (a tap's chunks, then the taps: template parameter TWO of gemm_conv_fwd_kernel), which keeps a 9 000-term fp32 chain inside the route's 2e-6 bar
+bool gemm_conv_supported_wide(const ConvGeom& g);
+int gemm_conv_forward_wide(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s);
+bool gemm_conv_plan_ints_wide(const ConvGeom& g, int v[6]);
+bool gemm_wgrad_supported_wide(const ConvGeom& g);
+int gemm_conv_wgrad_wide(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, hipStream_t s);
+bool gemm_wgrad_plan_ints_wide(const ConvGeom& g, int v[5]);
+
 // the forward's accumulator tiles per wave (1, 2 or 4, from Cout): shared with the route's x6 form (kernels_gemm_x6.hip)
 int gemm_fwd_nt(const ConvGeom& g);
 

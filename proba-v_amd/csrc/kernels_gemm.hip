@@ -19,6 +19,10 @@
 //   it), so a non-finite dY reaches exactly the filter taps whose windows read a real input.  The bias gradient is summed from the fetched dY rows
 //   before that zeroing, by the workgroups of tap 0 / input tile 0, in a fixed order.  Each workgroup writes its tile of its slab; the slabs are
 //   summed in a fixed order by slab_sum_later.  No atomics: bitwise reproducible on any device.
+//
+// The wide geometries (gemm_conv_supported_wide / gemm_wgrad_supported_wide: 5x5x5, pads up to k - 1, mirrored H/W pads of 2, a mirrored depth pad -- the 19-frame reducer's,
+//   probav_engine_set_gemm_exotic) run on the same two kernels: nothing above is tied to three taps per axis, gemm_reflect folds any pad below the extent, and the mirrored depth
+//   index is a branch on the uniform g.reflect_t.  A launch of the old predicates takes the arm it always took: the same bits.
 #include "probav_common.h"
 #include "kernels_gemm.h"
 #include "x6_device.h"
@@ -40,7 +44,10 @@ constexpr int GF_BM = 128;                  // voxels per workgroup
 constexpr int GF_KC = 16;                   // input channels per K chunk
 constexpr int GF_AS = GF_KC + 1;            // A row stride in LDS (odd: the 32 rows a half-wave reads fall in 32 banks)
 
-template <int NT, bool GATE>
+// TWO: the sum in two levels -- a tap's chunks into `acc`, the taps' sums into `tot` -- for the launches of more than 27 taps (5x5x5: K = 125 Cin, where one fp32 chain of
+// 9 000 terms at 72 channels came to 3.6e-6 of max |ref|).  The order is still a function of (tap, chunk, channel pair) alone.  A template parameter: the instances the route
+// launched before it (TWO = false) are the code they were
+template <int NT, bool GATE, bool TWO>
 __global__ __launch_bounds__(256) void gemm_conv_fwd_kernel(ConvGeom g, const float* __restrict__ x, const float* __restrict__ gate, const float* __restrict__ w,
                                                             const float* __restrict__ bias, const float* __restrict__ skip, float* __restrict__ y)
 {
@@ -82,8 +89,10 @@ __global__ __launch_bounds__(256) void gemm_conv_fwd_kernel(ConvGeom g, const fl
             float v = 0.f;
             if (vn[i] >= 0 && ch_ok) {
                 int ih = vh[i] + a - g.ph, iw = vw[i] + b - g.pw;
-                const int id = vt[i] + c - g.pt;
-                bool pad = id < 0 || id >= g.Ti;
+                int id = vt[i] + c - g.pt;
+                bool pad = false;
+                if (g.reflect_t) id = gemm_reflect(id, g.Ti);          // (uniform) the mirrored depth pad of the wide geometries: no tap of it is padding
+                else pad = id < 0 || id >= g.Ti;
                 if (g.reflect_hw) { ih = gemm_reflect(ih, g.Hi); iw = gemm_reflect(iw, g.Wi); }
                 else pad = pad || ih < 0 || ih >= g.Hi || iw < 0 || iw >= g.Wi;
                 if (!pad) {
@@ -103,11 +112,18 @@ __global__ __launch_bounds__(256) void gemm_conv_fwd_kernel(ConvGeom g, const fl
         }
     };
 
-    gemm_f32x16 acc[NT];
+    gemm_f32x16 acc[NT], tot[TWO ? NT : 1];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+    if constexpr (TWO) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tot[nt][r] = 0.f;
+    }
+    [[maybe_unused]] int left = nchunk;             // (TWO) chunks left of the current tap
 
     fetch(0);
     for (int it = 0; it < niter; ++it) {
@@ -127,6 +143,13 @@ __global__ __launch_bounds__(256) void gemm_conv_fwd_kernel(ConvGeom g, const fl
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[nt] = GEMM_MFMA(av, Bs[k * BS + nt * 32 + (lane & 31)], acc[nt]);
         }
+        if constexpr (TWO) if (--left == 0) {       // (uniform) the tap is complete: its sum joins the total
+            left = nchunk;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { tot[TWO ? nt : 0][r] += acc[nt][r]; acc[nt][r] = 0.f; }
+        }
         __syncthreads();
     }
 
@@ -140,7 +163,7 @@ __global__ __launch_bounds__(256) void gemm_conv_fwd_kernel(ConvGeom g, const fl
         for (int r = 0; r < 16; ++r) {
             const long v = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             if (v >= nvox) continue;
-            float o = acc[nt][r] + bv;
+            float o = (TWO ? tot[TWO ? nt : 0][r] : acc[nt][r]) + bv;
             if (g.relu) o = relu_keep_nan(o);
             if (skip) o += skip[v * g.Cout + co];
             y[v * g.Cout + co] = o;
@@ -168,26 +191,75 @@ static bool gemm_common_supported(const ConvGeom& g, int maxpad)
 
 bool gemm_conv_supported(const ConvGeom& g) { return gemm_common_supported(g, 2); }
 
+// The wide geometries (the 19-frame reducer's, which the engine calls exotic): k x k x k and k x k x 1 for k in {1, 3, 5}, zero pads up to `maxzero` and never above
+// k - 1, mirrored H/W and depth pads up to 2 on an extent above the pad (gemm_reflect folds once).  The kernels are the ones above: they run taps = kh kw kt outer
+// from the geometry, and the mirrored depth index is a branch on the uniform g.reflect_t
+static bool gemm_wide_supported(const ConvGeom& g, int maxzero)
+{
+    if (g.N < 1 || g.Cin < 1 || g.Cout < 1 || g.Hi < 1 || g.Wi < 1 || g.Ti < 1 || g.Ho < 1 || g.Wo < 1 || g.To < 1) return false;
+    if (g.kh != g.kw || (g.kh != 1 && g.kh != 3 && g.kh != 5) || (g.kt != g.kh && g.kt != 1)) return false;
+    if (g.ph < 0 || g.pw < 0 || g.pt < 0 || g.ph > g.kh - 1 || g.pw > g.kw - 1 || g.pt > g.kt - 1) return false;
+    const int mh = g.reflect_hw ? 2 : maxzero, mt = g.reflect_t ? 2 : maxzero;
+    if (g.ph > mh || g.pw > mh || g.pt > mt) return false;
+    if (g.reflect_hw && (g.Hi <= g.ph || g.Wi <= g.pw)) return false;
+    if (g.reflect_t && g.Ti <= g.pt) return false;
+    if (g.Ho != g.Hi + 2 * g.ph - g.kh + 1 || g.Wo != g.Wi + 2 * g.pw - g.kw + 1 || g.To != g.Ti + 2 * g.pt - g.kt + 1) return false;
+    const long lim = (long)1 << 30;
+    if ((long)g.N * g.Hi * g.Wi * g.Ti >= lim || (long)g.N * g.Ho * g.Wo * g.To >= lim) return false;
+    if ((long)g.kh * g.kw * g.kt * g.Cin * (long)g.Cout >= lim) return false;
+    return true;
+}
+
+bool gemm_conv_supported_wide(const ConvGeom& g) { return gemm_wide_supported(g, 4); }
+
 int gemm_fwd_nt(const ConvGeom& g) { return g.Cout <= 32 ? 1 : (g.Cout <= 64 ? 2 : 4); }
+
+static void gemm_conv_plan_fill(const ConvGeom& g, int v[6])
+{
+    const int bn = 32 * gemm_fwd_nt(g);
+    const long nvox = (long)g.N * g.Ho * g.Wo * g.To;
+    v[0] = GF_BM; v[1] = bn; v[2] = (int)((nvox + GF_BM - 1) / GF_BM); v[3] = (g.Cout + bn - 1) / bn; v[4] = GF_KC; v[5] = (g.Cin + GF_KC - 1) / GF_KC;
+}
+
+bool gemm_conv_plan_ints_wide(const ConvGeom& g, int v[6])
+{
+    if (!gemm_conv_supported_wide(g)) return false;
+    gemm_conv_plan_fill(g, v);
+    return true;
+}
 
 bool gemm_conv_plan_ints(const ConvGeom& g, int v[6])
 {
     if (!gemm_conv_supported(g)) return false;
-    const int bn = 32 * gemm_fwd_nt(g);
-    const long nvox = (long)g.N * g.Ho * g.Wo * g.To;
-    v[0] = GF_BM; v[1] = bn; v[2] = (int)((nvox + GF_BM - 1) / GF_BM); v[3] = (g.Cout + bn - 1) / bn; v[4] = GF_KC; v[5] = (g.Cin + GF_KC - 1) / GF_KC;
+    gemm_conv_plan_fill(g, v);
     return true;
 }
+
+static int gemm_conv_launch(const ConvGeom& g, const int v[6], const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s, bool two = false);
 
 int gemm_conv_forward(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s)
 {
     int v[6];
     if (!gemm_conv_plan_ints(g, v)) { set_error("gemm_conv_forward: geometry not supported", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_conv_launch(g, v, x, gate, w, bias, skip, y, s);
+}
+
+int gemm_conv_forward_wide(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s)
+{
+    int v[6];
+    if (!gemm_conv_plan_ints_wide(g, v)) { set_error("gemm_conv_forward_wide: geometry not supported", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_conv_launch(g, v, x, gate, w, bias, skip, y, s, g.kh * g.kw * g.kt > 27);     // more taps than any launch of the old predicate: the two-level sum
+}
+
+static int gemm_conv_launch(const ConvGeom& g, const int v[6], const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s, bool two)
+{
     if (v[3] > 65535) { set_error("gemm_conv_forward: Cout too large", hipSuccess); return PROBAV_EINVAL; }
     const dim3 grid((unsigned)v[2], (unsigned)v[3]), block(256);
 #define PROBAV_GF(NT) do { \
-        if (gate) hipLaunchKernelGGL((gemm_conv_fwd_kernel<NT, true>), grid, block, 0, s, g, x, gate, w, bias, skip, y); \
-        else hipLaunchKernelGGL((gemm_conv_fwd_kernel<NT, false>), grid, block, 0, s, g, x, gate, w, bias, skip, y); } while (0)
+        if (two && gate) hipLaunchKernelGGL((gemm_conv_fwd_kernel<NT, true, true>), grid, block, 0, s, g, x, gate, w, bias, skip, y); \
+        else if (two) hipLaunchKernelGGL((gemm_conv_fwd_kernel<NT, false, true>), grid, block, 0, s, g, x, gate, w, bias, skip, y); \
+        else if (gate) hipLaunchKernelGGL((gemm_conv_fwd_kernel<NT, true, false>), grid, block, 0, s, g, x, gate, w, bias, skip, y); \
+        else hipLaunchKernelGGL((gemm_conv_fwd_kernel<NT, false, false>), grid, block, 0, s, g, x, gate, w, bias, skip, y); } while (0)
     switch (gemm_fwd_nt(g)) {
     case 1: PROBAV_GF(1); break;
     case 2: PROBAV_GF(2); break;
@@ -257,8 +329,10 @@ __global__ __launch_bounds__(256) void gemm_conv_wgrad_kernel(ConvGeom g, const 
         for (int p = 0; p < 2; ++p) {
             const bool live = pv[p] < v1;
             int ih = vh[p] + a - g.ph, iw = vw[p] + b - g.pw;
-            const int id = vt[p] + c - g.pt;
-            bool pad = id < 0 || id >= g.Ti;
+            int id = vt[p] + c - g.pt;
+            bool pad = false;
+            if (g.reflect_t) id = gemm_reflect(id, g.Ti);              // (uniform) the mirrored depth pad of the wide geometries
+            else pad = id < 0 || id >= g.Ti;
             if (g.reflect_hw) { ih = gemm_reflect(ih, g.Hi); iw = gemm_reflect(iw, g.Wi); }
             else pad = pad || ih < 0 || ih >= g.Hi || iw < 0 || iw >= g.Wi;
             const long xoff = ((((long)vn[p] * g.Hi + ih) * g.Wi + iw) * g.Ti + id) * g.Cin;
@@ -342,14 +416,34 @@ bool gemm_wgrad_supported(const ConvGeom& g)
     return ncit * ncot <= 65535;
 }
 
+bool gemm_wgrad_supported_wide(const ConvGeom& g)
+{
+    if (!gemm_wide_supported(g, 2)) return false;
+    const long ncit = (g.Cin + GW_T - 1) / GW_T, ncot = (g.Cout + GW_T - 1) / GW_T;
+    return ncit * ncot <= 65535;
+}
+
+static void gemm_wgrad_plan_fill(const ConvGeom& g, int v[5]);
+bool gemm_wgrad_plan_ints_wide(const ConvGeom& g, int v[5])
+{
+    if (!gemm_wgrad_supported_wide(g)) return false;
+    gemm_wgrad_plan_fill(g, v);
+    return true;
+}
+
 bool gemm_wgrad_plan_ints(const ConvGeom& g, int v[5])
 {
     if (!gemm_wgrad_supported(g)) return false;
+    gemm_wgrad_plan_fill(g, v);
+    return true;
+}
+
+static void gemm_wgrad_plan_fill(const ConvGeom& g, int v[5])
+{
     int slabs; long vps;
     gemm_wgrad_slabs(g, slabs, vps);
     const int ncit = (g.Cin + GW_T - 1) / GW_T, ncot = (g.Cout + GW_T - 1) / GW_T;
     v[0] = slabs; v[1] = (int)vps; v[2] = GW_T; v[3] = GW_T; v[4] = slabs * g.kh * g.kw * g.kt * ncit * ncot;
-    return true;
 }
 
 size_t gemm_wgrad_partial_floats(const ConvGeom& g)
@@ -359,9 +453,22 @@ size_t gemm_wgrad_partial_floats(const ConvGeom& g)
     return (size_t)slabs * ((size_t)g.kh * g.kw * g.kt * g.Cin * g.Cout + g.Cout);
 }
 
+static int gemm_wgrad_launch(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, hipStream_t s);
+
 int gemm_conv_wgrad(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, hipStream_t s)
 {
     if (!gemm_wgrad_supported(g)) { set_error("gemm_conv_wgrad: geometry not supported", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_wgrad_launch(g, x, dy, gate, dw, db, partial, s);
+}
+
+int gemm_conv_wgrad_wide(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, hipStream_t s)
+{
+    if (!gemm_wgrad_supported_wide(g)) { set_error("gemm_conv_wgrad_wide: geometry not supported", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_wgrad_launch(g, x, dy, gate, dw, db, partial, s);
+}
+
+static int gemm_wgrad_launch(const ConvGeom& g, const float* x, const float* dy, const float* gate, float* dw, float* db, float* partial, hipStream_t s)
+{
     int slabs; long vps;
     gemm_wgrad_slabs(g, slabs, vps);
     const int taps = g.kh * g.kw * g.kt;

@@ -12,5 +12,8 @@ namespace probav {
 int gemm_x6_conv_forward(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s);
 // launch plan, as gemm_conv_plan_ints
 bool gemm_x6_conv_plan_ints(const ConvGeom& g, int v[6]);
+// the same kernel on the wide geometries (gemm_conv_supported_wide of kernels_gemm.h): where the engine's fourth switch hands it an exotic launch
+int gemm_x6_conv_forward_wide(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s);
+bool gemm_x6_conv_plan_ints_wide(const ConvGeom& g, int v[6]);
 
 }  // namespace probav

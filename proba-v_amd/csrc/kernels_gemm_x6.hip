@@ -22,6 +22,9 @@
 //   0.f, whose three pieces are zero: a zero in both operands' pieces, never LDS garbage.  A padded tap is multiplied, not skipped.  The order of
 //   additions of an output element is (tap, chunk, piece pair) and the MFMA's own order over the 16 channels: nothing of its row, tile or batch.
 //
+// The wide geometries (gemm_conv_supported_wide of kernels_gemm.h: the 19-frame reducer's 5x5x5 and mirrored layers, probav_engine_set_gemm_exotic) run on this kernel too:
+//   the mirrored depth index is a branch on the uniform g.reflect_t, everything else follows from the geometry.
+//
 // The backward-filter stays on the fp32 route (gemm_conv_wgrad_kernel): an x6 form of it -- both operands cut per tap, 27 times per voxel -- was measured
 // slower than the fp32 kernel and is not part of this unit ('The general matrix route').
 #include "probav_common.h"
@@ -103,8 +106,10 @@ __global__ __launch_bounds__(256) void gemm_conv_fwd_x6_kernel(ConvGeom g, const
         for (int j = 0; j < 8; ++j) { ra[j] = 0.f; rg[j] = 1.f; }
         if (vn >= 0 && ch < g.Cin) {
             int ih = vh + a - g.ph, iw = vw + b - g.pw;
-            const int id = vt + c - g.pt;
-            bool pad = id < 0 || id >= g.Ti;
+            int id = vt + c - g.pt;
+            bool pad = false;
+            if (g.reflect_t) id = gx_reflect(id, g.Ti);                // (uniform) the mirrored depth pad of the wide geometries: no tap of it is padding
+            else pad = id < 0 || id >= g.Ti;
             if (g.reflect_hw) { ih = gx_reflect(ih, g.Hi); iw = gx_reflect(iw, g.Wi); }
             else pad = pad || ih < 0 || ih >= g.Hi || iw < 0 || iw >= g.Wi;
             if (!pad) {
@@ -212,10 +217,30 @@ bool gemm_x6_conv_plan_ints(const ConvGeom& g, int v[6])
     return v[0] == GX_BM && v[4] == GX_KC;              // the fp32 route's tiles: one report for both arithmetics
 }
 
+bool gemm_x6_conv_plan_ints_wide(const ConvGeom& g, int v[6])
+{
+    if (!gemm_conv_plan_ints_wide(g, v)) return false;
+    return v[0] == GX_BM && v[4] == GX_KC;
+}
+
+static int gemm_x6_conv_launch(const ConvGeom& g, const int v[6], const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s);
+
 int gemm_x6_conv_forward(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s)
 {
     int v[6];
     if (!gemm_x6_conv_plan_ints(g, v)) { set_error("gemm_x6_conv_forward: geometry not supported", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_x6_conv_launch(g, v, x, gate, w, bias, skip, y, s);
+}
+
+int gemm_x6_conv_forward_wide(const ConvGeom& g, const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s)
+{
+    int v[6];
+    if (!gemm_x6_conv_plan_ints_wide(g, v)) { set_error("gemm_x6_conv_forward_wide: geometry not supported", hipSuccess); return PROBAV_EINVAL; }
+    return gemm_x6_conv_launch(g, v, x, gate, w, bias, skip, y, s);
+}
+
+static int gemm_x6_conv_launch(const ConvGeom& g, const int v[6], const float* x, const float* gate, const float* w, const float* bias, const float* skip, float* y, hipStream_t s)
+{
     if (v[3] > 65535) { set_error("gemm_x6_conv_forward: Cout too large", hipSuccess); return PROBAV_EINVAL; }
     const dim3 grid((unsigned)v[2], (unsigned)v[3]), block(256);
 #define PROBAV_GX(NT) do { \

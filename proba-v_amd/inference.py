@@ -52,6 +52,8 @@ def add_inference_args(p, where=""):
                    "(WDSRModel.set_gemm_pair): a block's expConv, ReLU and decConv in one launch, the hidden tensor never in memory; the same bits")
     p.add_argument("--gemm-x6", dest="gemm_x6", action="store_true", help=where + "with --gemm-route: the route's convolution launches (forward, backward-data) on the 16-bit matrix pipe "
                    "(WDSRModel.set_gemm_x6): six bf16 piece products per fp32 product; results equal to rounding")
+    p.add_argument("--gemm-exotic", dest="gemm_exotic", action="store_true", help=where + "with --gemm-route: the 19-frame reducer's 5x5x5 and mirrored-pad launches on the route's "
+                   "kernels (WDSRModel.set_gemm_exotic) instead of the generic VALU kernels; a cfg of 7, 9 or 13 frames has none")
 
 
 def inference_options(p, opt, applies=True, needs=""):
@@ -62,13 +64,15 @@ def inference_options(p, opt, applies=True, needs=""):
     if not applies:
         for given, flag in ((opt.ensemble != "none", "--ensemble"), (opt.weights != "raw", "--weights"), (opt.tile_stride != 0, "--tile-stride"),
                             (opt.frame_windows != 0, "--frame-windows"), (opt.fuse, "--fuse"), (opt.gemm_route, "--gemm-route"), (opt.gemm_pair, "--gemm-pair"),
-                            (opt.gemm_x6, "--gemm-x6")):
+                            (opt.gemm_x6, "--gemm-x6"), (opt.gemm_exotic, "--gemm-exotic")):
             if given:
                 p.error("%s applies to %s (a folder of PNGs is scored as it is)" % (flag, needs))
     if opt.gemm_pair and not opt.gemm_route:
         p.error("--gemm-pair needs --gemm-route")
     if opt.gemm_x6 and not opt.gemm_route:
         p.error("--gemm-x6 needs --gemm-route")
+    if opt.gemm_exotic and not opt.gemm_route:
+        p.error("--gemm-exotic needs --gemm-route")
     if opt.ensemble == "none" and opt.ensemble_permute:
         p.error("--ensemble-permute needs --ensemble d8")
     if opt.tile_stride == 0 and opt.tile_window is not None:
@@ -107,10 +111,10 @@ def inference_options(p, opt, applies=True, needs=""):
     return opt.inference
 
 
-def load_model(config, cfg_path, band, weights, who, gemm_route=False, gemm_pair=False, gemm_x6=False):
+def load_model(config, cfg_path, band, weights, who, gemm_route=False, gemm_pair=False, gemm_x6=False, gemm_exotic=False):
     """The cfg's network on the device with its latest checkpoint restored (`weights`: "raw" or "ema") -> (model, trainer).  `who` names the
     command in the error of a checkpoint without an "ema" entry.  gemm_route: the engine's general matrix route (--gemm-route); gemm_pair: its fused pointwise pair (--gemm-pair);
-    gemm_x6: its convolution launches in x6 arithmetic (--gemm-x6)."""
+    gemm_x6: its convolution launches in x6 arithmetic (--gemm-x6); gemm_exotic: the 19-frame reducer's exotic launches on the route (--gemm-exotic)."""
     from .modelsTF import WDSRConv3D
     from .trainClass import ModelTrainer
     mean, std = BAND_STATS["NIR" if band == "NIR" else "RED"]
@@ -125,6 +129,8 @@ def load_model(config, cfg_path, band, weights, who, gemm_route=False, gemm_pair
         model.set_gemm_pair(True)
     if gemm_x6:
         model.set_gemm_x6(True)
+    if gemm_exotic:
+        model.set_gemm_exotic(True)
     basename = os.path.basename(cfg_path).split(".")[0]
     try:
         trainer = ModelTrainer(model, None, None, None, os.path.join(config["model_out"], "ckpt_%s" % basename, band),

@@ -237,6 +237,21 @@ class WDSRModel(torch.nn.Module):
         """Whether the wish for the route's x6 arithmetic is on (`set_gemm_x6`, or PROBAV_GEMM_X6 at engine creation)."""
         return bool(_lib.lib().probav_engine_gemm_x6(self._handle()))
 
+    def set_gemm_exotic(self, on):
+        """probav_engine_set_gemm_exotic: the 19-frame reducer's exotic launches on the route's kernels.  With the route on (`set_gemm_route`), the launches
+        the engine otherwise returns to the generic direct (VALU) kernels because their geometry is exotic -- forward and backward-filter of the 5x5x5 layer and
+        of the 3x3x3 layers on mirrored pads of 2, and the 5x5x5 layer's backward-data -- run on the route instead: the convolutions in the route's arithmetic
+        (`set_gemm_x6`), the backward-filter in fp32.  Only a network of 19 frames has such launches; any other is unchanged.  Off by default
+        (PROBAV_GEMM_EXOTIC=1 turns the wish on at engine creation); `set_impl`, `set_gemm_route`, `set_gemm_pair` and `set_gemm_x6` keep it.  The reverse
+        pass's scratch changes size at 19 frames, so the sizes the ops cache per engine are asked for again."""
+        _lib.check(_lib.lib().probav_engine_set_gemm_exotic(self._handle(), int(bool(on))), "probav_engine_set_gemm_exotic")
+        ops.forget_engine(self._handle().value)
+
+    @property
+    def gemm_exotic(self):
+        """Whether the wish for the route's exotic launches is on (`set_gemm_exotic`, or PROBAV_GEMM_EXOTIC at engine creation)."""
+        return bool(_lib.lib().probav_engine_gemm_exotic(self._handle()))
+
     def set_side_stream_mode(self, mode):
         """probav_engine_side_stream: 0 = everything on the caller's stream; 1 = the slab sums, the residual path and the upscale layer's backward-filter on the
         engine's low-priority side stream; 2 = also the blocks' backward-filter kernels (the engine's default)."""

@@ -108,7 +108,7 @@ def main(config, opt):
     options = opt.inference
     logger.info("[ INFO ] Loading data...")
     inputs = load_inputs(config, opt.totest, opt.band, options)
-    model, _ = load_model(config, opt.cfg, opt.band, options.weights, "test.py", gemm_route=opt.gemm_route, gemm_pair=opt.gemm_pair, gemm_x6=opt.gemm_x6)
+    model, _ = load_model(config, opt.cfg, opt.band, options.weights, "test.py", gemm_route=opt.gemm_route, gemm_pair=opt.gemm_pair, gemm_x6=opt.gemm_x6, gemm_exotic=opt.gemm_exotic)
     logger.info("[ INFO ] Generating predictions...")
     log_options(options)
     y_preds = (predict(model, inputs, options, config, micro_batch=16, launch_batch=16) if opt.reference_loop

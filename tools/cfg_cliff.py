@@ -16,7 +16,10 @@ configuration, ms per training step (forward + shift-L1 + backward), patches/s, 
     --ab --x6          the same A/B with the route AND the pair on in both legs (the last row: the pair off) and the route's x6 arithmetic (WDSRModel.set_gemm_x6)
                        alternated: ms per step x6 off / on -- the off leg is the fp32 route, the yardstick of the same run --, the off leg's spread, whether on is
                        below off by more than three times that spread, and the TFLOP/s of the route's kernel classes in each leg (fp32 classes off, _x6 classes on)
-                       against the published peaks: 157.3 TFLOP/s fp32 matrix, 2500 / 6 = 417 TFLOP/s of fp32-equivalent products in x6"""
+                       against the published peaks: 157.3 TFLOP/s fp32 matrix, 2500 / 6 = 417 TFLOP/s of fp32-equivalent products in x6
+    --ab --exotic      the same A/B with the route, the pair AND x6 on in both legs (one row: x6 off) and the route's exotic launches (WDSRModel.set_gemm_exotic)
+                       alternated: the 19-frame rows, which have nine such launches a step, and the 9-frame 64-filter and shipped rows, which have none and must
+                       not move; ms per step off / on, the off leg's spread, the census and the training workspace bytes of each leg, and the kernel classes of each leg"""
 import argparse
 import ctypes
 import json
@@ -220,6 +223,39 @@ def run_ab_x6(P, T, B, decay, F, E, steps, windows, pair=True):
             "faster_by_more_than_three_spreads": bool(off - on > 3 * spread * off), "classes_off": cls[False], "classes_on": cls[True]}
 
 
+def run_ab_exotic(P, T, B, decay, F, E, steps, windows, x6=True):
+    """run_ab with the route, its fused pair and (x6=True) its x6 arithmetic on in both legs and the route's exotic launches alternated.  The reverse scratch
+    moves with the switch at 19 frames."""
+    model, step = build(P, T, B, decay, F, E, True, True, x6)
+    h = model._handle()
+    legs, ws, census, cls = {False: [], True: []}, {}, {}, {}
+    for w in range(windows):
+        for on in (False, True):
+            model.set_gemm_exotic(on)
+            ws[on] = int(L.lib().probav_workspace_bytes(h, B, 1))
+            counts = (ctypes.c_int32 * 4)()
+            L.check(L.lib().probav_engine_route_counts(h, B, ctypes.byref(counts)), "probav_engine_route_counts")
+            census[on] = list(counts)
+            step()
+            step()                                              # (the switch resizes the reverse pass's scratch: the first steps allocate)
+            legs[on].append(sum(timed(step, steps)) / steps)
+    for on in (False, True):
+        model.set_gemm_exotic(on)
+        got = class_tflops(model, step, range(2, 13))
+        cls[on] = {CLASS_NAMES[c]: {"launches": v[2], "ms": round(v[1], 3), "tflops": round(v[0], 2),
+                                    "of_peak": round(v[0] / (X6_PEAK_TFLOPS if c >= 8 else FP32_PEAK_TFLOPS), 4)} for c, v in got.items() if v[2]}
+    arith = int(L.lib().probav_engine_gemm_arith(h))
+    release(model)
+    med = lambda v: sorted(v)[len(v) // 2]
+    off, on = med(legs[False]), med(legs[True])
+    spread = (max(legs[False]) - min(legs[False])) / off
+    return {"gemm_arith": arith, "ms_per_step_exotic_off": round(off, 3), "ms_per_step_exotic_on": round(on, 3), "on_over_off": round(on / off, 4),
+            "off_windows_ms": [round(v, 3) for v in legs[False]], "on_windows_ms": [round(v, 3) for v in legs[True]], "off_spread": round(spread, 4),
+            "faster_by_more_than_three_spreads": bool(off - on > 3 * spread * off), "inside_one_spread": bool(abs(off - on) <= spread * off),
+            "census_off": census[False], "census_on": census[True], "train_workspace_bytes_off": ws[False], "train_workspace_bytes_on": ws[True],
+            "classes_off": cls[False], "classes_on": cls[True]}
+
+
 # name, P, T, B, decay, F, E
 TABLE = (("shipped: patch 16, 9 frames, decay 0.8", 16, 9, 128, 0.8, 32, 8),
          ("7 frames", 16, 7, 128, 0.8, 32, 8),
@@ -237,6 +273,9 @@ AB_TABLE = (TABLE[0], TABLE[6], TABLE[7], TABLE[8], TABLE[9], ("filters 64, 13 f
 PAIR_TABLE = (TABLE[8], TABLE[9], TABLE[7], AB_TABLE[5], TABLE[0])
 # the rows of --ab --x6: the pair's rows with the pair on, and the 64-filter row with the pair off, where the pointwise launches change hands too
 X6_TABLE = tuple(r + (True,) for r in PAIR_TABLE) + ((TABLE[8][0] + ", pair off",) + TABLE[8][1:] + (False,),)
+# the rows of --ab --exotic: 19 frames at the shipped channels and at 64 filters (x6 on, and off), and the two rows without an exotic launch, which must not move
+EXOTIC_TABLE = (TABLE[3] + (True,), ("19 frames, filters 64", 16, 19, 64, 0.8, 64, 8, True), ("19 frames, filters 64, x6 off", 16, 19, 64, 0.8, 64, 8, False),
+                TABLE[8] + (True,), TABLE[0] + (True,))
 
 
 if __name__ == "__main__":
@@ -247,6 +286,7 @@ if __name__ == "__main__":
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--pair", action="store_true")
     ap.add_argument("--x6", action="store_true")
+    ap.add_argument("--exotic", action="store_true")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--windows", type=int, default=3)
     opt = ap.parse_args()
@@ -256,6 +296,12 @@ if __name__ == "__main__":
         ap.error("--x6 needs --ab or --gemm-route")
     if opt.x6 and opt.ab and opt.pair:
         ap.error("--ab --x6 has the pair on in its legs: no --pair")
+    if opt.exotic and (not opt.ab or opt.pair or opt.x6):
+        ap.error("--exotic is --ab --exotic: the route, the pair and x6 are on in its legs")
+    if opt.exotic:
+        for name, P, T, B, decay, F, E, x6 in (r for r in EXOTIC_TABLE if opt.filters is None or r[5] == opt.filters):
+            print(json.dumps(dict({"config": name, "batch": B}, **run_ab_exotic(P, T, B, decay, F, E, opt.steps or 4, opt.windows, x6))), flush=True)
+        sys.exit(0)
     table = (PAIR_TABLE if opt.pair else AB_TABLE) if opt.ab else TABLE
     if opt.x6 and opt.ab:
         table = tuple(r for r in X6_TABLE if opt.filters is None or r[5] == opt.filters)

@@ -65,6 +65,9 @@ def parser(argv=None):
     p.add_argument("--gemm-x6", dest="gemm_x6", action="store_true",
                    help="with --gemm-route: the route's convolution launches (forward, backward-data) on the 16-bit matrix pipe (WDSRModel.set_gemm_x6): six bf16 piece products per "
                         "fp32 product, results equal to rounding; combines freely with --gemm-pair, which stays fp32")
+    p.add_argument("--gemm-exotic", dest="gemm_exotic", action="store_true",
+                   help="with --gemm-route: the 19-frame reducer's 5x5x5 and mirrored-pad launches (forward, backward-filter, the 5x5x5 backward-data) on the route's kernels "
+                        "(WDSRModel.set_gemm_exotic) instead of the generic VALU kernels; a cfg of 7, 9 or 13 frames has none; combines freely with --gemm-pair and --gemm-x6")
     opt = p.parse_args(argv)
     if opt.fusion_input is not None and opt.modelType != "fusionNet":
         p.error("--fusion-input needs --modelType fusionNet")
@@ -80,6 +83,10 @@ def parser(argv=None):
         p.error("--gemm-x6 is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
     if opt.gemm_x6 and not opt.gemm_route:
         p.error("--gemm-x6 needs --gemm-route")
+    if opt.gemm_exotic and opt.modelType == "fusionNet":
+        p.error("--gemm-exotic is a switch of the patchNet engine: it cannot be combined with --modelType fusionNet")
+    if opt.gemm_exotic and not opt.gemm_route:
+        p.error("--gemm-exotic needs --gemm-route")
     if opt.random_crops and opt.online_aug:
         p.error("--random-crops and --online-aug are mutually exclusive")
     if not opt.random_crops and (opt.crop_positions != "all" or opt.crop_seed != 0 or opt.crops_per_epoch is not None):
@@ -96,13 +103,15 @@ def parser(argv=None):
 
 
 def apply_engine_options(model, opt):
-    """The engine switches among the flags, set on the freshly built model: --gemm-route, --gemm-pair, --gemm-x6."""
+    """The engine switches among the flags, set on the freshly built model: --gemm-route, --gemm-pair, --gemm-x6, --gemm-exotic."""
     if opt.gemm_route:
         model.set_gemm_route(True)
     if opt.gemm_pair:
         model.set_gemm_pair(True)
     if opt.gemm_x6:
         model.set_gemm_x6(True)
+    if opt.gemm_exotic:
+        model.set_gemm_exotic(True)
 
 
 def training_scenes(dataDir, band):
